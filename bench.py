@@ -17,6 +17,11 @@ N > 1 : the same matrix and n, 2D grid chosen by the planner for an A that is mu
         applied consistently (--grid reference: the reference rule with rA = 1) --, one rank per GPU over
         torch.distributed (control plane gloo, device payloads over RCCL); strong scaling (total work fixed).
 Prints ONE JSON line on rank 0.
+
+--dump-outputs DIR writes C as the last timed step left it to DIR/C.npy (DIR/C_rank<r>.npy per rank for N > 1), in the
+product's dtype; a C larger than the dump budget is written as a fixed seeded sample of its rows, named in the JSON line
+under "dump".  The inputs are generated deterministically, so two builds run with the same arguments can be compared
+output for output.
 """
 import argparse
 import ctypes as C
@@ -33,6 +38,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak (MI355X_MICROARCH.md: 8.0 TB/s spec, ~6.3 TB/s achievable)
+DUMP_BYTES = 48 << 20   # --dump-outputs: bytes written in all (shared by the ranks)
 
 # kernel symbol behind every variant name (what rocprofv3 --kernel-trace shows for it)
 KERNEL_SYMBOL = {"csr-rowgroup": "crp::spmm_rm_f64_kernel<LPR,VW,NV>", "rowpanel-R4": "crp::spmm_panel_f64_kernel<4,...>",
@@ -195,6 +201,19 @@ def cpu_baseline(rp, ci, va, k, n, budget_s=20.0):
                       % (m, len(ci), n, reps, dt)}
 
 
+def output_sample(Cmat, budget):
+    """What --dump-outputs writes of the device matrix C: all of it when it fits `budget` bytes, else a fixed seeded sample
+    of its rows (the same rows on every run with the same arguments).  Not timed.  -> (host array, description)."""
+    import torch
+    rows, row_bytes = Cmat.shape[0], Cmat.shape[1] * Cmat.element_size()
+    if rows * row_bytes <= budget:
+        return Cmat.cpu().numpy(), "all %d rows" % rows
+    take = max(1, budget // row_bytes)
+    sel = np.sort(np.random.default_rng(0).choice(rows, size=take, replace=False))
+    got = Cmat.index_select(0, torch.from_numpy(sel).to(Cmat.device)).cpu().numpy()
+    return got, "%d of %d rows: numpy default_rng(0).choice(%d, %d, replace=False), sorted" % (take, rows, rows, take)
+
+
 def measured_traffic(matrix, data, n, world, kernel_name, dtype="f64"):
     """HBM bytes per launch from the committed rocprofv3 PMC passes (profiles/r04_traffic.json: 2 x FETCH_SIZE +
     WRITE_SIZE, gfx950 correction applied; tools/prof_pmc.sh) -- a pointer to that run, not a measurement of this one:
@@ -265,6 +284,7 @@ def measure_f32(args, matrix, mtx, steps, lib, torch, dev):
         per_step.append(ms.value)
         lib.crp_event_destroy(a)
         lib.crp_event_destroy(b)
+    dump = output_sample(Cmat, DUMP_BYTES) if args.dump_outputs else None
     kern_ms = float(np.mean(per_step))
     from crp_spmm_amd import gen
     alg = gen.alg_bytes(m, int(np.unique(ci).size), n, nnz, vb=4)       # A once, needed B rows once, C once, fp32 values
@@ -279,10 +299,10 @@ def measure_f32(args, matrix, mtx, steps, lib, torch, dev):
             "achieved": alg / (kern_ms * 1e-3) / 1e9, "kernel_info": ki,
             "kernel": {"team2-R8": "crp::spmm_team2_kernel<float,NV,HAS_B1>", "csr-rowgroup": "crp::spmm_rm_f32_kernel<LPR,VW>"}.get(vname, vname),
             "traffic": f32_traffic[0], "traffic_source": f32_traffic[1], "first_exec_s": None, "check_rel_err": err,
-            "step_ms_min": float(np.min(per_step)), "step_ms_max": float(np.max(per_step))}
+            "step_ms_min": float(np.min(per_step)), "step_ms_max": float(np.max(per_step)), "dump": dump}
 
 
-def measure(args, matrix, mtx, steps, lib, torch, dist, comm, dev, world, rank, with_cpu):
+def measure(args, matrix, mtx, steps, lib, torch, dist, comm, dev, world, rank, with_cpu, with_dump=False):
     from crp_spmm_amd import engine, planner
     distributed = world > 1
     t_stage = time.time()
@@ -429,6 +449,7 @@ def measure(args, matrix, mtx, steps, lib, torch, dist, comm, dev, world, rank, 
         t = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t[0])
+    dump = output_sample(Cmat, DUMP_BYTES // world) if with_dump else None
 
     ms_per_step = elapsed / steps * 1e3
     kern_ms = float(np.mean(per_step))
@@ -445,7 +466,7 @@ def measure(args, matrix, mtx, steps, lib, torch, dist, comm, dev, world, rank, 
         "label": label, "data": data, "rows": m, "nnz": nnz, "n": n, "grid": "%dx%d" % (pm, pn),
         "value": flops * steps / elapsed / 1e9, "ms_per_step": ms_per_step, "kern_ms": kern_ms, "alg_bytes": alg_bytes,
         "achieved": achieved, "kernel_info": ki, "kernel": kname, "traffic": traffic, "traffic_source": tsrc,
-        "first_exec_s": t_first, "check_rel_err": err,
+        "first_exec_s": t_first, "check_rel_err": err, "dump": dump,
     }
     res["step_ms_min"], res["step_ms_max"] = float(np.min(per_step)), float(np.max(per_step))
     res["host_pointer_exec_ms"] = None
@@ -490,7 +511,11 @@ def main():
     ap.add_argument("--check", type=int, default=1)
     ap.add_argument("--host-exec", type=int, default=1, help="also time rp_spmm_exec with host B / C (config.host_pointer_exec_ms)")
     ap.add_argument("--sweep-variants", action="store_true", help="also time the other kernel variants (stderr)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write C of the last timed step to DIR/<name>.npy (see module docstring)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -526,8 +551,16 @@ def main():
         args.no_also = True
     else:
         main_res = measure(args, args.matrix, mtx, args.steps, lib, torch, dist, comm, dev, world, rank,
-                           with_cpu=(rank == 0 and world == 1 and not args.no_cpu_baseline))
+                           with_cpu=(rank == 0 and world == 1 and not args.no_cpu_baseline), with_dump=bool(args.dump_outputs))
     rccl_info = main_res.get("rccl")
+    dump_info = None
+    if args.dump_outputs:
+        arr, rows_note = main_res.pop("dump")
+        name = "C" if world == 1 else "C_rank%d" % rank
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
+        dump_info = {"dir": args.dump_outputs, "files": {name: {"shape": list(arr.shape), "dtype": str(arr.dtype), "rows": rows_note}}}
+        del arr
     also = None
     if world == 1 and mtx is None and args.matrix == "pwtk" and args.variant == 0 and not args.no_also:
         r2 = measure(args, "pwtk_shell", None, min(args.steps, 100), lib, torch, dist, comm, dev, world, rank, with_cpu=False)
@@ -560,6 +593,8 @@ def main():
     }
     if "cpu_baseline" in r:
         out["cpu_baseline"] = r["cpu_baseline"]
+    if dump_info is not None:
+        out["dump"] = dump_info
     if rank == 0:
         print(json.dumps(out))
         sys.stdout.flush()

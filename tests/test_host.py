@@ -571,6 +571,10 @@ def test_parallel_ingest_and_cache(crp, orc, tmp_path):
     st, nr, nc, row, col, val = mmio.mm_read_sparse_RPI(f1)
     t_par = time.time() - t0
     assert st == 0 and (nr, nc) == (m, m)
+    # the reference's reader keeps the file's entries in file order and appends the mirror of every off-diagonal one
+    off = r != c
+    assert np.array_equal(row, np.concatenate([r, c[off]])) and np.array_equal(col, np.concatenate([c, r[off]]))
+    assert np.array_equal(val, np.concatenate([v, v[off]]))
     if orc.ref() is not None:
         rr = orc.ref_mm_read(str(f1))
         assert rr[0] == 0 and np.array_equal(row, rr[3]) and np.array_equal(col, rr[4]) and np.array_equal(val, rr[5])

@@ -1,6 +1,7 @@
 """CPU: the oracle (oracle/crp_oracle.c + numpy) against the golden vectors
 produced by the reference's own code (oracle/_ref) and by MKL, against _ref
 itself when it is present, and against closed forms."""
+import hashlib
 import os
 
 import numpy as np
@@ -68,32 +69,52 @@ def test_spmm_closed_form(orc):
 
 
 def test_restatement_matches_compiled_reference(orc):
-    """When oracle/_ref is present: restatement == reference on fresh random inputs."""
-    if orc.ref() is None:
-        pytest.skip("oracle/_ref not built (no /root/reference on this machine)")
+    """Restatement == reference on seeded random inputs: against the reference's answers stored in
+    tests/golden/ref_random.npz (make_golden_random.py), and against oracle/_ref itself when it is built."""
     from crp_spmm_amd import gen
+    g = np.load(os.path.join(GOLDEN, "ref_random.npz"), allow_pickle=False)
+    live = orc.ref() is not None
     for seed, (m, k) in enumerate([(900, 900), (400, 1300), (1300, 400)]):
         rp, ci, va = gen.random_csr(m, k, 15, seed=seed, empty_every=13 if seed else 0)
+        sha = hashlib.sha256(rp.astype(np.int32).tobytes() + ci.astype(np.int32).tobytes() + va.astype(np.float64).tobytes())
+        assert sha.hexdigest() == str(g["s%d_input_sha256" % seed]), "gen.random_csr changed: regenerate ref_random.npz"
         for P in (1, 2, 3, 5, 6, 8, 12):
-            a, b = orc.csr_row_partition(rp, P), orc.csr_row_partition(rp, P, use_ref=True)
-            assert np.array_equal(a, b)
+            t = "s%d_P%d_" % (seed, P)
+            a = orc.csr_row_partition(rp, P)
+            assert np.array_equal(a, g[t + "rb"])
+            if live:
+                assert np.array_equal(a, orc.csr_row_partition(rp, P, use_ref=True))
             x = orc.even_displs(k, P) if m != k else a
             s1, t1 = orc.csr_row_part_comm_size(k, rp, ci, a, x)
-            s2, t2 = orc.csr_row_part_comm_size(k, rp, ci, a, x, use_ref=True)
-            assert np.array_equal(s1, s2) and t1 == t2
+            assert np.array_equal(s1, g[t + "comm_sizes"]) and t1 == int(g[t + "comm_total"]), (seed, P)
+            if live:
+                s2, t2 = orc.csr_row_part_comm_size(k, rp, ci, a, x, use_ref=True)
+                assert np.array_equal(s1, s2) and t1 == t2
             for n in (1, 16, 256, 2048):
                 r1 = orc.part2d_from_1d(P, m, n, k, a, rp, ci)
-                r2 = orc.part2d_from_1d(P, m, n, k, a, rp, ci, use_ref=True)
+                r2 = orc.part2d_from_1d(P, m, n, k, a, rp, ci, use_ref=True) if live else None
                 for key in r1:
-                    assert np.array_equal(np.asarray(r1[key]), np.asarray(r2[key])), (P, n, key)
-        assert orc.prime_factorization(360) == orc.prime_factorization(360, use_ref=True) == [2, 2, 2, 3, 3, 5]
+                    assert np.array_equal(np.asarray(r1[key]), g["%sn%d_%s" % (t, n, key)]), (seed, P, n, key)
+                    if live:
+                        assert np.array_equal(np.asarray(r1[key]), np.asarray(r2[key])), (P, n, key)
+        assert orc.prime_factorization(360) == list(g["prime_360"]) == [2, 2, 2, 3, 3, 5]
+        if live:
+            assert orc.prime_factorization(360, use_ref=True) == [2, 2, 2, 3, 3, 5]
         rows = np.repeat(np.arange(m), np.diff(rp)).astype(np.int32)
         perm = np.random.default_rng(seed).permutation(rows.size)
         o = orc.coo2csr(m, rows[perm], ci[perm], va[perm])
-        r = orc.coo2csr(m, rows[perm], ci[perm], va[perm], use_ref=True)
-        assert all(np.array_equal(u, v) for u, v in zip(o, r))
-    for length, nblk in [(10, 3), (7, 7), (5, 8), (0, 2)]:
-        for i in range(-1, nblk + 2):
+        order = g["s%d_coo2csr_order" % seed]
+        want = (g["s%d_coo2csr_rowptr" % seed], ci[perm][order], va[perm][order])
+        assert all(np.array_equal(u, v) for u, v in zip(o, want)), seed
+        if live:
+            r = orc.coo2csr(m, rows[perm], ci[perm], va[perm], use_ref=True)
+            assert all(np.array_equal(u, v) for u, v in zip(o, r))
+    spos = [tuple(int(x) for x in row) for row in g["block_spos"]]
+    assert [row[:3] for row in spos] == [(length, nblk, i) for length, nblk in [(10, 3), (7, 7), (5, 8), (0, 2)]
+                                         for i in range(-1, nblk + 2)]
+    for length, nblk, i, s, z in spos:
+        assert orc.block_spos(length, nblk, i) == (s, z), (length, nblk, i)
+        if live:
             assert orc.block_spos(length, nblk, i) == orc.block_spos(length, nblk, i, use_ref=True)
 
 
