@@ -9,6 +9,7 @@ Contents: ``csrc/`` (HIP kernels + the C ABI declared in ``include/``),
 ``engine`` (RpSpmm / Para2dSpmm, mirrors of rp_spmm_* / para2d_spmm_*),
 ``comm`` (crp_comm_t over torch.distributed: gloo on CPU, nccl == RCCL on GPU),
 ``planner`` / ``mmio`` (host planner and Matrix Market ingest),
+``partition`` (graph-based 1D row partitioning, part-method 1, and P A P^T on host or device),
 ``hip`` (device-level kernel wrappers), ``gen`` (synthetic inputs).
 """
 from . import _lib  # noqa: F401

@@ -97,7 +97,7 @@ _LL = C.c_longlong
 
 # name -> (restype, argtypes); every symbol declared in include/crpspmm_hip.h,
 # include/crp_comm.h, include/crp_engine.h, include/utils.h, include/spmat_part.h,
-# include/mmio_utils.h, include/crp_rccl.h.  tests/test_host.py (the ABI test there) checks that the library
+# include/mmio_utils.h, include/crp_rccl.h, include/crp_part.h.  tests/test_host.py (the ABI test there) checks that the library
 # exports every function the headers declare.
 SIGNATURES = {
     # crpspmm_hip.h
@@ -237,6 +237,10 @@ SIGNATURES = {
     "crp_csr_cache_write": (_I, [C.c_char_p, _I, _I, c_int_p, c_int_p, c_dbl_p]),
     "crp_csr_cache_read": (_I, [C.c_char_p, c_int_p, c_int_p, C.POINTER(c_int_p), C.POINTER(c_int_p), C.POINTER(c_dbl_p)]),
     "crp_crpspmm_plan_grid": (None, [_I, _I, _I, _I, c_int_p, c_int_p, c_int_p, c_int_p, c_int_p]),
+    # crp_part.h
+    "crp_graph_row_order": (_I, [_I, _I, c_int_p, c_int_p, c_int_p, c_int_p]),
+    "crp_csr_permute_sym": (_I, [_I, _V, _V, _V, _V, _V, _V, _V, _V]),
+    "crp_graph_row_partition": (_I, [_I, _I, c_int_p, c_int_p, c_dbl_p, c_int_p, c_int_p, _I]),
     # dev_type.h
     "is_dev_type_valid": (_I, [_I]),
     "dev_type_malloc": (_V, [C.c_size_t, _I]),

@@ -4,12 +4,15 @@
  *   3  test_spmm_2dpg.exe    <mtx> <n> <nproc> <part-method>             planner dump, serial
  *   4  test_crpspmm.exe      <mtx> <n> <ntest> [check] [use-CUDA]        older all-in-one engine
  * Command lines and printed lines follow the reference's programs of the same names; the code is
- * built on harness.[ch].  part-method must be 0 (METIS is not part of this build).  With check = 1
- * rank 0 compares against a naive product and the exit code reports the result. */
+ * built on harness.[ch].  part-method 0 is the native nonzero-balanced row split; 1 is the graph partition
+ * of include/crp_part.h in place of the reference's METIS (symmetric files only, A permuted to P A P^T on
+ * rank 0 before it is dealt out); any other method is refused.  With check = 1 rank 0 compares against a
+ * naive product and the exit code reports the result. */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include "harness.h"
+#include "crp_part.h"
 #include "crpspmm.h"
 #include "mat_redist.h"
 #include "para2d_spmm.h"
@@ -21,11 +24,25 @@
 #error "compile with -DCRP_DRIVER=1..4"
 #endif
 
-__attribute__((unused)) static int refuse_metis(const hx_world *w, int method)
+__attribute__((unused)) static int refuse_method(const hx_world *w, int method)
 {
-    if (method == 0) return 0;
-    if (w->rank == 0) printf("METIS 1D row partitioning is not available in this build (part-method must be 0)\n");
+    if (method == 0 || method == 1) return 0;
+    if (w->rank == 0) printf("part-method %d is not available in this build (0: native, 1: graph partitioning)\n", method);
     return 1;
+}
+
+/* part-method 1 on rank 0: the graph partition's cuts, A replaced by P A P^T (on the device when there is one) */
+__attribute__((unused)) static void graph_partition(const hx_world *w, hx_matrix *A, int nproc, int *cuts)
+{
+    int *perm = (int *) malloc(sizeof(int) * ((size_t) A->m + 1));
+    const int rc = crp_graph_row_partition(A->m, nproc, A->ptr, A->idx, A->val, perm, cuts, -1);
+    free(perm);
+    if (rc != 0)
+    {
+        printf("Graph 1D row partitioning failed with code %d\n", rc);
+        fflush(stdout);
+        MPI_Abort(w->comm, 3);
+    }
 }
 
 __attribute__((unused)) static double *dense(size_t rows, size_t cols)
@@ -47,16 +64,17 @@ int main(int argc, char **argv)
     if (argc < 5)
     {
         printf("Usage: %s <mtx-file> <num-of-B-col> <num-of-tests> <part-method> <check-correct>\n", argv[0]);
-        printf("<part-method>: 0 for native 1D partition (METIS partitioning is not available in this build)\n");
+        printf("<part-method>: 0 for native 1D partition, 1 for graph 1D partition (METIS-free, symmetric matrices only)\n");
         printf("<check-correct>: 0 or 1, optional, default value is 0\n");
         return 255;
     }
     const int n = atoi(argv[2]), n_test = atoi(argv[3]);
     int verify = argc > 5 ? atoi(argv[5]) : 0, status = 0;
+    const int method = atoi(argv[4]);
     hx_world w = hx_start(&argc, &argv);
-    if (refuse_metis(&w, atoi(argv[4]))) { MPI_Finalize(); return 254; }
+    if (refuse_method(&w, method)) { MPI_Finalize(); return 254; }
     hx_matrix A;
-    hx_load(&w, argv[1], n, &A);
+    hx_load(&w, argv[1], n, method == 1, &A);
     if (verify) verify = hx_can_verify(&w, &A, n);
 
     /* rows of A by nonzero count; rows of B like A when square, evenly otherwise */
@@ -64,8 +82,16 @@ int main(int argc, char **argv)
     int *cuts = (int *) malloc(sizeof(int) * (w.size + 1)), *b_cuts = (int *) malloc(sizeof(int) * (w.size + 1));
     if (w.rank == 0)
     {
-        printf("Using naive 1D row partitioning\n");
-        csr_mat_row_partition(A.m, A.ptr, w.size, cuts);
+        if (method == 1)
+        {
+            printf("Using graph 1D row partitioning (METIS-free)\n");
+            graph_partition(&w, &A, w.size, cuts);
+        }
+        else
+        {
+            printf("Using naive 1D row partitioning\n");
+            csr_mat_row_partition(A.m, A.ptr, w.size, cuts);
+        }
         for (int r = 0, len; r <= w.size; r++)
         {
             if (A.m == A.k) b_cuts[r] = cuts[r];
@@ -138,16 +164,17 @@ int main(int argc, char **argv)
     if (argc < 5)
     {
         printf("Usage: %s <mtx-file> <num-of-B-col> <num-of-tests> <part-method> <check-correct>\n", argv[0]);
-        printf("<part-method>: 0 for native 1D partition (METIS partitioning is not available in this build)\n");
+        printf("<part-method>: 0 for native 1D partition, 1 for graph 1D partition (METIS-free, symmetric matrices only)\n");
         printf("<check-correct>: 0 or 1, optional, default value is 0\n");
         return 255;
     }
     const int n = atoi(argv[2]), n_test = atoi(argv[3]);
     int verify = argc > 5 ? atoi(argv[5]) : 0, status = 0;
+    const int method = atoi(argv[4]);
     hx_world w = hx_start(&argc, &argv);
-    if (refuse_metis(&w, atoi(argv[4]))) { MPI_Finalize(); return 254; }
+    if (refuse_method(&w, method)) { MPI_Finalize(); return 254; }
     hx_matrix A;
-    hx_load(&w, argv[1], n, &A);
+    hx_load(&w, argv[1], n, method == 1, &A);
     if (verify) verify = hx_can_verify(&w, &A, n);
 
     /* plan on rank 0, then everybody gets the grid and the four partition arrays */
@@ -157,7 +184,13 @@ int main(int argc, char **argv)
         const double t0 = get_wtime_sec();
         int *cuts1d = (int *) malloc(sizeof(int) * (w.size + 1));
         size_t cost = 0;
-        csr_mat_row_partition(A.m, A.ptr, w.size, cuts1d);
+        if (method == 1)
+        {
+            printf("Using graph 1D row partitioning (METIS-free)\n");
+            graph_partition(&w, &A, w.size, cuts1d);
+        }
+        else
+            csr_mat_row_partition(A.m, A.ptr, w.size, cuts1d);
         calc_spmm_part2d_from_1d(w.size, A.m, n, A.k, cuts1d, A.ptr, A.idx, 1, &grid[0], &grid[1], &cost, &src_rows, &b_rows,
                                  &c_rows, &cols, 0);
         free(cuts1d);
@@ -227,20 +260,27 @@ int main(int argc, char **argv)
     if (argc < 5)
     {
         printf("Usage: %s <mtx-file> <num-of-B-col> <num-of-processes> <part-method>\n", argv[0]);
-        printf("<part-method>: 0 for native 1D partition (METIS partitioning is not available in this build)\n");
+        printf("<part-method>: 0 for native 1D partition, 1 for graph 1D partition (METIS-free, symmetric matrices only)\n");
         return 255;
     }
     const int n = atoi(argv[2]), P = atoi(argv[3]);
+    const int method = atoi(argv[4]);
     hx_world w = hx_start(&argc, &argv);             /* serial program; MPI only because the loader reports through it */
-    if (refuse_metis(&w, atoi(argv[4]))) { MPI_Finalize(); return 254; }
+    if (refuse_method(&w, method)) { MPI_Finalize(); return 254; }
     hx_matrix A;
-    hx_load(&w, argv[1], n, &A);
+    hx_load(&w, argv[1], n, method == 1, &A);
     printf("============================================================\n");
     int *cuts1d = (int *) malloc(sizeof(int) * (P + 1)), pm = 0, pn = 0;
     int *src_rows = NULL, *b_rows = NULL, *c_rows = NULL, *cols = NULL;
     size_t cost = 0;
     double t0 = get_wtime_sec();
-    csr_mat_row_partition(A.m, A.ptr, P, cuts1d);
+    if (method == 1)
+    {
+        printf("Using graph 1D row partitioning (METIS-free)\n");
+        graph_partition(&w, &A, P, cuts1d);
+    }
+    else
+        csr_mat_row_partition(A.m, A.ptr, P, cuts1d);
     const double t_1d = get_wtime_sec() - t0;
     printf("Calculate 1D row partitioning time = %.2f s\n", t_1d);
     t0 = get_wtime_sec();
@@ -288,7 +328,7 @@ int main(int argc, char **argv)
     int verify = argc > 4 ? atoi(argv[4]) : 0, status = 0;
     hx_world w = hx_start(&argc, &argv);
     hx_matrix A;
-    hx_load(&w, argv[1], n, &A);
+    hx_load(&w, argv[1], n, 0, &A);
     if (verify) verify = hx_can_verify(&w, &A, n);
 
     const double t0 = get_wtime_sec();

@@ -17,7 +17,7 @@ hx_world hx_start(int *argc, char ***argv)
     return w;
 }
 
-void hx_load(const hx_world *w, const char *path, int n_cols, hx_matrix *A)
+void hx_load(const hx_world *w, const char *path, int n_cols, int need_symm, hx_matrix *A)
 {
     memset(A, 0, sizeof(*A));
     if (w->rank == 0)
@@ -28,7 +28,7 @@ void hx_load(const hx_world *w, const char *path, int n_cols, hx_matrix *A)
         printf("Rank 0 read matrix A from file %s", path);
         fflush(stdout);
         const double t0 = get_wtime_sec();
-        if (mm_read_sparse_RPI(path, 0, &A->m, &A->k, &nnz, &r, &c, &v) != 0)
+        if (mm_read_sparse_RPI(path, need_symm, &A->m, &A->k, &nnz, &r, &c, &v) != 0)
         {
             printf("\nCannot ingest %s\n", path);
             MPI_Abort(w->comm, 2);

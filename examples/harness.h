@@ -28,8 +28,9 @@ typedef struct
 typedef struct { int rank, size; MPI_Comm comm; } hx_world;
 
 hx_world hx_start(int *argc, char ***argv);
-/* rank 0 reads the file ("B has ..", "Rank 0 read matrix A ..", "A size = .." lines), everybody learns m, k */
-void hx_load(const hx_world *w, const char *path, int n_cols, hx_matrix *A);
+/* rank 0 reads the file ("B has ..", "Rank 0 read matrix A ..", "A size = .." lines), everybody learns m, k;
+ * need_symm = 1 refuses a file whose banner is not "symmetric" (the ingest aborts) */
+void hx_load(const hx_world *w, const char *path, int n_cols, int need_symm, hx_matrix *A);
 /* 0 when a dense m x n or k x n matrix would overflow int indexing (with the reference's two lines) */
 int hx_can_verify(const hx_world *w, const hx_matrix *A, int n_cols);
 /* rows [cuts[r], cuts[r+1]) go to rank r; cuts valid on rank 0 on entry, on every rank on return */

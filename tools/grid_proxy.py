@@ -9,9 +9,11 @@ columns outside the block x n / pn x 8 bytes, what rp_spmm_init's plan would req
 T_local, the halo bytes, and the speed-up bounds T(1 GPU) / T_local (exchange fully hidden behind the interior rows' product,
 which the engine overlaps) and T(1 GPU) / (T_local + halo bytes / link rate) (exchange not hidden at all; --link-gbs, default
 the 153 GB/s of one xGMI link: a block's halo comes from its two neighbours over two links, so this is the pessimistic end).
-Row blocks are the planner's nnz-balanced contiguous blocks; per grid the block with the largest halo is measured.
+Row blocks are the planner's nnz-balanced contiguous blocks (--part-method 0) or the pm parts of the graph row partition of
+include/crp_part.h with A permuted to P A P^T on the device first (--part-method 1, the example programs' part-method 1); per grid
+the block with the largest halo is measured.
 
-usage: grid_proxy.py [--matrix kkt240] [--n 256] [--gpus 8] [--steps 10] [--out FILE.jsonl]
+usage: grid_proxy.py [--matrix kkt240] [--n 256] [--gpus 8] [--steps 10] [--part-method 0|1] [--out FILE.jsonl]
 """
 import argparse
 import ctypes as C
@@ -33,27 +35,47 @@ def main():
     ap.add_argument("--gpus", type=int, default=8)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--link-gbs", type=float, default=153.0)
+    ap.add_argument("--part-method", type=int, default=0, choices=(0, 1))
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
     import crp_spmm_amd
     import bench
-    from crp_spmm_amd import hip
+    from crp_spmm_amd import hip, partition
     lib = crp_spmm_amd.load()
     dev = torch.device("cuda", 0)
     t0 = time.time()
-    label, data, m, k, rp, ci, va = bench.build_matrix(a.matrix, None)
-    nnz = int(rp[-1])
+    label, data, m, k, rp0, ci0, va0 = bench.build_matrix(a.matrix, None)
+    nnz = int(rp0[-1])
     print("[grid_proxy %6.1f s] %s: %d rows, %d nnz" % (time.time() - t0, label, m, nnz), file=sys.stderr, flush=True)
     stream = torch.cuda.current_stream().cuda_stream
     grids = [(pm, a.gpus // pm) for pm in range(1, a.gpus + 1) if a.gpus % pm == 0 and a.n % (a.gpus // pm) == 0]
     grids = [(1, 1)] + grids
     lines = []
     for pm, pn in grids:
-        # nnz-balanced contiguous row blocks, as csr_mat_row_partition makes them (src/spmat_part.c:12-36); per grid the block
-        # with the LARGEST halo is measured (the exec time of a grid is its slowest rank's)
-        cuts = [int(np.searchsorted(rp, nnz * b // pm)) for b in range(pm + 1)]
-        cuts[0], cuts[-1] = 0, m
+        rp, ci, va = rp0, ci0, va0
+        if a.part_method == 1 and pm > 1:
+            # graph row partition into pm parts, A permuted to P A P^T on the device
+            tp = time.time()
+            perm, displs = partition.graph_row_order(rp0, ci0, pm)
+            tq = time.time()
+            dx = [torch.from_numpy(x).to(dev) for x in (rp0, ci0, va0, perm)]
+            torch.cuda.synchronize()
+            tr = time.perf_counter()
+            out = partition.permute_sym(*dx)
+            torch.cuda.synchronize()
+            ts = time.perf_counter()
+            rp, ci, va = (t.cpu().numpy() for t in out)
+            del dx, out
+            torch.cuda.empty_cache()
+            cuts = [int(x) for x in displs]
+            print("[grid_proxy] graph partition pm = %d: order %.1f s (host), permute %.1f ms (device)" % (pm, tq - tp, (ts - tr) * 1e3),
+                  file=sys.stderr, flush=True)
+        else:
+            # nnz-balanced contiguous row blocks, as csr_mat_row_partition makes them (src/spmat_part.c:12-36)
+            cuts = [int(np.searchsorted(rp, nnz * b // pm)) for b in range(pm + 1)]
+            cuts[0], cuts[-1] = 0, m
+        # per grid the block with the LARGEST halo is measured (the exec time of a grid is its slowest rank's)
         best = None
         for b in range(pm):
             c0, c1 = cuts[b], cuts[b + 1]
@@ -111,7 +133,7 @@ def main():
             lib.crp_event_destroy(x)
             lib.crp_event_destroy(y)
         rv = int(lib.crp_csr_dev_last_variant(A.handle))
-        line = {"grid": "%d x %d" % (pm, pn), "block": blk, "block_rows": ml, "block_nnz": e1 - e0, "n_local": nl, "kernel_variant": lib.crp_spmm_variant_name(rv).decode(),
+        line = {"grid": "%d x %d" % (pm, pn), "part_method": a.part_method, "block": blk, "block_rows": ml, "block_nnz": e1 - e0, "n_local": nl, "kernel_variant": lib.crp_spmm_variant_name(rv).decode(),
                 "T_local_ms": float(np.mean(per)), "ms_min": float(np.min(per)), "ms_max": float(np.max(per)), "halo_rows": halo,
                 "halo_MB": halo * nl * 8 / 1e6, "exchange_ms_one_link": halo * nl * 8 / (a.link_gbs * 1e9) * 1e3, "first_product_s": first, "check_rel_err": err}
         lines.append(line)
