@@ -95,18 +95,14 @@ hipError_t spmm_rm_f64_narrow(const PanelArgs &p, const SpmmArgs &a, hipStream_t
 // spmm_kernels.hip
 hipError_t spmm_rm_f64_rowgroup(const SpmmArgs &a, hipStream_t s);
 hipError_t spmm_cm_f64(const SpmmArgs &a, hipStream_t s);
-bool spmm_panel_applicable(const SpmmArgs &a);
 hipError_t spmm_rm_f64_panel(const PanelArgs &p, const SpmmArgs &a, hipStream_t s);
 
 // team2r_kernel.hip (Team2RHost streams; the argument block is Team2NArgs: same arrays, tvoff in units of 16 bytes)
-bool spmm_team2r_applicable(const Team2NArgs &t, const SpmmArgs &a);
 hipError_t spmm_rm_f64_team2r(const Team2NArgs &t, const SpmmArgs &a, hipStream_t s);
 hipError_t team2r_fill_rows(const Team2NArgs &t, const SpmmArgs &a, hipStream_t s);      // the C rows into the entry table: once per row map
 
 // team2_kernel.hip
-bool spmm_team2_applicable(const SpmmArgs &a);
 hipError_t spmm_rm_f64_team2(const Team2Args &t, const SpmmArgs &a, hipStream_t s);
-bool spmm_team2_applicable_f32(const SpmmArgsF32 &a);
 hipError_t spmm_rm_f32_team2(const Team2Args &t, const SpmmArgsF32 &a, hipStream_t s);
 
 // spmm_f32.hip: CSR row-group kernel of the fp32 path (any width, both sources)

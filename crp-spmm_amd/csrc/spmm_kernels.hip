@@ -801,8 +801,6 @@ static hipError_t launch_panel_addr(const PanelArgs &p, const SpmmArgs &a, hipSt
 
 // The row-panel kernels need one lane per column (pair): below ~24 columns most lanes of the
 // wave would idle and the CSR row-group kernel (several rows per wave) is the better shape.
-bool spmm_panel_applicable(const SpmmArgs &a) { return a.n >= 24; }
-
 template <int R>
 static hipError_t launch_panel_shape(const PanelArgs &p, const SpmmArgs &a, hipStream_t s)
 {

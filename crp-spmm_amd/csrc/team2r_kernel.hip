@@ -411,13 +411,6 @@ hipError_t team2r_fill_rows(const Team2NArgs &t, const SpmmArgs &a, hipStream_t 
     return hipGetLastError();
 }
 
-// 24 <= n <= 128 / G (even), 16-byte aligned operands
-bool spmm_team2r_applicable(const Team2NArgs &t, const SpmmArgs &a)
-{
-    return a.n >= 24 && a.n <= 128 / t.G && (a.n % 2 == 0) && (a.ldB0 % 2 == 0) && (a.ldC % 2 == 0) && (a.B1 == nullptr || a.ldB1 % 2 == 0) &&
-           (((uintptr_t) a.B0 | (uintptr_t) a.B1 | (uintptr_t) a.C) % 16 == 0);
-}
-
 hipError_t spmm_rm_f64_team2r(const Team2NArgs &t, const SpmmArgs &a, hipStream_t s)
 {
     const bool has_b1 = a.B1 != nullptr;

@@ -236,6 +236,27 @@ def locality_order_host(rowptr, colidx, ncol=None, nparts=8):
     return perm[:m], dict(groups=int(info[0]), parts=int(info[1]), mean_dist_before=info[2], mean_dist_after=info[3])
 
 
+SHAPES = ("aligned", "ld+1", "b1", "misaligned")      # operand shapes of crp_spmm_plan_host
+
+
+def spmm_plan_host(rowptr, colidx, widths, variant=0, dtype="f64", shape="aligned", ncol=None):
+    """crp_spmm_plan_host -> (info dict, resolved variants as a list, one per width): the kernel choice of the device path, on the host."""
+    lib = L.load()
+    rp = np.ascontiguousarray(rowptr, dtype=np.int32)
+    ci = np.ascontiguousarray(colidx, dtype=np.int32)
+    if ci.size == 0:
+        ci = np.zeros(1, np.int32)
+    m = rp.size - 1
+    w = np.ascontiguousarray(widths, dtype=np.int32)
+    res = np.zeros(max(w.size, 1), dtype=np.int32)
+    info = np.zeros(5, dtype=np.int32)
+    L.check(lib.crp_spmm_plan_host(m, m if ncol is None else int(ncol), rp.ctypes.data_as(L.c_int_p), ci.ctypes.data_as(L.c_int_p),
+                                   w.size, w.ctypes.data_as(L.c_int_p), int(variant), int(dtype == "f32"), SHAPES.index(shape),
+                                   res.ctypes.data_as(L.c_int_p), info.ctypes.data_as(L.c_int_p)), "crp_spmm_plan_host")
+    return (dict(auto_variant=int(info[0]), reordered=int(info[1]), team2_min_n=int(info[2]), team2_pays=int(info[3]),
+                 panels_sparse=int(info[4])), [int(x) for x in res[:w.size]])
+
+
 def spmm_csr_f32(A, B0, C_out, n=None, B1=None, variant=0, stream=None):
     """crp_spmm_csr_f32: C := A * B with values, B and C in fp32 (row-major float32 torch tensors on the device)."""
     lib = L.load()

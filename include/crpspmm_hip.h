@@ -127,16 +127,17 @@ int crp_csr_dev_auto_variant(crp_csr_dev_p A);
  * CRPSPMM_REORDER=0|1 overrides).  Results do not depend on it: C rows are written through a row map and
  * every row's products are still summed in the kernel variant's own order. */
 int crp_csr_dev_reordered(crp_csr_dev_p A);
-/* the variant `variant = 0` (auto) runs for a row-major fp64 product of n columns with 16-byte aligned operands and even n,
- * ldB, ldC: the create-time choice (crp_csr_dev_auto_variant), replaced by 5 (team2-R8) from 96 columns on (from 33 when the
- * row-panel format would ask for more than 12 B row slices per row of A, from 48 when the matrix has no stride lattice; from 33 when
- * fewer than 35 % of the (row, entry) pairs of the R = 8 panels exist; for 61 .. 64 columns otherwise) where 64 consecutive rows share columns, and by 1
- * below 24 columns.  Operands that are not aligned like that fall back (5 -> 3 -> 1): what a product actually launched is
- * crp_csr_dev_last_variant().  Variants 4 and 6 (the round-1 LDS team kernel, the narrow team kernel of round 3) were
- * measured slower than what auto picks at every width and removed in round 4: asking for them returns -1;
- * variant 7 (team2r-R8: lane groups own rows, csrc/team2r_kernel.hip) replaces the create-time choice at 24 <= n <= 32 when fewer
- * than 35 % of the (row, entry) pairs of the R = 8 panels exist and 64 consecutive rows share columns (CRPSPMM_TEAM2R=0|1 forces; asked
- * for explicitly it runs up to 64 columns). */
+/* the variant that a variant-0 (auto) row-major fp64 product of n columns launches on this matrix when B0 and C are 16-byte aligned
+ * with ldB0 = ldC = n and there is no B1 (csrc/dispatch.cpp, resolve_f64: the rules crp_spmm_csr_f64 follows; after such a
+ * product it equals crp_csr_dev_last_variant()).  The create-time choice (crp_csr_dev_auto_variant), replaced for even n by 5
+ * (team2-R8) where 64 consecutive rows share columns: from 96 columns on (from 33 when the row-panel format would ask for more than
+ * 12 B row slices per row of A, from 48 when the matrix has no stride lattice; from 33 when fewer than 35 % of the (row, entry) pairs
+ * of the R = 8 panels exist; for 61 .. 64 columns otherwise); else by 7 (team2r-R8: lane groups own rows, csrc/team2r_kernel.hip) at
+ * 24 <= n <= 32 when fewer than 35 % of those pairs exist (CRPSPMM_TEAM2R=0|1 forces, then up to 64 columns); and by 1 below 24
+ * columns.  Once a variant-0 product found the row-owner streams too large (past their 32-bit offsets), 7 is no longer chosen: 3
+ * under CRPSPMM_TEAM2R=1, the choice without it otherwise.  Other operands may fall back further (5 -> 3 -> 1).  Variants 4 and 6
+ * (the round-1 LDS team kernel, the narrow team kernel of round 3) were measured slower than what auto picks at every width and
+ * removed in round 4: asking for them returns -1. */
 int crp_csr_dev_resolved_variant(crp_csr_dev_p A, int n);
 /* the variant the last crp_spmm_csr_f64 / _f32 on this matrix launched (after every fallback), or 0 before the first */
 int crp_csr_dev_last_variant(crp_csr_dev_p A);
@@ -218,6 +219,14 @@ int crp_team2r_format_host(int nrow, const int *rowptr, const int *colidx, const
  * nrow ints).  Returns 0, or 1 when the matrix does not qualify (not square, two-source indices, too small):
  * perm is then the identity.  info (4 doubles, may be NULL): row groups, parts, mean |pos(col) - pos(row)| before, after. */
 int crp_locality_order_host(int nrow, int ncol, const int *rowptr, const int *colidx, int nparts, int *perm, double *info);
+/* Host-only: the kernel choice of crp_csr_dev_create and crp_spmm_csr_f64 / _f32 for this matrix, without a device (the CPU tests
+ * of csrc/dispatch.cpp).  For every width widths[i] the variant a product with `variant` launches (f32: the fp32 path) into
+ * resolved[i], for the operand shape 0 = B0 and C 16-byte aligned with ld = n, 1 = ld = n + 1, 2 = as 0 with a B1, 3 = as 0 with
+ * B0 only 8-byte aligned.  info (5 ints, may be NULL): auto variant, reordered (crp_csr_dev_reordered), the team kernel's
+ * first width, whether teams share columns, whether the R = 8 panels are mostly holes.  Reads the CRPSPMM_* knobs as the
+ * product does.  Returns 0, or -1 on bad arguments. */
+int crp_spmm_plan_host(int nrow, int ncol, const int *rowptr, const int *colidx, int nwidth, const int *widths, int variant, int f32,
+                       int shape, int *resolved, int *info);
 
 /* ---- the hot kernel --------------------------------------------------------
  * C[nrow x n] := A * B (alpha = 1, beta = 0; C is overwritten, never read),

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import FP64_TOL, GOLDEN, GOLDEN_NAMES, load_golden
+from test_dispatch import TABLE as DISPATCH_TABLE
 
 pytestmark = pytest.mark.gpu
 
@@ -1058,3 +1059,53 @@ def test_create_with_device_values(crp, orc, gpu):
     assert orc.rel_fro_err(ref[rows], Cd.cpu().numpy()) <= FP64_TOL
     assert lib.crp_csr_dev_create_dv(m, k, rp.ctypes.data_as(_IP), ci.ctypes.data_as(_IP), va.ctypes.data_as(_DP), None, None, C.byref(h)) == -1
     lib.crp_csr_dev_destroy(C.byref(h))
+
+
+@pytest.mark.parametrize("knob,name", sorted(DISPATCH_TABLE))
+def test_dispatch_matches_host_plan(crp, orc, gpu, monkeypatch, knob, name):
+    """What the device path launches (crp_csr_dev_last_variant; crp_csr_dev_resolved_variant for aligned operands) is what
+    crp_spmm_plan_host says, on every cell of tests/test_dispatch.py's table, and every product matches the oracle."""
+    import torch
+    from crp_spmm_amd import _lib, hip
+    from test_dispatch import SHAPES, TABLE, WIDTHS, matrix
+    lib = _lib.load()
+    for var in ("CRPSPMM_TEAM2R", "CRPSPMM_SPMM_VARIANT", "CRPSPMM_REORDER"):
+        monkeypatch.delenv(var, raising=False)
+    if knob:
+        monkeypatch.setenv(*knob.split("="))
+    rp, ci, va = matrix(name)
+    m = len(rp) - 1
+    cells = [(c.split()[0], int(c.split()[1]), shape) for c in TABLE[(knob, name)][1] for shape in SHAPES]
+    plan = {c: hip.spmm_plan_host(rp, ci, WIDTHS, c[1], c[0], c[2])[1] for c in cells}
+    A = hip.CsrDev(m, m, rp, ci, va)
+    for i, n in enumerate(WIDTHS):
+        B = np.random.default_rng(n).normal(size=(m, n))
+        ref_d = _t(orc.spmm_csr(rp, ci, va, B, fast=True), gpu)
+        for dtype, variant, shape in cells:
+            dt = torch.float64 if dtype == "f64" else torch.float32
+            es = 8 if dtype == "f64" else 4
+            Bd = _t(B, gpu).to(dt)
+            C_out = torch.empty((m, n + (shape == "ld+1")), dtype=dt, device=gpu)[:, :n]
+            B1 = torch.zeros((m, n), dtype=dt, device=gpu) if shape == "b1" else None
+            if shape == "ld+1":
+                B0 = torch.zeros((m, n + 1), dtype=dt, device=gpu)[:, :n]
+                B0.copy_(Bd)
+            elif shape == "misaligned":
+                buf = torch.zeros(m * n + 16 // es, dtype=dt, device=gpu)
+                B0 = buf[8 // es:8 // es + m * n].view(m, n)
+                B0.copy_(Bd)
+                assert B0.data_ptr() % 16 == 8
+            else:
+                B0 = Bd
+            if dtype == "f64":
+                hip.spmm_csr(A, B0, C_out, n=n, B1=B1, variant=variant)
+            else:
+                hip.spmm_csr_f32(A, B0, C_out, n=n, B1=B1, variant=variant)
+            torch.cuda.synchronize()
+            want = plan[(dtype, variant, shape)][i]
+            assert lib.crp_csr_dev_last_variant(A.handle) == want, (dtype, variant, shape, n)
+            if (dtype, variant, shape) == ("f64", 0, "aligned"):
+                assert lib.crp_csr_dev_resolved_variant(A.handle, n) == want, n
+            err = (torch.linalg.norm(C_out.double() - ref_d) / torch.linalg.norm(ref_d)).item()
+            assert err <= (FP64_TOL if dtype == "f64" else FP32_TOL), (dtype, variant, shape, n, err)
+    A.free()
