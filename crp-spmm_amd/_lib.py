@@ -165,6 +165,9 @@ SIGNATURES = {
     "crp_gather_rows_f64": (_I, [_I, _I, _I, _V, _V, _LL, _V, _LL, _V]),
     "crp_scatter_rows_f64": (_I, [_I, _I, _I, _V, _V, _LL, _V, _LL, _V]),
     "crp_transpose_f64": (_I, [_I, _I, _V, _LL, _V, _LL, _V]),
+    "crp_gather_rows_f32": (_I, [_I, _I, _I, _V, _V, _LL, _V, _LL, _V]),
+    "crp_scatter_rows_f32": (_I, [_I, _I, _I, _V, _V, _LL, _V, _LL, _V]),
+    "crp_transpose_f32": (_I, [_I, _I, _V, _LL, _V, _LL, _V]),
     # crp_comm.h
     "crp_comm_self": (C.POINTER(CrpComm), []),
     # crp_engine.h
@@ -176,6 +179,7 @@ SIGNATURES = {
     "crp_rp_spmm_free": (None, [C.POINTER(_V)]),
     "crp_rp_spmm_exec": (None, [_V, _I, _V, _I, _V, _I]),
     "crp_rp_spmm_exec_ex": (None, [_V, _I, _V, _LL, _V, _LL, _V]),
+    "crp_rp_spmm_exec_f32_ex": (None, [_V, _I, _V, _LL, _V, _LL, _V]),
     "crp_rp_spmm_print_stat": (None, [_V]),
     "crp_rp_spmm_clear_stat": (None, [_V]),
     "crp_rp_spmm_get_plan": (None, [_V, C.POINTER(RpPlanView)]),
@@ -200,8 +204,10 @@ SIGNATURES = {
     "crp_para2d_spmm_replicated_on_device": (_I, [_V]),
     "crp_para2d_spmm_value_uploads": (_I, [_V]),
     "crp_rp_spmm_set_variant": (None, [_V, _I]),
+    "crp_rp_spmm_set_variant_f32": (None, [_V, _I]),
     "crp_rp_spmm_kernel_info": (None, [_V, c_int_p, c_int_p, c_int_p]),
     "crp_rp_spmm_alg_bytes": (_LL, [_V]),
+    "crp_rp_spmm_alg_bytes_f32": (_LL, [_V]),
     "crp_rp_spmm_update_values": (None, [_V, c_dbl_p]),
     "crp_rp_spmm_nnz": (_LL, [_V]),
     "crp_rp_spmm_dev_colidx_host": (c_int_p, [_V]),
@@ -212,6 +218,7 @@ SIGNATURES = {
     "crp_para2d_spmm_free": (None, [C.POINTER(_V)]),
     "crp_para2d_spmm_exec": (None, [_V, _I, _V, _I, _V, _I]),
     "crp_para2d_spmm_exec_ex": (None, [_V, _I, _V, _LL, _V, _LL, _V]),
+    "crp_para2d_spmm_exec_f32_ex": (None, [_V, _I, _V, _LL, _V, _LL, _V]),
     "crp_para2d_spmm_print_stat": (None, [_V]),
     "crp_para2d_spmm_clear_stat": (None, [_V]),
     "crp_para2d_spmm_rp": (_V, [_V]),

@@ -1030,5 +1030,26 @@ int crp_transpose_f64(int nrow, int ncol, const double *src, long long lds, doub
     return (int) crp::transpose_f64(nrow, ncol, src, lds, dst, ldd, (hipStream_t) stream);
 }
 
+int crp_gather_rows_f32(int layout, int nidx, int n, const int *ridx, const float *src, long long lds,
+                        float *dst, long long ldd, void *stream)
+{
+    if (nidx < 0 || n < 0 || (layout != 0 && layout != 1)) return -1;
+    return (int) crp::gather_rows_f32(layout, nidx, n, ridx, src, lds, dst, ldd, (hipStream_t) stream);
+}
+
+int crp_scatter_rows_f32(int layout, int nidx, int n, const int *ridx, const float *src, long long lds,
+                         float *dst, long long ldd, void *stream)
+{
+    if (nidx < 0 || n < 0 || (layout != 0 && layout != 1)) return -1;
+    return (int) crp::scatter_rows_f32(layout, nidx, n, ridx, src, lds, dst, ldd, (hipStream_t) stream);
+}
+
+int crp_transpose_f32(int nrow, int ncol, const float *src, long long lds, float *dst, long long ldd,
+                      void *stream)
+{
+    if (nrow < 0 || ncol < 0) return -1;
+    return (int) crp::transpose_f32(nrow, ncol, src, lds, dst, ldd, (hipStream_t) stream);
+}
+
 }  // extern "C"
 

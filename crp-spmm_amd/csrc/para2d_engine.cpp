@@ -212,6 +212,13 @@ void crp_para2d_spmm_exec_ex(crp_para2d_spmm_p e, int BC_layout, const double *B
     crp_rp_spmm_exec_ex(e->rp, BC_layout, B, ldB, C, ldC, stream);
 }
 
+void crp_para2d_spmm_exec_f32_ex(crp_para2d_spmm_p e, int BC_layout, const float *B, long long ldB, float *C,
+                                 long long ldC, void *stream)
+{
+    if (e == NULL) return;
+    crp_rp_spmm_exec_f32_ex(e->rp, BC_layout, B, ldB, C, ldC, stream);
+}
+
 int crp_para2d_spmm_replicated_on_device(crp_para2d_spmm_p e) { return (e && e->replicated_on_device) ? 1 : 0; }
 int crp_para2d_spmm_value_uploads(crp_para2d_spmm_p e) { return e ? e->value_uploads : -1; }
 

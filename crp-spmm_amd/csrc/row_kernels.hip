@@ -140,6 +140,141 @@ hipError_t transpose_f64(int nrow, int ncol, const double *src, int64_t lds, dou
     return hipGetLastError();
 }
 
+// ---- fp32 row movement and transpose (the fp32 exec of the engines; the fp64 kernels above are left as they are)
+//
+// Row-major: a workgroup of 256 lanes takes 256 / TPR rows at a time, TPR lanes per row walk the row's chunks of VW
+// floats (VW = 4: 16-byte accesses).  TPR is the smallest power of two >= the chunks of a row (at most 256), so a row of
+// 1024 floats is one workgroup of 16-byte accesses, and a row of 24 floats is 8 lanes of a 32-row group: every lane
+// moves whole chunks, the row index is read once per row, and no lane divides.
+template <int VW, int TPR, bool GATHER>
+__global__ __launch_bounds__(256) void move_rows_rm_f32_kernel(
+    const int nidx, const int cpr /* chunks per row */, const int *__restrict__ ridx,
+    const float *__restrict__ src, const int64_t lds, float *__restrict__ dst, const int64_t ldd)
+{
+    typedef float fv __attribute__((ext_vector_type(VW)));
+    constexpr int RPB = 256 / TPR;   // rows per workgroup and step
+    const int lane = threadIdx.x % TPR;
+    for (int64_t i = (int64_t) blockIdx.x * RPB + threadIdx.x / TPR; i < nidx; i += (int64_t) gridDim.x * RPB)
+    {
+        const int64_t r = ridx[i];
+        const int64_t srow = GATHER ? r : i;
+        const int64_t drow = GATHER ? i : r;
+        const float *s = src + srow * lds;
+        float *d = dst + drow * ldd;
+        for (int c = lane; c < cpr; c += TPR)
+        {
+            if constexpr (VW == 1) d[c] = s[c];
+            else *reinterpret_cast<fv *>(d + (int64_t) c * VW) = *reinterpret_cast<const fv *>(s + (int64_t) c * VW);
+        }
+    }
+}
+
+// Column-major: element (r, j) at r + j*ld; consecutive lanes walk the index list.
+template <bool GATHER>
+__global__ __launch_bounds__(256) void move_rows_cm_f32_kernel(
+    const int64_t nidx, const int n, const int *__restrict__ ridx,
+    const float *__restrict__ src, const int64_t lds, float *__restrict__ dst, const int64_t ldd)
+{
+    const int64_t total = nidx * (int64_t) n;
+    for (int64_t t = (int64_t) blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t) gridDim.x * 256)
+    {
+        const int64_t j = t / nidx;
+        const int64_t i = t - j * nidx;
+        const int64_t r = ridx[i];
+        if (GATHER) dst[i + j * ldd] = src[r + j * lds];
+        else        dst[r + j * ldd] = src[i + j * lds];
+    }
+}
+
+template <int VW, int TPR, bool GATHER>
+static void launch_rm_f32(int nidx, int cpr, const int *ridx, const float *src, int64_t lds, float *dst, int64_t ldd,
+                          hipStream_t s)
+{
+    const int blocks = grid_for((int64_t) nidx * TPR);   // 256 / TPR rows per workgroup, capped like every launch here
+    hipLaunchKernelGGL((move_rows_rm_f32_kernel<VW, TPR, GATHER>), dim3(blocks), dim3(256), 0, s, nidx, cpr, ridx, src,
+                       lds, dst, ldd);
+}
+
+template <int VW, bool GATHER>
+static void move_rows_rm_f32(int nidx, int cpr, const int *ridx, const float *src, int64_t lds, float *dst, int64_t ldd,
+                             hipStream_t s)
+{
+    if (cpr <= 4)        launch_rm_f32<VW, 4, GATHER>(nidx, cpr, ridx, src, lds, dst, ldd, s);
+    else if (cpr <= 8)   launch_rm_f32<VW, 8, GATHER>(nidx, cpr, ridx, src, lds, dst, ldd, s);
+    else if (cpr <= 16)  launch_rm_f32<VW, 16, GATHER>(nidx, cpr, ridx, src, lds, dst, ldd, s);
+    else if (cpr <= 32)  launch_rm_f32<VW, 32, GATHER>(nidx, cpr, ridx, src, lds, dst, ldd, s);
+    else if (cpr <= 64)  launch_rm_f32<VW, 64, GATHER>(nidx, cpr, ridx, src, lds, dst, ldd, s);
+    else if (cpr <= 128) launch_rm_f32<VW, 128, GATHER>(nidx, cpr, ridx, src, lds, dst, ldd, s);
+    else                 launch_rm_f32<VW, 256, GATHER>(nidx, cpr, ridx, src, lds, dst, ldd, s);
+}
+
+template <bool GATHER>
+static hipError_t move_rows_f32(int layout, int nidx, int n, const int *ridx, const float *src, int64_t lds,
+                                float *dst, int64_t ldd, hipStream_t s)
+{
+    if (nidx <= 0 || n <= 0) return hipSuccess;
+    if (layout == 0)
+    {
+        const uintptr_t a = (uintptr_t) src | (uintptr_t) dst;
+        if (n % 4 == 0 && lds % 4 == 0 && ldd % 4 == 0 && a % 16 == 0)
+            move_rows_rm_f32<4, GATHER>(nidx, n / 4, ridx, src, lds, dst, ldd, s);
+        else if (n % 2 == 0 && lds % 2 == 0 && ldd % 2 == 0 && a % 8 == 0)
+            move_rows_rm_f32<2, GATHER>(nidx, n / 2, ridx, src, lds, dst, ldd, s);
+        else
+            move_rows_rm_f32<1, GATHER>(nidx, n, ridx, src, lds, dst, ldd, s);
+    }
+    else
+    {
+        hipLaunchKernelGGL((move_rows_cm_f32_kernel<GATHER>), dim3(grid_for((int64_t) nidx * n)), dim3(256), 0, s,
+                           (int64_t) nidx, n, ridx, src, lds, dst, ldd);
+    }
+    return hipGetLastError();
+}
+
+hipError_t gather_rows_f32(int layout, int nidx, int n, const int *ridx, const float *src, int64_t lds,
+                           float *dst, int64_t ldd, hipStream_t s)
+{
+    return move_rows_f32<true>(layout, nidx, n, ridx, src, lds, dst, ldd, s);
+}
+
+hipError_t scatter_rows_f32(int layout, int nidx, int n, const int *ridx, const float *src, int64_t lds,
+                            float *dst, int64_t ldd, hipStream_t s)
+{
+    return move_rows_f32<false>(layout, nidx, n, ridx, src, lds, dst, ldd, s);
+}
+
+// 32x32 tile transpose through LDS; the 33-float row pitch puts the 32 elements of a tile column on 32 different banks.
+// dst[c][r] = src[r][c].
+__global__ __launch_bounds__(256) void transpose_f32_kernel(
+    const int nrow, const int ncol, const float *__restrict__ src, const int64_t lds,
+    float *__restrict__ dst, const int64_t ldd)
+{
+    __shared__ float tile[32][33];
+    const int tx = threadIdx.x % 32, ty = threadIdx.x / 32;   // 32 x 8
+    const int64_t r0 = (int64_t) blockIdx.x * 32, c0 = (int64_t) blockIdx.y * 32;   // rows on grid.x (2^31 limit)
+#pragma unroll
+    for (int k = 0; k < 32; k += 8)
+    {
+        const int64_t r = r0 + ty + k, c = c0 + tx;
+        if (r < nrow && c < ncol) tile[ty + k][tx] = src[r * lds + c];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 32; k += 8)
+    {
+        const int64_t c = c0 + ty + k, r = r0 + tx;
+        if (r < nrow && c < ncol) dst[c * ldd + r] = tile[tx][ty + k];
+    }
+}
+
+hipError_t transpose_f32(int nrow, int ncol, const float *src, int64_t lds, float *dst, int64_t ldd, hipStream_t s)
+{
+    if (nrow <= 0 || ncol <= 0) return hipSuccess;
+    dim3 grid((nrow + 31) / 32, (ncol + 31) / 32);
+    hipLaunchKernelGGL(transpose_f32_kernel, grid, dim3(256), 0, s, nrow, ncol, src, lds, dst, ldd);
+    return hipGetLastError();
+}
+
 // dst[map[i]] = src[i]: refresh the values of a derived sparse format from new CSR values
 __global__ __launch_bounds__(256) void scatter_vals_kernel(const int64_t n, const uint32_t *__restrict__ map,
                                                            const double *__restrict__ src, double *__restrict__ dst)

@@ -41,6 +41,7 @@ struct crp_rp_spmm
     // ---- device side
     bool plan_only = false;
     int  timing = 1, variant = 0;
+    int  variant_f32 = 0;                        // the fp32 exec's kernel variant (crp_spmm_csr_f32: 0, 1, 5)
     int  loc_B_nrow = 0;
     long long n_send_rows = 0, n_recv_rows = 0, n_needed_rows = 0;
     std::vector<int> dev_colidx_host;
@@ -53,6 +54,10 @@ struct crp_rp_spmm
     void *xstream = nullptr, *ev_packed = nullptr, *ev_landed = nullptr;
     int    *sridxs_dev = nullptr;
     double *sendbuf_dev = nullptr, *recvbuf_dev = nullptr;
+    // fp32 exchange, set up by the first fp32 exec: rows of round_up(glb_n, 4) floats, counts in 8-byte words
+    bool   x32_ready = false;
+    float *sendbuf32_dev = nullptr, *recvbuf32_dev = nullptr;
+    std::vector<long long> x32_scnts, x32_sdispls, x32_rcnts, x32_rdispls;
     void   *stream = nullptr;
     // staging (host-pointer API) and column-major temporaries, grown on demand
     double *B_stage = nullptr, *C_stage = nullptr, *B_rm = nullptr, *C_rm = nullptr;
@@ -345,6 +350,8 @@ void crp_rp_spmm_free(crp_rp_spmm_p *rp_spmm)
         crp_dev_free(e->sridxs_dev);
         crp_dev_free(e->sendbuf_dev);
         crp_dev_free(e->recvbuf_dev);
+        crp_dev_free(e->sendbuf32_dev);
+        crp_dev_free(e->recvbuf32_dev);
         if (e->ev_exec) crp_event_destroy(e->ev_exec);
         crp_dev_free(e->B_stage);
         crp_dev_free(e->C_stage);
@@ -356,8 +363,97 @@ void crp_rp_spmm_free(crp_rp_spmm_p *rp_spmm)
     *rp_spmm = NULL;
 }
 
-void crp_rp_spmm_exec_ex(crp_rp_spmm_p e, int BC_layout, const double *B, long long ldB, double *C,
-                         long long ldC, void *stream_)
+}  // extern "C"
+
+// ---- what the fp64 and the fp32 exec do differently: kernels, variant, exchange buffers -----------------------------
+// The fp32 exec packs rows of ld32 = round_up(n, 4) floats (16-byte rows for the packing kernel and for the team kernel's
+// second B source) and carries them through the communicator's fp64 all-to-all as opaque 8-byte words: no back end does
+// arithmetic on the payload, so crp_comm_t stays as it is.
+static long long ld32_of(int n) { return ((long long) n + 3) / 4 * 4; }
+
+template <class T> static T *grow_as(double **buf, size_t *cur, size_t need_elems)
+{
+    // staging buffers and temporaries are raw device bytes shared by both dtypes (sizes kept in doubles)
+    grow(buf, cur, (need_elems * sizeof(T) + sizeof(double) - 1) / sizeof(double));
+    return (T *) *buf;
+}
+
+struct Xchg
+{
+    void *send, *recv;                            // packed rows of ld elements
+    long long ld;
+    const long long *sc, *sd, *rc, *rd;           // counts / displacements in 8-byte words, as alltoallv_dev_f64 takes them
+};
+
+static Xchg exchange_of(crp_rp_spmm *e, const double *)
+{
+    return Xchg{e->sendbuf_dev, e->recvbuf_dev, (long long) e->glb_n, e->rB_scnts.data(), e->rB_sdispls.data(),
+                e->rB_rcnts.data(), e->rB_rdispls.data()};
+}
+
+// first fp32 exec: word counts (rows * ld32 / 2) and the fp32 exchange buffers
+static Xchg exchange_of(crp_rp_spmm *e, const float *)
+{
+    const long long ld = ld32_of(e->glb_n);
+    if (!e->x32_ready)
+    {
+        const long long n = e->glb_n;     // rB_* hold rows * glb_n elements
+        auto words = [&](const std::vector<long long> &v, std::vector<long long> &out) {
+            out.resize(v.size());
+            for (size_t q = 0; q < v.size(); q++) out[q] = n > 0 ? v[q] / n * ld / 2 : 0;
+        };
+        words(e->rB_scnts, e->x32_scnts);
+        words(e->rB_sdispls, e->x32_sdispls);
+        words(e->rB_rcnts, e->x32_rcnts);
+        words(e->rB_rdispls, e->x32_rdispls);
+        // the pad columns are zeroed here and never written again: no uninitialised byte crosses a link
+        auto alloc = [&](long long rows, float **buf) {
+            if (rows <= 0 || ld <= 0) return;
+            const size_t bytes = sizeof(float) * (size_t) rows * (size_t) ld;
+            void *p = NULL;
+            HIP_OK(crp_dev_malloc(&p, bytes));
+            *buf = (float *) p;
+            HIP_OK(crp_dev_memset(p, 0, bytes, NULL));
+        };
+        alloc(e->n_send_rows, &e->sendbuf32_dev);
+        alloc(e->n_recv_rows, &e->recvbuf32_dev);
+        HIP_OK(crp_stream_sync(NULL));
+        e->x32_ready = true;
+    }
+    return Xchg{e->sendbuf32_dev, e->recvbuf32_dev, ld, e->x32_scnts.data(), e->x32_sdispls.data(), e->x32_rcnts.data(),
+                e->x32_rdispls.data()};
+}
+
+static int gather(int nidx, int n, const int *ridx, const double *src, long long lds, double *dst, long long ldd, void *s)
+{
+    return crp_gather_rows_f64(0, nidx, n, ridx, src, lds, dst, ldd, s);
+}
+static int gather(int nidx, int n, const int *ridx, const float *src, long long lds, float *dst, long long ldd, void *s)
+{
+    return crp_gather_rows_f32(0, nidx, n, ridx, src, lds, dst, ldd, s);
+}
+static int transpose(int nrow, int ncol, const double *src, long long lds, double *dst, long long ldd, void *s)
+{
+    return crp_transpose_f64(nrow, ncol, src, lds, dst, ldd, s);
+}
+static int transpose(int nrow, int ncol, const float *src, long long lds, float *dst, long long ldd, void *s)
+{
+    return crp_transpose_f32(nrow, ncol, src, lds, dst, ldd, s);
+}
+static int spmm(crp_rp_spmm *e, crp_csr_dev_p A, int n, const double *B0, long long ldB0, const double *B1, long long ldB1,
+                double *C, long long ldC, void *s)
+{
+    return crp_spmm_csr_f64(A, 0, n, B0, ldB0, B1, ldB1, C, ldC, e->variant, s);
+}
+static int spmm(crp_rp_spmm *e, crp_csr_dev_p A, int n, const float *B0, long long ldB0, const float *B1, long long ldB1,
+                float *C, long long ldC, void *s)
+{
+    return crp_spmm_csr_f32(A, n, B0, ldB0, B1, ldB1, C, ldC, e->variant_f32, s);
+}
+
+// C := A * B on this rank, one dtype (crp_rp_spmm_exec_ex / crp_rp_spmm_exec_f32_ex)
+template <class T>
+static void exec_impl(crp_rp_spmm *e, int BC_layout, const T *B, long long ldB, T *C, long long ldC, void *stream_)
 {
     if (e == NULL) return;
     ASSERT_PRINTF(!e->plan_only, "rp_spmm_exec on a plan-only engine (no device state)\n");
@@ -385,48 +481,47 @@ void crp_rp_spmm_exec_ex(crp_rp_spmm_p e, int BC_layout, const double *B, long l
     }
 
     // ---- bring B to a device-resident row-major view (Bd, ldBd)
-    const double *Bd = B;
+    const Xchg x = exchange_of(e, B);
+    const T *Bd = B;
     long long ldBd = ldB;
     if (!B_on_dev && kb > 0 && n > 0)
     {
         // host operand: stage the whole local block (ld preserved)
         const size_t elems = (BC_layout == 0) ? (size_t) kb * (size_t) ldB : (size_t) n * (size_t) ldB;
-        grow(&e->B_stage, &e->B_stage_sz, elems);
+        T *stage = grow_as<T>(&e->B_stage, &e->B_stage_sz, elems);
         const size_t used = (BC_layout == 0) ? ((size_t) (kb - 1) * (size_t) ldB + (size_t) n)
                                              : ((size_t) (n - 1) * (size_t) ldB + (size_t) kb);
         // one copy straight from the caller's pageable memory: the runtime stages it through its own pinned buffers at
         // PCIe rate (measured: 16 ms per exec for B in + C out of the pwtk-size operands; an engine-owned pinned mirror
         // with a memcpy in front of the DMA took 46 ms, pipelined through two pinned chunks with threaded memcpy 35 ms)
-        HIP_OK(crp_dev_memcpy(e->B_stage, B, used * sizeof(double), 0, s));
-        Bd = e->B_stage;
+        HIP_OK(crp_dev_memcpy(stage, B, used * sizeof(T), 0, s));
+        Bd = stage;
     }
     if (BC_layout == 1 && kb > 0 && n > 0)
     {
-        grow(&e->B_rm, &e->B_rm_sz, (size_t) kb * (size_t) n);
+        T *rm = grow_as<T>(&e->B_rm, &e->B_rm_sz, (size_t) kb * (size_t) n);
         // column-major kb x n (ld ldB) == row-major n x kb; transpose to row-major kb x n
-        HIP_OK(crp_transpose_f64(n, kb, Bd, ldB, e->B_rm, n, s));
-        Bd = e->B_rm;
+        HIP_OK(transpose(n, kb, Bd, ldB, rm, n, s));
+        Bd = rm;
         ldBd = n;
     }
-    double *Cd = C;
+    T *Cd = C;
     long long ldCd = ldC;
     if (BC_layout == 1)
     {
-        grow(&e->C_rm, &e->C_rm_sz, (size_t) m * (size_t) n);
-        Cd = e->C_rm;
+        Cd = grow_as<T>(&e->C_rm, &e->C_rm_sz, (size_t) m * (size_t) n);
         ldCd = n;
     }
     else if (!C_on_dev && m > 0 && n > 0)
     {
-        grow(&e->C_stage, &e->C_stage_sz, (size_t) m * (size_t) ldC);
-        Cd = e->C_stage;
+        Cd = grow_as<T>(&e->C_stage, &e->C_stage_sz, (size_t) m * (size_t) ldC);
     }
 
     // ---- 1. pack the rows other ranks asked for (reference :232-262)
     if (timing) { HIP_OK(crp_stream_sync(s)); }
     t0 = get_wtime_sec();
     if (e->n_send_rows > 0 && n > 0)
-        HIP_OK(crp_gather_rows_f64(0, (int) e->n_send_rows, n, e->sridxs_dev, Bd, ldBd, e->sendbuf_dev, n, s));
+        HIP_OK(gather((int) e->n_send_rows, n, e->sridxs_dev, Bd, ldBd, (T *) x.send, x.ld, s));
     if (timing)
     {
         HIP_OK(crp_stream_sync(s));
@@ -444,25 +539,23 @@ void crp_rp_spmm_exec_ex(crp_rp_spmm_p e, int BC_layout, const double *B, long l
         // communicator is polled until the group is on the stream) -- with the exchange first, the whole interior product
         // (0.06 - 0.2 ms per GPU at pwtk size) could have passed before its launch was even issued.
         HIP_OK(crp_event_record(e->ev_packed, s));
-        HIP_OK(crp_spmm_csr_f64(e->A_int, 0, n, Bd, ldBd, e->recvbuf_dev, n, Cd, ldCd, e->variant, s));
+        HIP_OK(spmm(e, e->A_int, n, Bd, ldBd, (const T *) x.recv, x.ld, Cd, ldCd, s));
         HIP_OK(crp_stream_wait_event(e->xstream, e->ev_packed));
         {
             const double tx0 = get_wtime_sec();
-            e->comm->alltoallv_dev_f64(e->comm->ctx, e->sendbuf_dev, e->rB_scnts.data(), e->rB_sdispls.data(),
-                                       e->recvbuf_dev, e->rB_rcnts.data(), e->rB_rdispls.data(), e->xstream);
+            e->comm->alltoallv_dev_f64(e->comm->ctx, (const double *) x.send, x.sc, x.sd, (double *) x.recv, x.rc, x.rd, e->xstream);
             e->t_a2a_host += get_wtime_sec() - tx0;
         }
         HIP_OK(crp_event_record(e->ev_landed, e->xstream));
         HIP_OK(crp_stream_wait_event(s, e->ev_landed));
-        HIP_OK(crp_spmm_csr_f64(e->A_bnd, 0, n, Bd, ldBd, e->recvbuf_dev, n, Cd, ldCd, e->variant, s));
+        HIP_OK(spmm(e, e->A_bnd, n, Bd, ldBd, (const T *) x.recv, x.ld, Cd, ldCd, s));
     }
     else
     {
         if (e->nproc > 1)
         {
             const double tx0 = get_wtime_sec();
-            e->comm->alltoallv_dev_f64(e->comm->ctx, e->sendbuf_dev, e->rB_scnts.data(), e->rB_sdispls.data(),
-                                       e->recvbuf_dev, e->rB_rcnts.data(), e->rB_rdispls.data(), s);
+            e->comm->alltoallv_dev_f64(e->comm->ctx, (const double *) x.send, x.sc, x.sd, (double *) x.recv, x.rc, x.rd, s);
             e->t_a2a_host += get_wtime_sec() - tx0;
         }
         if (timing)
@@ -476,20 +569,16 @@ void crp_rp_spmm_exec_ex(crp_rp_spmm_p e, int BC_layout, const double *B, long l
         // ---- 3. local SpMM (reference :388-408)
         if (split)
         {
-            HIP_OK(crp_spmm_csr_f64(e->A_int, 0, n, Bd, ldBd, e->recvbuf_dev, n, Cd, ldCd, e->variant, s));
-            HIP_OK(crp_spmm_csr_f64(e->A_bnd, 0, n, Bd, ldBd, e->recvbuf_dev, n, Cd, ldCd, e->variant, s));
+            HIP_OK(spmm(e, e->A_int, n, Bd, ldBd, (const T *) x.recv, x.ld, Cd, ldCd, s));
+            HIP_OK(spmm(e, e->A_bnd, n, Bd, ldBd, (const T *) x.recv, x.ld, Cd, ldCd, s));
         }
-        else HIP_OK(crp_spmm_csr_f64(e->A_dev, 0, n, Bd, ldBd, e->recvbuf_dev, n, Cd, ldCd, e->variant, s));
+        else HIP_OK(spmm(e, e->A_dev, n, Bd, ldBd, (const T *) x.recv, x.ld, Cd, ldCd, s));
     }
     if (BC_layout == 1 && m > 0 && n > 0)
     {
-        double *Ccm = C;
-        if (!C_on_dev)
-        {
-            grow(&e->C_stage, &e->C_stage_sz, (size_t) n * (size_t) ldC);
-            Ccm = e->C_stage;
-        }
-        HIP_OK(crp_transpose_f64(m, n, Cd, n, Ccm, ldC, s));   // row-major n x m (ld ldC) == column-major m x n
+        T *Ccm = C;
+        if (!C_on_dev) Ccm = grow_as<T>(&e->C_stage, &e->C_stage_sz, (size_t) n * (size_t) ldC);
+        HIP_OK(transpose(m, n, Cd, n, Ccm, ldC, s));   // row-major n x m (ld ldC) == column-major m x n
         Cd = Ccm;
     }
     if (timing)
@@ -507,7 +596,7 @@ void crp_rp_spmm_exec_ex(crp_rp_spmm_p e, int BC_layout, const double *B, long l
         // between rows (columns) is never written
         const size_t w = (BC_layout == 0) ? (size_t) n : (size_t) m, h = (BC_layout == 0) ? (size_t) m : (size_t) n;
         (void) used;
-        HIP_OK(crp_dev_memcpy2d(C, (size_t) ldC * sizeof(double), Cd, (size_t) ldC * sizeof(double), w * sizeof(double), h, 1, s));
+        HIP_OK(crp_dev_memcpy2d(C, (size_t) ldC * sizeof(T), Cd, (size_t) ldC * sizeof(T), w * sizeof(T), h, 1, s));
         HIP_OK(crp_stream_sync(s));
     }
     else if (!B_on_dev || timing)
@@ -523,6 +612,20 @@ void crp_rp_spmm_exec_ex(crp_rp_spmm_p e, int BC_layout, const double *B, long l
     }
     e->t_exec += get_wtime_sec() - t_begin;
     e->n_exec++;
+}
+
+extern "C" {
+
+void crp_rp_spmm_exec_ex(crp_rp_spmm_p e, int BC_layout, const double *B, long long ldB, double *C,
+                         long long ldC, void *stream_)
+{
+    exec_impl<double>(e, BC_layout, B, ldB, C, ldC, stream_);
+}
+
+void crp_rp_spmm_exec_f32_ex(crp_rp_spmm_p e, int BC_layout, const float *B, long long ldB, float *C, long long ldC,
+                             void *stream_)
+{
+    exec_impl<float>(e, BC_layout, B, ldB, C, ldC, stream_);
 }
 
 void crp_rp_spmm_exec(crp_rp_spmm_p e, int BC_layout, const double *B, int ldB, double *C, int ldC)
@@ -647,6 +750,7 @@ void crp_rp_spmm_overlap_rows(crp_rp_spmm_p e, int *n_interior, int *n_boundary)
 
 void crp_rp_spmm_set_timing(crp_rp_spmm_p e, int timing) { if (e) e->timing = timing ? 1 : 0; }
 void crp_rp_spmm_set_variant(crp_rp_spmm_p e, int variant) { if (e) e->variant = variant; }
+void crp_rp_spmm_set_variant_f32(crp_rp_spmm_p e, int variant) { if (e) e->variant_f32 = variant; }
 
 long long crp_rp_spmm_nnz(crp_rp_spmm_p e) { return e ? (long long) e->A_val.size() : -1; }
 
@@ -656,6 +760,14 @@ long long crp_rp_spmm_alg_bytes(crp_rp_spmm_p e)
     const long long nnz = (long long) e->A_val.size();
     return 12LL * nnz + 4LL * ((long long) e->A_nrow + 1) + 8LL * e->glb_n * e->n_needed_rows +
            8LL * e->glb_n * (long long) e->A_nrow;
+}
+
+long long crp_rp_spmm_alg_bytes_f32(crp_rp_spmm_p e)
+{
+    if (e == NULL) return -1;
+    const long long nnz = (long long) e->A_val.size();
+    return 8LL * nnz + 4LL * ((long long) e->A_nrow + 1) + 4LL * e->glb_n * e->n_needed_rows +
+           4LL * e->glb_n * (long long) e->A_nrow;
 }
 
 // what the local kernel is for this engine's width: variant the auto choice resolves to (of the main device

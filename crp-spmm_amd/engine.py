@@ -30,21 +30,45 @@ def _dp(a):
     return a.ctypes.data_as(L.c_dbl_p)
 
 
-def _ptr_ld(x, layout):
-    """(address, leading dimension, keepalive) of a 2-D operand."""
+def _dtype_of(x):
+    """"f64" / "f32" for a 2-D float64 / float32 torch tensor or numpy array; TypeError for anything else."""
     try:
         import torch
         if isinstance(x, torch.Tensor):
-            if x.dtype != torch.float64 or x.dim() != 2:
-                raise TypeError("B and C must be 2-D float64")
+            if x.dim() == 2 and x.dtype in (torch.float64, torch.float32):
+                return "f64" if x.dtype == torch.float64 else "f32"
+            raise TypeError("B and C must be 2-D float64 or float32, got %s of %d dimensions" % (x.dtype, x.dim()))
+    except ImportError:
+        pass
+    if isinstance(x, np.ndarray) and x.ndim == 2 and x.dtype in (np.float64, np.float32):
+        return "f64" if x.dtype == np.float64 else "f32"
+    raise TypeError("B and C must be 2-D float64 or float32 torch tensors or numpy arrays")
+
+
+def _operands_dtype(B, C_out):
+    """The dtype B and C share ("f64" or "f32"); TypeError when they differ or are neither (before any C call)."""
+    db, dc = _dtype_of(B), _dtype_of(C_out)
+    if db != dc:
+        raise TypeError("B and C must have the same dtype (B is %s, C is %s)" % (db, dc))
+    return db
+
+
+def _ptr_ld(x, layout, f32=False):
+    """(address, leading dimension, keepalive) of a 2-D float64 (f32: float32) operand."""
+    name, isz = ("float32", 4) if f32 else ("float64", 8)
+    try:
+        import torch
+        if isinstance(x, torch.Tensor):
+            if x.dtype != (torch.float32 if f32 else torch.float64) or x.dim() != 2:
+                raise TypeError("B and C must be 2-D %s" % name)
             if x.stride(1) != 1:
                 raise ValueError("operand must be contiguous along its fast dimension")
             return x.data_ptr(), x.stride(0), x
     except ImportError:
         pass
-    if not isinstance(x, np.ndarray) or x.dtype != np.float64 or x.ndim != 2 or x.strides[1] != 8:
-        raise TypeError("B and C must be 2-D float64 torch tensors or numpy arrays, contiguous along the fast dimension")
-    return x.ctypes.data, x.strides[0] // 8, x
+    if not isinstance(x, np.ndarray) or x.dtype != np.dtype(name) or x.ndim != 2 or x.strides[1] != isz:
+        raise TypeError("B and C must be 2-D %s torch tensors or numpy arrays, contiguous along the fast dimension" % name)
+    return x.ctypes.data, x.strides[0] // isz, x
 
 
 def _current_stream(x):
@@ -90,9 +114,11 @@ class RpSpmm:
 
     def exec(self, BC_layout, B, C_out, stream=None):
         """rp_spmm_exec (src/rowpara_spmm.h:69-81); ldB / ldC come from the strides.
-        For layout 1 pass the operands as (n, ld) arrays holding the column-major data."""
-        bp, ldb, _kb = _ptr_ld(B, BC_layout)
-        cp, ldc, _kc = _ptr_ld(C_out, BC_layout)
+        For layout 1 pass the operands as (n, ld) arrays holding the column-major data.
+        float64 operands run the fp64 exec, float32 operands the fp32 exec (crp_rp_spmm_exec_f32_ex)."""
+        f32 = _operands_dtype(B, C_out) == "f32"
+        bp, ldb, _kb = _ptr_ld(B, BC_layout, f32)
+        cp, ldc, _kc = _ptr_ld(C_out, BC_layout, f32)
         # the kernels index the operands by the plan's sizes: a wrong shape would be an out-of-bounds device access
         kb = getattr(self, "loc_B_nrow", None)
         for name, x, rows in (("B", B, kb), ("C", C_out, self.A_nrow)):
@@ -105,7 +131,8 @@ class RpSpmm:
                 raise ValueError("%s has shape %s, the engine needs %s (layout %d)" % (name, got, want, BC_layout))
         if stream is None:
             stream = _current_stream(C_out)
-        self._lib.crp_rp_spmm_exec_ex(self.handle, BC_layout, bp, ldb, cp, ldc, stream)
+        fn = self._lib.crp_rp_spmm_exec_f32_ex if f32 else self._lib.crp_rp_spmm_exec_ex
+        fn(self.handle, BC_layout, bp, ldb, cp, ldc, stream)
 
     def print_stat(self):
         self._lib.crp_rp_spmm_print_stat(self.handle)
@@ -126,6 +153,12 @@ class RpSpmm:
     def set_variant(self, variant):
         self._lib.crp_rp_spmm_set_variant(self.handle, int(variant))
 
+    def set_variant_f32(self, variant):
+        """Kernel variant of the fp32 exec: 0 auto (default), 1 row-group, 5 team kernel."""
+        if int(variant) not in (0, 1, 5):
+            raise ValueError("fp32 variant must be 0, 1 or 5, got %r" % (variant,))
+        self._lib.crp_rp_spmm_set_variant_f32(self.handle, int(variant))
+
     def overlap_rows(self):
         """(interior rows, boundary rows) of the exchange / compute overlap split; (0, 0) when off."""
         a, b = C.c_int(), C.c_int()
@@ -138,6 +171,9 @@ class RpSpmm:
 
     def alg_bytes(self):
         return int(self._lib.crp_rp_spmm_alg_bytes(self.handle))
+
+    def alg_bytes_f32(self):
+        return int(self._lib.crp_rp_spmm_alg_bytes_f32(self.handle))
 
     def nnz(self):
         return int(self._lib.crp_rp_spmm_nnz(self.handle))
@@ -204,11 +240,14 @@ class Para2dSpmm:
         self.rp = RpSpmm._wrap(lib.crp_para2d_spmm_rp(self.handle), comm, lib)
 
     def exec(self, BC_layout, B, C_out, stream=None):
-        bp, ldb, _kb = _ptr_ld(B, BC_layout)
-        cp, ldc, _kc = _ptr_ld(C_out, BC_layout)
+        """float64 operands run the fp64 exec, float32 operands the fp32 exec (crp_para2d_spmm_exec_f32_ex)."""
+        f32 = _operands_dtype(B, C_out) == "f32"
+        bp, ldb, _kb = _ptr_ld(B, BC_layout, f32)
+        cp, ldc, _kc = _ptr_ld(C_out, BC_layout, f32)
         if stream is None:
             stream = _current_stream(C_out)
-        self._lib.crp_para2d_spmm_exec_ex(self.handle, BC_layout, bp, ldb, cp, ldc, stream)
+        fn = self._lib.crp_para2d_spmm_exec_f32_ex if f32 else self._lib.crp_para2d_spmm_exec_ex
+        fn(self.handle, BC_layout, bp, ldb, cp, ldc, stream)
 
     def print_stat(self):
         self._lib.crp_para2d_spmm_print_stat(self.handle)

@@ -87,6 +87,31 @@ def transpose(src, dst, stream=None):
                                   dst.stride(0), _stream(dst) if stream is None else stream), "crp_transpose_f64")
 
 
+def gather_rows_f32(ridx, src, dst, layout=0, stream=None):
+    """crp_gather_rows_f32: dst[i] = src[ridx[i]] (rows; layout 1: columns of (n, ld) tensors) on float32 cuda tensors."""
+    _move_rows_f32(ridx, src, dst, layout, False, stream)
+
+
+def scatter_rows_f32(ridx, src, dst, layout=0, stream=None):
+    """crp_scatter_rows_f32: dst[ridx[i]] = src[i]."""
+    _move_rows_f32(ridx, src, dst, layout, True, stream)
+
+
+def _move_rows_f32(ridx, src, dst, layout, scatter, stream):
+    lib = L.load()
+    fn = lib.crp_scatter_rows_f32 if scatter else lib.crp_gather_rows_f32
+    n = (src if scatter else dst).shape[1 if layout == 0 else 0]
+    L.check(fn(layout, ridx.numel(), n, ridx.data_ptr(), src.data_ptr(), src.stride(0), dst.data_ptr(),
+               dst.stride(0), _stream(dst) if stream is None else stream), "crp_gather/scatter_rows_f32")
+
+
+def transpose_f32(src, dst, stream=None):
+    """crp_transpose_f32: dst[c][r] = src[r][c] on float32 cuda tensors."""
+    lib = L.load()
+    L.check(lib.crp_transpose_f32(src.shape[0], src.shape[1], src.data_ptr(), src.stride(0), dst.data_ptr(),
+                                  dst.stride(0), _stream(dst) if stream is None else stream), "crp_transpose_f32")
+
+
 def device_info(dev=0):
     lib = L.load()
     name = C.create_string_buffer(256)

@@ -81,6 +81,13 @@ void crp_rp_spmm_exec(crp_rp_spmm_p rp_spmm, int BC_layout, const double *B, int
  * With device pointers and timing off nothing synchronises. */
 void crp_rp_spmm_exec_ex(crp_rp_spmm_p rp_spmm, int BC_layout, const double *B, long long ldB,
                          double *C, long long ldC, void *stream);
+/* The fp32 exec: B and C in fp32, fp32 FMAs (crp_spmm_csr_f32) on A's fp32 copies, which follow
+ * crp_rp_spmm_update_values.  Same operands, staging, streams, overlap split, statistics and completion rules as
+ * crp_rp_spmm_exec_ex; plan, init and A's fp64 values are shared with the fp64 exec, and both may be called on one
+ * engine.  Exchange: rows of ld32 = round_up(glb_n, 4) floats (pad columns zero) carried through the communicator's
+ * alltoallv_dev_f64 as opaque 8-byte words, counts rows * ld32 / 2. */
+void crp_rp_spmm_exec_f32_ex(crp_rp_spmm_p rp_spmm, int BC_layout, const float *B, long long ldB,
+                             float *C, long long ldC, void *stream);
 void crp_rp_spmm_print_stat(crp_rp_spmm_p rp_spmm);
 void crp_rp_spmm_clear_stat(crp_rp_spmm_p rp_spmm);
 /* rp_spmm_init for a caller that ALSO holds the values in device memory, in the order of A_val (A_val_dev: the panel a
@@ -108,9 +115,14 @@ void crp_rp_spmm_overlap_rows(crp_rp_spmm_p rp_spmm, int *n_interior, int *n_bou
 void crp_rp_spmm_set_timing(crp_rp_spmm_p rp_spmm, int timing);
 /* kernel variant for the local SpMM (crpspmm_hip.h: crp_spmm_variant_name). */
 void crp_rp_spmm_set_variant(crp_rp_spmm_p rp_spmm, int variant);
+/* kernel variant of the fp32 exec (crp_spmm_csr_f32): 0 auto (default), 1 row-group, 5 team kernel.  The fp32 exec
+ * never reads the fp64 variant, nor the fp64 exec this one. */
+void crp_rp_spmm_set_variant_f32(crp_rp_spmm_p rp_spmm, int variant);
 /* bytes of HBM the local kernel must touch per exec (SURVEY 8d bytes_alg for
  * this rank): 12*nnz + 4*(A_nrow+1) + 8*n*(distinct B rows) + 8*n*A_nrow. */
 long long crp_rp_spmm_alg_bytes(crp_rp_spmm_p rp_spmm);
+/* the same for the fp32 exec (4-byte values): 8*nnz + 4*(A_nrow+1) + 4*n*(distinct B rows) + 4*n*A_nrow. */
+long long crp_rp_spmm_alg_bytes_f32(crp_rp_spmm_p rp_spmm);
 long long crp_rp_spmm_nnz(crp_rp_spmm_p rp_spmm);
 /* What the local SpMM of this engine is (for reports): the kernel variant in use (crp_spmm_variant_name; the auto
  * choice resolved for the engine's glb_n), 1 if its formats hold the rows in the locality order of
@@ -131,6 +143,9 @@ void crp_para2d_spmm_exec(crp_para2d_spmm_p para2d_spmm, int BC_layout, const do
                           double *C, int ldC);
 void crp_para2d_spmm_exec_ex(crp_para2d_spmm_p para2d_spmm, int BC_layout, const double *B,
                              long long ldB, double *C, long long ldC, void *stream);
+/* fp32 exec of the grid column's row engine (crp_rp_spmm_exec_f32_ex). */
+void crp_para2d_spmm_exec_f32_ex(crp_para2d_spmm_p para2d_spmm, int BC_layout, const float *B,
+                                 long long ldB, float *C, long long ldC, void *stream);
 void crp_para2d_spmm_print_stat(crp_para2d_spmm_p para2d_spmm);
 void crp_para2d_spmm_clear_stat(crp_para2d_spmm_p para2d_spmm);
 crp_rp_spmm_p crp_para2d_spmm_rp(crp_para2d_spmm_p para2d_spmm);

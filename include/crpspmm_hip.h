@@ -262,6 +262,17 @@ int crp_scatter_rows_f64(int layout, int nidx, int n, const int *ridx,
  * src (equivalently col-major <-> row-major conversion). */
 int crp_transpose_f64(int nrow, int ncol, const double *src, long long lds,
                       double *dst, long long ldd, void *stream);
+/* fp32 forms of the three above, same contracts (the fp32 exec of the engines packs and transposes with them).
+ * Row-major rows move in 16-byte accesses when n, lds, ldd are multiples of 4 and src, dst 16-byte aligned
+ * (8-byte accesses for multiples of 2 and 8-byte alignment, single floats otherwise). */
+int crp_gather_rows_f32(int layout, int nidx, int n, const int *ridx,
+                        const float *src, long long lds,
+                        float *dst, long long ldd, void *stream);
+int crp_scatter_rows_f32(int layout, int nidx, int n, const int *ridx,
+                         const float *src, long long lds,
+                         float *dst, long long ldd, void *stream);
+int crp_transpose_f32(int nrow, int ncol, const float *src, long long lds,
+                      float *dst, long long ldd, void *stream);
 
 /* Diagnostics for the exchange / compute overlap (tools/overlap_probe.py): a stand-in for a transport's copy kernel --
  * `blocks` workgroups of 256 threads copy `bytes` (a multiple of 16) between device buffers and record the 100 MHz device
