@@ -138,6 +138,7 @@ SIGNATURES = {
     "crp_csr_dev_resolved_variant": (_I, [_V, _I]),
     "crp_csr_dev_last_variant": (_I, [_V]),
     "crp_csr_dev_lattice": (_I, [_V]),
+    "crp_csr_dev_team2_compact": (_I, [_V]),
     "crp_panel_format_host": (_I, [_I, c_int_p, c_int_p, c_dbl_p, _I, c_int_p, C.POINTER(c_int_p), C.POINTER(c_int_p),
                                    C.POINTER(C.POINTER(C.c_uint)), C.POINTER(c_dbl_p), C.POINTER(_LL),
                                    C.POINTER(c_int_p), c_int_p]),

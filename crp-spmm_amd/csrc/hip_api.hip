@@ -855,6 +855,7 @@ int crp_csr_dev_resolved_variant(crp_csr_dev_p A, int n)      // (an aligned ope
 }
 int crp_csr_dev_last_variant(crp_csr_dev_p A) { return A ? A->last_variant : -1; }
 int crp_csr_dev_lattice(crp_csr_dev_p A) { return A ? ((A->team2.built && A->team2.lattice) ? 1 : 0) : -1; }
+int crp_csr_dev_team2_compact(crp_csr_dev_p A) { return (A && A->team2.built) ? (A->team2.compact ? 1 : 0) : -1; }
 
 int crp_panel_format_host(int nrow, const int *rowptr, const int *colidx, const double *val, int R, int *npanel,
                           int **pptr, int **pcol, unsigned **pmask4, double **pval, long long *real_entries,

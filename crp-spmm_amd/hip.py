@@ -283,10 +283,12 @@ def spmm_plan_host(rowptr, colidx, widths, variant=0, dtype="f64", shape="aligne
 
 
 def spmm_csr_f32(A, B0, C_out, n=None, B1=None, variant=0, stream=None):
-    """crp_spmm_csr_f32: C := A * B with values, B and C in fp32 (row-major float32 torch tensors on the device)."""
+    """crp_spmm_csr_f32: C := A * B with values, B and C in fp32 (row-major float32 torch tensors on the device).
+    B0 = None: every column index is a receive-buffer one (B1 rows only)."""
     lib = L.load()
     if n is None:
         n = C_out.shape[1]
+    b0p, ldb0 = (B0.data_ptr(), B0.stride(0)) if B0 is not None else (None, 0)
     b1p, ldb1 = (B1.data_ptr(), B1.stride(0)) if B1 is not None else (None, 0)
-    L.check(lib.crp_spmm_csr_f32(A.handle, n, B0.data_ptr(), B0.stride(0), b1p, ldb1, C_out.data_ptr(), C_out.stride(0), variant,
+    L.check(lib.crp_spmm_csr_f32(A.handle, n, b0p, ldb0, b1p, ldb1, C_out.data_ptr(), C_out.stride(0), variant,
                                  _stream(C_out) if stream is None else stream), "crp_spmm_csr_f32")

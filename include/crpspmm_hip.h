@@ -144,6 +144,9 @@ int crp_csr_dev_last_variant(crp_csr_dev_p A);
 /* 1 when the team formats built so far found the two nested strides of a mesh numbered along its lines (their
  * teams are then blocks of neighbouring mesh lines), 0 otherwise / not built yet. */
 int crp_csr_dev_lattice(crp_csr_dev_p A);
+/* 1 when the team format (variant 5) of this matrix holds compact value blocks (only the values that exist), 0 when it holds 8 values
+ * per part, -1 before it is built (csrc/dispatch.cpp, team2_compact: fixed by whichever product builds it first). */
+int crp_csr_dev_team2_compact(crp_csr_dev_p A);
 /* Host-only: build the row-panel format the rowpanel kernels consume (R = 4 or 8)
  * and return malloc'd copies (caller frees).  Panel p owns entries pptr[p] .. pptr[p+1]
  * (padded to multiples of 8 with mask-0 entries); entry q has column pcol[q] (two-source

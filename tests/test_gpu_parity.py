@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import FP64_TOL, GOLDEN, GOLDEN_NAMES, load_golden
+from fp32_ref import check_f32_bound
 from test_dispatch import TABLE as DISPATCH_TABLE
 
 pytestmark = pytest.mark.gpu
@@ -776,6 +777,7 @@ def test_fp32_path_vs_fp64_oracle(crp, orc, gpu, n):
             torch.cuda.synchronize()
             got = Cd.cpu().numpy().astype(np.float64)
             assert orc.rel_fro_err(ref, got) <= FP32_TOL, (name, n, variant, orc.rel_fro_err(ref, got))
+            check_f32_bound(rp, ci, va, B.astype(np.float32), got, "%s n=%d variant %d" % (name, n, variant))
         A.free()
 
 
@@ -805,6 +807,7 @@ def test_fp32_two_source_and_update(crp, orc, gpu):
             hip.spmm_csr_f32(A, B0, Cd, n=n, B1=B1, variant=variant)
             torch.cuda.synchronize()
             assert orc.rel_fro_err(ref, Cd.cpu().numpy().astype(np.float64)) <= FP32_TOL, variant
+            check_f32_bound(rp, ci, vals, B.astype(np.float32), Cd.cpu().numpy(), "two sources variant %d" % variant)
     A.free()
 
 
