@@ -48,7 +48,7 @@ struct PanelDev
     bool      built = false;
     int       R = 0, npanel = 0;
     DevBuf<int> pptr, pcol, porder;
-    int       norder = 0, team_waves = 4;
+    int       norder = 0;
     DevBuf<int> psync;
     DevBuf<uint32_t> pmask4, pmap;
     DevBuf<double> pval;
@@ -202,7 +202,6 @@ static int ensure_panel(crp_csr_dev *A, int idx, hipStream_t stream)
     d.R = h.R;
     d.npanel = h.npanel;
     d.norder = (int) h.porder.size();
-    d.team_waves = h.team_waves;
     d.fill = h.fill();
     d.entries = (long long) h.pcol.size();
     hipError_t e = upload(d.pmap, h.pmap.data(), sizeof(uint32_t) * h.pmap.size(), sizeof(uint32_t));
@@ -730,6 +729,12 @@ int crp_csr_dev_row_part_comm_size(crp_csr_dev_p A, int nblk, const int *rblk_pt
 //  removed in round 4; the numbers stay so that 5 and 7 keep their meaning)
 static const char *k_variant_names[] = {"auto", "csr-rowgroup", "rowpanel-R4", "rowpanel-R8", "(removed)", "team2-R8", "(removed)", "team2r-R8"};
 int crp_spmm_variant_count(void) { return (int) (sizeof(k_variant_names) / sizeof(k_variant_names[0])); }
+// the variants a caller may name: fp64 all but the removed ones, fp32 the ones with an fp32 instance
+static bool variant_valid(int variant, bool f32)
+{
+    if (f32) return variant == 0 || variant == 1 || variant == 5;
+    return variant >= 0 && variant < crp_spmm_variant_count() && variant != 4 && variant != 6;
+}
 const char *crp_spmm_variant_name(int variant)
 {
     if (variant < 0 || variant >= crp_spmm_variant_count()) return NULL;
@@ -741,7 +746,7 @@ int crp_spmm_csr_f64(crp_csr_dev_p A, int layout, int n, const double *B0, long 
 {
     if (A == NULL || n < 0) return -1;
     if (layout != CRP_LAYOUT_ROW_MAJOR && layout != CRP_LAYOUT_COL_MAJOR) return -1;
-    if (variant < 0 || variant >= crp_spmm_variant_count() || variant == 4 || variant == 6) return -1;
+    if (!variant_valid(variant, false)) return -1;
     if (A->nrow == 0 || n == 0) return 0;
     if (C == NULL || (B0 == NULL && B1 == NULL && A->nnz > 0)) return -1;
     if (layout == CRP_LAYOUT_ROW_MAJOR && (ldC < n || (B0 && ldB0 < n) || (B1 && ldB1 < n))) return -4;
@@ -803,11 +808,9 @@ int crp_spmm_csr_f64(crp_csr_dev_p A, int layout, int n, const double *B0, long 
     const PanelDev &d = A->pan[v - 2];
     crp::PanelArgs p;
     memset(&p, 0, sizeof(p));
-    p.R = d.R; p.npanel = d.npanel; p.pptr = d.pptr; p.porder = d.porder; p.norder = d.norder; p.team_waves = d.team_waves; p.psync = d.psync; p.pcol = d.pcol; p.pmask4 = d.pmask4; p.pval = d.pval;
+    p.R = d.R; p.npanel = d.npanel; p.pptr = d.pptr; p.porder = d.porder; p.norder = d.norder; p.psync = d.psync; p.pcol = d.pcol; p.pmask4 = d.pmask4; p.pval = d.pval;
     p.b0_rows = A->b0_rows; p.b1_rows = A->b1_rows;
     p.cmo = d.cmo; p.cbase = d.cbase; p.cval = d.cval;
-    p.narrow64 = false;                    // (the two-piece instance loses to the row-panel kernel even on compact values: nlpkkt
-                                           //  stand-in n = 64 1.36 against 1.13 ms, pwtk stand-in 0.135 against 0.119; CRPSPMM_NARROW_MAX=64 forces it)
     return (int) crp::spmm_rm_f64_panel(p, a, s);
 }
 
@@ -817,7 +820,7 @@ int crp_spmm_csr_f32(crp_csr_dev_p A, int n, const float *B0, long long ldB0, co
                      long long ldC, int variant, void *stream)
 {
     if (A == NULL || n < 0) return -1;
-    if (variant != 0 && variant != 1 && variant != 5) return -1;
+    if (!variant_valid(variant, true)) return -1;
     if (A->nrow == 0 || n == 0) return 0;
     if (C == NULL || (B0 == NULL && B1 == NULL && A->nnz > 0)) return -1;
     if (ldC < n || (B0 && ldB0 < n) || (B1 && ldB1 < n)) return -4;
@@ -987,8 +990,7 @@ int crp_spmm_plan_host(int nrow, int ncol, const int *rowptr, const int *colidx,
     if (nrow < 0 || rowptr == NULL || (rowptr[nrow] > 0 && colidx == NULL) || nwidth < 0 || (nwidth > 0 && (widths == NULL || resolved == NULL)))
         return -1;
     if (shape < 0 || shape > 3) return -1;
-    if (f32 ? (variant != 0 && variant != 1 && variant != 5) : (variant < 0 || variant >= crp_spmm_variant_count() || variant == 4 || variant == 6))
-        return -1;
+    if (!variant_valid(variant, f32 != 0)) return -1;
     // the same order and traits as crp_csr_dev_create, the same rules as crp_spmm_csr_f64 / _f32 (no refused row-owner streams)
     const bool two_source = std::any_of(colidx, colidx + rowptr[nrow], [](int c) { return c < 0; });
     const crp::FormatOrder ord = crp::format_order(nrow, ncol, rowptr, colidx, two_source);

@@ -27,7 +27,6 @@ static Knobs read_knobs()
     k.spmm_variant = env_int("CRPSPMM_SPMM_VARIANT", 0);
     k.reorder = env_int("CRPSPMM_REORDER", -1);
     k.panel_order = env_int("CRPSPMM_PANEL_ORDER", -1);
-    k.narrow_max = env_int("CRPSPMM_NARROW_MAX", 0);
     k.team2_compact = env_int("CRPSPMM_TEAM2_COMPACT", -1);
     k.team2r = env_int("CRPSPMM_TEAM2R", -1);
     k.t2_latorder = env_int("CRPSPMM_T2_LATORDER", 1) != 0;

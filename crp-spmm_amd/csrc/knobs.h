@@ -15,7 +15,6 @@ struct Knobs
     int    spmm_variant;      // CRPSPMM_SPMM_VARIANT=1|2|3: what variant 0 resolves to below the team kernel's widths (0 = by the matrix)
     int    reorder;           // CRPSPMM_REORDER=0|1: locality order of the derived formats never / whenever the matrix qualifies (-1 = by gain)
     int    panel_order;       // CRPSPMM_PANEL_ORDER=0..3: row-panel processing order natural / breadth-first / lattice / team schedule (-1 = auto)
-    int    narrow_max;        // CRPSPMM_NARROW_MAX=32|64: widest operand of the narrow row-panel kernel (0 = 32, or 64 on compact values)
     int    team2_compact;     // CRPSPMM_TEAM2_COMPACT=0|1: value blocks of the team kernel with 8 values per part / compact (-1 = by panel fill)
     int    team2r;            // CRPSPMM_TEAM2R=0|1: the row-owner team kernel at 24..64 columns never / whenever applicable (-1 = by panel fill)
     bool   t2_latorder;       // CRPSPMM_T2_LATORDER=0: lattice teams keep the strips-along-the-teeth order (default 1: search against the L2 model)

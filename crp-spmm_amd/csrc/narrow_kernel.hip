@@ -1,4 +1,4 @@
-// narrow_kernel.hip -- row-panel SpMM for narrow operands (n <= 64 columns, fp64) on gfx950.
+// narrow_kernel.hip -- row-panel SpMM for narrow operands (n <= 32 columns, fp64) on gfx950.
 //
 // Same product as every kernel of this library (what mkl_sparse_d_mm computes at
 // /root/reference/src/rowpara_spmm.c:388-408 with alpha = 1, beta = 0), on the R = 8 row-panel format of
@@ -22,7 +22,6 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include "kernels.h"
-#include "knobs.h"
 #include "narrow_rows.inc"
 
 namespace crp {
@@ -32,8 +31,7 @@ typedef double d2 __attribute__((ext_vector_type(2)));
 
 }  // namespace
 
-// NP = 16-byte pieces per lane: 1 (n <= 32: columns 2 l, 2 l + 1 of lane l of a 16-lane group) or 2 (n <= 64: also columns
-// 32 + 2 l, 33 + 2 l -- the masks and the addressing of a step are then paid once for twice the FMAs).
+// One 16-byte piece per lane: columns 2 l, 2 l + 1 of lane l of a 16-lane group.
 // OFF32: B0 alone and smaller than 4 GiB -- every lane multiplies ITS column by the row stride once per 64 entries and
 // the 32-bit byte offsets travel through ds_bpermute like the masks (the 64-bit multiply per step and lane group of the
 // general path was 84 of its 230 vector cycles per step).
@@ -42,8 +40,8 @@ typedef double d2 __attribute__((ext_vector_type(2)));
 // finds its row's value at the entry's offset + the number of mask bits below its row.  For panels that are mostly holes (the
 // nlpkkt stand-in: 23 % of the (row, entry) pairs exist) A shrinks from 69 to ≈ 21 bytes per entry -- at n = 32 A was 60 % of
 // everything the kernel reads.
-template <int NP, bool HAS_B1, bool OFF32, bool COMPACT>
-__global__ __launch_bounds__(256, NP == 2 ? 4 : 7) void spmm_narrow_f64_kernel(
+template <bool HAS_B1, bool OFF32, bool COMPACT>
+__global__ __launch_bounds__(256, 7) void spmm_narrow_f64_kernel(
     const int norder, const int nrow, const int n, const int *__restrict__ porder, const int *__restrict__ pcol,
     const uint32_t *__restrict__ pmask4, const double *__restrict__ pval, const long long *__restrict__ cbase,
     const double *__restrict__ B0, const int64_t ldB0, const double *__restrict__ B1, const int64_t ldB1,
@@ -64,25 +62,19 @@ __global__ __launch_bounds__(256, NP == 2 ? 4 : 7) void spmm_narrow_f64_kernel(
     const int nent = __builtin_amdgcn_readfirstlane(rec.z) * 8;            // padded to a multiple of 8: mask-0 entries, valid column
 
     const int q = lane / LPG, l = lane % LPG;
-    bool ok[NP];
-    int bo[NP];                                                             // lanes past n read the row's first bytes: valid, never stored
-#pragma unroll
-    for (int p = 0; p < NP; p++)
-    {
-        ok[p] = (32 * p + 2 * l + 1) < n;
-        bo[p] = ok[p] ? 32 * p + 2 * l : 0;
-    }
+    const bool ok = (2 * l + 1) < n;
+    const int bo = ok ? 2 * l : 0;                                         // lanes past n read the row's first bytes: valid, never stored
     const uint8_t *pmask = reinterpret_cast<const uint8_t *>(pmask4);
     const double *const vpanel = COMPACT ? pval + cbase[panel] : pval;       // compact: the panel's first value
     const int myrow = lane & 7;
-    double a[16 * NP];
+    double a[16];
 #pragma unroll
-    for (int i = 0; i < 16 * NP; i++) a[i] = 0.0;
+    for (int i = 0; i < 16; i++) a[i] = 0.0;
 
     const uint32_t ld32 = (uint32_t) (ldB0 * 8);
     const char *const B0b = reinterpret_cast<const char *>(B0);
     const int sh0 = q * 4;                                                  // ds_bpermute address of lane q
-    auto fetch = [&](const int mycol, const int mymask, const int ebase, const int s, double &v, d2 (&b)[NP], int &mk) {
+    auto fetch = [&](const int mycol, const int mymask, const int ebase, const int s, double &v, d2 &b, int &mk) {
         const int src = s * G + q;
         if constexpr (!COMPACT) v = pval[(size_t) (ebase + src) * 8 + (size_t) (lane & 7)];
         if constexpr (OFF32)
@@ -90,16 +82,14 @@ __global__ __launch_bounds__(256, NP == 2 ? 4 : 7) void spmm_narrow_f64_kernel(
             const int idx = sh0 + s * (G * 4);
             const uint32_t off = (uint32_t) __builtin_amdgcn_ds_bpermute(idx, mycol);      // mycol holds the byte offset of the row
             mk = __builtin_amdgcn_ds_bpermute(idx, mymask);
-#pragma unroll
-            for (int p = 0; p < NP; p++) b[p] = *reinterpret_cast<const d2 *>(B0b + off + bo[p] * 8);
+            b = *reinterpret_cast<const d2 *>(B0b + off + (ok ? l * 16 : 0));      // (= bo * 8)
         }
         else
         {
             const int col = __shfl(mycol, src);
             mk = __shfl(mymask, src);
             const double *brow = (!HAS_B1 || col >= 0) ? (B0 + (int64_t) col * ldB0) : (B1 + (int64_t) (~col) * ldB1);
-#pragma unroll
-            for (int p = 0; p < NP; p++) b[p] = *reinterpret_cast<const d2 *>(brow + bo[p]);
+            b = *reinterpret_cast<const d2 *>(brow + bo);
         }
         if constexpr (COMPACT)
         {
@@ -114,16 +104,12 @@ __global__ __launch_bounds__(256, NP == 2 ? 4 : 7) void spmm_narrow_f64_kernel(
     // One step (narrow_rows.inc): the eight row masks of the lanes' entries first (vector compares into SGPR pairs, EXEC
     // still full), then per row EXEC := its mask and the row's FMAs.  (EXEC written by the scalar unit needs no wait
     // states before a DPP instruction; written by v_cmpx it needs five, which cost 40 idle cycles per step and wave.)
-    auto rows = [&](const double v, const d2 (&b)[NP], const int mk) {
+    auto rows = [&](const double v, const d2 &b, const int mk) {
         int t;
         uint64_t x0, x1, x2, x3, x4, x5, x6, x7;
 #define CRP_NARROW_TMP [t] "=&v"(t), [x0] "=&s"(x0), [x1] "=&s"(x1), [x2] "=&s"(x2), [x3] "=&s"(x3), [x4] "=&s"(x4), [x5] "=&s"(x5), \
                        [x6] "=&s"(x6), [x7] "=&s"(x7)
-        if constexpr (NP == 1)
-            asm volatile(CRP_NARROW_STEP_NP1 : CRP_NARROW_ACC_NP1(a), CRP_NARROW_TMP : [v] "v"(v), [b0x] "v"(b[0].x), [b0y] "v"(b[0].y), [mk] "v"(mk));
-        else
-            asm volatile(CRP_NARROW_STEP_NP2 : CRP_NARROW_ACC_NP2(a), CRP_NARROW_TMP
-                         : [v] "v"(v), [b0x] "v"(b[0].x), [b0y] "v"(b[0].y), [b1x] "v"(b[NP - 1].x), [b1y] "v"(b[NP - 1].y), [mk] "v"(mk));
+        asm volatile(CRP_NARROW_STEP : CRP_NARROW_ACC(a), CRP_NARROW_TMP : [v] "v"(v), [b0x] "v"(b.x), [b0y] "v"(b.y), [mk] "v"(mk));
 #undef CRP_NARROW_TMP
     };
     for (int base = 0; base < nent; base += 64)
@@ -133,27 +119,26 @@ __global__ __launch_bounds__(256, NP == 2 ? 4 : 7) void spmm_narrow_f64_kernel(
         if constexpr (OFF32) mycol = (int) ((uint32_t) mycol * ld32);
         const int mymask = (lane < ce) ? (COMPACT ? (int) pmask4[e0 + base + lane] : (int) pmask[e0 + base + lane]) : 0;
         const int nstep = ce / G;                                          // even
-        // NP = 1: two steps per iteration, their loads in flight together (the compiler's wait before an asm statement
+        // Two steps per iteration, their loads in flight together (the compiler's wait before an asm statement
         // cannot be counted across the loop's back edge, so a deeper software pipeline would not overlap anything).
         // (Tried: the block's 16 steps spelled out with a three-step prefetch -- it needs the operand pointers without
         //  __restrict__ and a "memory" clobber on the step, or the optimiser sinks every prefetch to its use; then the
         //  waits are vmcnt(6) as intended, at 80-88 VGPRs: 0.063 ms against 0.062 -- the kernel is bound by its vector
         //  instructions, not by exposed latency.)
-        // NP = 2: one step (twice the bytes per step already, and two would spill at four waves per SIMD)
-        for (int s = 0; s < nstep; s += (NP == 1 ? 2 : 1))
+        for (int s = 0; s < nstep; s += 2)
         {
             double v0, v1;
-            d2 b0[NP], b1[NP];
+            d2 b0, b1;
             int m0, m1;
             fetch(mycol, mymask, e0 + base, s, v0, b0, m0);
-            if constexpr (NP == 1) fetch(mycol, mymask, e0 + base, s + 1, v1, b1, m1);
+            fetch(mycol, mymask, e0 + base, s + 1, v1, b1, m1);
             rows(v0, b0, m0);
-            if constexpr (NP == 1) rows(v1, b1, m1);
+            rows(v1, b1, m1);
         }
     }
     // the G partial sums of every row: lanes l, l + 16, l + 32, l + 48 -> all of them hold the total
 #pragma unroll
-    for (int i = 0; i < 16 * NP; i++)
+    for (int i = 0; i < 16; i++)
     {
         a[i] += __shfl_xor(a[i], 16);
         a[i] += __shfl_xor(a[i], 32);
@@ -168,28 +153,22 @@ __global__ __launch_bounds__(256, NP == 2 ? 4 : 7) void spmm_narrow_f64_kernel(
             if (row < nrow)
             {
                 double *crow = C + (int64_t) (rowmap ? rowmap[row] : row) * ldC;
-#pragma unroll
-                for (int p = 0; p < NP; p++)
-                    if (ok[p])
-                    {
-                        d2 t2 = {a[(r * NP + p) * 2], a[(r * NP + p) * 2 + 1]};
-                        __builtin_nontemporal_store(t2, reinterpret_cast<d2 *>(crow + 32 * p + 2 * l));
-                    }
+                if (ok)
+                {
+                    d2 t2 = {a[r * 2], a[r * 2 + 1]};
+                    __builtin_nontemporal_store(t2, reinterpret_cast<d2 *>(crow + 2 * l));
+                }
             }
         }
     }
 }
 
-// n <= 64, even, 16-byte aligned operands, an order laid out for four-wave workgroups (team_waves == 4), R = 8
+// 24 <= n <= 32, even, 16-byte aligned operands, R = 8
+// (Two 16-byte pieces per lane for 32 < n <= 64 lost to the row-panel kernel: 128 VGPRs leave four waves per SIMD with one
+//  step in flight each -- pwtk stand-in n = 64: 0.168 ms against 0.117, nlpkkt stand-in on compact values 1.36 against 1.13.)
 bool spmm_narrow_applicable(const PanelArgs &p, const SpmmArgs &a)
 {
-    // (NP = 2, i.e. 32 < n <= 64, is built but not chosen on the full-value format: 128 VGPRs leave four waves per SIMD with
-    //  one step in flight each -- pwtk stand-in n = 64: 0.168 ms against 0.117 for the row-panel kernel; with 32 lanes per
-    //  entry and two entries per instruction it was 0.115: no gain either; at five waves per SIMD (96 VGPRs, the epilogue's
-    //  sums spilled) 0.209.  CRPSPMM_NARROW_MAX=64 selects it; p.narrow64 = panels that are mostly holes, on compact values.)
-    const int nmax_env = knobs().narrow_max;
-    const int nmax = nmax_env > 0 ? nmax_env : (p.narrow64 && p.cmo != nullptr ? 64 : 32);
-    return p.R == 8 && p.team_waves == 4 && a.n >= 24 && a.n <= nmax && a.n <= 64 && (a.n % 2 == 0) && (a.ldB0 % 2 == 0) && (a.ldC % 2 == 0) &&
+    return p.R == 8 && a.n >= 24 && a.n <= 32 && (a.n % 2 == 0) && (a.ldB0 % 2 == 0) && (a.ldC % 2 == 0) &&
            (a.B1 == nullptr || a.ldB1 % 2 == 0) && (((uintptr_t) a.B0 | (uintptr_t) a.B1 | (uintptr_t) a.C) % 16 == 0);
 }
 
@@ -201,18 +180,11 @@ hipError_t spmm_rm_f64_narrow(const PanelArgs &p, const SpmmArgs &a, hipStream_t
     // 32-bit byte offsets: B0 alone, every addressed byte below 4 GiB
     const bool off32 = !has_b1 && (uint64_t) p.b0_rows * (uint64_t) a.ldB0 * 8ull < (1ull << 32);
     const bool compact = p.cmo != nullptr && p.cbase != nullptr && p.cval != nullptr;
-#define CRP_NARROW_GO(NP_, HB1_, O32_, CP_)                                                                                            \
-    hipLaunchKernelGGL((spmm_narrow_f64_kernel<NP_, HB1_, O32_, CP_>), grid, dim3(256), 0, s, p.norder, a.nrow, a.n, p.porder, p.pcol, \
+#define CRP_NARROW_GO(HB1_, O32_, CP_)                                                                                        \
+    hipLaunchKernelGGL((spmm_narrow_f64_kernel<HB1_, O32_, CP_>), grid, dim3(256), 0, s, p.norder, a.nrow, a.n, p.porder, p.pcol, \
                        CP_ ? p.cmo : p.pmask4, CP_ ? p.cval : p.pval, p.cbase, a.B0, a.ldB0, a.B1, a.ldB1, a.C, a.ldC, a.rowmap)
-#define CRP_NARROW_PICK(NP_)                                                                                                     \
-    do                                                                                                                           \
-    {                                                                                                                            \
-        if (compact) { if (has_b1) CRP_NARROW_GO(NP_, true, false, true); else if (off32) CRP_NARROW_GO(NP_, false, true, true); else CRP_NARROW_GO(NP_, false, false, true); } \
-        else { if (has_b1) CRP_NARROW_GO(NP_, true, false, false); else if (off32) CRP_NARROW_GO(NP_, false, true, false); else CRP_NARROW_GO(NP_, false, false, false); }     \
-    } while (0)
-    if (a.n <= 32) CRP_NARROW_PICK(1);
-    else CRP_NARROW_PICK(2);
-#undef CRP_NARROW_PICK
+    if (compact) { if (has_b1) CRP_NARROW_GO(true, false, true); else if (off32) CRP_NARROW_GO(false, true, true); else CRP_NARROW_GO(false, false, true); }
+    else { if (has_b1) CRP_NARROW_GO(true, false, false); else if (off32) CRP_NARROW_GO(false, true, false); else CRP_NARROW_GO(false, false, false); }
 #undef CRP_NARROW_GO
     return hipGetLastError();
 }

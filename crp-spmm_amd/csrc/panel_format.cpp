@@ -630,12 +630,11 @@ static void build_key_csr(int n, F raw, std::vector<long long> *iptr, big_vector
     });
 }
 
-void build_teams(const PanelHost &p, int nrow, const int *rowptr, const int *colidx, TeamHost *out, int T, const int *colpos, bool balanced, int mix_mode,
+void build_teams(const PanelHost &p, int nrow, const int *rowptr, const int *colidx, TeamHost *out, int T, const int *colpos, bool balanced,
                  TeamSeed *seed)
 {
-    constexpr int TMAX = 16;
-    if (T != 4 && T != 6 && T != 8 && T != 16) T = 4;
-    const int TI = T / 2;                 // lattice teams: TI teeth along i times 2 along j
+    constexpr int TMAX = 8;
+    if (T != 8) T = 4;
     out->T = T;
     const int np = p.npanel, R = p.R;
     double D1 = 0, D2 = 0;
@@ -643,16 +642,11 @@ void build_teams(const PanelHost &p, int nrow, const int *rowptr, const int *col
     PhaseClock clk;
     bool lattice = (np >= 64) && detect_stride_lattice(nrow, rowptr, colidx, R, &D1, &D2, &M);
     clk.lap("build_teams: lattice detection");
-    // teams of eight (team2): shape of a team in tooth coordinates, si x sj teeth x st consecutive panels along
-    // the teeth
-    int si = TI, sj = 2, st = 1;
-    if (T >= 8)
-    {
-        // 2 x 2 teeth x 2 consecutive panels: 4.98 union entries per row on the pwtk stand-in, against 6.5 for
-        // 4 x 2 x 1 and 5.4 for eight consecutive panels (0.351 / 0.418 / 0.424 ms with the first team2 kernel);
-        // teams of sixteen: 2 x 2 x 4
-        si = 2; sj = 2; st = T / 4;
-    }
+    // shape of a lattice team in tooth coordinates: si x sj teeth x st consecutive panels along the teeth.  Teams of eight
+    // (team2): 2 x 2 teeth x 2 consecutive panels -- 4.98 union entries per row on the pwtk stand-in, against 6.5 for
+    // 4 x 2 x 1 and 5.4 for eight consecutive panels (0.351 / 0.418 / 0.424 ms with the first team2 kernel)
+    constexpr int si = 2, sj = 2;
+    const int st = T / 4;
     out->st = st;
     out->lattice = lattice;
     // entries of every panel before its padding (counted once, by all threads: the builders ask several times per panel)
@@ -704,7 +698,6 @@ void build_teams(const PanelHost &p, int nrow, const int *rowptr, const int *col
             long long small = 0;
             for (int q = 0; q < np; q++) small += (2LL * rc[(size_t) q] * np < tot);
             mix = small * 100 >= 15LL * np;
-            if (mix_mode >= 0) mix = mix_mode != 0;
         }
         std::vector<int> pord((size_t) np);
         for (int q = 0; q < np; q++) pord[(size_t) q] = q;
@@ -1078,7 +1071,7 @@ void build_teams(const PanelHost &p, int nrow, const int *rowptr, const int *col
         }, &iptr, &ikey);
         std::vector<int> super_of, sslot;
         int ns = 0;
-        greedy_cluster(nteam, iptr, ikey, T == 16 ? 32 : 64, 1 << 13, &super_of, &sslot, &ns);   // the workgroups resident on an XCD
+        greedy_cluster(nteam, iptr, ikey, 64, 1 << 13, &super_of, &sslot, &ns);   // the workgroups resident on an XCD
         // order of the super-teams: the slab order of locality.cpp on their graph (two super-teams are adjacent when
         // they share a B row; weight = union entries) -- eight slabs, one per XCD, each swept along its long axis,
         // so that an XCD's L2 sees one compact region and consecutive generations are neighbours
@@ -1191,7 +1184,7 @@ void build_team2(const PanelHost &p, int nrow, const int *rowptr, const int *col
     // The balanced passes of build_teams break the ties of the phase key (a lattice team has twenty nodes per key value): in
     // plain column order the nodes of one wave come in runs, the rounds then hold four parts of one wave and none of another,
     // and a round lasts as long as its busiest wave -- pwtk stand-in 0.304 -> 0.315 ms at n = 256, 0.199 -> 0.210 at n = 128.
-    build_teams(p, nrow, rowptr, colidx, &th, T, colpos, true, -1, seed);
+    build_teams(p, nrow, rowptr, colidx, &th, T, colpos, true, seed);
     const bool with_vals = !p.pval.empty() || p.pcol.empty();             // (structure-only panels: the caller scatters the values through vmap)
     clk.lap("build_team2: build_teams total");
     // Phase key of a union entry: (position of its B row in the processing order) mod S, S = rows a team advances
@@ -1661,7 +1654,7 @@ bool build_team2r(const PanelHost &p, int nrow, const int *rowptr, const int *co
     //  teams of one kind of panel give the waves of a round more equal steps (useful / issued row slots 0.53 against 0.32) and are
     //  slower all the same: nlpkkt stand-in n = 32 0.533 against 0.500 ms, at nlpkkt240 size 8.96 against 7.83, where the kernel is
     //  bound by what it fetches from beyond L2)
-    build_teams(p, nrow, rowptr, colidx, &th, T, colpos, false, -1, seed);
+    build_teams(p, nrow, rowptr, colidx, &th, T, colpos, false, seed);
     const bool with_vals = !p.pval.empty() || p.pcol.empty();
     clk.lap("build_team2r: build_teams total");
     const int nteam = th.nteam;
@@ -1952,7 +1945,6 @@ bool build_team2r(const PanelHost &p, int nrow, const int *rowptr, const int *co
 void apply_team_schedule(PanelHost *p, const TeamHost &t)
 {
     const int R = p->R, T = t.T;
-    p->team_waves = T;
     big_vector<int> ncol(p->pcol.size(), 0);
     big_vector<uint32_t> nmask4(p->pmask4.size(), 0u);
     big_vector<double> nval(p->pval.size(), 0.0);

@@ -52,7 +52,6 @@ struct PanelHost
     big_vector<uint32_t>  pmap;    // nnz: slot (q*R + r) in pval of CSR nonzero p (for value updates)
     std::vector<int>      porder;  // processing order of the panels (npanel positions; team schedule: 4 per team, -1 = none)
     std::vector<int>      psync;   // team schedule only: per workgroup, the rounds its waves start together
-    int team_waves = 4;            // waves per workgroup the processing order is laid out for (4, or 6 under the team schedule)
     long long real_entries = 0;    // entries before padding
     double fill() const;           // nnz / (real_entries * R)
     long long nnz = 0;
@@ -106,9 +105,9 @@ void lattice_coords(int panel, int R, double D1, double D2, int M, int *i, int *
 struct TeamHost
 {
     int nteam = 0;
-    int T = 4;                     // panels (= waves) per team: 4 (2 x 2 teeth) or 6 (3 x 2 teeth)
+    int T = 4;                     // panels (= waves) per team: 4 (2 x 2 teeth) or 8 (2 x 2 teeth x 2 along them)
     bool lattice = false;
-    int st = 1;                    // lattice teams of 8 / 16: consecutive panels along the teeth (the team's advance = 8 st rows)
+    int st = 1;                    // lattice teams: consecutive panels along the teeth (the team's advance = 8 st rows)
     bool clustered = false;        // T = 8 off a lattice: panels grouped by shared columns (plocal = slot of every panel in its team)
     std::vector<int>      plocal;
     std::vector<int>      tpanel;  // T * nteam: panel of wave w, or -1
@@ -135,9 +134,9 @@ struct TeamSeed
 };
 // colpos (optional, matrices in a locality order): position of row c of A in the order the panels were built on.
 // balanced = false: the union entries of a team stay in column order (the caller orders them itself).
+// T = 4 or 8 panels per team (anything else builds teams of 4).
 void build_teams(const PanelHost &p, int nrow, const int *rowptr, const int *colidx, TeamHost *out, int T = 4, const int *colpos = nullptr,
-                 bool balanced = true, int mix_mode = -1,       // mix_mode: panels of two kinds in one team (median-column order): -1 = by rule, 0 / 1
-                 TeamSeed *seed = nullptr);
+                 bool balanced = true, TeamSeed *seed = nullptr);
 
 // Team schedule for the row-panel kernel itself (no LDS sharing): the entries of every panel are
 // re-ordered to the order in which its wave meets them in the team's balanced schedule, and the

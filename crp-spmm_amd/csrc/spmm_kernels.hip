@@ -16,12 +16,6 @@
 #include <type_traits>
 #include "kernels.h"
 
-#ifdef CRP_ABL_PLAINSTORE     // timing experiment: C through the default (write-back) store path
-#define CRP_STORE(val, ptr) (*(ptr) = (val))
-#else
-#define CRP_STORE(val, ptr) __builtin_nontemporal_store((val), (ptr))
-#endif
-
 namespace crp {
 
 typedef double d2 __attribute__((ext_vector_type(2)));
@@ -235,6 +229,7 @@ __device__ __forceinline__ void static_for(F &&f)
 
 constexpr int PANEL_RING  = 8;
 constexpr int PANEL_CHUNK = 32;
+constexpr int PANEL_WPW   = 4;     // waves per workgroup (the processing order is laid out for four)
 
 typedef int i4v __attribute__((ext_vector_type(4)));
 
@@ -375,53 +370,6 @@ __device__ __forceinline__ void fmac_rows(double (&acc)[R][NV][VW], const double
     if constexpr (BIT + 1 < R) fmac_rows<R, NV, VW, BIT + 1>(acc, a, slot, mask);
 }
 
-// DPP delivery of the values: a VGPR pair `vv` holds 16 consecutive values of the panel's value
-// array (lane l has value l & 15: 16 / R entries), read with ONE ds_read_b64 per 16 values; the FMA takes
-// its scalar factor through DPP row_newbcast:LANE (every lane reads lane LANE of its own row of 16), the
-// only DPP control 64-bit operations have on gfx90a+.  This replaces R uniform-address LDS reads per
-// entry.  The DPP source was written by an LDS read (no VALU-write -> DPP-read hazard); s_bitcmp +
-// s_cbranch in front of the first FMA are two wait states in any case.
-template <int NV, int VW, int BIT, int LANE>
-__device__ __forceinline__ void fmac_row_masked_dpp(double (&acc)[NV][VW], const double vv,
-                                                    const typename SlotT<VW>::type (&slot)[NV], const uint32_t mask)
-{
-#define CRP_DPPF(A, B) "v_fmac_f64_dpp " A ", %[vv], " B " row_newbcast:%[ln] row_mask:0xf bank_mask:0xf\n\t"
-    if constexpr (NV == 2 && VW == 2)
-        asm volatile("s_bitcmp0_b32 %[m], %[bit]\n\ts_cbranch_scc1 1f\n\t"
-                     CRP_DPPF("%0", "%4") CRP_DPPF("%1", "%5") CRP_DPPF("%2", "%6") CRP_DPPF("%3", "%7") "1:"
-                     : "+v"(acc[0][0]), "+v"(acc[0][1]), "+v"(acc[1][0]), "+v"(acc[1][1])
-                     : "v"(slot[0].x), "v"(slot[0].y), "v"(slot[1].x), "v"(slot[1].y), [vv] "v"(vv), [m] "s"(mask),
-                       [bit] "n"(BIT), [ln] "n"(LANE)
-                     : "scc");
-    else if constexpr (NV == 1 && VW == 2)
-        asm volatile("s_bitcmp0_b32 %[m], %[bit]\n\ts_cbranch_scc1 1f\n\t" CRP_DPPF("%0", "%2") CRP_DPPF("%1", "%3") "1:"
-                     : "+v"(acc[0][0]), "+v"(acc[0][1])
-                     : "v"(slot[0].x), "v"(slot[0].y), [vv] "v"(vv), [m] "s"(mask), [bit] "n"(BIT), [ln] "n"(LANE)
-                     : "scc");
-    else if constexpr (NV == 2 && VW == 1)
-        asm volatile("s_bitcmp0_b32 %[m], %[bit]\n\ts_cbranch_scc1 1f\n\t" CRP_DPPF("%0", "%2") CRP_DPPF("%1", "%3") "1:"
-                     : "+v"(acc[0][0]), "+v"(acc[1][0])
-                     : "v"(slot[0]), "v"(slot[1]), [vv] "v"(vv), [m] "s"(mask), [bit] "n"(BIT), [ln] "n"(LANE)
-                     : "scc");
-    else
-    {
-        static_assert(NV == 1 && VW == 1, "unsupported tile shape");
-        asm volatile("s_bitcmp0_b32 %[m], %[bit]\n\ts_cbranch_scc1 1f\n\t" CRP_DPPF("%0", "%1") "1:"
-                     : "+v"(acc[0][0])
-                     : "v"(slot[0]), [vv] "v"(vv), [m] "s"(mask), [bit] "n"(BIT), [ln] "n"(LANE)
-                     : "scc");
-    }
-#undef CRP_DPPF
-}
-
-template <int R, int NV, int VW, int LANE0, int BIT = 0>
-__device__ __forceinline__ void fmac_rows_dpp(double (&acc)[R][NV][VW], const double vv,
-                                              const typename SlotT<VW>::type (&slot)[NV], const uint32_t mask)
-{
-    fmac_row_masked_dpp<NV, VW, BIT, LANE0 + BIT>(acc[BIT], vv, slot, mask);
-    if constexpr (BIT + 1 < R) fmac_rows_dpp<R, NV, VW, LANE0, BIT + 1>(acc, vv, slot, mask);
-}
-
 // Narrow tiles (one vector access per lane): the scalar unit, shared by the four SIMDs of a CU, is
 // what bounds them -- s_bitcmp + s_cbranch per row is 16 scalar instructions per entry against 8 FMAs.
 // Here the row mask goes into EXEC instead: one s_bfe_i64 per row writes all-ones or zero, the FMA
@@ -481,23 +429,16 @@ template <int R, int NV, int VW>
 __device__ __forceinline__ void panel_consume1(const typename SlotT<VW>::type (&slot)[NV], const uint32_t mask,
                                                const double (&a)[R], double (&acc)[R][NV][VW])
 {
-#if defined(CRP_ABL_FULLMASK)   // timing experiment only: every row takes the FMA path (wrong results)
-    fmac_rows<R, NV, VW>(acc, a, slot, (uint32_t) __builtin_amdgcn_readfirstlane((int) (mask | 0xFFu)));
-#elif defined(CRP_ABL_NOFMA)    // timing experiment only: no row takes the FMA path
-    fmac_rows<R, NV, VW>(acc, a, slot, (uint32_t) __builtin_amdgcn_readfirstlane((int) (mask & 0u)));
-#else
     if constexpr (R == 8 && NV == 1)
         fmac_rows_exec8<VW>(acc, a, slot, (uint32_t) __builtin_amdgcn_readfirstlane((int) mask));
     else
         fmac_rows<R, NV, VW>(acc, a, slot, (uint32_t) __builtin_amdgcn_readfirstlane((int) mask));
-#endif
 }
 
-// DEPTH = number of 8-slot ring sets: round r lives in set r % DEPTH and is refilled, slot by
-// slot, with round r + DEPTH while it is consumed, so 8*DEPTH - 1 entries stay in flight.
-// WPW = waves per workgroup: 4, or 6 when the processing order was laid out for teams of six panels
-template <int R, int NV, int VW, int DEPTH, bool ADDR64, bool HAS_B1, int WPW, bool DPP>
-__global__ __launch_bounds__(64 * WPW) void spmm_panel_f64_kernel(
+// One ring set of 8 slots: round r is refilled, slot by slot, with round r + 1 while it is consumed,
+// so 7 entries stay in flight.  Four waves per workgroup, one panel each.
+template <int R, int NV, int VW, bool ADDR64, bool HAS_B1>
+__global__ __launch_bounds__(64 * PANEL_WPW) void spmm_panel_f64_kernel(
     const int norder, const int nrow, const int n, const int *__restrict__ porder,
     const int *__restrict__ pptr, const int *__restrict__ pcol, const uint32_t *__restrict__ pmask4,
     const double *__restrict__ pval,
@@ -511,7 +452,7 @@ __global__ __launch_bounds__(64 * WPW) void spmm_panel_f64_kernel(
     constexpr int NS = (CHUNK * R) / 128;        // staging loads per lane and chunk (16 B each, 64 lanes)
     static_assert(NS >= 1 && NS * 128 == CHUNK * R, "chunk must be a whole number of wave-wide 16-byte loads");
     typedef typename SlotT<VW>::type ST;
-    __shared__ __attribute__((aligned(16))) double lds_vals[WPW][2][CHUNK * R];
+    __shared__ __attribute__((aligned(16))) double lds_vals[PANEL_WPW][2][CHUNK * R];
 
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -521,7 +462,7 @@ __global__ __launch_bounds__(64 * WPW) void spmm_panel_f64_kernel(
     // row into all eight.  Placement only affects speed, never the result.
     const int cpx   = (gridDim.x + 7) >> 3;
     const int wg    = (blockIdx.x & 7) * cpx + (blockIdx.x >> 3);
-    const int slot_id = __builtin_amdgcn_readfirstlane((int) (wg * WPW + wave));
+    const int slot_id = __builtin_amdgcn_readfirstlane((int) (wg * PANEL_WPW + wave));
     if (slot_id >= norder) return;
     // one 16-byte record per position: panel (-1: none), first entry, rounds -- a single scalar load
     // instead of the chain order -> panel -> entry range
@@ -529,13 +470,11 @@ __global__ __launch_bounds__(64 * WPW) void spmm_panel_f64_kernel(
     const int panel = rec.x;
     // team schedule: the four waves of the workgroup meet at a barrier before each of the first nb
     // rounds (nb < the rounds of every panel of the team), so that they reach shared B rows together
-#ifndef CRP_TEAM_SYNC_K
-#define CRP_TEAM_SYNC_K 1
-#endif
+    constexpr int SYNC_K = 1;                    // rounds per barrier
     const int nb = psync ? psync[wg] : 0;
     if (panel < 0)
     {
-        for (int r = 0; r < nb; r += CRP_TEAM_SYNC_K) asm volatile("s_barrier" ::: "memory");
+        for (int r = 0; r < nb; r += SYNC_K) asm volatile("s_barrier" ::: "memory");
         return;
     }
     double *myvals = &lds_vals[__builtin_amdgcn_readfirstlane(wave)][0][0];
@@ -572,13 +511,13 @@ __global__ __launch_bounds__(64 * WPW) void spmm_panel_f64_kernel(
     const int nr = rec.z;                              // rounds of this panel (entry counts are padded to whole rounds)
     if (nr > 0)
     {
-        ST ring[DEPTH][RING][NV];
+        ST ring[RING][NV];
         d2 stage[NS];                                   // next chunk's values of entry `lane`, in flight
         int cA[RING];                                   // column indices of the round refilled next
         int cP[RING];                                   // ... and of the round after it (scalar loads run two rounds ahead)
 
         // ---- prologue: the values of chunk 0 are requested first (asm-issued like every load of the
-        // loop), the B rows of rounds 0..DEPTH-1 right behind them, and only then are the values
+        // loop), the B rows of round 0 right behind them, and only then are the values
         // waited for and parked in LDS: one memory latency instead of two in a row per wave
         {
             // the chunk's CHUNK*R values are contiguous: lane l moves doubles [2*NS*l, 2*NS*(l+1))
@@ -586,55 +525,34 @@ __global__ __launch_bounds__(64 * WPW) void spmm_panel_f64_kernel(
 #pragma unroll
             for (int t = 0; t < NS; t++) glb_load_asm<2>(stage[t], src + 16 * t);
         }
-#pragma unroll
-        for (int d = 0; d < DEPTH; d++)
         {
-            if (d < nr)
-            {
-                int c0[RING];
+            int c0[RING];
 #pragma unroll
-                for (int k = 0; k < RING; k++) c0[k] = pcol[q0 + d * RING + k];
+            for (int k = 0; k < RING; k++) c0[k] = pcol[q0 + k];
 #pragma unroll
-                for (int k = 0; k < RING; k++) panel_issue1<ADDR64, HAS_B1, NV, VW>(ring[d][k], c0[k], s0, s1, voff);
-            }
+            for (int k = 0; k < RING; k++) panel_issue1<ADDR64, HAS_B1, NV, VW>(ring[k], c0[k], s0, s1, voff);
         }
         {
-            // younger than the staging loads: the ring loads just issued (at least one set; waiting for
-            // "at most RING*NV outstanding" only over-waits when a second set was issued)
+            // younger than the staging loads: the ring loads just issued
             wait_vmcnt<RING * NV>();
             double *dst = myvals + lane * (2 * NS);
 #pragma unroll
             for (int t = 0; t < NS; t++) *reinterpret_cast<d2 *>(dst + 2 * t) = stage[t];
         }
-        if constexpr (DPP)
-        {
-            // hipcc allocates the loop's ring registers apart from the prologue's in this body and moves
-            // them with v_mov before the loop: the moves must not read registers whose loads are still in
-            // flight, so the prologue's loads are drained here and the ring is pinned behind the wait
-            // (costs one exposed latency per panel; the loop itself never copies a ring register).
-            wait_vmcnt<0>();
 #pragma unroll
-            for (int d = 0; d < DEPTH; d++)
+        for (int k = 0; k < RING; k++) cA[k] = pcol[q0 + RING + k];     // (arrays are padded)
 #pragma unroll
-                for (int k = 0; k < RING; k++)
-#pragma unroll
-                    for (int v = 0; v < NV; v++) asm volatile("" : "+v"(ring[d][k][v]));
-        }
-#pragma unroll
-        for (int k = 0; k < RING; k++) cA[k] = pcol[q0 + DEPTH * RING + k];     // (arrays are padded)
-#pragma unroll
-        for (int k = 0; k < RING; k++) cP[k] = pcol[q0 + (DEPTH + 1) * RING + k];
+        for (int k = 0; k < RING; k++) cP[k] = pcol[q0 + 2 * RING + k];
 
-        // One round: consume the 8 slots of ring set `set` (entries of round r) and, when `refill`,
-        // re-issue each slot for round r + DEPTH right after its FMAs.  All VMEM of the loop is issued
+        // One round: consume the 8 slots of the ring (entries of round r) and, when `refill`,
+        // re-issue each slot for round r + 1 right after its FMAs.  All VMEM of the loop is issued
         // from asm, so every wait below is hand-counted: N = loads YOUNGER than the one waited for.
-        auto round = [&](const int r, auto set_tag, auto refill_tag) {
-            constexpr int  set = decltype(set_tag)::value;
+        auto round = [&](const int r, auto refill_tag) {
             constexpr bool refill = decltype(refill_tag)::value;
             const int q = q0 + r * RING;
             int cB[RING];
 #pragma unroll
-            for (int k = 0; k < RING; k++) cB[k] = pcol[q + (DEPTH + 2) * RING + k];   // scalar loads, two rounds ahead
+            for (int k = 0; k < RING; k++) cB[k] = pcol[q + 3 * RING + k];   // scalar loads, two rounds ahead
             const uint32_t m_lo = pmask4[(q >> 2)], m_hi = pmask4[(q >> 2) + 1];
             // values: chunk c = r / RPC sits in LDS buffer c & 1; the last round of a chunk fetches the
             // next chunk (every lane one entry; reads past the panel are padded) before its refills ...
@@ -646,32 +564,17 @@ __global__ __launch_bounds__(64 * WPW) void spmm_panel_f64_kernel(
                 for (int t = 0; t < NS; t++) glb_load_asm<2>(stage[t], src + 16 * t);
             }
             const double *lv = myvals + ((r / RPC) & 1) * (CHUNK * R) + (r % RPC) * (RING * R);
-            // DPP: the round's RING * R values in RING * R / 16 reads, lane l holding value l & 15 of its 16
-            constexpr int NVV = (RING * R) / 16;
-            double vv[NVV];
-            if constexpr (DPP)
-            {
-#pragma unroll
-                for (int j = 0; j < NVV; j++) vv[j] = lv[j * 16 + (lane & 15)];
-            }
             static_for<0, RING>([&](auto kc) {
                 constexpr int k = decltype(kc)::value;
                 double a_cur[R];
-                if constexpr (!DPP)
-                {
 #pragma unroll
-#ifdef CRP_ABL_NOVALS      // timing experiment: no LDS broadcast of the values
-                    for (int rr = 0; rr < R; rr++) a_cur[rr] = 1.0 + rr;
-#else
-                    for (int rr = 0; rr < R; rr++) a_cur[rr] = lv[k * R + rr];      // uniform-address LDS broadcast
-#endif
-                }
+                for (int rr = 0; rr < R; rr++) a_cur[rr] = lv[k * R + rr];      // uniform-address LDS broadcast
                 const uint32_t mask = ((k < 4 ? m_lo : m_hi) >> (8 * (k & 3))) & 0xFFu;
-                // younger than slot k of this round: slots k+1..7 of the round, the DEPTH-1 rounds issued
-                // after it, and (refill) the k slots re-issued so far; the staging loads of a chunk's
+                // younger than slot k of this round: slots k+1..7 of the round and (refill) the k slots
+                // re-issued so far; the staging loads of a chunk's
                 // last round are ignored (N too small only over-waits).  Rounds without refill use the
                 // bound that is exact for the panel's last round.
-                if constexpr (refill) wait_vmcnt<(RING * DEPTH - 1) * NV>();
+                if constexpr (refill) wait_vmcnt<(RING - 1) * NV>();
                 else
                 {
                     switch (k)
@@ -686,11 +589,8 @@ __global__ __launch_bounds__(64 * WPW) void spmm_panel_f64_kernel(
                         default: wait_vmcnt<0>(); break;
                     }
                 }
-                if constexpr (DPP)
-                    fmac_rows_dpp<R, NV, VW, ((k * R) % 16)>(acc, vv[(k * R) / 16], ring[set][k],
-                                                             (uint32_t) __builtin_amdgcn_readfirstlane((int) mask));
-                else panel_consume1<R, NV, VW>(ring[set][k], mask, a_cur, acc);
-                if constexpr (refill) panel_issue1<ADDR64, HAS_B1, NV, VW>(ring[set][k], cA[k], s0, s1, voff);
+                panel_consume1<R, NV, VW>(ring[k], mask, a_cur, acc);
+                if constexpr (refill) panel_issue1<ADDR64, HAS_B1, NV, VW>(ring[k], cA[k], s0, s1, voff);
             });
             if (last_of_chunk)
             {
@@ -711,37 +611,12 @@ __global__ __launch_bounds__(64 * WPW) void spmm_panel_f64_kernel(
         };
 
         int r = 0;
-        if constexpr (DEPTH == 1)
+        for (; r + 1 < nr; r++)
         {
-            for (; r + 1 < nr; r++)
-            {
-                if (r < nb && (r % CRP_TEAM_SYNC_K) == 0) asm volatile("s_barrier" ::: "memory");
-                round(r, std::integral_constant<int, 0>{}, std::true_type{});
-            }
-            round(r, std::integral_constant<int, 0>{}, std::false_type{});
+            if (r < nb && (r % SYNC_K) == 0) asm volatile("s_barrier" ::: "memory");
+            round(r, std::true_type{});
         }
-        else
-        {
-            static_assert(DEPTH == 2, "ring depth is 1 or 2 sets");
-            for (; r + 3 < nr; r += 2)
-            {
-                round(r, std::integral_constant<int, 0>{}, std::true_type{});
-                round(r + 1, std::integral_constant<int, 1>{}, std::true_type{});
-            }
-            // tail: 1 to 3 rounds left; only a round that still has a successor DEPTH ahead refills
-            if (r + 2 < nr)
-            {
-                round(r, std::integral_constant<int, 0>{}, std::true_type{});
-                round(r + 1, std::integral_constant<int, 1>{}, std::false_type{});
-                round(r + 2, std::integral_constant<int, 0>{}, std::false_type{});
-            }
-            else if (r + 1 < nr)
-            {
-                round(r, std::integral_constant<int, 0>{}, std::false_type{});
-                round(r + 1, std::integral_constant<int, 1>{}, std::false_type{});
-            }
-            else round(r, std::integral_constant<int, 0>{}, std::false_type{});
-        }
+        round(r, std::false_type{});
     }
 #pragma unroll
     for (int r = 0; r < R; r++)
@@ -759,31 +634,23 @@ __global__ __launch_bounds__(64 * WPW) void spmm_panel_f64_kernel(
                         d2 t;
                         t.x = acc[r][v][0];
                         t.y = acc[r][v][1];
-                        CRP_STORE(t, reinterpret_cast<d2 *>(crow + coff[v]));
+                        __builtin_nontemporal_store(t, reinterpret_cast<d2 *>(crow + coff[v]));
                     }
-                    else CRP_STORE(acc[r][v][0], crow + coff[v]);
+                    else __builtin_nontemporal_store(acc[r][v][0], crow + coff[v]);
                 }
         }
     }
 }
 
-template <int R, int NV, int VW, int DEPTH, bool ADDR64, bool HAS_B1, int WPW>
-static hipError_t launch_panel_w(const PanelArgs &p, const SpmmArgs &a, hipStream_t s)
-{
-    constexpr int TW = 64 * VW * NV;
-    const int nwg = (p.norder + WPW - 1) / WPW;
-    dim3 grid((nwg + 7) / 8 * 8, (a.n + TW - 1) / TW);      // multiple of 8 for the XCD remap
-    // value delivery: uniform-address LDS broadcast (the DPP row_newbcast body needs 216 VGPRs against 160: not instantiated)
-    hipLaunchKernelGGL((spmm_panel_f64_kernel<R, NV, VW, DEPTH, ADDR64, HAS_B1, WPW, false>), grid, dim3(64 * WPW), 0, s, p.norder, a.nrow,
-                       a.n, p.porder, p.pptr, p.pcol, p.pmask4, p.pval, a.B0, a.ldB0, a.B1, a.ldB1, a.C, a.ldC, a.rowmap, p.psync);
-    return hipGetLastError();
-}
-
-template <int R, int NV, int VW, int DEPTH, bool ADDR64, bool HAS_B1>
+template <int R, int NV, int VW, bool ADDR64, bool HAS_B1>
 static hipError_t launch_panel(const PanelArgs &p, const SpmmArgs &a, hipStream_t s)
 {
-    if (p.team_waves != 4) return hipErrorInvalidValue;      // (the order is laid out for four-wave workgroups)
-    return launch_panel_w<R, NV, VW, DEPTH, ADDR64, HAS_B1, 4>(p, a, s);
+    constexpr int TW = 64 * VW * NV;
+    const int nwg = (p.norder + PANEL_WPW - 1) / PANEL_WPW;
+    dim3 grid((nwg + 7) / 8 * 8, (a.n + TW - 1) / TW);      // multiple of 8 for the XCD remap
+    hipLaunchKernelGGL((spmm_panel_f64_kernel<R, NV, VW, ADDR64, HAS_B1>), grid, dim3(64 * PANEL_WPW), 0, s, p.norder, a.nrow,
+                       a.n, p.porder, p.pptr, p.pcol, p.pmask4, p.pval, a.B0, a.ldB0, a.B1, a.ldB1, a.C, a.ldC, a.rowmap, p.psync);
+    return hipGetLastError();
 }
 
 template <int R, int NV, int VW>
@@ -793,10 +660,9 @@ static hipError_t launch_panel_addr(const PanelArgs &p, const SpmmArgs &a, hipSt
     const bool has_b1 = (a.B1 != nullptr) && (p.b1_rows > 0);
     const bool small = ((uint64_t) p.b0_rows * (uint64_t) a.ldB0 * 8ull < (1ull << 32)) &&
                        (!has_b1 || (uint64_t) p.b1_rows * (uint64_t) a.ldB1 * 8ull < (1ull << 32));
-    // ring depth: one set of 8 slots (two sets, 15 entries in flight, need 326 VGPRs and ran 40 % slower: not instantiated)
     if (small)
-        return has_b1 ? launch_panel<R, NV, VW, 1, false, true>(p, a, s) : launch_panel<R, NV, VW, 1, false, false>(p, a, s);
-    return has_b1 ? launch_panel<R, NV, VW, 1, true, true>(p, a, s) : launch_panel<R, NV, VW, 1, true, false>(p, a, s);
+        return has_b1 ? launch_panel<R, NV, VW, false, true>(p, a, s) : launch_panel<R, NV, VW, false, false>(p, a, s);
+    return has_b1 ? launch_panel<R, NV, VW, true, true>(p, a, s) : launch_panel<R, NV, VW, true, false>(p, a, s);
 }
 
 // The row-panel kernels need one lane per column (pair): below ~24 columns most lanes of the

@@ -26,7 +26,7 @@
 // against 0.062: not taken there.  The teams are team2's (primal and dual panels of a KKT system together: with teams of one kind
 // the B rows both kinds share come from beyond L2 twice and the gain is gone at nlpkkt240 size), the union entries of a team go
 // to its rounds in natural order (dealt like cards they balance the waves of a round and cost 15 %).  A round takes ~3000 cycles of
-// which (s_memtime stamps, -DT2R_DBG) ~1400 are the issue of the next round's four DMAs per wave, ~900 the FMAs with their two
+// which (s_memtime stamps) ~1400 are the issue of the next round's four DMAs per wave, ~900 the FMAs with their two
 // dependent LDS reads per four steps, ~400 the barrier: latency-bound at four waves per SIMD.  The first version read a record per
 // round through the scalar cache (2100 + 2300 of 5800 cycles per round were those misses): records now ride in the blocks.
 #include <hip/hip_runtime.h>
@@ -44,10 +44,11 @@ typedef double d2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u2 __attribute__((ext_vector_type(2)));
 constexpr int T2R_NSET = 3, T2R_BLKB = 80 * TEAM2R_LCAP + 64, T2R_WBLK = T2R_NSET * T2R_BLKB;
-constexpr int t2r_setb(int rd) { return 8192 * rd + 512; }                  // slots + the slice of zeros (512 bytes: a slice of the G = 2 instance)
-constexpr int t2r_lds(int rd) { return T2R_NSET * t2r_setb(rd) + 8 * T2R_WBLK; }
-static_assert(T2R_BLKB == 1024 && 5 * TEAM2R_LCAP + 4 <= 64 && 2 * t2r_lds(2) <= 160 * 1024 && 3 * t2r_lds(1) <= 160 * 1024,
-              "block layout; two (full rounds) or three (half rounds) workgroups per CU");
+constexpr int T2R_RD = TEAM2R_ROWDMA;                                           // row DMAs per wave and round
+constexpr int T2R_ZERO = 8192 * T2R_RD;                                         // the slice of zeros behind the slots of a ring set
+constexpr int T2R_SETB = T2R_ZERO + 512;                                    // slots + the slice of zeros (512 bytes: a slice of the G = 2 instance)
+constexpr int T2R_LDS = T2R_NSET * T2R_SETB + 8 * T2R_WBLK;
+static_assert(T2R_BLKB == 1024 && 5 * TEAM2R_LCAP + 4 <= 64 && 2 * T2R_LDS <= 160 * 1024, "block layout; two workgroups per CU");
 #define T2R_GPTR(p) ((const __attribute__((address_space(1))) void *) (p))
 #define T2R_LPTR(p) ((__attribute__((address_space(3))) void *) (p))
 // One chunk = four steps of TWO rows' accumulators (lane group q's rows h0 G + q and (h0 + 1) G + q), all in one asm statement
@@ -119,23 +120,25 @@ static_assert(T2R_BLKB == 1024 && 5 * TEAM2R_LCAP + 4 <= 64 && 2 * t2r_lds(2) <=
 //     128-byte row of the entry table, loaded into scalar registers ONE TEAM AHEAD.
 // (The first version read a record per round through the scalar cache: measured with s_memtime, 2100 of a round's 5800 cycles were
 //  that load's miss, another 2300 the load of the round's step count, against ~300 for the barrier and ~400 for the FMAs.)
+// stagger, chain_k and dbg are constant at the launch (1, 0, nullptr) but stay kernel arguments: without them the register
+// allocation shifts and the G = 4 instance measured 0.6 % slower (kkt stand-in n = 32).
 struct T2RRec { uint32_t w[10]; };                                          // Lp, block offset, up to 8 columns
 struct T2RTeam { int nr; long long vb; T2RRec r0, r1; };
 
-template <int G, bool HAS_B1, int RD>
+template <int G, bool HAS_B1>
 __global__ __launch_bounds__(512, 4) void spmm_team2r_kernel(const int ngrid, const uint32_t *__restrict__ tent, const double *__restrict__ tval,
                                                              const int n, const double *__restrict__ B0, const int64_t ldB0,
                                                              const double *__restrict__ B1, const int64_t ldB1, double *__restrict__ C,
                                                              const int64_t ldC, const int stagger, const int chain_k, unsigned long long *dbg)
 {
-    constexpr int LPG = 64 / G, SLOTB = 1024 / G, PERW = RD * G, NH = 8 / G;
-    constexpr int T2R_SETB = t2r_setb(RD), ZERO = 8192 * RD;
+    constexpr int LPG = 64 / G, SLOTB = 1024 / G, PERW = T2R_RD * G, NH = 8 / G;
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6));
     const int cpx = ngrid >> 3;                                             // entries per XCD run (ngrid is a multiple of 8)
-    const int wx0 = (int) (gridDim.x >> 3);                                 // workgroups per XCD
-    // a workgroup's chain of entries: every wx0-th of its XCD's run (chain_k = 0), or chain_k consecutive ones
+    // a workgroup's chain of entries: every wx-th of its XCD's run, wx = workgroups per XCD (consecutive entries instead: no
+    // better, 6.59 against 6.48 ms at nlpkkt240 size)
+    const int wx0 = (int) (gridDim.x >> 3);
     const int wx = chain_k > 0 ? 1 : wx0;
     const int e_first = (int) (blockIdx.x & 7) * cpx + (chain_k > 0 ? (int) (blockIdx.x >> 3) * chain_k : (int) (blockIdx.x >> 3));
     const int e_end = chain_k > 0 ? min((int) ((blockIdx.x & 7) + 1) * cpx, e_first + chain_k) : (int) ((blockIdx.x & 7) + 1) * cpx;
@@ -146,7 +149,7 @@ __global__ __launch_bounds__(512, 4) void spmm_team2r_kernel(const int ngrid, co
     const uint32_t blk0 = (uint32_t) (T2R_NSET * T2R_SETB + wave * T2R_WBLK);            // relative to lds (DMA destinations), + lds0 for reads
     // the slices of zeros (one per ring set: offsets are relative to the set; 512 bytes: a slice of the G = 2 instance)
     if (threadIdx.x < T2R_NSET * 32)
-        *reinterpret_cast<d2 *>(lds + (threadIdx.x >> 5) * T2R_SETB + ZERO + (threadIdx.x & 31) * 16) = d2{0.0, 0.0};
+        *reinterpret_cast<d2 *>(lds + (threadIdx.x >> 5) * T2R_SETB + T2R_ZERO + (threadIdx.x & 31) * 16) = d2{0.0, 0.0};
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                      // written before this wave reaches the first round's barrier
     double a[NH][2], pa[NH][2];
 #pragma unroll
@@ -175,7 +178,7 @@ __global__ __launch_bounds__(512, 4) void spmm_team2r_kernel(const int ngrid, co
     auto fetch = [&](const T2RRec &R, const int set, const long long vb) {  // the four DMAs of a round
         const int Lp = (int) R.w[0];
 #pragma unroll
-        for (int j = 0; j < RD; j++)
+        for (int j = 0; j < T2R_RD; j++)
         {
             // (readfirstlane: or the optimiser turns the selection into a per-lane load of R.w[2 + j G + q] from a stack copy)
             int col = __builtin_amdgcn_readfirstlane((int) R.w[2 + j * G]);
@@ -251,26 +254,12 @@ __global__ __launch_bounds__(512, 4) void spmm_team2r_kernel(const int ngrid, co
     // rounds issued and not yet consumed, oldest first: steps | last round of its team << 8, entry
     int f0 = 0, f1 = 0, f2 = 0, g0 = 0, g1 = 0, g2 = 0, ahead = 0;
     int si = 0, sc = 0;                                                     // ring set of the next round to issue / to consume
-#ifdef T2R_DBG
-    long long th = 0, tfe = 0;
-#endif
     auto issue_next = [&]() {
         T2RRec R;
-#ifdef T2R_DBG
-        const long long q0 = clock64();
-#endif
         if (ir == 0) R = tm.r0;
         else if (ir == 1) R = tm.r1;
         else R = header(sc, f0 & 0xFF);                                     // rounds ir - 2 (being consumed now) and ir - 1 are the ones in flight
-#ifdef T2R_DBG
-        const long long q1 = clock64();
-#endif
         fetch(R, si, cvb);
-#ifdef T2R_DBG
-        const long long q2 = clock64();
-        th += q1 - q0;
-        tfe += q2 - q1;
-#endif
         const int desc = (int) R.w[0] | ((ir == cnr - 1) ? 256 : 0);
         // (selects, not branches: the optimiser turns a three-way branch into an indexed array on the stack)
         f0 = ahead == 0 ? desc : f0; g0 = ahead == 0 ? ie : g0;
@@ -298,39 +287,25 @@ __global__ __launch_bounds__(512, 4) void spmm_team2r_kernel(const int ngrid, co
     int pe = 0;
     bool pending = false;
     const bool early = stagger == 0 || (wave & 1) == 0;
-#ifdef T2R_DBG
-    long long tw = 0, tb = 0, ti = 0, tf = 0, tc = 0, nrd = 0;
-#define T2R_CLK(x) const long long x = clock64()
-#else
-#define T2R_CLK(x)
-#endif
     while (ahead > 0)
     {
-        T2R_CLK(c0);
-        // this wave's DMAs of the round to consume (RD rows + the block) have landed (those of the round behind it may still fly; stores of the
+        // this wave's DMAs of the round to consume (T2R_RD rows + the block) have landed (those of the round behind it may still fly; stores of the
         // last flush count too, which can only make this wait longer: loads complete in order) ...
-        if (ahead > 1)
-        {
-            if constexpr (RD == 2) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-        }
+        static_assert(T2R_RD == 2, "the wait below counts the T2R_RD + 1 DMAs of the round behind");
+        if (ahead > 1) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         // ... and everybody's; every wave is also done reading the round before, whose set the next issue takes
-        T2R_CLK(c1);
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-        T2R_CLK(c2);
         // Half of the waves issue the next round's DMAs now, the other half after their FMAs: all 32 DMA instructions of a round
         // at once queue up behind each other in the CU's one address unit (measured: ~1400 of a round's ~3000 cycles in this
-        // phase, the unit itself 36 % busy), while nothing else of the workgroup runs.  CRPSPMM_T2R_STAGGER=0: all at once.
+        // phase, the unit itself 36 % busy), while nothing else of the workgroup runs.
         if (early && cnr > 0) issue_next();
-        T2R_CLK(c3);
         if (pending)
         {
             flush(pe);
             pending = false;
         }
-        T2R_CLK(c4);
         const int Lp = f0 & 0xFF;
         const uint32_t rs = lds0 + (uint32_t) (sc * T2R_SETB + l * 16);
         const uint32_t vs = lds0 + blk0 + (uint32_t) (sc * T2R_BLKB);
@@ -373,20 +348,8 @@ __global__ __launch_bounds__(512, 4) void spmm_team2r_kernel(const int ngrid, co
         f1 = f2; g1 = g2;
         ahead--;
         sc = sc == T2R_NSET - 1 ? 0 : sc + 1;
-#ifdef T2R_DBG
-        T2R_CLK(c5);
-        tw += c1 - c0; tb += c2 - c1; ti += c3 - c2; tf += c4 - c3; tc += c5 - c4; nrd++;
-#endif
     }
     if (pending) flush(pe);
-#ifdef T2R_DBG
-    if (dbg != nullptr && lane == 0)
-    {
-        atomicAdd(dbg + 0, (unsigned long long) tw); atomicAdd(dbg + 1, (unsigned long long) tb); atomicAdd(dbg + 2, (unsigned long long) ti);
-        atomicAdd(dbg + 3, (unsigned long long) tf); atomicAdd(dbg + 4, (unsigned long long) tc); atomicAdd(dbg + 5, (unsigned long long) nrd);
-        atomicAdd(dbg + 6, (unsigned long long) th); atomicAdd(dbg + 7, (unsigned long long) tfe);
-    }
-#endif
 }
 
 // the C rows of every (entry, wave)'s panel into the entry table (words 24 .. 31; -1 = no such row)
@@ -427,25 +390,15 @@ hipError_t spmm_rm_f64_team2r(const Team2NArgs &t, const SpmmArgs &a, hipStream_
     const int run = t.ngrid / 8;                                            // entries of an XCD's run
     const int per_xcd = std::max(1, std::min(run, std::max(2 * ncu / 8, (run + 6) / 7)));
     dim3 grid(per_xcd * 8);
-    // a workgroup's chain = every per_xcd-th entry of the run (consecutive entries instead: no better, 6.59 against 6.48 ms)
-    const int chain_k = 0;
-    unsigned long long *dbg = nullptr;
-    const int stagger = 1;
-#define CRP_T2R_GO(G_, HB1_, RD_)                                                                                                                   \
+#define CRP_T2R_GO(G_, HB1_)                                                                                                                        \
     do                                                                                                                                              \
     {                                                                                                                                               \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&spmm_team2r_kernel<G_, HB1_, RD_>), hipFuncAttributeMaxDynamicSharedMemorySize, t2r_lds(RD_)); \
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&spmm_team2r_kernel<G_, HB1_>), hipFuncAttributeMaxDynamicSharedMemorySize, T2R_LDS); \
         if (e != hipSuccess) return e;                                                                                                              \
-        hipLaunchKernelGGL((spmm_team2r_kernel<G_, HB1_, RD_>), grid, dim3(512), t2r_lds(RD_), s, t.ngrid, t.tent, t.tval, a.n, a.B0, a.ldB0, a.B1, a.ldB1, a.C, a.ldC, stagger, chain_k, dbg); \
+        hipLaunchKernelGGL((spmm_team2r_kernel<G_, HB1_>), grid, dim3(512), T2R_LDS, s, t.ngrid, t.tent, t.tval, a.n, a.B0, a.ldB0, a.B1, a.ldB1, a.C, a.ldC, 1, 0, nullptr); \
     } while (0)
-#define CRP_T2R_PICK(RD_)                                                                                       \
-    do                                                                                                          \
-    {                                                                                                           \
-        if (t.G == 4) { if (has_b1) CRP_T2R_GO(4, true, RD_); else CRP_T2R_GO(4, false, RD_); }                  \
-        else { if (has_b1) CRP_T2R_GO(2, true, RD_); else CRP_T2R_GO(2, false, RD_); }                           \
-    } while (0)
-    CRP_T2R_PICK(TEAM2R_ROWDMA);
-#undef CRP_T2R_PICK
+    if (t.G == 4) { if (has_b1) CRP_T2R_GO(4, true); else CRP_T2R_GO(4, false); }
+    else { if (has_b1) CRP_T2R_GO(2, true); else CRP_T2R_GO(2, false); }
 #undef CRP_T2R_GO
     return hipGetLastError();
 }

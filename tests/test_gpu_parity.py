@@ -812,7 +812,7 @@ def test_fp32_two_source_and_update(crp, orc, gpu):
 
 
 @pytest.mark.parametrize("n", [24, 26, 30, 32, 48, 64])
-def test_narrow_kernel(crp, orc, gpu, monkeypatch, n):
+def test_narrow_kernel(crp, orc, gpu, n):
     """The narrow-operand kernel (csrc/narrow_kernel.hip: row-panel format, four entries per instruction; variant 3 at
     24 <= n <= 32, even n, 16-byte aligned operands): random / banded / empty-row matrices with padded leading dimensions,
     the two-source column index (general addressing path), non-finite B rows next to absent pairs, value updates,
@@ -820,10 +820,7 @@ def test_narrow_kernel(crp, orc, gpu, monkeypatch, n):
     import torch
     from crp_spmm_amd import gen, hip
     lib = crp.load()
-    # (the values of the panels without their holes are taken when under 60 % of the (row, entry) pairs exist: the kkt case below;
-    #  n = 48, 64: the two-piece instance, taken by itself only for panels that are mostly holes, forced here)
-    if n > 32:
-        monkeypatch.setenv("CRPSPMM_NARROW_MAX", "64")
+    # (the values of the panels without their holes are taken when under 60 % of the (row, entry) pairs exist: the kkt case below)
     cases = [gen.random_csr(777, 1234, 70, seed=n, empty_every=13), gen.banded_fem(5000, offsets=(1, 2, 3, 40, 41, 900), seed=n),
              gen.random_csr(13, 40, 5, seed=1), gen.kkt3d(10)]
     for rp, ci, va in cases:

@@ -41,18 +41,10 @@ The reads of part i + 1 are issued before the wait for part i.
 fp32 instances (gen(..., f32=True)): the same loop with 128-byte value slots (8 floats per part: ds_read_b32, lane l
 holds value l & 7); per row one v_mov_b32_dpp broadcasts the value and NV * 2 x v_pk_fma_f32 take the four floats of the
 lane's 16-byte piece two at a time (accumulators are 64-bit pairs, as in fp64).
-T2_BPOL (environment, generation time) appends a cache policy to the B-row DMAs; measured on the pwtk stand-in:
-nt +35 % time, sc0 / sc1 / sc0 sc1 within +-2 %; the committed file uses none.
 
 usage: tools/gen_team2_asm.py > crp-spmm_amd/csrc/team2_consume.inc
 """
-import os
 import sys
-
-# cache policy of the B-row DMA (experiment knob at generation time): '', ' nt', ' sc0', ' sc1', ' sc0 sc1'
-BPOL = os.environ.get('T2_BPOL', '')
-# ... of the value and record DMAs (A's streams are read once)
-APOL = os.environ.get('T2_APOL', '')
 
 D = 3
 NSET = 4
@@ -189,9 +181,9 @@ def gen(nv, has_b1, f32=False, compact=True, half=False):
             emit(".Lt2bj%d%s:" % (k, tag))
         if half:
             emit("s_mov_b64 exec, 0xffffffff")       # 32 lanes x 16 bytes = the 512-byte slice (the value DMA below sets EXEC again)
-        emit("global_load_lds_dwordx4 %%[voffa], s[%d:%d]%s" % (RB, RB + 1, BPOL))
+        emit("global_load_lds_dwordx4 %%[voffa], s[%d:%d]" % (RB, RB + 1))
         if nv == 2:
-            emit("global_load_lds_dwordx4 %%[voffb], s[%d:%d] offset:1024%s" % (RB, RB + 1, BPOL))
+            emit("global_load_lds_dwordx4 %%[voffb], s[%d:%d] offset:1024" % (RB, RB + 1))
         # the wave's value block of round r + D: offset in units of 4 values, 4 (q + 1) lanes of 16 bytes (fp32: 2 (q + 1))
         emit("s_and_b32 s%d, %%[w2], 0xfffff" % T)
         emit("s_add_u32 m0, %%[vringw], %d" % (kd * vslot))      # (early: no s_nop in front of the DMA that reads it)
@@ -205,7 +197,7 @@ def gen(nv, has_b1, f32=False, compact=True, half=False):
             emit("s_bfm_b64 exec, s%d, 0" % T)
         else:
             emit("s_mov_b64 exec, 0x%x" % ((1 << (vslot // 16)) - 1))
-        emit("global_load_lds_dwordx4 v%d, %%[vbase]%s" % (TV, APOL))
+        emit("global_load_lds_dwordx4 v%d, %%[vbase]" % TV)
         emit("s_mov_b64 exec, -1")
         emit(".Lt2ni%d%s:" % (k, tag))
         # -- next record block (one wave, every 8 rounds)
@@ -216,9 +208,9 @@ def gen(nv, has_b1, f32=False, compact=True, half=False):
         emit("s_xor_b32 %%[recdst], %%[recdst], %d" % recblk)
         emit("s_mov_b32 m0, %[recdst]")
         emit("s_nop 0")
-        emit("global_load_lds_dwordx4 %%[lane16], s[%d:%d]%s" % (RS, RS + 1, APOL))
+        emit("global_load_lds_dwordx4 %%[lane16], s[%d:%d]" % (RS, RS + 1))
         for piece in range(1, recblk // 1024):      # (an immediate offset moves the global AND the LDS address)
-            emit("global_load_lds_dwordx4 %%[lane16], s[%d:%d] offset:%d%s" % (RS, RS + 1, 1024 * piece, APOL))
+            emit("global_load_lds_dwordx4 %%[lane16], s[%d:%d] offset:%d" % (RS, RS + 1, 1024 * piece))
         emit(".Lt2nr%d%s:" % (k, tag))
         # -- record of the next round (LDS reads return in order: it is there when the parts are done)
         if k < NSET - 1:

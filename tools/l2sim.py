@@ -4,8 +4,7 @@ over the 8 XCDs (workgroup i runs on XCD i % 8, `--wgs` workgroups resident per 
 round of 8 rows per time step) against one LRU of `--rows` B rows per XCD, and prints the rows that miss.
 A planning tool for the team order / union order (csrc/panel_format.cpp); measured counterparts: profiles/r02_traffic.json.
 
-usage: l2sim.py [--matrix pwtk|pwtk_shell|...] [--rows 1400] [--wgs 64] [--n 256]
-Environment knobs of the packer (CRPSPMM_TEAM2_PHASE, CRPSPMM_TEAM2_SHAPE, ...) apply."""
+usage: l2sim.py [--matrix pwtk|pwtk_shell|...] [--rows 1400] [--wgs 64] [--n 256]"""
 import argparse
 import os
 import sys
