@@ -4,19 +4,25 @@
 One "step" = one C := A * B of the hot path (rp_spmm_exec / para2d_spmm_exec,
 /root/reference/src/rowpara_spmm.c:212-422) with A, B and C resident in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--n 256] [--matrix pwtk | --mtx FILE]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--n 256] [--matrix pwtk | --mtx FILE] [--full]
 
 N = 1 : BASELINE configs[1] -- pwtk x n = 256, fp64, 1 MI355X, rp_spmm HIP kernel.  The matrix is the real
         pwtk.mtx when --mtx names it or $CRPSPMM_MTX_DIR holds it (read through the library's own Matrix-Market
         ingest, examples/mmio_utils.c:11-190 restated in csrc/mmio_utils.cpp); otherwise -- no SuiteSparse files
         and no network in the containers -- the seeded stand-in gen.banded_fem(217918), and the JSON says so.
-        The default run also times the IRREGULAR pwtk-class stand-in (gen.shell_fem: jittered shell mesh, 6
+        With --full the run also times the IRREGULAR pwtk-class stand-in (gen.shell_fem: jittered shell mesh, 6
         unknowns per node) with the same protocol and reports it under config.also (--no-also skips it).
 N > 1 : the same matrix and n, 2D grid chosen by the planner for an A that is multiplied (steps + warmup)
         times -- crp_spmm_part2d_amortized, the reference's cost terms with its "rA = times A is reused"
         applied consistently (--grid reference: the reference rule with rA = 1) --, one rank per GPU over
         torch.distributed (control plane gloo, device payloads over RCCL); strong scaling (total work fixed).
 Prints ONE JSON line on rank 0.
+
+A plain run does what the headline figure needs and nothing else: it sets up, warms up, times the K steps, writes
+--dump-outputs and prints the line.  --full adds the closed-form check of C after the warm-up (config.check_rel_err;
+--check 0 / 1 overrides) and, after the timed steps, the host-pointer call (config.host_pointer_exec_ms; --host-exec 0 / 1
+overrides), the CPU baseline (cpu_baseline, N = 1; --no-cpu-baseline skips it) and the irregular stand-in above
+(config.also; --no-also skips it).  What a plain run leaves out is null or absent in its line.
 
 --dump-outputs DIR writes C as the last timed step left it to DIR/C.npy (DIR/C_rank<r>.npy per rank for N > 1), in the
 product's dtype; a C larger than the dump budget is written as a fixed seeded sample of its rows, named in the JSON line
@@ -419,7 +425,7 @@ def measure(args, matrix, mtx, steps, lib, torch, dist, comm, dev, world, rank, 
                 step()
             torch.cuda.synchronize()
 
-    stage("checked; timing %d steps" % steps)
+    stage("%stiming %d steps" % ("checked; " if args.check else "", steps))
     # ---- timed region: K steps between barrier + synchronize; HIP events per step on the launch stream
     ev = [(C.c_void_p(), C.c_void_p()) for _ in range(steps)]
     for a, b in ev:
@@ -494,7 +500,9 @@ def measure(args, matrix, mtx, steps, lib, torch, dist, comm, dev, world, rank, 
     return res
 
 
-def main():
+def parse_args(argv=None):
+    """Command line -> args, with what --full decides resolved: args.check and args.host_exec (0 / 1), args.cpu_baseline
+    and args.also (whether those legs run where they apply)."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
@@ -506,16 +514,30 @@ def main():
     ap.add_argument("--dtype", default="f64", choices=("f64", "f32"), help="f32: the fp32 value path (one GPU, device-level API)")
     ap.add_argument("--grid", default="amortized", choices=("amortized", "reference", "timed"),
                     help="N > 1: planner rule for the process grid (see module docstring)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="skip the irregular pwtk-class stand-in of the default run")
-    ap.add_argument("--check", type=int, default=1)
-    ap.add_argument("--host-exec", type=int, default=1, help="also time rp_spmm_exec with host B / C (config.host_pointer_exec_ms)")
+    ap.add_argument("--full", action="store_true",
+                    help="also check C, time the host-pointer call, the CPU baseline and the irregular stand-in (see module docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-also", action="store_true", help="with --full: skip the irregular pwtk-class stand-in")
+    ap.add_argument("--check", type=int, default=None, help="check C against its closed form (default: 1 with --full, else 0)")
+    ap.add_argument("--host-exec", type=int, default=None,
+                    help="also time rp_spmm_exec with host B / C (config.host_pointer_exec_ms; default: 1 with --full, else 0)")
     ap.add_argument("--sweep-variants", action="store_true", help="also time the other kernel variants (stderr)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write C of the last timed step to DIR/<name>.npy (see module docstring)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.check is None:
+        args.check = int(args.full)
+    if args.host_exec is None:
+        args.host_exec = int(args.full)
+    args.cpu_baseline = args.full and not args.no_cpu_baseline
+    args.also = args.full and not args.no_also
+    return args
+
+
+def main():
+    args = parse_args()
 
     import torch
     import torch.distributed as dist
@@ -548,10 +570,10 @@ def main():
         if world != 1:
             raise SystemExit("--dtype f32 is a one-GPU measurement")
         main_res = measure_f32(args, args.matrix, mtx, args.steps, lib, torch, dev)
-        args.no_also = True
+        args.also = False
     else:
         main_res = measure(args, args.matrix, mtx, args.steps, lib, torch, dist, comm, dev, world, rank,
-                           with_cpu=(rank == 0 and world == 1 and not args.no_cpu_baseline), with_dump=bool(args.dump_outputs))
+                           with_cpu=(rank == 0 and world == 1 and args.cpu_baseline), with_dump=bool(args.dump_outputs))
     rccl_info = main_res.get("rccl")
     dump_info = None
     if args.dump_outputs:
@@ -562,7 +584,7 @@ def main():
         dump_info = {"dir": args.dump_outputs, "files": {name: {"shape": list(arr.shape), "dtype": str(arr.dtype), "rows": rows_note}}}
         del arr
     also = None
-    if world == 1 and mtx is None and args.matrix == "pwtk" and args.variant == 0 and not args.no_also:
+    if world == 1 and mtx is None and args.matrix == "pwtk" and args.variant == 0 and args.also:
         r2 = measure(args, "pwtk_shell", None, min(args.steps, 100), lib, torch, dist, comm, dev, world, rank, with_cpu=False)
         also = {"workload": "%s x n=%d" % (r2["label"], r2["n"]), "nnz": r2["nnz"], "ms_per_step": r2["ms_per_step"],
                 "GFLOP/s": r2["value"], "kernel": r2["kernel"], "roofline_frac": r2["achieved"] / HBM_PEAK_GBS,
@@ -578,7 +600,7 @@ def main():
         "ms_per_step": r["ms_per_step"], "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
         "dtype": args.dtype, "data": r["data"],
         "config": {"workload": "%s x n=%d, rp_spmm/para2d_spmm exec, operands resident in HBM" % (r["label"], r["n"]),
-                   "rows": r["rows"], "nnz": r["nnz"], "n": r["n"], "grid": r["grid"], "kernel_variant": args.variant,
+                   "rows": r["rows"], "nnz": r["nnz"], "n": r["n"], "grid": r["grid"], "full": args.full, "kernel_variant": args.variant,
                    "kernel_variant_resolved": r["kernel_info"]["variant_name"],
                    "locality_order": r["kernel_info"]["reordered"], "lattice_detected": r["kernel_info"]["lattice"],
                    "rccl_ranks": rccl_ranks, "rccl": rccl_info, "first_exec_s": r["first_exec_s"],

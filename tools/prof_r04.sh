@@ -4,7 +4,7 @@
 #   prof_r04.sh stats   : rocprofv3 kernel statistics of the default bench command
 #   prof_r04.sh pmc A   : PMC passes (one counter group per pass, tools/prof_pmc.sh) for workload A in
 #                         {pwtk, shell, kkt, fem3d, fem3d_f32}; "queen" = the three fetch passes + WRITE_SIZE at Queen_4147 size, fp32
-#   prof_r04.sh bench   : the default bench line (with the CPU baseline), the n = 32 / 256 / 1024 sweep, the other stand-ins
+#   prof_r04.sh bench   : the --full bench line (with the CPU baseline), the n = 32 / 256 / 1024 sweep, the other stand-ins
 #   prof_r04.sh big     : Queen_4147-size fp32 n = 1024, nlpkkt240-size width sweeps (light and 13-point coupling)
 set -o pipefail
 OUT=gpurun_out/r04
@@ -36,7 +36,7 @@ pmc)
   grep -E "^==|FETCH_SIZE KB|WRITE_SIZE|TCC_HIT|TCC_MISS" $OUT/pmc_$2*.txt | cut -c1-200
   ;;
 bench)
-  timeout -k 10 600 python bench.py > $OUT/bench_n1.json 2> $OUT/bench_n1.err || { tail -5 $OUT/bench_n1.err; exit 1; }
+  timeout -k 10 600 python bench.py --full > $OUT/bench_n1.json 2> $OUT/bench_n1.err || { tail -5 $OUT/bench_n1.err; exit 1; }
   cut -c1-1500 $OUT/bench_n1.json
   bash tools/sweep.sh 1 $OUT/sweep.jsonl > /dev/null || exit 1
   for cfg in "kkt 256" "kkt 128" "kkt 64" "kkt 32" "fem3d 256" "fem3d 1024" "fem3d 128" "pwtk 128" "pwtk 64" "pwtk_shell 128"; do
