@@ -126,6 +126,9 @@ SIGNATURES = {
     "crp_event_elapsed_ms": (_I, [_V, _V, C.POINTER(C.c_float)]),
     "crp_csr_dev_create": (_I, [_I, _I, c_int_p, c_int_p, c_dbl_p, C.POINTER(_V)]),
     "crp_csr_dev_create_dv": (_I, [_I, _I, c_int_p, c_int_p, c_dbl_p, _V, c_int_p, C.POINTER(_V)]),
+    "crp_csr_dev_create_t": (_I, [_I, _I, c_int_p, c_int_p, c_dbl_p, C.POINTER(_V)]),
+    "crp_csr_dev_is_transposed": (_I, [_V]),
+    "crp_csr_transpose": (_I, [_I, _I, _V, _V, _V, _V, _V, _V, _V, _V]),
     "crp_csr_dev_destroy": (_I, [C.POINTER(_V)]),
     "crp_csr_dev_update_values": (_I, [_V, _V, _V]),
     "crp_csr_dev_set_rowmap": (_I, [_V, c_int_p, _I]),
@@ -165,6 +168,7 @@ SIGNATURES = {
     "crp_spmm_variant_count": (_I, []),
     "crp_gather_rows_f64": (_I, [_I, _I, _I, _V, _V, _LL, _V, _LL, _V]),
     "crp_scatter_rows_f64": (_I, [_I, _I, _I, _V, _V, _LL, _V, _LL, _V]),
+    "crp_scatter_add_rows_f64": (_I, [_I, _I, _V, _V, _V, _V, _LL, _V, _LL, _V]),
     "crp_transpose_f64": (_I, [_I, _I, _V, _LL, _V, _LL, _V]),
     "crp_gather_rows_f32": (_I, [_I, _I, _I, _V, _V, _LL, _V, _LL, _V]),
     "crp_scatter_rows_f32": (_I, [_I, _I, _I, _V, _V, _LL, _V, _LL, _V]),
@@ -181,6 +185,8 @@ SIGNATURES = {
     "crp_rp_spmm_exec": (None, [_V, _I, _V, _I, _V, _I]),
     "crp_rp_spmm_exec_ex": (None, [_V, _I, _V, _LL, _V, _LL, _V]),
     "crp_rp_spmm_exec_f32_ex": (None, [_V, _I, _V, _LL, _V, _LL, _V]),
+    "crp_rp_spmm_exec_t_ex": (None, [_V, _I, _V, _LL, _V, _LL, _V]),
+    "crp_rp_spmm_transposed_built": (_I, [_V]),
     "crp_rp_spmm_print_stat": (None, [_V]),
     "crp_rp_spmm_clear_stat": (None, [_V]),
     "crp_rp_spmm_get_plan": (None, [_V, C.POINTER(RpPlanView)]),

@@ -16,6 +16,7 @@
 #include "dispatch.h"
 #include "locality.h"
 #include "knobs.h"
+#include "csr_transpose.h"
 
 // a device allocation that frees itself (move-only)
 template <typename T> struct DevBuf
@@ -127,6 +128,10 @@ struct crp_csr_dev
     // crp_csr_dev_update_values() with a DEVICE pointer leaves the host copies (h_val / f_val) behind: formats built
     // afterwards take their values from the device CSR through their fresh slot maps (refresh_values_after_build)
     bool      host_vals_stale = false;
+    // crp_csr_dev_create_t: this handle holds A^T; tmap[q] = position in A's arrays of nonzero q (device and host copies), so
+    // that value updates, which come in A's order, can be gathered into this handle's order.  Empty for every other handle.
+    DevBuf<int> tmap;
+    std::vector<int> h_tmap;
     // The R = 8 panels in column order WITHOUT values (pcol, masks, slot map: 7 bytes per nonzero at fill 0.23) and the teams built on
     // them: shared by the team formats of this matrix (team2, team2r for <= 32 and <= 64 columns) -- a further operand width costs the
     // streams of its format, not the panels and the clustering again.  Dropped once the two that variant 0 uses exist.
@@ -543,6 +548,37 @@ __global__ void gather_row_vals_kernel(const int nrow, const int *__restrict__ d
     }
 }
 
+// the host side of a handle whose device CSR is in place: the host copies, the locality order, the traits
+static int csr_dev_host_side(crp_csr_dev *A, const int *rowptr, const int *colidx, const double *val)
+{
+    const int nrow = A->nrow, ncol = A->ncol;
+    const long long nnz = A->nnz;
+    for (long long p = 0; p < nnz; p++)
+    {
+        const int c = colidx[p];
+        if (c >= 0) { if (c + 1LL > A->b0_rows) A->b0_rows = c + 1LL; }
+        else if ((long long) (~c) + 1 > A->b1_rows) A->b1_rows = (long long) (~c) + 1;
+    }
+    if (A->b0_rows > ncol && ncol > 0) return -2;      // a column index addresses a row past B0
+    A->h_rowptr.assign(rowptr, rowptr + nrow + 1);
+    if (nnz > 0)
+    {
+        A->h_colidx.assign(colidx, colidx + nnz);
+        A->h_val.assign(val, val + nnz);
+    }
+    A->ord = crp::format_order(nrow, ncol, rowptr, colidx, A->b1_rows > 0);
+    if (!A->ord.perm.empty())
+    {
+        A->f_val.resize((size_t) nnz);
+        for (long long q = 0; q < nnz; q++) A->f_val[(size_t) q] = val[A->ord.f_nz[(size_t) q]];
+        CRP_TRY(upload(A->rowmap_fmt, A->ord.perm.data(), sizeof(int) * (size_t) nrow, 0));
+    }
+    A->traits = crp::matrix_traits(nrow, fmt_rowptr(A), fmt_colidx(A));
+    // (the derived formats are built by the first product that uses them: a matrix multiplied by wide operands only never
+    //  needs its row-panel format -- 20 GB for the nlpkkt240-size stand-in)
+    return 0;
+}
+
 static int csr_dev_create_impl(int nrow, int ncol, const int *rowptr, const int *colidx, const double *val, const double *val_dev,
                                const int *src_start, crp_csr_dev_p *out)
 {
@@ -583,29 +619,8 @@ static int csr_dev_create_impl(int nrow, int ncol, const int *rowptr, const int 
         }
     }
     if (e != hipSuccess) return (int) e;
-    for (long long p = 0; p < nnz; p++)
-    {
-        const int c = colidx[p];
-        if (c >= 0) { if (c + 1LL > A->b0_rows) A->b0_rows = c + 1LL; }
-        else if ((long long) (~c) + 1 > A->b1_rows) A->b1_rows = (long long) (~c) + 1;
-    }
-    if (A->b0_rows > ncol && ncol > 0) return -2;      // a column index addresses a row past B0
-    A->h_rowptr.assign(rowptr, rowptr + nrow + 1);
-    if (nnz > 0)
-    {
-        A->h_colidx.assign(colidx, colidx + nnz);
-        A->h_val.assign(val, val + nnz);
-    }
-    A->ord = crp::format_order(nrow, ncol, rowptr, colidx, A->b1_rows > 0);
-    if (!A->ord.perm.empty())
-    {
-        A->f_val.resize((size_t) nnz);
-        for (long long q = 0; q < nnz; q++) A->f_val[(size_t) q] = val[A->ord.f_nz[(size_t) q]];
-        CRP_TRY(upload(A->rowmap_fmt, A->ord.perm.data(), sizeof(int) * (size_t) nrow, 0));
-    }
-    A->traits = crp::matrix_traits(nrow, fmt_rowptr(A.get()), fmt_colidx(A.get()));
-    // (the derived formats are built by the first product that uses them: a matrix multiplied by wide operands only never
-    //  needs its row-panel format -- 20 GB for the nlpkkt240-size stand-in)
+    const int rc = csr_dev_host_side(A.get(), rowptr, colidx, val);
+    if (rc != 0) return rc;
     *out = A.release();
     return 0;
 }
@@ -622,6 +637,54 @@ int crp_csr_dev_create_dv(int nrow, int ncol, const int *rowptr, const int *coli
     if (val_dev == NULL) return -1;
     return csr_dev_create_impl(nrow, ncol, rowptr, colidx, val_host, val_dev, src_start, out);
 }
+
+int crp_csr_dev_create_t(int nrow, int ncol, const int *rowptr, const int *colidx, const double *val, crp_csr_dev_p *out)
+{
+    if (out == NULL) return CRP_CSR_T_EARG;
+    *out = NULL;
+    if (nrow < 0 || ncol < 0 || rowptr == NULL) return CRP_CSR_T_EARG;
+    if (rowptr[0] != 0) return CRP_CSR_T_EPTR;
+    const long long nnz = rowptr[nrow];
+    if (nnz < 0) return CRP_CSR_T_EPTR;
+    if (nnz > 0 && (colidx == NULL || val == NULL)) return CRP_CSR_T_EARG;
+    std::unique_ptr<crp_csr_dev> A(new (std::nothrow) crp_csr_dev);
+    if (A == NULL) return -3;
+    A->nrow = ncol;                                  // the handle is A^T
+    A->ncol = nrow;
+    A->nnz  = nnz;
+    const size_t n1 = (size_t) (nnz > 0 ? nnz : 1);
+    // A's arrays go up once, into temporaries that live until the transpose is done
+    DevBuf<int> a_rowptr, a_colidx;
+    DevBuf<double> a_val;
+    hipError_t e = a_rowptr.alloc(sizeof(int) * ((size_t) nrow + 1));
+    if (e == hipSuccess) e = a_colidx.alloc(sizeof(int) * n1);
+    if (e == hipSuccess) e = a_val.alloc(sizeof(double) * n1);
+    if (e == hipSuccess) e = A->rowptr.alloc(sizeof(int) * ((size_t) ncol + 1));
+    if (e == hipSuccess) e = A->colidx.alloc(sizeof(int) * n1);
+    if (e == hipSuccess) e = A->val.alloc(sizeof(double) * n1);
+    if (e == hipSuccess) e = A->tmap.alloc(sizeof(int) * n1);
+    if (e == hipSuccess) e = hipMemcpy(a_rowptr, rowptr, sizeof(int) * ((size_t) nrow + 1), hipMemcpyHostToDevice);
+    if (e == hipSuccess && nnz > 0) e = hipMemcpy(a_colidx, colidx, sizeof(int) * (size_t) nnz, hipMemcpyHostToDevice);
+    if (e == hipSuccess && nnz > 0) e = hipMemcpy(a_val, val, sizeof(double) * (size_t) nnz, hipMemcpyHostToDevice);
+    if (e != hipSuccess) return (int) e;
+    int rc = crp::csr_transpose_dev(nrow, ncol, a_rowptr, a_colidx, a_val, A->rowptr, A->colidx, A->val, A->tmap, nullptr);
+    if (rc != 0) return rc;
+    // the transposed arrays come back for the host-side format builders; tmap stays in device memory as well
+    std::vector<int> t_rowptr((size_t) ncol + 1), t_colidx(n1);
+    std::vector<double> t_val(n1);
+    A->h_tmap.resize((size_t) nnz);
+    e = hipMemcpy(t_rowptr.data(), A->rowptr, sizeof(int) * ((size_t) ncol + 1), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && nnz > 0) e = hipMemcpy(t_colidx.data(), A->colidx, sizeof(int) * (size_t) nnz, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && nnz > 0) e = hipMemcpy(t_val.data(), A->val, sizeof(double) * (size_t) nnz, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && nnz > 0) e = hipMemcpy(A->h_tmap.data(), A->tmap, sizeof(int) * (size_t) nnz, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return (int) e;
+    rc = csr_dev_host_side(A.get(), t_rowptr.data(), t_colidx.data(), t_val.data());
+    if (rc != 0) return rc;
+    *out = A.release();
+    return 0;
+}
+
+int crp_csr_dev_is_transposed(crp_csr_dev_p A) { return A ? (A->tmap ? 1 : 0) : -1; }
 
 int crp_csr_dev_destroy(crp_csr_dev_p *A_)
 {
@@ -644,11 +707,20 @@ int crp_csr_dev_update_values(crp_csr_dev_p A, const double *val, void *stream)
     int is_dev = 0;
     crp_dev_ptr_is_device(val, &is_dev);
     const hipStream_t s = (hipStream_t) stream;
-    CRP_TRY(hipMemcpyAsync(A->val, val, sizeof(double) * (size_t) A->nnz, is_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    // a handle for A^T (crp_csr_dev_create_t) takes val in A's order: from device memory the device CSR gathers it through tmap,
+    // from host memory the host copy does the same gather and goes up as it is
+    if (A->tmap && is_dev) CRP_TRY(crp::gather_vals_f64(A->nnz, A->tmap, val, A->val, s));
+    else
+    {
+        if (A->tmap)
+            for (long long q = 0; q < A->nnz; q++) A->h_val[(size_t) q] = val[A->h_tmap[(size_t) q]];
+        CRP_TRY(hipMemcpyAsync(A->val, A->tmap ? A->h_val.data() : val, sizeof(double) * (size_t) A->nnz,
+                               is_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    }
     if (!is_dev)
     {
-        memcpy(A->h_val.data(), val, sizeof(double) * (size_t) A->nnz);   // formats built later see the new values
-        for (size_t q = 0; q < A->f_val.size(); q++) A->f_val[q] = val[A->ord.f_nz[q]];
+        if (!A->tmap) memcpy(A->h_val.data(), val, sizeof(double) * (size_t) A->nnz);   // formats built later see the new values
+        for (size_t q = 0; q < A->f_val.size(); q++) A->f_val[q] = A->h_val[(size_t) A->ord.f_nz[q]];
         A->host_vals_stale = false;
     }
     else A->host_vals_stale = true;      // formats built later are refreshed from the device CSR (ensure_*)
@@ -1024,6 +1096,14 @@ int crp_scatter_rows_f64(int layout, int nidx, int n, const int *ridx, const dou
 {
     if (nidx < 0 || n < 0 || (layout != 0 && layout != 1)) return -1;
     return (int) crp::scatter_rows_f64(layout, nidx, n, ridx, src, lds, dst, ldd, (hipStream_t) stream);
+}
+
+int crp_scatter_add_rows_f64(int nseg, int n, const int *seg_row, const int *seg_ptr, const int *seg_pos, const double *src,
+                             long long lds, double *dst, long long ldd, void *stream)
+{
+    if (nseg < 0 || n < 0) return -1;
+    if (nseg > 0 && n > 0 && (seg_row == NULL || seg_ptr == NULL || seg_pos == NULL || src == NULL || dst == NULL)) return -1;
+    return (int) crp::scatter_add_rows_f64(nseg, n, seg_row, seg_ptr, seg_pos, src, lds, dst, ldd, (hipStream_t) stream);
 }
 
 int crp_transpose_f64(int nrow, int ncol, const double *src, long long lds, double *dst, long long ldd,

@@ -112,6 +112,9 @@ hipError_t gather_rows_f64(int layout, int nidx, int n, const int *ridx, const d
 hipError_t scatter_rows_f64(int layout, int nidx, int n, const int *ridx, const double *src, int64_t lds,
                             double *dst, int64_t ldd, hipStream_t s);
 hipError_t scatter_vals_f64(int64_t n, const uint32_t *map, const double *src, double *dst, hipStream_t s);
+hipError_t gather_vals_f64(int64_t n, const int *map, const double *src, double *dst, hipStream_t s);      // dst[i] = src[map[i]]
+hipError_t scatter_add_rows_f64(int nseg, int n, const int *seg_row, const int *seg_ptr, const int *seg_pos, const double *src,
+                                int64_t lds, double *dst, int64_t ldd, hipStream_t s);
 hipError_t convert_f64_f32(int64_t n, const double *src, float *dst, hipStream_t s);
 hipError_t transpose_f64(int nrow, int ncol, const double *src, int64_t lds, double *dst, int64_t ldd,
                          hipStream_t s);

@@ -25,17 +25,13 @@
 #include "crp_part.h"
 #include "crpspmm_hip.h"
 #include "graph_part.h"
+#include "scan_sort.h"
 
 namespace crp {
 
 namespace {
 
-constexpr int WAVE = 64;
-constexpr int LDS_PAIRS = 4096;         // largest row sorted in LDS (partition.py: PERMUTE_LDS_PAIRS)
-constexpr int MID_THREADS = 256;
-constexpr int LONG_THREADS = 1024;
-constexpr int SCAN_THREADS = 256, SCAN_ITEMS = 8, SCAN_TILE = SCAN_THREADS * SCAN_ITEMS;
-constexpr uint64_t PAD = ~(uint64_t) 0;
+using namespace devsort;                // scan_sort.h: the tier limits, the scan, the sorts' building blocks
 enum { F_PTR = 1, F_PERM = 2, F_COL = 4 };
 
 struct Census
@@ -46,13 +42,6 @@ struct Census
 __device__ inline uint64_t row_key(const int *perm, const int *colidx, int in, int t)
 {
     return ((uint64_t) (uint32_t) perm[colidx[in + t]] << 32) | (uint32_t) t;
-}
-
-__device__ inline int pow2_at_least(int x)
-{
-    int n = 1;
-    while (n < x) n <<= 1;
-    return n;
 }
 
 // ---- pass 1
@@ -90,78 +79,9 @@ __global__ void k_scatter_lengths(int nrow, int nnz, const int *__restrict__ row
     if (flags) atomicOr(&cs->flags, flags);
 }
 
-// ---- pass 2: exclusive scan of x[0 .. n) in place
-template <int NT>
-__device__ inline int block_exclusive_scan(int v, int *s, int *total = nullptr)
-{
-    const int tid = threadIdx.x;
-    s[tid] = v;
-    __syncthreads();
-    for (int off = 1; off < NT; off <<= 1)
-    {
-        const int add = tid >= off ? s[tid - off] : 0;
-        __syncthreads();
-        s[tid] += add;
-        __syncthreads();
-    }
-    const int incl = s[tid];
-    if (total) *total = s[NT - 1];
-    __syncthreads();
-    return incl - v;
-}
-
-__global__ void __launch_bounds__(SCAN_THREADS) k_scan_tile_sums(int n, const int *__restrict__ x, int *bsum)
-{
-    __shared__ int s[SCAN_THREADS];
-    const long long base = (long long) blockIdx.x * SCAN_TILE + (long long) threadIdx.x * SCAN_ITEMS;
-    int v = 0;
-    for (int j = 0; j < SCAN_ITEMS; j++)
-        if (base + j < n) v += x[base + j];
-    const int ex = block_exclusive_scan<SCAN_THREADS>(v, s);
-    if (threadIdx.x == SCAN_THREADS - 1) bsum[blockIdx.x] = ex + v;
-}
-
-__global__ void __launch_bounds__(1024) k_scan_block_sums(int nb, int *bsum)
-{
-    __shared__ int s[1024];
-    int carry = 0;
-    for (int b0 = 0; b0 < nb; b0 += 1024)
-    {
-        const int b = b0 + (int) threadIdx.x;
-        const int v = b < nb ? bsum[b] : 0;
-        int chunk = 0;
-        const int ex = block_exclusive_scan<1024>(v, s, &chunk);
-        if (b < nb) bsum[b] = carry + ex;
-        carry += chunk;
-    }
-}
-
-__global__ void __launch_bounds__(SCAN_THREADS) k_scan_tile_apply(int n, int *x, const int *__restrict__ bsum)
-{
-    __shared__ int s[SCAN_THREADS];
-    const long long base = (long long) blockIdx.x * SCAN_TILE + (long long) threadIdx.x * SCAN_ITEMS;
-    int v[SCAN_ITEMS], sum = 0;
-    for (int j = 0; j < SCAN_ITEMS; j++)
-    {
-        v[j] = base + j < n ? x[base + j] : 0;
-        sum += v[j];
-    }
-    int run = bsum[blockIdx.x] + block_exclusive_scan<SCAN_THREADS>(sum, s);
-    for (int j = 0; j < SCAN_ITEMS; j++)
-        if (base + j < n)
-        {
-            x[base + j] = run;
-            run += v[j];
-        }
-}
+// ---- pass 2: the exclusive scan of scan_sort.h
 
 // ---- pass 3
-__device__ inline uint64_t shfl_xor_u64(uint64_t v, int mask)
-{
-    const int lo = __shfl_xor((int) (uint32_t) v, mask), hi = __shfl_xor((int) (uint32_t) (v >> 32), mask);
-    return ((uint64_t) (uint32_t) hi << 32) | (uint32_t) lo;
-}
-
 // rows of 1 .. 64 entries: one wave per row, one key per lane
 __global__ void __launch_bounds__(256) k_sort_short(int nrow, const int *__restrict__ rowptr, const int *__restrict__ colidx,
                                                     const double *__restrict__ val, const int *__restrict__ perm,
@@ -174,42 +94,13 @@ __global__ void __launch_bounds__(256) k_sort_short(int nrow, const int *__restr
         if (len == 0 || len > WAVE) continue;                       // (wave-uniform)
         const int out = rowptr1[perm[i]], np2 = pow2_at_least(len);
         uint64_t key = lane < len ? row_key(perm, colidx, in, lane) : PAD;
-        for (int k = 2; k <= np2; k <<= 1)
-            for (int j = k >> 1; j > 0; j >>= 1)
-            {
-                const uint64_t other = shfl_xor_u64(key, j);
-                const bool up = (lane & k) == 0, lower = (lane & j) == 0;
-                key = (lower == up) ? (key < other ? key : other) : (key < other ? other : key);
-            }
+        key = wave_bitonic(key, lane, np2);
         if (lane < len)
         {
             colidx1[out + lane] = (int) (key >> 32);
             val1[out + lane] = val[in + (int) (uint32_t) key];
         }
     }
-}
-
-// bitonic sort of s[0 .. np2) (np2 a power of two) by the threads of one workgroup
-__device__ inline void block_bitonic(uint64_t *s, int np2)
-{
-    for (int k = 2; k <= np2; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1)
-        {
-            for (int t = threadIdx.x; t < np2; t += blockDim.x)
-            {
-                const int p = t ^ j;
-                if (p > t)
-                {
-                    const uint64_t a = s[t], b = s[p];
-                    if ((a > b) == ((t & k) == 0))
-                    {
-                        s[t] = b;
-                        s[p] = a;
-                    }
-                }
-            }
-            __syncthreads();
-        }
 }
 
 __device__ inline void sort_row_in(uint64_t *s, int i, const int *rowptr, const int *colidx, const double *val, const int *perm,
@@ -264,7 +155,7 @@ int csr_permute_sym_dev(int nrow, const int *rowptr, const int *colidx, const do
     Census cs = {0, 0, 0, 0};
     char *work = nullptr;
     uint64_t *scratch = nullptr;
-    const int nb = (nrow + 1 + SCAN_TILE - 1) / SCAN_TILE;
+    const int nb = scan_tiles(nrow + 1);
     int *hit = nullptr, *lists = nullptr, *bsum = nullptr;
     Census *dcs = nullptr;
     long long span = 0;
@@ -311,10 +202,7 @@ int csr_permute_sym_dev(int nrow, const int *rowptr, const int *colidx, const do
         goto done;
     }
     // ---- pass 2
-    hipLaunchKernelGGL(k_scan_tile_sums, dim3(nb), dim3(SCAN_THREADS), 0, st, nrow + 1, rowptr1, bsum);
-    hipLaunchKernelGGL(k_scan_block_sums, dim3(1), dim3(1024), 0, st, nb, bsum);
-    hipLaunchKernelGGL(k_scan_tile_apply, dim3(nb), dim3(SCAN_THREADS), 0, st, nrow + 1, rowptr1, bsum);
-    PERM_TRY(hipGetLastError());
+    PERM_TRY(exclusive_scan_inplace(nrow + 1, rowptr1, bsum, st));
     // ---- pass 3
     {
         const long long blocks = std::min<long long>((nrow + 3) / 4, 1 << 20);

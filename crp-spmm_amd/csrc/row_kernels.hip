@@ -289,6 +289,65 @@ hipError_t scatter_vals_f64(int64_t n, const uint32_t *map, const double *src, d
     return hipGetLastError();
 }
 
+// dst[i] = src[map[i]]: the values of a transposed handle from values in the original order (crp_csr_dev_update_values)
+__global__ __launch_bounds__(256) void gather_vals_kernel(const int64_t n, const int *__restrict__ map, const double *__restrict__ src,
+                                                          double *__restrict__ dst)
+{
+    for (int64_t i = (int64_t) blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t) gridDim.x * 256) dst[i] = src[map[i]];
+}
+
+hipError_t gather_vals_f64(int64_t n, const int *map, const double *src, double *dst, hipStream_t s)
+{
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(gather_vals_kernel, dim3(grid_for(n)), dim3(256), 0, s, n, map, src, dst);
+    return hipGetLastError();
+}
+
+// Segmented accumulate: dst[seg_row[t]] += src[seg_pos[k]] for k = seg_ptr[t] .. seg_ptr[t + 1] - 1, in that order.  One
+// thread owns a chunk of VW doubles of one destination row and adds the segment's source rows one after the other: the
+// destination rows are distinct, so nothing races and the sum has one order.
+template <int VW>
+__global__ __launch_bounds__(256) void scatter_add_rows_kernel(const int64_t nseg, const int cpr /* chunks per row */,
+                                                               const int *__restrict__ seg_row, const int *__restrict__ seg_ptr,
+                                                               const int *__restrict__ seg_pos, const double *__restrict__ src,
+                                                               const int64_t lds, double *__restrict__ dst, const int64_t ldd)
+{
+    const int64_t total = nseg * (int64_t) cpr;
+    for (int64_t x = (int64_t) blockIdx.x * 256 + threadIdx.x; x < total; x += (int64_t) gridDim.x * 256)
+    {
+        const int64_t t = x / cpr;
+        const int     c = (int) (x - t * cpr) * VW;
+        const int     k0 = seg_ptr[t], k1 = seg_ptr[t + 1];
+        double *out = dst + (int64_t) seg_row[t] * ldd + c;
+        if constexpr (VW == 2)
+        {
+            d2 acc = *reinterpret_cast<const d2 *>(out);
+            for (int k = k0; k < k1; k++) acc += *reinterpret_cast<const d2 *>(src + (int64_t) seg_pos[k] * lds + c);
+            *reinterpret_cast<d2 *>(out) = acc;
+        }
+        else
+        {
+            double acc = *out;
+            for (int k = k0; k < k1; k++) acc += src[(int64_t) seg_pos[k] * lds + c];
+            *out = acc;
+        }
+    }
+}
+
+hipError_t scatter_add_rows_f64(int nseg, int n, const int *seg_row, const int *seg_ptr, const int *seg_pos, const double *src,
+                                int64_t lds, double *dst, int64_t ldd, hipStream_t s)
+{
+    if (nseg <= 0 || n <= 0) return hipSuccess;
+    const bool vec2 = (n % 2 == 0) && (lds % 2 == 0) && (ldd % 2 == 0) && (((uintptr_t) src | (uintptr_t) dst) % 16 == 0);
+    if (vec2)
+        hipLaunchKernelGGL((scatter_add_rows_kernel<2>), dim3(grid_for((int64_t) nseg * (n / 2))), dim3(256), 0, s, (int64_t) nseg, n / 2,
+                           seg_row, seg_ptr, seg_pos, src, lds, dst, ldd);
+    else
+        hipLaunchKernelGGL((scatter_add_rows_kernel<1>), dim3(grid_for((int64_t) nseg * n)), dim3(256), 0, s, (int64_t) nseg, n, seg_row,
+                           seg_ptr, seg_pos, src, lds, dst, ldd);
+    return hipGetLastError();
+}
+
 // fp32 copy of fp64 values (the fp32 path keeps A's values in fp64 as the caller gave them and derives its own copy)
 __global__ void convert_f64_f32_kernel(const int64_t n, const double *__restrict__ src, float *__restrict__ dst)
 {

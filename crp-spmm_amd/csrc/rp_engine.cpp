@@ -59,6 +59,16 @@ struct crp_rp_spmm
     float *sendbuf32_dev = nullptr, *recvbuf32_dev = nullptr;
     std::vector<long long> x32_scnts, x32_sdispls, x32_rcnts, x32_rdispls;
     void   *stream = nullptr;
+    // transposed product (crp_rp_spmm_exec_t_ex), built by its first call: the transpose of the two-source local matrix cut by
+    // rows -- At_loc writes this rank's C block, At_rem the rows owed to peers (into recvbuf_dev, in the forward plan's peer order)
+    bool t_built = false;
+    crp_csr_dev_p At_loc = nullptr, At_rem = nullptr;
+    std::vector<int> t_src;                      // position in A_val of every nonzero of At_loc, then of At_rem
+    size_t t_loc_nnz = 0;
+    // the rows that come back (one per row this rank sends in the forward exchange), grouped by the C row they add to:
+    // acc_dev = rows[n_acc] | ptr[n_acc + 1] | positions in sendbuf_dev[n_send_rows], ascending inside a group
+    int  n_acc = 0;
+    int *acc_dev = nullptr;
     // staging (host-pointer API) and column-major temporaries, grown on demand
     double *B_stage = nullptr, *C_stage = nullptr, *B_rm = nullptr, *C_rm = nullptr;
     size_t  B_stage_sz = 0, C_stage_sz = 0, B_rm_sz = 0, C_rm_sz = 0;
@@ -344,6 +354,9 @@ void crp_rp_spmm_free(crp_rp_spmm_p *rp_spmm)
         crp_csr_dev_destroy(&e->A_dev);
         crp_csr_dev_destroy(&e->A_int);
         crp_csr_dev_destroy(&e->A_bnd);
+        crp_csr_dev_destroy(&e->At_loc);
+        crp_csr_dev_destroy(&e->At_rem);
+        crp_dev_free(e->acc_dev);
         if (e->xstream) crp_stream_destroy(e->xstream);
         if (e->ev_packed) crp_event_destroy(e->ev_packed);
         if (e->ev_landed) crp_event_destroy(e->ev_landed);
@@ -614,7 +627,237 @@ static void exec_impl(crp_rp_spmm *e, int BC_layout, const T *B, long long ldB, 
     e->n_exec++;
 }
 
+// ---- C := A^T * B (crp_rp_spmm_exec_t_ex) --------------------------------------------------------------------------------------
+// First call: the two-source local matrix, its remote columns renumbered behind the local ones, is transposed on the device
+// (crp_csr_transpose) and cut by rows into At_loc and At_rem; the rows that come back are grouped by the C row they add to.
+static void build_transposed(crp_rp_spmm *e)
+{
+    const int m = e->A_nrow, kb = e->loc_B_nrow, nr = (int) e->n_recv_rows;
+    const long long ncol_ll = (long long) kb + nr;
+    ASSERT_PRINTF(ncol_ll < INT_MAX, "rp_spmm_exec_t: %lld local + received rows pass the 32-bit row index\n", ncol_ll);
+    const int ncol = (int) ncol_ll;
+    const size_t nnz = e->A_val.size(), n1 = nnz > 0 ? nnz : 1;
+    std::vector<int> col(n1, 0), rp_t((size_t) ncol + 1, 0), ci_t(n1, 0);
+    std::vector<double> va_t(n1, 0.0);
+    e->t_src.assign(n1, 0);
+    for (size_t p = 0; p < nnz; p++)
+    {
+        const int c = e->dev_colidx_host[p];
+        col[p] = c >= 0 ? c : kb + ~c;
+    }
+    {
+        // device temporaries: val | val_t | rowptr | rowptr_t | col | col_t | tmap
+        const size_t vb = sizeof(double) * n1, ib = sizeof(int) * n1, rb = sizeof(int) * ((size_t) m + 1), tb = sizeof(int) * ((size_t) ncol + 1);
+        void *d = NULL;
+        HIP_OK(crp_dev_malloc(&d, 2 * vb + rb + tb + 3 * ib));
+        char *b = (char *) d;
+        double *d_val = (double *) b, *d_val_t = (double *) (b + vb);
+        int *d_rp = (int *) (b + 2 * vb), *d_rp_t = (int *) (b + 2 * vb + rb), *d_col = (int *) (b + 2 * vb + rb + tb), *d_col_t = d_col + n1,
+            *d_tmap = d_col_t + n1;
+        HIP_OK(crp_dev_memcpy(d_rp, e->A_rowptr.data(), rb, 0, e->stream));
+        HIP_OK(crp_dev_memcpy(d_col, col.data(), ib, 0, e->stream));
+        HIP_OK(crp_dev_memcpy(d_val, nnz > 0 ? e->A_val.data() : va_t.data(), vb, 0, e->stream));
+        HIP_OK(crp_csr_transpose(m, ncol, d_rp, d_col, d_val, d_rp_t, d_col_t, d_val_t, d_tmap, e->stream));
+        HIP_OK(crp_dev_memcpy(rp_t.data(), d_rp_t, tb, 1, e->stream));
+        HIP_OK(crp_dev_memcpy(ci_t.data(), d_col_t, ib, 1, e->stream));
+        HIP_OK(crp_dev_memcpy(va_t.data(), d_val_t, vb, 1, e->stream));
+        HIP_OK(crp_dev_memcpy(e->t_src.data(), d_tmap, ib, 1, e->stream));
+        HIP_OK(crp_stream_sync(e->stream));
+        HIP_OK(crp_dev_free(d));
+    }
+    e->t_loc_nnz = (size_t) rp_t[(size_t) kb];
+    HIP_OK(crp_csr_dev_create(kb, m, rp_t.data(), ci_t.data(), va_t.data(), &e->At_loc));
+    if (nr > 0)
+    {
+        std::vector<int> rp_r((size_t) nr + 1);
+        for (int i = 0; i <= nr; i++) rp_r[(size_t) i] = rp_t[(size_t) kb + (size_t) i] - (int) e->t_loc_nnz;
+        // (an empty part still gets valid pointers: the arrays hold at least one element)
+        const size_t off = e->t_loc_nnz < n1 ? e->t_loc_nnz : 0;
+        HIP_OK(crp_csr_dev_create(nr, m, rp_r.data(), ci_t.data() + off, va_t.data() + off, &e->At_rem));
+    }
+    if (e->n_send_rows > 0)
+    {
+        // incoming position q adds to C row rB_sridxs[q]: a row several peers asked for comes back several times
+        const size_t ns = (size_t) e->n_send_rows;
+        std::vector<int> cnt((size_t) kb + 1, 0);
+        for (size_t q = 0; q < ns; q++) cnt[(size_t) e->rB_sridxs[q] + 1]++;
+        std::vector<int> rows, ptr(1, 0), start((size_t) kb, 0);
+        for (int r = 0; r < kb; r++)
+            if (cnt[(size_t) r + 1] > 0)
+            {
+                start[(size_t) r] = ptr.back();
+                rows.push_back(r);
+                ptr.push_back(ptr.back() + cnt[(size_t) r + 1]);
+            }
+        std::vector<int> pos(ns);
+        for (size_t q = 0; q < ns; q++) pos[(size_t) start[(size_t) e->rB_sridxs[q]]++] = (int) q;       // (ascending q inside a group)
+        e->n_acc = (int) rows.size();
+        std::vector<int> all(rows);
+        all.insert(all.end(), ptr.begin(), ptr.end());
+        all.insert(all.end(), pos.begin(), pos.end());
+        void *d = NULL;
+        HIP_OK(crp_dev_malloc(&d, sizeof(int) * all.size()));
+        e->acc_dev = (int *) d;
+        HIP_OK(crp_dev_memcpy(e->acc_dev, all.data(), sizeof(int) * all.size(), 0, e->stream));
+        HIP_OK(crp_stream_sync(e->stream));
+    }
+    if (e->nproc > 1)
+    {
+        if (e->xstream == nullptr) HIP_OK(crp_stream_create(&e->xstream));
+        if (e->ev_packed == nullptr) HIP_OK(crp_event_create(&e->ev_packed));
+        if (e->ev_landed == nullptr) HIP_OK(crp_event_create(&e->ev_landed));
+    }
+    e->t_built = true;
+}
+
+// new values (A_val, already copied into e->A_val) for the transposed matrices
+static void update_transposed_values(crp_rp_spmm *e)
+{
+    const size_t nnz = e->A_val.size();
+    e->split_vals.resize(nnz);
+    for (size_t q = 0; q < nnz; q++) e->split_vals[q] = e->A_val[(size_t) e->t_src[q]];
+    if (e->t_loc_nnz > 0) HIP_OK(crp_csr_dev_update_values(e->At_loc, e->split_vals.data(), e->stream));
+    if (e->At_rem != nullptr && nnz > e->t_loc_nnz)
+        HIP_OK(crp_csr_dev_update_values(e->At_rem, e->split_vals.data() + e->t_loc_nnz, e->stream));
+    HIP_OK(crp_stream_sync(e->stream));
+}
+
+static void exec_t_impl(crp_rp_spmm *e, int BC_layout, const double *B, long long ldB, double *C, long long ldC, void *stream_)
+{
+    if (e == NULL) return;
+    ASSERT_PRINTF(!e->plan_only, "rp_spmm_exec_t on a plan-only engine (no device state)\n");
+    ASSERT_PRINTF(BC_layout == 0 || BC_layout == 1, "BC_layout must be 0 or 1\n");
+    const double t_begin = get_wtime_sec();
+    if (!e->t_built) build_transposed(e);
+    void *s = stream_;
+    // B has A's rows, C the rows of this rank's block of the forward operand
+    const int n = e->glb_n, mb = e->A_nrow, mc = e->loc_B_nrow;
+    const bool timing = e->timing != 0;
+    double t0, t1;
+
+    int B_on_dev = 0, C_on_dev = 0;
+    HIP_OK(crp_dev_ptr_is_device(B, &B_on_dev));
+    HIP_OK(crp_dev_ptr_is_device(C, &C_on_dev));
+
+    // ---- operands as device-resident row-major views, staged and transposed as in exec_impl
+    const double *Bd = B;
+    long long ldBd = ldB;
+    if (!B_on_dev && mb > 0 && n > 0)
+    {
+        const size_t elems = (BC_layout == 0) ? (size_t) mb * (size_t) ldB : (size_t) n * (size_t) ldB;
+        double *stage = grow_as<double>(&e->B_stage, &e->B_stage_sz, elems);
+        const size_t used = (BC_layout == 0) ? ((size_t) (mb - 1) * (size_t) ldB + (size_t) n) : ((size_t) (n - 1) * (size_t) ldB + (size_t) mb);
+        HIP_OK(crp_dev_memcpy(stage, B, used * sizeof(double), 0, s));
+        Bd = stage;
+    }
+    if (BC_layout == 1 && mb > 0 && n > 0)
+    {
+        double *rm = grow_as<double>(&e->B_rm, &e->B_rm_sz, (size_t) mb * (size_t) n);
+        HIP_OK(transpose(n, mb, Bd, ldB, rm, n, s));
+        Bd = rm;
+        ldBd = n;
+    }
+    double *Cd = C;
+    long long ldCd = ldC;
+    if (BC_layout == 1)
+    {
+        Cd = grow_as<double>(&e->C_rm, &e->C_rm_sz, (size_t) mc * (size_t) n);
+        ldCd = n;
+    }
+    else if (!C_on_dev && mc > 0 && n > 0)
+    {
+        Cd = grow_as<double>(&e->C_stage, &e->C_stage_sz, (size_t) mc * (size_t) ldC);
+    }
+
+    auto reverse_exchange = [&](void *xs) {
+        // the forward plan backwards: what this rank receives there it sends here, from recvbuf_dev into sendbuf_dev
+        const double tx0 = get_wtime_sec();
+        e->comm->alltoallv_dev_f64(e->comm->ctx, e->recvbuf_dev, e->rB_rcnts.data(), e->rB_rdispls.data(), e->sendbuf_dev,
+                                   e->rB_scnts.data(), e->rB_sdispls.data(), xs);
+        e->t_a2a_host += get_wtime_sec() - tx0;
+    };
+    auto product = [&](crp_csr_dev_p A, double *out, long long ldo) {
+        HIP_OK(crp_spmm_csr_f64(A, 0, n, Bd, ldBd, NULL, 0, out, ldo, e->variant, s));
+    };
+    auto accumulate = [&]() {
+        if (e->n_acc == 0 || n == 0) return;
+        const int *acc_row = e->acc_dev, *acc_ptr = acc_row + e->n_acc, *acc_pos = acc_ptr + e->n_acc + 1;
+        HIP_OK(crp_scatter_add_rows_f64(e->n_acc, n, acc_row, acc_ptr, acc_pos, e->sendbuf_dev, n, Cd, ldCd, s));
+    };
+
+    if (timing) { HIP_OK(crp_stream_sync(s)); }
+    t0 = get_wtime_sec();
+    if (e->nproc > 1 && !timing)
+    {
+        // the exchange on its own stream beside the local product, which is enqueued first (see exec_impl)
+        if (e->At_rem != nullptr) product(e->At_rem, e->recvbuf_dev, n);
+        HIP_OK(crp_event_record(e->ev_packed, s));
+        product(e->At_loc, Cd, ldCd);
+        HIP_OK(crp_stream_wait_event(e->xstream, e->ev_packed));
+        reverse_exchange(e->xstream);
+        HIP_OK(crp_event_record(e->ev_landed, e->xstream));
+        HIP_OK(crp_stream_wait_event(s, e->ev_landed));
+        accumulate();
+    }
+    else
+    {
+        auto lap = [&](double *bucket) {
+            if (!timing) return;
+            HIP_OK(crp_stream_sync(s));
+            t1 = get_wtime_sec();
+            *bucket += t1 - t0;
+            t0 = t1;
+        };
+        if (e->At_rem != nullptr) product(e->At_rem, e->recvbuf_dev, n);
+        lap(&e->t_spmm);
+        if (e->nproc > 1) reverse_exchange(s);
+        lap(&e->t_a2a);
+        product(e->At_loc, Cd, ldCd);
+        lap(&e->t_spmm);
+        accumulate();
+        lap(&e->t_unpack);
+    }
+    if (BC_layout == 1 && mc > 0 && n > 0)
+    {
+        double *Ccm = C;
+        if (!C_on_dev) Ccm = grow_as<double>(&e->C_stage, &e->C_stage_sz, (size_t) n * (size_t) ldC);
+        HIP_OK(transpose(mc, n, Cd, n, Ccm, ldC, s));
+        Cd = Ccm;
+    }
+    if (timing)
+    {
+        HIP_OK(crp_stream_sync(s));
+        e->t_spmm += get_wtime_sec() - t0;
+    }
+
+    if (!C_on_dev && mc > 0 && n > 0)
+    {
+        const size_t w = (BC_layout == 0) ? (size_t) n : (size_t) mc, h = (BC_layout == 0) ? (size_t) mc : (size_t) n;
+        HIP_OK(crp_dev_memcpy2d(C, (size_t) ldC * sizeof(double), Cd, (size_t) ldC * sizeof(double), w * sizeof(double), h, 1, s));
+        HIP_OK(crp_stream_sync(s));
+    }
+    else if (!B_on_dev || timing)
+    {
+        HIP_OK(crp_stream_sync(s));
+    }
+    else
+    {
+        if (e->ev_exec == nullptr) HIP_OK(crp_event_create(&e->ev_exec));
+        HIP_OK(crp_event_record(e->ev_exec, s));
+        e->exec_pending = true;
+    }
+    e->t_exec += get_wtime_sec() - t_begin;
+    e->n_exec++;
+}
+
 extern "C" {
+
+void crp_rp_spmm_exec_t_ex(crp_rp_spmm_p e, int BC_layout, const double *B, long long ldB, double *C, long long ldC, void *stream_)
+{
+    exec_t_impl(e, BC_layout, B, ldB, C, ldC, stream_);
+}
+
+int crp_rp_spmm_transposed_built(crp_rp_spmm_p e) { return (e && e->t_built) ? 1 : 0; }
 
 void crp_rp_spmm_exec_ex(crp_rp_spmm_p e, int BC_layout, const double *B, long long ldB, double *C,
                          long long ldC, void *stream_)
@@ -739,6 +982,7 @@ void crp_rp_spmm_update_values(crp_rp_spmm_p e, const double *A_val)
         }
         else HIP_OK(crp_csr_dev_update_values(e->A_dev, A_val, e->stream));
         HIP_OK(crp_stream_sync(e->stream));
+        if (e->t_built) update_transposed_values(e);
     }
 }
 

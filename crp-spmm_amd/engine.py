@@ -134,6 +134,31 @@ class RpSpmm:
         fn = self._lib.crp_rp_spmm_exec_f32_ex if f32 else self._lib.crp_rp_spmm_exec_ex
         fn(self.handle, BC_layout, bp, ldb, cp, ldc, stream)
 
+    def exec_t(self, BC_layout, B, C_out, stream=None):
+        """C := A^T * B (crp_rp_spmm_exec_t_ex), fp64 only: B is this rank's A_nrow x glb_n block (partitioned like A's
+        rows), C_out its loc_B_nrow x glb_n block of the result (partitioned by B_row_displs); layouts and operands as
+        ``exec``.  The first call builds the transposed device matrices (``transposed_built``)."""
+        if _operands_dtype(B, C_out) != "f64":
+            raise TypeError("exec_t is fp64 only: B and C must be float64")
+        bp, ldb, _kb = _ptr_ld(B, BC_layout)
+        cp, ldc, _kc = _ptr_ld(C_out, BC_layout)
+        for name, x, rows in (("B", B, self.A_nrow), ("C", C_out, getattr(self, "loc_B_nrow", None))):
+            if rows is None:
+                continue
+            want = (rows, self.glb_n) if BC_layout == 0 else (self.glb_n, rows)
+            got = tuple(x.shape)
+            if (BC_layout == 0 and (got[0] < want[0] or got[1] != want[1])) or \
+               (BC_layout == 1 and (got[0] != want[0] or got[1] < want[1])):
+                raise ValueError("%s has shape %s, the engine needs %s (layout %d)" % (name, got, want, BC_layout))
+        if stream is None:
+            stream = _current_stream(C_out)
+        self._lib.crp_rp_spmm_exec_t_ex(self.handle, BC_layout, bp, ldb, cp, ldc, stream)
+
+    @property
+    def transposed_built(self):
+        """True once an ``exec_t`` has built the transposed device matrices (crp_rp_spmm_transposed_built)."""
+        return bool(self._lib.crp_rp_spmm_transposed_built(self.handle))
+
     def print_stat(self):
         self._lib.crp_rp_spmm_print_stat(self.handle)
 

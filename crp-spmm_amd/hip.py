@@ -7,6 +7,20 @@ import numpy as np
 from . import _lib as L
 
 
+# negative return codes of crp_csr_transpose / crp_csr_dev_create_t (include/crpspmm_hip.h, CRP_CSR_T_E*)
+T_EARG, T_ECOL, T_EPTR, T_EMIXED = -1, -3, -4, -5
+_T_ERRORS = {T_EARG: "bad argument", T_ECOL: "column index out of range", T_EPTR: "rowptr does not start at 0 or decreases",
+             T_EMIXED: "host and device pointers mixed"}
+
+
+class TransposeError(ValueError):
+    """A bad input to the CSR transpose (a CRP_CSR_T_E* code); ``code`` holds the code."""
+
+    def __init__(self, what, code):
+        super().__init__("%s: %s (code %d)" % (what, _T_ERRORS.get(code, "error"), code))
+        self.code = code
+
+
 class CsrDev:
     """Device-resident CSR (crp_csr_dev_create)."""
 
@@ -22,6 +36,55 @@ class CsrDev:
         L.check(lib.crp_csr_dev_create(nrow, ncol, rp.ctypes.data_as(L.c_int_p), ci.ctypes.data_as(L.c_int_p),
                                        va.ctypes.data_as(L.c_dbl_p), C.byref(self.handle)), "crp_csr_dev_create")
         self.nrow, self.ncol = nrow, ncol
+
+    @classmethod
+    def from_transpose(cls, nrow, ncol, rowptr, colidx, val):
+        """A handle for A^T from the host CSR of the nrow x ncol matrix A (crp_csr_dev_create_t): transposed on the
+        device.  ``self.nrow`` is ncol.  ``update_values`` takes values in A's order."""
+        lib = L.load()
+        rp = np.ascontiguousarray(rowptr, dtype=np.int32)
+        ci = np.ascontiguousarray(colidx, dtype=np.int32)
+        va = np.ascontiguousarray(val, dtype=np.float64)
+        if ci.size == 0:
+            ci, va = np.zeros(1, np.int32), np.zeros(1, np.float64)
+        self = cls.__new__(cls)
+        self._lib = lib
+        self.handle = C.c_void_p()
+        rc = lib.crp_csr_dev_create_t(nrow, ncol, rp.ctypes.data_as(L.c_int_p), ci.ctypes.data_as(L.c_int_p),
+                                      va.ctypes.data_as(L.c_dbl_p), C.byref(self.handle))
+        if rc < 0:
+            raise TransposeError("crp_csr_dev_create_t", rc)
+        L.check(rc, "crp_csr_dev_create_t")
+        self.nrow, self.ncol = ncol, nrow
+        return self
+
+    @property
+    def is_transposed(self):
+        return bool(self._lib.crp_csr_dev_is_transposed(self.handle))
+
+    def update_values(self, val, stream=None):
+        """crp_csr_dev_update_values: new values in the order given at create (for a ``from_transpose`` handle: A's order);
+        a numpy array (host pointer) or a float64 torch tensor on the device."""
+        if isinstance(val, np.ndarray):
+            keep = np.ascontiguousarray(val, dtype=np.float64)
+            ptr, size = keep.ctypes.data, keep.size
+        else:
+            import torch
+            if not (isinstance(val, torch.Tensor) and val.is_cuda and val.dtype == torch.float64 and val.is_contiguous()):
+                raise TypeError("val must be a numpy array or a contiguous float64 torch tensor on the device")
+            keep, ptr, size = val, val.data_ptr(), val.numel()
+            if stream is None:
+                stream = _stream(val)
+        if size != self.nnz:
+            raise ValueError("val has %d entries, the matrix %d nonzeros" % (size, self.nnz))
+        L.check(self._lib.crp_csr_dev_update_values(self.handle, C.c_void_p(ptr or None), C.c_void_p(stream)),
+                "crp_csr_dev_update_values")
+        if isinstance(val, np.ndarray):
+            L.check(self._lib.crp_stream_sync(C.c_void_p(stream)), "crp_stream_sync")      # `keep` may go away
+
+    def resolved_variant(self, n):
+        """crp_csr_dev_resolved_variant: what a variant-0 product of n columns launches on this matrix."""
+        return int(self._lib.crp_csr_dev_resolved_variant(self.handle, int(n)))
 
     @property
     def nnz(self):
@@ -68,6 +131,59 @@ def spmm_csr(A, B0, C_out, n=None, layout=0, B1=None, variant=0, stream=None):
                                  B0.stride(0) if B0 is not None else 0, b1p, ld1, C_out.data_ptr(),
                                  C_out.stride(0), variant, _stream(C_out) if stream is None else stream),
             "crp_spmm_csr_f64")
+
+
+def csr_transpose(rowptr, colidx, val, ncol, stream=None):
+    """crp_csr_transpose -> (rowptr_t, colidx_t, val_t, tmap): A^T of the CSR (rowptr, colidx, val) with ncol columns;
+    tmap[q] = position in the input of output entry q.  numpy arrays: host code; torch tensors on the GPU (int32 rowptr /
+    colidx, float64 val): the HIP kernels on `stream` (default: the current torch stream), results as tensors on the same
+    device.  A bad input raises TransposeError with the C code."""
+    lib = L.load()
+    try:
+        import torch
+        tensors = [isinstance(t, torch.Tensor) and t.is_cuda for t in (rowptr, colidx, val)]
+    except ImportError:
+        tensors = [False] * 3
+    ncol = int(ncol)
+    if any(tensors):
+        import torch
+        if not all(tensors):
+            raise TransposeError("csr_transpose", T_EMIXED)
+        for t, dt in ((rowptr, torch.int32), (colidx, torch.int32), (val, torch.float64)):
+            if t.dtype != dt or not t.is_contiguous():
+                raise TransposeError("csr_transpose", T_EARG)
+        nrow, nnz = rowptr.numel() - 1, colidx.numel()
+        if nrow < 0 or ncol < 0 or val.numel() != nnz:
+            raise TransposeError("csr_transpose", T_EARG)
+        dev = rowptr.device
+        rowptr_t = torch.empty(ncol + 1, dtype=torch.int32, device=dev)
+        colidx_t = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)
+        val_t = torch.empty(max(nnz, 1), dtype=torch.float64, device=dev)
+        tmap = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)
+        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        rc = lib.crp_csr_transpose(nrow, ncol, C.c_void_p(rowptr.data_ptr()), C.c_void_p(colidx.data_ptr() or None),
+                                   C.c_void_p(val.data_ptr() or None), C.c_void_p(rowptr_t.data_ptr()),
+                                   C.c_void_p(colidx_t.data_ptr()), C.c_void_p(val_t.data_ptr()), C.c_void_p(tmap.data_ptr()),
+                                   C.c_void_p(st))
+    else:
+        rowptr = np.ascontiguousarray(rowptr, dtype=np.int32)
+        colidx = np.ascontiguousarray(colidx, dtype=np.int32)
+        val = np.ascontiguousarray(val, dtype=np.float64)
+        nrow, nnz = rowptr.size - 1, colidx.size
+        if nrow < 0 or ncol < 0 or val.size != nnz:
+            raise TransposeError("csr_transpose", T_EARG)
+        rowptr_t = np.zeros(ncol + 1, np.int32)
+        colidx_t = np.zeros(max(nnz, 1), np.int32)
+        val_t = np.zeros(max(nnz, 1), np.float64)
+        tmap = np.zeros(max(nnz, 1), np.int32)
+        ci = colidx if nnz else np.zeros(1, np.int32)
+        va = val if nnz else np.zeros(1, np.float64)
+        rc = lib.crp_csr_transpose(nrow, ncol, rowptr.ctypes.data, ci.ctypes.data, va.ctypes.data, rowptr_t.ctypes.data,
+                                   colidx_t.ctypes.data, val_t.ctypes.data, tmap.ctypes.data, None)
+    if rc < 0:
+        raise TransposeError("crp_csr_transpose", rc)
+    L.check(rc, "crp_csr_transpose")
+    return rowptr_t, colidx_t[:nnz], val_t[:nnz], tmap[:nnz]
 
 
 def gather_rows(ridx, src, dst, layout=0, scatter=False, stream=None):

@@ -88,6 +88,19 @@ void crp_rp_spmm_exec_ex(crp_rp_spmm_p rp_spmm, int BC_layout, const double *B, 
  * alltoallv_dev_f64 as opaque 8-byte words, counts rows * ld32 / 2. */
 void crp_rp_spmm_exec_f32_ex(crp_rp_spmm_p rp_spmm, int BC_layout, const float *B, long long ldB,
                              float *C, long long ldC, void *stream);
+/* C := A^T * B (fp64), A being the GLOBAL matrix whose row block this rank holds.  B is this rank's A_nrow x glb_n block
+ * of the operand (partitioned like A's rows), C this rank's loc_B_nrow x glb_n block of the result (partitioned by
+ * B_row_displs).  Layouts, host or device operands, staging, streams and completion rules as crp_rp_spmm_exec_ex.  The
+ * first call builds the transposed device matrices from the engine's two-source local matrix (nothing before it does;
+ * crp_rp_spmm_transposed_built: 0, then 1): its transpose cut by rows into the part that writes C and the part that
+ * writes the rows owed to peers.  One call: the peers' part, the forward exchange plan run backwards (receive counts
+ * as send counts), the local part beside it when timing is off, then the incoming rows added to C row by row in a fixed
+ * order (crp_scatter_add_rows_f64) -- repeated calls are bit-identical.  Products bill to the SpMM time, the exchange to
+ * the redistribution time, the accumulate to the unpack time of print_stat.  crp_rp_spmm_update_values refreshes the
+ * transposed matrices once they exist.  A plan-only engine aborts as in exec. */
+void crp_rp_spmm_exec_t_ex(crp_rp_spmm_p rp_spmm, int BC_layout, const double *B, long long ldB,
+                           double *C, long long ldC, void *stream);
+int crp_rp_spmm_transposed_built(crp_rp_spmm_p rp_spmm);
 void crp_rp_spmm_print_stat(crp_rp_spmm_p rp_spmm);
 void crp_rp_spmm_clear_stat(crp_rp_spmm_p rp_spmm);
 /* rp_spmm_init for a caller that ALSO holds the values in device memory, in the order of A_val (A_val_dev: the panel a

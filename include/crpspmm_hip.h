@@ -109,6 +109,33 @@ long long crp_csr_dev_bytes(crp_csr_dev_p A);
 int crp_csr_dev_row_part_comm_size(crp_csr_dev_p A, int nblk, const int *rblk_ptr, const int *x_displs, int *comm_sizes,
                                    int *total_size);
 
+/* ---- transpose of a CSR, and handles for A^T ------------------------------------
+ * rowptr_t / colidx_t / val_t / tmap := A^T for the nrow x ncol CSR (rowptr, colidx, val).  Row c of the output lists the
+ * rows of A that hold column c in ascending row order; duplicates of one (row, column) pair keep their original order;
+ * tmap[q] = position in the input of output entry q and val_t[q] = val[tmap[q]] -- a stable sort of the nonzeros by
+ * column, so the result is unique and host and device outputs agree bit for bit.  rowptr_t holds ncol + 1 entries,
+ * colidx_t / val_t / tmap nnz; val_t and tmap may be NULL (val may be NULL when val_t is).  Either every pointer is a host
+ * pointer (host code) or every pointer is a device pointer (HIP kernels on `stream`, which the call synchronises; column
+ * counts by integer atomics, the order inside a row by a sort, values moved and never added).  The inputs are checked
+ * first -- rowptr[0] == 0, rowptr never decreases, every column in [0, ncol): a negative column (the two-source
+ * encoding) is refused -- and a bad input returns its code before colidx_t, val_t or tmap is written.
+ * Returns 0, a CRP_CSR_T_E* code (< 0), or a HIP error (> 0). */
+#define CRP_CSR_T_EARG   (-1)   /* null pointer, negative size */
+#define CRP_CSR_T_ECOL   (-3)   /* a column index outside [0, ncol) */
+#define CRP_CSR_T_EPTR   (-4)   /* rowptr does not start at 0 or decreases */
+#define CRP_CSR_T_EMIXED (-5)   /* host and device pointers mixed in one call */
+int crp_csr_transpose(int nrow, int ncol, const int *rowptr, const int *colidx, const double *val,
+                      int *rowptr_t, int *colidx_t, double *val_t, int *tmap, void *stream);
+/* A device-resident handle for A^T from A's host CSR (arguments as crp_csr_dev_create, plain column indices only): A's
+ * arrays go up once, are transposed on the device (crp_csr_transpose) and come back for the host-side format builders;
+ * tmap stays in device memory.  crp_csr_dev_nrow() of the result is ncol.  Everything else applies to it as to any other
+ * handle: it IS the handle crp_csr_dev_create would give for the transposed arrays.  crp_csr_dev_update_values() keeps
+ * its contract -- values in the order given at create, which is A's order; the handle gathers them through tmap.
+ * Returns 0, a CRP_CSR_T_E* code for a bad CSR, -3 out of host memory, or a HIP error (> 0).  Blocking. */
+int crp_csr_dev_create_t(int nrow, int ncol, const int *rowptr, const int *colidx, const double *val, crp_csr_dev_p *out);
+/* 1 for a handle made by crp_csr_dev_create_t, 0 for any other, -1 for NULL */
+int crp_csr_dev_is_transposed(crp_csr_dev_p A);
+
 /* what variant 0 resolves to for this matrix: 1 csr-rowgroup, 2 rowpanel-R4, 3 rowpanel-R8
  * (chosen at create time from how many columns the rows of a panel share;
  * CRPSPMM_SPMM_VARIANT=1|2|3 overrides). */
@@ -261,6 +288,12 @@ int crp_gather_rows_f64(int layout, int nidx, int n, const int *ridx,
 int crp_scatter_rows_f64(int layout, int nidx, int n, const int *ridx,
                          const double *src, long long lds,
                          double *dst, long long ldd, void *stream);
+/* segmented accumulate (row-major): dst[seg_row[t]][0:n] += src[seg_pos[k]][0:n] for k = seg_ptr[t] .. seg_ptr[t + 1] - 1,
+ * added one after the other in that order, for t < nseg.  seg_row holds distinct rows, so no two threads touch one
+ * element: no atomics, and repeated calls are bit-identical (the reduce of C of the row-parallel engine's transposed
+ * product, where one local row can come back from several peers).  seg_row / seg_ptr / seg_pos are device arrays. */
+int crp_scatter_add_rows_f64(int nseg, int n, const int *seg_row, const int *seg_ptr, const int *seg_pos,
+                             const double *src, long long lds, double *dst, long long ldd, void *stream);
 /* out-of-place transpose: dst[c][r] = src[r][c] for an nrow x ncol row-major
  * src (equivalently col-major <-> row-major conversion). */
 int crp_transpose_f64(int nrow, int ncol, const double *src, long long lds,
