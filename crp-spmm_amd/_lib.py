@@ -164,6 +164,8 @@ SIGNATURES = {
     "crp_spmm_plan_host": (_I, [_I, _I, c_int_p, c_int_p, _I, c_int_p, _I, _I, _I, c_int_p, c_int_p]),
     "crp_spmm_csr_f32": (_I, [_V, _I, _V, _LL, _V, _LL, _V, _LL, _I, _V]),
     "crp_spmm_csr_f64": (_I, [_V, _I, _I, _V, _LL, _V, _LL, _V, _LL, _I, _V]),
+    "crp_sddmm_csr_f64": (_I, [_V, _I, _V, _LL, _V, _LL, _V, _LL, _V, _V, _I, _V]),
+    "crp_sddmm_csr_f32": (_I, [_V, _I, _V, _LL, _V, _LL, _V, _LL, _V, _V, _I, _V]),
     "crp_spmm_variant_name": (C.c_char_p, [_I]),
     "crp_spmm_variant_count": (_I, []),
     "crp_gather_rows_f64": (_I, [_I, _I, _I, _V, _V, _LL, _V, _LL, _V]),
@@ -187,6 +189,9 @@ SIGNATURES = {
     "crp_rp_spmm_exec_f32_ex": (None, [_V, _I, _V, _LL, _V, _LL, _V]),
     "crp_rp_spmm_exec_t_ex": (None, [_V, _I, _V, _LL, _V, _LL, _V]),
     "crp_rp_spmm_transposed_built": (_I, [_V]),
+    "crp_rp_spmm_sddmm_ex": (None, [_V, _I, _V, _LL, _V, _LL, _V, _I, _V]),
+    "crp_rp_spmm_sddmm_f32_ex": (None, [_V, _I, _V, _LL, _V, _LL, _V, _I, _V]),
+    "crp_rp_spmm_sddmm_built": (_I, [_V]),
     "crp_rp_spmm_print_stat": (None, [_V]),
     "crp_rp_spmm_clear_stat": (None, [_V]),
     "crp_rp_spmm_get_plan": (None, [_V, C.POINTER(RpPlanView)]),

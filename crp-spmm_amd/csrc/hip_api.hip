@@ -371,6 +371,30 @@ template <class V> static typename V::value_type *dup(const V &v)
     return p;
 }
 
+static hipError_t sddmm_launch(const crp::SddmmArgs<double> &a, hipStream_t s) { return crp::sddmm_rm_f64(a, s); }
+static hipError_t sddmm_launch(const crp::SddmmArgs<float> &a, hipStream_t s) { return crp::sddmm_rm_f32(a, s); }
+// out[p] = < X[row(p)], Y[col(p)] > over A's pattern (sddmm_kernels.hip), one dtype.  Every argument is checked before anything is
+// launched or allocated: a negative return has written nothing.
+template <class T>
+static int sddmm_csr(crp_csr_dev *A, int n, const T *X, long long ldX, const T *Y0, long long ldY0, const T *Y1, long long ldY1, T *out,
+                     const int *out_pos, int mode, const T *val, hipStream_t s)
+{
+    crp::SddmmArgs<T> a;
+    a.nrow = A->nrow; a.n = n; a.rowptr = A->rowptr; a.colidx = A->colidx; a.val = val;
+    a.X = X; a.ldX = ldX; a.Y0 = Y0; a.ldY0 = ldY0; a.Y1 = Y1; a.ldY1 = ldY1;
+    a.out = out; a.rowmap = A->rowmap; a.out_pos = out_pos; a.mode = mode;
+    return (int) sddmm_launch(a, s);
+}
+static int sddmm_check(const crp_csr_dev *A, int n, const void *X, long long ldX, const void *Y0, long long ldY0, const void *Y1,
+                       long long ldY1, const void *out, int mode)
+{
+    if (A == NULL || X == NULL || Y0 == NULL || out == NULL) return -1;
+    if (n < 1 || (mode != 0 && mode != 1)) return -1;
+    if (Y1 == NULL && A->b1_rows > 0) return -1;        // a column code names the second source
+    if (ldX < n || ldY0 < n || (Y1 != NULL && ldY1 < n)) return -4;
+    return 0;
+}
+
 extern "C" {
 
 const char *crp_hip_version(void) { return "crpspmm-hip 0.1 gfx950"; }
@@ -920,6 +944,28 @@ int crp_spmm_csr_f32(crp_csr_dev_p A, int n, const float *B0, long long ldB0, co
     crp::Team2Args t;
     team2_args(d, &t);
     return (int) crp::spmm_rm_f32_team2(t, a, s);
+}
+
+int crp_sddmm_csr_f64(crp_csr_dev_p A, int n, const double *X, long long ldX, const double *Y0, long long ldY0, const double *Y1,
+                      long long ldY1, double *out, const int *out_pos, int mode, void *stream)
+{
+    const int rc = sddmm_check(A, n, X, ldX, Y0, ldY0, Y1, ldY1, out, mode);
+    if (rc != 0 || A->nnz == 0) return rc;
+    return sddmm_csr<double>(A, n, X, ldX, Y0, ldY0, Y1, ldY1, out, out_pos, mode, A->val, (hipStream_t) stream);
+}
+
+int crp_sddmm_csr_f32(crp_csr_dev_p A, int n, const float *X, long long ldX, const float *Y0, long long ldY0, const float *Y1,
+                      long long ldY1, float *out, const int *out_pos, int mode, void *stream)
+{
+    const int rc = sddmm_check(A, n, X, ldX, Y0, ldY0, Y1, ldY1, out, mode);
+    if (rc != 0 || A->nnz == 0) return rc;
+    const hipStream_t s = (hipStream_t) stream;
+    if (mode == 1 && A->val32 == nullptr)               // the fp32 copy of the values, as crp_spmm_csr_f32 derives it
+    {
+        CRP_TRY(A->val32.alloc(sizeof(float) * (size_t) A->nnz));
+        CRP_TRY(crp::convert_f64_f32(A->nnz, A->val, A->val32, s));
+    }
+    return sddmm_csr<float>(A, n, X, ldX, Y0, ldY0, Y1, ldY1, out, out_pos, mode, A->val32, s);
 }
 
 int crp_csr_dev_auto_variant(crp_csr_dev_p A) { return A ? A->traits.auto_variant : -1; }

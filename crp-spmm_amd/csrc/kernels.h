@@ -86,6 +86,25 @@ struct Team2NArgs         // panel_format.h, Team2RHost (the row-owner team kern
     uint32_t       *tent;      // the entry table (Team2RHost::tent)
 };
 
+template <typename T> struct SddmmArgs     // sddmm_kernels.hip: out[p] = < X[row(p)], Y[col(p)] > over the CSR pattern
+{
+    int nrow;
+    int n;
+    const int *rowptr;
+    const int *colidx;
+    const T   *val;         // the values in T (mode 1), else unused
+    const T   *X;
+    int64_t    ldX;
+    const T   *Y0;
+    int64_t    ldY0;
+    const T   *Y1;
+    int64_t    ldY1;
+    T         *out;
+    const int *rowmap;      // nullptr, or the X row of every row (row-subset matrices)
+    const int *out_pos;     // nullptr, or where nonzero p writes: out[out_pos[p]]
+    int        mode;        // 0: the dot, 1: the dot times val[p]
+};
+
 // narrow_kernel.hip: row-panel format, n <= 64 (several entries of a panel per instruction)
 bool spmm_narrow_applicable(const PanelArgs &p, const SpmmArgs &a);
 hipError_t spmm_rm_f64_narrow(const PanelArgs &p, const SpmmArgs &a, hipStream_t s);
@@ -105,6 +124,10 @@ hipError_t spmm_rm_f32_team2(const Team2Args &t, const SpmmArgsF32 &a, hipStream
 
 // spmm_f32.hip: CSR row-group kernel of the fp32 path (any width, both sources)
 hipError_t spmm_rm_f32_rowgroup(const SpmmArgsF32 &a, hipStream_t s);
+
+// sddmm_kernels.hip: row-major operands, any width and alignment, both sources
+hipError_t sddmm_rm_f64(const SddmmArgs<double> &a, hipStream_t s);
+hipError_t sddmm_rm_f32(const SddmmArgs<float> &a, hipStream_t s);
 
 // row_kernels.hip
 hipError_t gather_rows_f64(int layout, int nidx, int n, const int *ridx, const double *src, int64_t lds,

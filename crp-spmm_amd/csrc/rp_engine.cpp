@@ -69,6 +69,12 @@ struct crp_rp_spmm
     // acc_dev = rows[n_acc] | ptr[n_acc + 1] | positions in sendbuf_dev[n_send_rows], ascending inside a group
     int  n_acc = 0;
     int *acc_dev = nullptr;
+    // SDDMM (crp_rp_spmm_sddmm_ex), uploaded by its first call: where the nonzeros of A_int / A_bnd sit in A_val (int_src / bnd_src
+    // as int32 device arrays; none for the unsplit engine), and the staging buffer of a host `out`
+    bool sd_built = false;
+    int *sd_int_pos = nullptr, *sd_bnd_pos = nullptr;
+    double *sd_out = nullptr;
+    size_t  sd_out_sz = 0;
     // staging (host-pointer API) and column-major temporaries, grown on demand
     double *B_stage = nullptr, *C_stage = nullptr, *B_rm = nullptr, *C_rm = nullptr;
     size_t  B_stage_sz = 0, C_stage_sz = 0, B_rm_sz = 0, C_rm_sz = 0;
@@ -357,6 +363,9 @@ void crp_rp_spmm_free(crp_rp_spmm_p *rp_spmm)
         crp_csr_dev_destroy(&e->At_loc);
         crp_csr_dev_destroy(&e->At_rem);
         crp_dev_free(e->acc_dev);
+        crp_dev_free(e->sd_int_pos);
+        crp_dev_free(e->sd_bnd_pos);
+        crp_dev_free(e->sd_out);
         if (e->xstream) crp_stream_destroy(e->xstream);
         if (e->ev_packed) crp_event_destroy(e->ev_packed);
         if (e->ev_landed) crp_event_destroy(e->ev_landed);
@@ -464,6 +473,76 @@ static int spmm(crp_rp_spmm *e, crp_csr_dev_p A, int n, const float *B0, long lo
     return crp_spmm_csr_f32(A, n, B0, ldB0, B1, ldB1, C, ldC, e->variant_f32, s);
 }
 
+// The half that exec and sddmm share: pack the rows of the row-major device operand Bd that other ranks asked for, exchange them
+// (the received rows land in x.recv in final order), and run the local kernels -- product(A, part) once for A_dev (part 0), or for
+// A_int (1) and A_bnd (2).  With timing off and a split engine the interior part is enqueued on s beside the exchange, which runs
+// on the engine's second stream, and the boundary part after the rows have landed; with timing on the phases run in sequence and
+// bill to t_pack and t_a2a (t0 is left at the start of the kernels, which the caller bills).
+template <class T, class F>
+static void pack_exchange_run(crp_rp_spmm *e, const Xchg &x, const T *Bd, long long ldBd, void *s, double &t0, F &&product)
+{
+    const int n = e->glb_n;
+    const bool timing = e->timing != 0;
+    double t1;
+    // ---- 1. pack the rows other ranks asked for (reference :232-262)
+    if (timing) { HIP_OK(crp_stream_sync(s)); }
+    t0 = get_wtime_sec();
+    if (e->n_send_rows > 0 && n > 0)
+        HIP_OK(gather((int) e->n_send_rows, n, e->sridxs_dev, Bd, ldBd, (T *) x.send, x.ld, s));
+    if (timing)
+    {
+        HIP_OK(crp_stream_sync(s));
+        t1 = get_wtime_sec();
+        e->t_pack += t1 - t0;
+        t0 = t1;
+    }
+
+    // ---- 2. exchange (reference :275-309); received rows land in final order
+    const bool split = (e->A_int != nullptr);
+    if (split && !timing)
+    {
+        // The exchange runs on its own stream beside the interior rows' product.  The product is ENQUEUED FIRST: it does not
+        // depend on the exchange, and issuing a group of sends / receives can hold the host for a while (a non-blocking RCCL
+        // communicator is polled until the group is on the stream) -- with the exchange first, the whole interior product
+        // (0.06 - 0.2 ms per GPU at pwtk size) could have passed before its launch was even issued.
+        HIP_OK(crp_event_record(e->ev_packed, s));
+        product(e->A_int, 1);
+        HIP_OK(crp_stream_wait_event(e->xstream, e->ev_packed));
+        {
+            const double tx0 = get_wtime_sec();
+            e->comm->alltoallv_dev_f64(e->comm->ctx, (const double *) x.send, x.sc, x.sd, (double *) x.recv, x.rc, x.rd, e->xstream);
+            e->t_a2a_host += get_wtime_sec() - tx0;
+        }
+        HIP_OK(crp_event_record(e->ev_landed, e->xstream));
+        HIP_OK(crp_stream_wait_event(s, e->ev_landed));
+        product(e->A_bnd, 2);
+    }
+    else
+    {
+        if (e->nproc > 1)
+        {
+            const double tx0 = get_wtime_sec();
+            e->comm->alltoallv_dev_f64(e->comm->ctx, (const double *) x.send, x.sc, x.sd, (double *) x.recv, x.rc, x.rd, s);
+            e->t_a2a_host += get_wtime_sec() - tx0;
+        }
+        if (timing)
+        {
+            HIP_OK(crp_stream_sync(s));
+            t1 = get_wtime_sec();
+            e->t_a2a += t1 - t0;
+            t0 = t1;
+        }
+
+        // ---- 3. the local kernels (reference :388-408)
+        if (split)
+        {
+            product(e->A_int, 1);
+            product(e->A_bnd, 2);
+        }
+        else product(e->A_dev, 0);
+    }
+}
+
 // C := A * B on this rank, one dtype (crp_rp_spmm_exec_ex / crp_rp_spmm_exec_f32_ex)
 template <class T>
 static void exec_impl(crp_rp_spmm *e, int BC_layout, const T *B, long long ldB, T *C, long long ldC, void *stream_)
@@ -530,63 +609,8 @@ static void exec_impl(crp_rp_spmm *e, int BC_layout, const T *B, long long ldB, 
         Cd = grow_as<T>(&e->C_stage, &e->C_stage_sz, (size_t) m * (size_t) ldC);
     }
 
-    // ---- 1. pack the rows other ranks asked for (reference :232-262)
-    if (timing) { HIP_OK(crp_stream_sync(s)); }
-    t0 = get_wtime_sec();
-    if (e->n_send_rows > 0 && n > 0)
-        HIP_OK(gather((int) e->n_send_rows, n, e->sridxs_dev, Bd, ldBd, (T *) x.send, x.ld, s));
-    if (timing)
-    {
-        HIP_OK(crp_stream_sync(s));
-        t1 = get_wtime_sec();
-        e->t_pack += t1 - t0;
-        t0 = t1;
-    }
-
-    // ---- 2. exchange (reference :275-309); received rows land in final order
-    const bool split = (e->A_int != nullptr);
-    if (split && !timing)
-    {
-        // The exchange runs on its own stream beside the interior rows' product.  The product is ENQUEUED FIRST: it does not
-        // depend on the exchange, and issuing a group of sends / receives can hold the host for a while (a non-blocking RCCL
-        // communicator is polled until the group is on the stream) -- with the exchange first, the whole interior product
-        // (0.06 - 0.2 ms per GPU at pwtk size) could have passed before its launch was even issued.
-        HIP_OK(crp_event_record(e->ev_packed, s));
-        HIP_OK(spmm(e, e->A_int, n, Bd, ldBd, (const T *) x.recv, x.ld, Cd, ldCd, s));
-        HIP_OK(crp_stream_wait_event(e->xstream, e->ev_packed));
-        {
-            const double tx0 = get_wtime_sec();
-            e->comm->alltoallv_dev_f64(e->comm->ctx, (const double *) x.send, x.sc, x.sd, (double *) x.recv, x.rc, x.rd, e->xstream);
-            e->t_a2a_host += get_wtime_sec() - tx0;
-        }
-        HIP_OK(crp_event_record(e->ev_landed, e->xstream));
-        HIP_OK(crp_stream_wait_event(s, e->ev_landed));
-        HIP_OK(spmm(e, e->A_bnd, n, Bd, ldBd, (const T *) x.recv, x.ld, Cd, ldCd, s));
-    }
-    else
-    {
-        if (e->nproc > 1)
-        {
-            const double tx0 = get_wtime_sec();
-            e->comm->alltoallv_dev_f64(e->comm->ctx, (const double *) x.send, x.sc, x.sd, (double *) x.recv, x.rc, x.rd, s);
-            e->t_a2a_host += get_wtime_sec() - tx0;
-        }
-        if (timing)
-        {
-            HIP_OK(crp_stream_sync(s));
-            t1 = get_wtime_sec();
-            e->t_a2a += t1 - t0;
-            t0 = t1;
-        }
-
-        // ---- 3. local SpMM (reference :388-408)
-        if (split)
-        {
-            HIP_OK(spmm(e, e->A_int, n, Bd, ldBd, (const T *) x.recv, x.ld, Cd, ldCd, s));
-            HIP_OK(spmm(e, e->A_bnd, n, Bd, ldBd, (const T *) x.recv, x.ld, Cd, ldCd, s));
-        }
-        else HIP_OK(spmm(e, e->A_dev, n, Bd, ldBd, (const T *) x.recv, x.ld, Cd, ldCd, s));
-    }
+    // ---- 1 - 3. pack, exchange, local SpMM
+    pack_exchange_run(e, x, Bd, ldBd, s, t0, [&](crp_csr_dev_p A, int) { HIP_OK(spmm(e, A, n, Bd, ldBd, (const T *) x.recv, x.ld, Cd, ldCd, s)); });
     if (BC_layout == 1 && m > 0 && n > 0)
     {
         T *Ccm = C;
@@ -619,6 +643,122 @@ static void exec_impl(crp_rp_spmm *e, int BC_layout, const T *B, long long ldB, 
     else
     {
         // asynchronous return: remember where this exec ends (crp_rp_spmm_update_values waits for it)
+        if (e->ev_exec == nullptr) HIP_OK(crp_event_create(&e->ev_exec));
+        HIP_OK(crp_event_record(e->ev_exec, s));
+        e->exec_pending = true;
+    }
+    e->t_exec += get_wtime_sec() - t_begin;
+    e->n_exec++;
+}
+
+// ---- out[p] = < X[row(p)], Y[col(p)] > over this rank's rows of A (crp_rp_spmm_sddmm_ex / _f32_ex) --------------------------------
+static int sddmm(crp_csr_dev_p A, int n, const double *X, long long ldX, const double *Y0, long long ldY0, const double *Y1, long long ldY1,
+                 double *out, const int *out_pos, int mode, void *s)
+{
+    return crp_sddmm_csr_f64(A, n, X, ldX, Y0, ldY0, Y1, ldY1, out, out_pos, mode, s);
+}
+static int sddmm(crp_csr_dev_p A, int n, const float *X, long long ldX, const float *Y0, long long ldY0, const float *Y1, long long ldY1,
+                 float *out, const int *out_pos, int mode, void *s)
+{
+    return crp_sddmm_csr_f32(A, n, X, ldX, Y0, ldY0, Y1, ldY1, out, out_pos, mode, s);
+}
+
+// first SDDMM call of a split engine: the parts write through int_src / bnd_src into the order of A_val
+static void build_sddmm(crp_rp_spmm *e)
+{
+    auto up = [&](const std::vector<long long> &src, int **dst) {
+        if (src.empty()) return;
+        std::vector<int> pos(src.begin(), src.end());          // (positions in A_val: below 2^31, as A_rowptr is int)
+        void *d = NULL;
+        HIP_OK(crp_dev_malloc(&d, sizeof(int) * pos.size()));
+        *dst = (int *) d;
+        HIP_OK(crp_dev_memcpy(*dst, pos.data(), sizeof(int) * pos.size(), 0, e->stream));
+        HIP_OK(crp_stream_sync(e->stream));
+    };
+    if (e->A_int != nullptr)
+    {
+        up(e->int_src, &e->sd_int_pos);
+        up(e->bnd_src, &e->sd_bnd_pos);
+    }
+    e->sd_built = true;
+}
+
+template <class T>
+static void sddmm_impl(crp_rp_spmm *e, int layout, const T *X, long long ldX, const T *Y, long long ldY, T *out, int mode, void *stream_)
+{
+    if (e == NULL) return;
+    ASSERT_PRINTF(!e->plan_only, "rp_spmm_sddmm on a plan-only engine (no device state)\n");
+    ASSERT_PRINTF(layout == 0 || layout == 1, "layout must be 0 or 1\n");
+    ASSERT_PRINTF(mode == 0 || mode == 1, "mode must be 0 or 1\n");
+    const double t_begin = get_wtime_sec();
+    if (!e->sd_built) build_sddmm(e);
+    void *s = stream_;
+    const int n = e->glb_n, kb = e->loc_B_nrow, m = e->A_nrow;
+    const size_t nnz = e->A_val.size();
+    const bool timing = e->timing != 0;
+    double t0;
+
+    int X_on_dev = 0, Y_on_dev = 0, out_on_dev = 0;
+    HIP_OK(crp_dev_ptr_is_device(X, &X_on_dev));
+    HIP_OK(crp_dev_ptr_is_device(Y, &Y_on_dev));
+    HIP_OK(crp_dev_ptr_is_device(out, &out_on_dev));
+
+    // ---- operands as device-resident row-major views, staged and transposed as in exec_impl: Y takes B's buffers, X takes C's
+    const Xchg x = exchange_of(e, Y);
+    auto view = [&](const T *P, long long ld, int rows, int on_dev, double **stage, size_t *stage_sz, double **rm, size_t *rm_sz,
+                    long long *ld_out) -> const T * {
+        const T *Pd = P;
+        *ld_out = ld;
+        if (rows <= 0 || n <= 0) return Pd;
+        if (!on_dev)
+        {
+            const size_t elems = (layout == 0) ? (size_t) rows * (size_t) ld : (size_t) n * (size_t) ld;
+            T *st = grow_as<T>(stage, stage_sz, elems);
+            const size_t used = (layout == 0) ? ((size_t) (rows - 1) * (size_t) ld + (size_t) n) : ((size_t) (n - 1) * (size_t) ld + (size_t) rows);
+            HIP_OK(crp_dev_memcpy(st, P, used * sizeof(T), 0, s));
+            Pd = st;
+        }
+        if (layout == 1)
+        {
+            T *r = grow_as<T>(rm, rm_sz, (size_t) rows * (size_t) n);
+            HIP_OK(transpose(n, rows, Pd, ld, r, n, s));      // column-major rows x n (ld) == row-major n x rows
+            Pd = r;
+            *ld_out = n;
+        }
+        return Pd;
+    };
+    long long ldYd = ldY, ldXd = ldX;
+    const T *Yd = view(Y, ldY, kb, Y_on_dev, &e->B_stage, &e->B_stage_sz, &e->B_rm, &e->B_rm_sz, &ldYd);
+    const T *Xd = view(X, ldX, m, X_on_dev, &e->C_stage, &e->C_stage_sz, &e->C_rm, &e->C_rm_sz, &ldXd);
+    T *outd = out;
+    if (!out_on_dev && nnz > 0) outd = grow_as<T>(&e->sd_out, &e->sd_out_sz, nnz);
+
+    if (n == 0 && nnz > 0) HIP_OK(crp_dev_memset(outd, 0, nnz * sizeof(T), s));      // empty dots
+
+    // ---- pack Y, exchange, the kernels: the parts of a split engine write through their positions in A_val
+    pack_exchange_run(e, x, Yd, ldYd, s, t0, [&](crp_csr_dev_p A, int part) {
+        if (n == 0 || crp_csr_dev_nnz(A) == 0) return;
+        const int *pos = part == 1 ? e->sd_int_pos : (part == 2 ? e->sd_bnd_pos : nullptr);
+        HIP_OK(sddmm(A, n, Xd, ldXd, Yd, ldYd, (const T *) x.recv, x.ld, outd, pos, mode, s));
+    });
+    if (timing)
+    {
+        HIP_OK(crp_stream_sync(s));
+        e->t_spmm += get_wtime_sec() - t0;
+    }
+
+    if (!out_on_dev && nnz > 0)
+    {
+        HIP_OK(crp_dev_memcpy(out, outd, nnz * sizeof(T), 1, s));
+        HIP_OK(crp_stream_sync(s));
+    }
+    else if (!X_on_dev || !Y_on_dev || timing)
+    {
+        HIP_OK(crp_stream_sync(s));
+    }
+    else
+    {
+        // asynchronous return: crp_rp_spmm_update_values waits for this call as for an exec
         if (e->ev_exec == nullptr) HIP_OK(crp_event_create(&e->ev_exec));
         HIP_OK(crp_event_record(e->ev_exec, s));
         e->exec_pending = true;
@@ -858,6 +998,20 @@ void crp_rp_spmm_exec_t_ex(crp_rp_spmm_p e, int BC_layout, const double *B, long
 }
 
 int crp_rp_spmm_transposed_built(crp_rp_spmm_p e) { return (e && e->t_built) ? 1 : 0; }
+
+void crp_rp_spmm_sddmm_ex(crp_rp_spmm_p e, int layout, const double *X, long long ldX, const double *Y, long long ldY, double *out,
+                          int mode, void *stream_)
+{
+    sddmm_impl<double>(e, layout, X, ldX, Y, ldY, out, mode, stream_);
+}
+
+void crp_rp_spmm_sddmm_f32_ex(crp_rp_spmm_p e, int layout, const float *X, long long ldX, const float *Y, long long ldY, float *out,
+                              int mode, void *stream_)
+{
+    sddmm_impl<float>(e, layout, X, ldX, Y, ldY, out, mode, stream_);
+}
+
+int crp_rp_spmm_sddmm_built(crp_rp_spmm_p e) { return (e && e->sd_built) ? 1 : 0; }
 
 void crp_rp_spmm_exec_ex(crp_rp_spmm_p e, int BC_layout, const double *B, long long ldB, double *C,
                          long long ldC, void *stream_)

@@ -71,6 +71,30 @@ def _ptr_ld(x, layout, f32=False):
     return x.ctypes.data, x.strides[0] // isz, x
 
 
+def _out_ptr(out, f32, nnz):
+    """(address, keepalive) of the 1-D contiguous float64 (f32: float32) result of ``sddmm``, which must hold nnz entries."""
+    name = "float32" if f32 else "float64"
+    try:
+        import torch
+        if isinstance(out, torch.Tensor):
+            if out.dtype != (torch.float32 if f32 else torch.float64) or out.dim() != 1:
+                raise TypeError("out must be 1-D %s, like the operands" % name)
+            if not out.is_contiguous():
+                raise ValueError("out must be contiguous")
+            if out.numel() != nnz:
+                raise ValueError("out has %d entries, this rank's rows of A %d nonzeros" % (out.numel(), nnz))
+            return out.data_ptr() or None, out
+    except ImportError:
+        pass
+    if not isinstance(out, np.ndarray) or out.dtype != np.dtype(name) or out.ndim != 1:
+        raise TypeError("out must be a 1-D %s torch tensor or numpy array, like the operands" % name)
+    if not out.flags.c_contiguous or not out.flags.writeable:
+        raise ValueError("out must be contiguous and writeable")
+    if out.size != nnz:
+        raise ValueError("out has %d entries, this rank's rows of A %d nonzeros" % (out.size, nnz))
+    return out.ctypes.data or None, out
+
+
 def _current_stream(x):
     try:
         import torch
@@ -153,6 +177,39 @@ class RpSpmm:
         if stream is None:
             stream = _current_stream(C_out)
         self._lib.crp_rp_spmm_exec_t_ex(self.handle, BC_layout, bp, ldb, cp, ldc, stream)
+
+    def sddmm(self, BC_layout, X, Y, out, mode=0, stream=None):
+        """Sampled dense-dense product over this rank's rows of A (crp_rp_spmm_sddmm_ex / _f32_ex, by the operands' dtype):
+        out[p] = <X[i], Y[c]> for every local nonzero p = (i, c), in the order of the A_val given to init; mode 1: times
+        the engine's current value of p.  X is this rank's A_nrow x glb_n block, Y its loc_B_nrow x glb_n block (layouts and
+        operands as ``exec``), ``out`` a 1-D array or tensor of nnz entries of the same dtype, on the host or the device.
+        Mixed dtypes, wrong shapes and a wrong ``out`` length raise before the library is called."""
+        dt = _operands_dtype(X, Y)
+        f32 = dt == "f32"
+        if mode not in (0, 1):
+            raise ValueError("mode must be 0 or 1, got %r" % (mode,))
+        xp, ldx, _kx = _ptr_ld(X, BC_layout, f32)
+        yp, ldy, _ky = _ptr_ld(Y, BC_layout, f32)
+        for name, x, rows in (("X", X, self.A_nrow), ("Y", Y, getattr(self, "loc_B_nrow", None))):
+            if rows is None:
+                continue
+            want = (rows, self.glb_n) if BC_layout == 0 else (self.glb_n, rows)
+            got = tuple(x.shape)
+            if (BC_layout == 0 and (got[0] < want[0] or got[1] != want[1])) or \
+               (BC_layout == 1 and (got[0] != want[0] or got[1] < want[1])):
+                raise ValueError("%s has shape %s, the engine needs %s (layout %d)" % (name, got, want, BC_layout))
+        op, _ko = _out_ptr(out, f32, self.nnz())
+        if stream is None:
+            stream = _current_stream(out)
+        if stream is None:
+            stream = _current_stream(X)
+        fn = self._lib.crp_rp_spmm_sddmm_f32_ex if f32 else self._lib.crp_rp_spmm_sddmm_ex
+        fn(self.handle, BC_layout, xp, ldx, yp, ldy, op, int(mode), stream)
+
+    @property
+    def sddmm_built(self):
+        """True once a ``sddmm`` has uploaded the positions its row parts write through (crp_rp_spmm_sddmm_built)."""
+        return bool(self._lib.crp_rp_spmm_sddmm_built(self.handle))
 
     @property
     def transposed_built(self):

@@ -82,6 +82,81 @@ class CsrDev:
         if isinstance(val, np.ndarray):
             L.check(self._lib.crp_stream_sync(C.c_void_p(stream)), "crp_stream_sync")      # `keep` may go away
 
+    def set_rowmap(self, rowmap, c_nrow):
+        """crp_csr_dev_set_rowmap: row t of this (row-subset) matrix writes row rowmap[t] of C and reads row rowmap[t] of
+        the X of ``sddmm``, both of c_nrow rows; None restores the identity."""
+        if rowmap is None:
+            L.check(self._lib.crp_csr_dev_set_rowmap(self.handle, None, 0), "crp_csr_dev_set_rowmap")
+            self._x_nrow = self.nrow
+            return
+        rm = np.ascontiguousarray(rowmap, dtype=np.int32)
+        if rm.size != self.nrow:
+            raise ValueError("rowmap has %d entries, the matrix %d rows" % (rm.size, self.nrow))
+        L.check(self._lib.crp_csr_dev_set_rowmap(self.handle, rm.ctypes.data_as(L.c_int_p), int(c_nrow)), "crp_csr_dev_set_rowmap")
+        self._x_nrow = int(c_nrow)
+
+    def sddmm(self, X, Y0, Y1=None, out=None, out_pos=None, mode=0, stream=None):
+        """Sampled dense-dense product over this matrix's pattern (crp_sddmm_csr_f64 / _f32, by the operands' dtype):
+        out[p] = <X[i], Y[c]> for nonzero p = (i, c), times the matrix's value of p in mode 1; c >= 0 reads row c of Y0,
+        c < 0 row ~c of Y1.  X, Y0, Y1 are 2-D row-major float64 or float32 cuda tensors of one dtype and width; ``out`` a
+        1-D tensor of that dtype (allocated with nnz entries when None); ``out_pos`` an int32 cuda tensor of nnz entries:
+        nonzero p writes out[out_pos[p]] (``out`` is then required and must hold every position named).  Returns ``out``.
+        Mixed dtypes, wrong shapes and a short ``out`` raise before the library is called."""
+        import torch
+        ops = [("X", X), ("Y0", Y0)] + ([("Y1", Y1)] if Y1 is not None else [])
+        for name, t in ops:
+            if not (isinstance(t, torch.Tensor) and t.dim() == 2):
+                raise TypeError("%s must be a 2-D torch tensor on the device" % name)
+            if t.dtype not in (torch.float64, torch.float32):
+                raise TypeError("%s must be float64 or float32, got %s" % (name, t.dtype))
+            if t.dtype != X.dtype:
+                raise TypeError("X, Y0 and Y1 must have one dtype (X is %s, %s is %s)" % (X.dtype, name, t.dtype))
+            if t.shape[1] > 1 and t.stride(1) != 1:
+                raise ValueError("%s must be contiguous along its rows" % name)
+        if mode not in (0, 1):
+            raise ValueError("mode must be 0 or 1, got %r" % (mode,))
+        n = int(X.shape[1])
+        if n < 1:
+            raise ValueError("the operands need at least one column")
+        for name, t in ops[1:]:
+            if t.shape[1] != n:
+                raise ValueError("%s has %d columns, X has %d" % (name, t.shape[1], n))
+        x_nrow = getattr(self, "_x_nrow", self.nrow)
+        if X.shape[0] < x_nrow:
+            raise ValueError("X has %d rows, the matrix needs %d" % (X.shape[0], x_nrow))
+        if Y0.shape[0] < self.ncol:
+            raise ValueError("Y0 has %d rows, the matrix has %d columns" % (Y0.shape[0], self.ncol))
+        nnz = self.nnz
+        if out_pos is not None:
+            if not (isinstance(out_pos, torch.Tensor) and out_pos.dtype == torch.int32 and out_pos.dim() == 1
+                    and out_pos.is_contiguous()):
+                raise TypeError("out_pos must be a contiguous 1-D int32 torch tensor on the device")
+            if out_pos.numel() != nnz:
+                raise ValueError("out_pos has %d entries, the matrix %d nonzeros" % (out_pos.numel(), nnz))
+            if out is None:
+                raise ValueError("out_pos needs an out to write into")
+        if out is None:
+            if not X.is_cuda:
+                raise TypeError("X must be on the device")
+            out = torch.empty(nnz, dtype=X.dtype, device=X.device)
+        if not (isinstance(out, torch.Tensor) and out.dim() == 1 and out.is_contiguous()):
+            raise TypeError("out must be a contiguous 1-D torch tensor on the device")
+        if out.dtype != X.dtype:
+            raise TypeError("out must have the operands' dtype (out is %s, X is %s)" % (out.dtype, X.dtype))
+        if out_pos is None and out.numel() < nnz:
+            raise ValueError("out has %d entries, the matrix %d nonzeros" % (out.numel(), nnz))
+        for name, t in ops + [("out", out)] + ([("out_pos", out_pos)] if out_pos is not None else []):
+            if not t.is_cuda or t.device != X.device:
+                raise TypeError("%s must be on the device, with X" % name)      # (all pointers are device pointers)
+        if nnz == 0:
+            return out
+        fn = self._lib.crp_sddmm_csr_f64 if X.dtype == torch.float64 else self._lib.crp_sddmm_csr_f32
+        y1p, ld1 = (Y1.data_ptr(), Y1.stride(0)) if Y1 is not None else (None, 0)
+        L.check(fn(self.handle, n, X.data_ptr(), X.stride(0), Y0.data_ptr(), Y0.stride(0), y1p, ld1, out.data_ptr() or None,
+                   out_pos.data_ptr() if out_pos is not None else None, int(mode), _stream(out) if stream is None else stream),
+                fn.__name__)
+        return out
+
     def resolved_variant(self, n):
         """crp_csr_dev_resolved_variant: what a variant-0 product of n columns launches on this matrix."""
         return int(self._lib.crp_csr_dev_resolved_variant(self.handle, int(n)))

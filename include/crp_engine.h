@@ -101,6 +101,27 @@ void crp_rp_spmm_exec_f32_ex(crp_rp_spmm_p rp_spmm, int BC_layout, const float *
 void crp_rp_spmm_exec_t_ex(crp_rp_spmm_p rp_spmm, int BC_layout, const double *B, long long ldB,
                            double *C, long long ldC, void *stream);
 int crp_rp_spmm_transposed_built(crp_rp_spmm_p rp_spmm);
+/* Sampled dense-dense product over this rank's rows of A (crp_sddmm_csr_f64 / _f32 in crpspmm_hip.h): for every local nonzero
+ * p = (i, c) of the GLOBAL matrix, out[p] = < X[i][0:glb_n], Y[c][0:glb_n] >, times the engine's current value of p in mode 1
+ * (mode 0: the plain dot).  X is this rank's A_nrow x glb_n block (partitioned like A's rows and like C of exec), Y its
+ * loc_B_nrow x glb_n block (partitioned by B_row_displs, like B of exec), out one value per local nonzero IN THE ORDER OF THE
+ * A_val GIVEN TO INIT -- the order crp_rp_spmm_update_values takes.  X, Y and out may each be a host or a device pointer.
+ * A row-parallel SDDMM needs exactly the rows of Y that exec needs of B: one call packs Y by the forward plan's send list,
+ * runs the forward exchange as exec issues it, and forms the dots with the local rows of Y as the first and the receive
+ * buffer as the second source -- with timing off and a split engine the interior rows' dots on the caller's stream beside the
+ * exchange, the boundary rows' after the rows have landed.  The parts of a split engine write through device copies of their
+ * nonzeros' positions in A_val, uploaded by the first SDDMM call and by nothing before it (crp_rp_spmm_sddmm_built: 0, then
+ * 1).  Every entry is formed in the fixed order of crp_sddmm_csr_f64, so the result is bit-identical across rank counts,
+ * timing modes and repeated calls.  Layouts (1: X and Y column-major, transposed on the device first), staging, streams,
+ * statistics (pack, redistribution and SpMM time; n_exec counts these calls too) and completion rules as crp_rp_spmm_exec_ex:
+ * with device pointers and timing off nothing synchronises, and a later crp_rp_spmm_update_values does not overtake the
+ * call.  The fp32 form exchanges rows as crp_rp_spmm_exec_f32_ex does.  A plan-only engine aborts as in exec; a NULL engine
+ * is a no-op. */
+void crp_rp_spmm_sddmm_ex(crp_rp_spmm_p rp_spmm, int layout, const double *X, long long ldX,
+                          const double *Y, long long ldY, double *out, int mode, void *stream);
+void crp_rp_spmm_sddmm_f32_ex(crp_rp_spmm_p rp_spmm, int layout, const float *X, long long ldX,
+                              const float *Y, long long ldY, float *out, int mode, void *stream);
+int crp_rp_spmm_sddmm_built(crp_rp_spmm_p rp_spmm);
 void crp_rp_spmm_print_stat(crp_rp_spmm_p rp_spmm);
 void crp_rp_spmm_clear_stat(crp_rp_spmm_p rp_spmm);
 /* rp_spmm_init for a caller that ALSO holds the values in device memory, in the order of A_val (A_val_dev: the panel a
