@@ -140,6 +140,7 @@ SIGNATURES = {
     "crp_csr_dev_reordered": (_I, [_V]),
     "crp_csr_dev_resolved_variant": (_I, [_V, _I]),
     "crp_csr_dev_last_variant": (_I, [_V]),
+    "crp_csr_dev_last_kernel": (C.c_char_p, [_V]),
     "crp_csr_dev_lattice": (_I, [_V]),
     "crp_csr_dev_team2_compact": (_I, [_V]),
     "crp_panel_format_host": (_I, [_I, c_int_p, c_int_p, c_dbl_p, _I, c_int_p, C.POINTER(c_int_p), C.POINTER(c_int_p),

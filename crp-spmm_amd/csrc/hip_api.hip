@@ -115,6 +115,7 @@ struct crp_csr_dev
     bool     team2r_refused = false;   // a variant-0 product found the row-owner streams too large: variant 0 no longer takes them
     long long rowmap_epoch = 0;    // bumped by crp_csr_dev_set_rowmap: the team2r entry tables hold C rows
     int      last_variant = 0;     // what the last product launched (crp_csr_dev_last_variant)
+    const char *last_kernel = "";  // ... and the kernel instance, as its launcher named it (crp_csr_dev_last_kernel)
     long long b0_rows = 0, b1_rows = 0;   // 1 + largest local / receive-buffer row a column index addresses
     DevBuf<float> val32;                  // fp32 copy of val (fp32 path), built on first use
     DevBuf<int> rowmap;                   // row-subset matrices: C row of every row (device), else nullptr
@@ -837,8 +838,8 @@ const char *crp_spmm_variant_name(int variant)
     return k_variant_names[variant];
 }
 
-int crp_spmm_csr_f64(crp_csr_dev_p A, int layout, int n, const double *B0, long long ldB0, const double *B1,
-                     long long ldB1, double *C, long long ldC, int variant, void *stream)
+static int spmm_csr_f64(crp_csr_dev_p A, int layout, int n, const double *B0, long long ldB0, const double *B1,
+                        long long ldB1, double *C, long long ldC, int variant, void *stream)
 {
     if (A == NULL || n < 0) return -1;
     if (layout != CRP_LAYOUT_ROW_MAJOR && layout != CRP_LAYOUT_COL_MAJOR) return -1;
@@ -910,10 +911,20 @@ int crp_spmm_csr_f64(crp_csr_dev_p A, int layout, int n, const double *B0, long 
     return (int) crp::spmm_rm_f64_panel(p, a, s);
 }
 
+// (the launcher that runs names its kernel instance in crp::t_last_kernel: kept on the handle, "" when nothing was launched)
+int crp_spmm_csr_f64(crp_csr_dev_p A, int layout, int n, const double *B0, long long ldB0, const double *B1,
+                     long long ldB1, double *C, long long ldC, int variant, void *stream)
+{
+    crp::t_last_kernel = "";
+    const int rc = spmm_csr_f64(A, layout, n, B0, ldB0, B1, ldB1, C, ldC, variant, stream);
+    if (A != NULL) A->last_kernel = crp::t_last_kernel;
+    return rc;
+}
+
 // C[nrow x n] := A * B with values, B and C in fp32 (row-major only): the fp32 instance of the team kernel where it
 // applies and pays (variant 0 / 5), the fp32 CSR row-group kernel otherwise (variant 1, any width and alignment)
-int crp_spmm_csr_f32(crp_csr_dev_p A, int n, const float *B0, long long ldB0, const float *B1, long long ldB1, float *C,
-                     long long ldC, int variant, void *stream)
+static int spmm_csr_f32(crp_csr_dev_p A, int n, const float *B0, long long ldB0, const float *B1, long long ldB1, float *C,
+                        long long ldC, int variant, void *stream)
 {
     if (A == NULL || n < 0) return -1;
     if (!variant_valid(variant, true)) return -1;
@@ -946,6 +957,15 @@ int crp_spmm_csr_f32(crp_csr_dev_p A, int n, const float *B0, long long ldB0, co
     return (int) crp::spmm_rm_f32_team2(t, a, s);
 }
 
+int crp_spmm_csr_f32(crp_csr_dev_p A, int n, const float *B0, long long ldB0, const float *B1, long long ldB1, float *C,
+                     long long ldC, int variant, void *stream)
+{
+    crp::t_last_kernel = "";
+    const int rc = spmm_csr_f32(A, n, B0, ldB0, B1, ldB1, C, ldC, variant, stream);
+    if (A != NULL) A->last_kernel = crp::t_last_kernel;
+    return rc;
+}
+
 int crp_sddmm_csr_f64(crp_csr_dev_p A, int n, const double *X, long long ldX, const double *Y0, long long ldY0, const double *Y1,
                       long long ldY1, double *out, const int *out_pos, int mode, void *stream)
 {
@@ -975,6 +995,7 @@ int crp_csr_dev_resolved_variant(crp_csr_dev_p A, int n)      // (an aligned ope
     return A ? crp::resolve_f64(A->traits, operand_of(n, nullptr, n, nullptr, 0, nullptr, n), 0, A->team2r_refused, crp::knobs()) : -1;
 }
 int crp_csr_dev_last_variant(crp_csr_dev_p A) { return A ? A->last_variant : -1; }
+const char *crp_csr_dev_last_kernel(crp_csr_dev_p A) { return A ? A->last_kernel : NULL; }
 int crp_csr_dev_lattice(crp_csr_dev_p A) { return A ? ((A->team2.built && A->team2.lattice) ? 1 : 0) : -1; }
 int crp_csr_dev_team2_compact(crp_csr_dev_p A) { return (A && A->team2.built) ? (A->team2.compact ? 1 : 0) : -1; }
 

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 
 namespace crp {
 
@@ -104,6 +105,20 @@ template <typename T> struct SddmmArgs     // sddmm_kernels.hip: out[p] = < X[ro
     const int *out_pos;     // nullptr, or where nonzero p writes: out[out_pos[p]]
     int        mode;        // 0: the dot, 1: the dot times val[p]
 };
+
+// The instance every SpMM launcher names at its hipLaunchKernelGGL, from its own template arguments ("rowgroup<16,2,1>",
+// "panel<8,2,2,a32,b1>", "team2<f64,NV1,b0,compact>", ...): a string with static storage, per host thread.  hip_api.hip copies
+// it into the handle after the product (crp_csr_dev_last_kernel); nothing else reads it.
+extern thread_local const char *t_last_kernel;
+// "<family><a,b,c>" once per instantiation (the function-local buffer is the instance's name for the life of the library)
+#define CRP_KERNEL_NAME(...)                                                         \
+    do                                                                               \
+    {                                                                                \
+        static char name_[48];                                                       \
+        static const int once_ = snprintf(name_, sizeof(name_), __VA_ARGS__);        \
+        (void) once_;                                                                \
+        ::crp::t_last_kernel = name_;                                                \
+    } while (0)
 
 // narrow_kernel.hip: row-panel format, n <= 64 (several entries of a panel per instruction)
 bool spmm_narrow_applicable(const PanelArgs &p, const SpmmArgs &a);

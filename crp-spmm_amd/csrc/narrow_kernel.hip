@@ -181,10 +181,13 @@ hipError_t spmm_rm_f64_narrow(const PanelArgs &p, const SpmmArgs &a, hipStream_t
     const bool off32 = !has_b1 && (uint64_t) p.b0_rows * (uint64_t) a.ldB0 * 8ull < (1ull << 32);
     const bool compact = p.cmo != nullptr && p.cbase != nullptr && p.cval != nullptr;
 #define CRP_NARROW_GO(HB1_, O32_, CP_)                                                                                        \
+    t_last_kernel = (HB1_ ? (CP_ ? "narrow<b1,o64,compact>" : "narrow<b1,o64,full>")                                          \
+                          : O32_ ? (CP_ ? "narrow<b0,o32,compact>" : "narrow<b0,o32,full>")                                   \
+                                 : (CP_ ? "narrow<b0,o64,compact>" : "narrow<b0,o64,full>"));                                 \
     hipLaunchKernelGGL((spmm_narrow_f64_kernel<HB1_, O32_, CP_>), grid, dim3(256), 0, s, p.norder, a.nrow, a.n, p.porder, p.pcol, \
                        CP_ ? p.cmo : p.pmask4, CP_ ? p.cval : p.pval, p.cbase, a.B0, a.ldB0, a.B1, a.ldB1, a.C, a.ldC, a.rowmap)
-    if (compact) { if (has_b1) CRP_NARROW_GO(true, false, true); else if (off32) CRP_NARROW_GO(false, true, true); else CRP_NARROW_GO(false, false, true); }
-    else { if (has_b1) CRP_NARROW_GO(true, false, false); else if (off32) CRP_NARROW_GO(false, true, false); else CRP_NARROW_GO(false, false, false); }
+    if (compact) { if (has_b1) { CRP_NARROW_GO(true, false, true); } else if (off32) { CRP_NARROW_GO(false, true, true); } else { CRP_NARROW_GO(false, false, true); } }
+    else { if (has_b1) { CRP_NARROW_GO(true, false, false); } else if (off32) { CRP_NARROW_GO(false, true, false); } else { CRP_NARROW_GO(false, false, false); } }
 #undef CRP_NARROW_GO
     return hipGetLastError();
 }

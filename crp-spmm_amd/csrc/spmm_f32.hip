@@ -70,6 +70,7 @@ static hipError_t launch_f32(const SpmmArgsF32 &a, hipStream_t s)
 {
     constexpr int RPB = 256 / LPR, TW = LPR * VW;
     dim3 grid((a.nrow + RPB - 1) / RPB, (a.n + TW - 1) / TW);
+    CRP_KERNEL_NAME("rowgroup_f32<%d,%d>", LPR, VW);
     hipLaunchKernelGGL((spmm_rm_f32_kernel<LPR, VW>), grid, dim3(256), 0, s, a.nrow, a.n, a.rowptr, a.colidx, a.val, a.B0, a.ldB0,
                        a.B1, a.ldB1, a.C, a.ldC, a.rowmap);
     return hipGetLastError();

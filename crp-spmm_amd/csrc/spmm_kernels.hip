@@ -18,6 +18,8 @@
 
 namespace crp {
 
+thread_local const char *t_last_kernel = "";
+
 typedef double d2 __attribute__((ext_vector_type(2)));
 
 template <int LPR>
@@ -164,6 +166,7 @@ static hipError_t launch_rm(const SpmmArgs &a, hipStream_t s)
     constexpr int RPB = 256 / LPR;
     constexpr int TW  = LPR * VW * NV;
     dim3 grid((a.nrow + RPB - 1) / RPB, (a.n + TW - 1) / TW);
+    CRP_KERNEL_NAME("rowgroup<%d,%d,%d>", LPR, VW, NV);
     hipLaunchKernelGGL((spmm_rm_f64_kernel<LPR, VW, NV>), grid, dim3(256), 0, s,
                        a.nrow, a.n, a.rowptr, a.colidx, a.val, a.B0, a.ldB0, a.B1, a.ldB1, a.C, a.ldC, a.rowmap);
     return hipGetLastError();
@@ -648,6 +651,7 @@ static hipError_t launch_panel(const PanelArgs &p, const SpmmArgs &a, hipStream_
     constexpr int TW = 64 * VW * NV;
     const int nwg = (p.norder + PANEL_WPW - 1) / PANEL_WPW;
     dim3 grid((nwg + 7) / 8 * 8, (a.n + TW - 1) / TW);      // multiple of 8 for the XCD remap
+    CRP_KERNEL_NAME("panel<%d,%d,%d,%s,%s>", R, NV, VW, ADDR64 ? "a64" : "a32", HAS_B1 ? "b1" : "b0");
     hipLaunchKernelGGL((spmm_panel_f64_kernel<R, NV, VW, ADDR64, HAS_B1>), grid, dim3(64 * PANEL_WPW), 0, s, p.norder, a.nrow,
                        a.n, p.porder, p.pptr, p.pcol, p.pmask4, p.pval, a.B0, a.ldB0, a.B1, a.ldB1, a.C, a.ldC, a.rowmap, p.psync);
     return hipGetLastError();
@@ -723,6 +727,7 @@ __global__ __launch_bounds__(256) void spmm_cm_f64_kernel(
 hipError_t spmm_cm_f64(const SpmmArgs &a, hipStream_t s)
 {
     dim3 grid((a.nrow + 255) / 256, a.n);
+    t_last_kernel = "cm";
     hipLaunchKernelGGL(spmm_cm_f64_kernel, grid, dim3(256), 0, s,
                        a.nrow, a.n, a.rowptr, a.colidx, a.val, a.B0, a.ldB0, a.B1, a.ldB1, a.C, a.ldC, a.rowmap);
     return hipGetLastError();

@@ -390,15 +390,16 @@ hipError_t spmm_rm_f64_team2r(const Team2NArgs &t, const SpmmArgs &a, hipStream_
     const int run = t.ngrid / 8;                                            // entries of an XCD's run
     const int per_xcd = std::max(1, std::min(run, std::max(2 * ncu / 8, (run + 6) / 7)));
     dim3 grid(per_xcd * 8);
-#define CRP_T2R_GO(G_, HB1_)                                                                                                                        \
+#define CRP_T2R_GO(G_, HB1_, NAME_)                                                                                                                 \
     do                                                                                                                                              \
     {                                                                                                                                               \
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&spmm_team2r_kernel<G_, HB1_>), hipFuncAttributeMaxDynamicSharedMemorySize, T2R_LDS); \
         if (e != hipSuccess) return e;                                                                                                              \
+        t_last_kernel = "team2r<" #G_ "," NAME_ ">";                                                                                                \
         hipLaunchKernelGGL((spmm_team2r_kernel<G_, HB1_>), grid, dim3(512), T2R_LDS, s, t.ngrid, t.tent, t.tval, a.n, a.B0, a.ldB0, a.B1, a.ldB1, a.C, a.ldC, 1, 0, nullptr); \
     } while (0)
-    if (t.G == 4) { if (has_b1) CRP_T2R_GO(4, true); else CRP_T2R_GO(4, false); }
-    else { if (has_b1) CRP_T2R_GO(2, true); else CRP_T2R_GO(2, false); }
+    if (t.G == 4) { if (has_b1) CRP_T2R_GO(4, true, "b1"); else CRP_T2R_GO(4, false, "b0"); }
+    else { if (has_b1) CRP_T2R_GO(2, true, "b1"); else CRP_T2R_GO(2, false, "b0"); }
 #undef CRP_T2R_GO
     return hipGetLastError();
 }

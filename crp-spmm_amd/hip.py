@@ -162,6 +162,11 @@ class CsrDev:
         return int(self._lib.crp_csr_dev_resolved_variant(self.handle, int(n)))
 
     @property
+    def last_kernel(self):
+        """crp_csr_dev_last_kernel: the kernel instance the last product on this handle launched, e.g. ``panel<8,2,2,a32,b0>``."""
+        return (self._lib.crp_csr_dev_last_kernel(self.handle) or b"").decode()
+
+    @property
     def nnz(self):
         return int(self._lib.crp_csr_dev_nnz(self.handle))
 

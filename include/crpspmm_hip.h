@@ -168,6 +168,11 @@ int crp_csr_dev_reordered(crp_csr_dev_p A);
 int crp_csr_dev_resolved_variant(crp_csr_dev_p A, int n);
 /* the variant the last crp_spmm_csr_f64 / _f32 on this matrix launched (after every fallback), or 0 before the first */
 int crp_csr_dev_last_variant(crp_csr_dev_p A);
+/* the kernel instance that product launched, named by its launcher from its own template arguments: "rowgroup<LPR,VW,NV>", "cm"
+ * (column-major), "panel<R,NV,VW,a32|a64,b0|b1>", "narrow<b0|b1,o32|o64,compact|full>", "team2r<G,b0|b1>",
+ * "team2<f64|f32,NVH|NV1|NV2,b0|b1,compact|full>", "rowgroup_f32<LPR,VW>"; "" before the first product and after one that launched
+ * nothing (an empty matrix, n = 0, an error before the launch).  The string lives as long as the library. */
+const char *crp_csr_dev_last_kernel(crp_csr_dev_p A);
 /* 1 when the team formats built so far found the two nested strides of a mesh numbered along its lines (their
  * teams are then blocks of neighbouring mesh lines), 0 otherwise / not built yet. */
 int crp_csr_dev_lattice(crp_csr_dev_p A);

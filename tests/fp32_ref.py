@@ -58,6 +58,15 @@ def decode_cols(colidx):
     return neg, np.where(neg, ~ci, ci)
 
 
+def split_two_source(ci, k, lo, hi):
+    """Columns [lo, hi) -> B0 rows (code c - lo), the rest -> B1 rows in ascending order (code ~position).  -> (codes, the B1 rows)."""
+    remote = np.concatenate([np.arange(0, lo), np.arange(hi, k)])
+    pos = np.full(k, -1)
+    pos[remote] = np.arange(remote.size)
+    codes = np.where((ci >= lo) & (ci < hi), ci - lo, ~pos[ci]).astype(np.int32)
+    return codes, remote
+
+
 def csr_f32_sequential(rowptr, codes, val64, B0, B1=None, rowmap=None, nrow_c=None):
     """What the CSR row-group kernel computes, bit for bit: acc = 0.0f; acc = fmaf(fp32(val[p]), B[col(p)][j], acc) for p in
     ascending order; codes < 0 read B1[~code].  val64 is rounded to fp32 to nearest even, as convert_f64_f32_kernel's (float) cast.

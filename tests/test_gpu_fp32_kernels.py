@@ -81,13 +81,7 @@ def _bits_equal(a, b):
                                                  b.view(np.uint32 if b.dtype == np.float32 else np.uint64))
 
 
-def _split_two_source(ci, k, lo, hi):
-    """Columns [lo, hi) -> B0 rows (code c - lo), the rest -> B1 rows in ascending order (code ~position)."""
-    remote = np.concatenate([np.arange(0, lo), np.arange(hi, k)])
-    pos = np.full(k, -1)
-    pos[remote] = np.arange(remote.size)
-    codes = np.where((ci >= lo) & (ci < hi), ci - lo, ~pos[ci]).astype(np.int32)
-    return codes, remote
+_split_two_source = F.split_two_source
 
 
 def _rowgroup_matrix(n):

@@ -19,7 +19,8 @@ def _t(x, dev):
     return torch.from_numpy(np.ascontiguousarray(x)).to(dev)
 
 
-def _spmm(crp, dev, rp, ci, va, k, B, n, layout=0, B1=None, ldpad=0, variant=0):
+def _spmm(crp, dev, rp, ci, va, k, B, n, layout=0, B1=None, ldpad=0, variant=0, kernels=None):
+    """kernels: a list that receives the name of the kernel instance the product launched (crp_csr_dev_last_kernel)."""
     import torch
     from crp_spmm_amd import hip
     A = hip.CsrDev(len(rp) - 1, k, rp, ci, va)
@@ -33,6 +34,8 @@ def _spmm(crp, dev, rp, ci, va, k, B, n, layout=0, B1=None, ldpad=0, variant=0):
             B1d = _t(B1[:, :n], dev)
         hip.spmm_csr(A, Bd[:, :n] if ldpad else Bd, Cd[:, :n] if ldpad else Cd, n=n, B1=B1d, variant=variant)
         torch.cuda.synchronize()
+        if kernels is not None:
+            kernels.append(A.last_kernel)
         out = Cd.cpu().numpy()
         if ldpad:
             assert np.isnan(out[:, n:]).all()       # padding between rows is never written
@@ -816,10 +819,12 @@ def test_narrow_kernel(crp, orc, gpu, n):
     """The narrow-operand kernel (csrc/narrow_kernel.hip: row-panel format, four entries per instruction; variant 3 at
     24 <= n <= 32, even n, 16-byte aligned operands): random / banded / empty-row matrices with padded leading dimensions,
     the two-source column index (general addressing path), non-finite B rows next to absent pairs, value updates,
-    bit-identical repeats, and B rows past 4 GiB (64-bit addressing path)."""
+    bit-identical repeats, and B rows past 4 GiB (64-bit addressing path).  Every variant-3 product here ran the narrow kernel at
+    n <= 32 and the one-column-per-lane row-panel kernel at 48 and 64 columns (crp_csr_dev_last_kernel)."""
     import torch
     from crp_spmm_amd import gen, hip
     lib = crp.load()
+    ran = []
     # (the values of the panels without their holes are taken when under 60 % of the (row, entry) pairs exist: the kkt case below)
     cases = [gen.random_csr(777, 1234, 70, seed=n, empty_every=13), gen.banded_fem(5000, offsets=(1, 2, 3, 40, 41, 900), seed=n),
              gen.random_csr(13, 40, 5, seed=1), gen.kkt3d(10)]
@@ -829,7 +834,7 @@ def test_narrow_kernel(crp, orc, gpu, n):
         B = np.random.default_rng(n).uniform(-2, 2, size=(k, n))
         ref = orc.spmm_csr(rp, ci, va, B)
         for ldpad in (0, 2, 6):
-            got = _spmm(crp, gpu, rp, ci, va, k, B, n, ldpad=ldpad, variant=3)
+            got = _spmm(crp, gpu, rp, ci, va, k, B, n, ldpad=ldpad, variant=3, kernels=ran)
             assert orc.rel_fro_err(ref, got) <= FP64_TOL, (m, ldpad)
     # two-source column index
     m, k = 500, 900
@@ -840,14 +845,14 @@ def test_narrow_kernel(crp, orc, gpu, n):
     pos[remote_rows] = np.arange(remote_rows.size)
     c2 = np.where((ci >= lo) & (ci < hi), ci - lo, ~pos[ci]).astype(np.int32)
     B = np.random.default_rng(n + 1).normal(size=(k, n))
-    got = _spmm(crp, gpu, rp, c2, va, hi - lo, B[lo:hi], n, B1=B[remote_rows], variant=3)
+    got = _spmm(crp, gpu, rp, c2, va, hi - lo, B[lo:hi], n, B1=B[remote_rows], variant=3, kernels=ran)
     assert orc.rel_fro_err(orc.spmm_csr(rp, ci, va, B), got) <= FP64_TOL
     # non-finite B rows: an Inf that a panel-mate reads must not leak NaNs into rows without that column
     used = np.unique(ci)
     B[used[::17]] = np.inf
     B[used[5::29]] = np.nan
     ref = orc.spmm_csr(rp, ci, va, B)
-    got = _spmm(crp, gpu, rp, ci, va, k, B, n, variant=3)
+    got = _spmm(crp, gpu, rp, ci, va, k, B, n, variant=3, kernels=ran)
     assert np.array_equal(np.isnan(ref), np.isnan(got)) and np.array_equal(np.isinf(ref), np.isinf(got))
     fin = np.isfinite(ref)
     assert np.abs(ref[fin] - got[fin]).max() <= 1e-12 * np.abs(ref[fin]).max()
@@ -867,7 +872,10 @@ def test_narrow_kernel(crp, orc, gpu, n):
     hip.spmm_csr(A, Bd, Cd, n=n, variant=3)
     torch.cuda.synchronize()
     assert orc.rel_fro_err(orc.spmm_csr(rp, ci, v2, Bf), Cd.cpu().numpy()) <= FP64_TOL
+    ran.append(A.last_kernel)
     A.free()
+    want = "narrow<" if n <= 32 else "panel<8,1,1,"
+    assert len(ran) == 15 and all(name.startswith(want) for name in ran), (n, want, ran)
     if n == 32:
         # B rows addressed past 4 GiB: the 64-bit addressing path
         kb, ld = 1100, 1 << 19
@@ -884,6 +892,7 @@ def test_narrow_kernel(crp, orc, gpu, n):
         hip.spmm_csr(Ab, Bbig[:, :n], Cb, n=n, variant=3)
         torch.cuda.synchronize()
         assert orc.rel_fro_err(orc.spmm_csr(rpb, cib, vab, Bb), Cb.cpu().numpy()) <= FP64_TOL
+        assert Ab.last_kernel == "narrow<b0,o64,compact>", Ab.last_kernel
         Ab.free()
         del Bbig
         torch.cuda.empty_cache()
