@@ -172,6 +172,8 @@ SIGNATURES = {
     "crp_gather_rows_f64": (_I, [_I, _I, _I, _V, _V, _LL, _V, _LL, _V]),
     "crp_scatter_rows_f64": (_I, [_I, _I, _I, _V, _V, _LL, _V, _LL, _V]),
     "crp_scatter_add_rows_f64": (_I, [_I, _I, _V, _V, _V, _V, _LL, _V, _LL, _V]),
+    "crp_sum_segments_f64": (_I, [_I, _LL, _V, _LL, _V, _V]),
+    "crp_sum_segments_f32": (_I, [_I, _LL, _V, _LL, _V, _V]),
     "crp_transpose_f64": (_I, [_I, _I, _V, _LL, _V, _LL, _V]),
     "crp_gather_rows_f32": (_I, [_I, _I, _I, _V, _V, _LL, _V, _LL, _V]),
     "crp_scatter_rows_f32": (_I, [_I, _I, _I, _V, _V, _LL, _V, _LL, _V]),
@@ -198,6 +200,7 @@ SIGNATURES = {
     "crp_rp_spmm_get_plan": (None, [_V, C.POINTER(RpPlanView)]),
     "crp_rp_spmm_overlap_rows": (None, [_V, c_int_p, c_int_p]),
     "crp_rp_spmm_set_timing": (None, [_V, _I]),
+    "crp_rp_spmm_timing": (_I, [_V]),
     # crp_rccl.h
     "crp_rccl_get_unique_id": (_I, [_V]),
     "crp_rccl_create": (_I, [_V, _I, _I, C.POINTER(_V)]),
@@ -232,6 +235,13 @@ SIGNATURES = {
     "crp_para2d_spmm_exec": (None, [_V, _I, _V, _I, _V, _I]),
     "crp_para2d_spmm_exec_ex": (None, [_V, _I, _V, _LL, _V, _LL, _V]),
     "crp_para2d_spmm_exec_f32_ex": (None, [_V, _I, _V, _LL, _V, _LL, _V]),
+    "crp_para2d_spmm_update_values": (None, [_V, c_dbl_p]),
+    "crp_para2d_spmm_exec_t_ex": (None, [_V, _I, _V, _LL, _V, _LL, _V]),
+    "crp_para2d_spmm_sddmm_ex": (None, [_V, _I, _V, _LL, _V, _LL, _V, _I, _V]),
+    "crp_para2d_spmm_sddmm_f32_ex": (None, [_V, _I, _V, _LL, _V, _LL, _V, _I, _V]),
+    "crp_para2d_spmm_sddmm_built": (_I, [_V]),
+    "crp_para2d_spmm_slice_nnz": (_LL, [_V]),
+    "crp_para2d_spmm_row_slice_nnz": (_I, [_V, c_ll_p]),
     "crp_para2d_spmm_print_stat": (None, [_V]),
     "crp_para2d_spmm_clear_stat": (None, [_V]),
     "crp_para2d_spmm_rp": (_V, [_V]),

@@ -1173,6 +1173,22 @@ int crp_scatter_add_rows_f64(int nseg, int n, const int *seg_row, const int *seg
     return (int) crp::scatter_add_rows_f64(nseg, n, seg_row, seg_ptr, seg_pos, src, lds, dst, ldd, (hipStream_t) stream);
 }
 
+int crp_sum_segments_f64(int nseg, long long len, const double *src, long long seg_stride, double *out, void *stream)
+{
+    if (src == NULL || out == NULL || nseg < 1 || len < 0) return -1;
+    if (nseg > 1 && seg_stride < len) return -4;
+    if (len == 0) return 0;
+    return (int) crp::sum_segments_f64(nseg, len, src, seg_stride, out, (hipStream_t) stream);
+}
+
+int crp_sum_segments_f32(int nseg, long long len, const float *src, long long seg_stride, float *out, void *stream)
+{
+    if (src == NULL || out == NULL || nseg < 1 || len < 0) return -1;
+    if (nseg > 1 && seg_stride < len) return -4;
+    if (len == 0) return 0;
+    return (int) crp::sum_segments_f32(nseg, len, src, seg_stride, out, (hipStream_t) stream);
+}
+
 int crp_transpose_f64(int nrow, int ncol, const double *src, long long lds, double *dst, long long ldd,
                       void *stream)
 {

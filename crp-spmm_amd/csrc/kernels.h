@@ -153,6 +153,9 @@ hipError_t scatter_vals_f64(int64_t n, const uint32_t *map, const double *src, d
 hipError_t gather_vals_f64(int64_t n, const int *map, const double *src, double *dst, hipStream_t s);      // dst[i] = src[map[i]]
 hipError_t scatter_add_rows_f64(int nseg, int n, const int *seg_row, const int *seg_ptr, const int *seg_pos, const double *src,
                                 int64_t lds, double *dst, int64_t ldd, hipStream_t s);
+// out[p] = the sum over j < nseg of src[j * seg_stride + p], added left to right (p < len)
+hipError_t sum_segments_f64(int nseg, int64_t len, const double *src, int64_t seg_stride, double *out, hipStream_t s);
+hipError_t sum_segments_f32(int nseg, int64_t len, const float *src, int64_t seg_stride, float *out, hipStream_t s);
 hipError_t convert_f64_f32(int64_t n, const double *src, float *dst, hipStream_t s);
 hipError_t transpose_f64(int nrow, int ncol, const double *src, int64_t lds, double *dst, int64_t ldd,
                          hipStream_t s);

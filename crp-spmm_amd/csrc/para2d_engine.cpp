@@ -9,6 +9,11 @@
 // offers allgatherv_dev (RCCL), on the host through allgatherv_bytes otherwise; the replication-cost statistic is
 // computed without the reference's rank (P-1) -> rank 0 message, which
 // deadlocks at one rank (reference :102-109).
+//
+// Beyond A*B the engine offers what the row engine offers on the panel: new values (update_values: the slices' values
+// all-gathered along the grid row into panel order), C := A^T*B (a forward) and SDDMM, whose dots over all n columns are the
+// sum of the grid row's partial dots over their column slices: a reduce-scatter along the grid row (the panel being the
+// concatenation of the row's slices in rank order, every rank's share is one contiguous run) and crp_sum_segments_*.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -27,7 +32,138 @@ struct crp_para2d_spmm
     double t_init = 0.0, t_ag_A = 0.0;
     int    value_uploads = 1;              // times the panel's values went host -> device (0: filled from the device all-gather)
     bool   replicated_on_device = false;   // the panel's colidx / val were all-gathered between device buffers
+    bool   plan_only = false;
+    int    pn = 1, pi = 0, pj = 0;
+    std::vector<long long> row_nnz;        // pn: nonzeros of the grid row's A0 slices
+    std::vector<long long> row_off;        // pn + 1: their prefix sums = where every slice starts in the panel
+    // ---- state of update_values / sddmm on a grid with pn > 1: nothing below exists before the first such call
+    crp_comm_t *comm_row = nullptr;        // owned; split again from comm_glb by the first update_values / sddmm
+    std::vector<double> panel_val;         // update_values: the panel's values as gathered
+    void  *sd_part = nullptr;              // partial dots of the panel: row_off[pn] entries (these three are sized for fp64, used by both dtypes)
+    void  *sd_recv = nullptr;              // the pn runs received: fp64 stride slice nnz, fp32 stride round_up(slice nnz, 2)
+    void  *sd_out = nullptr;               // staging of a host `out`
+    float *sd_send32 = nullptr;            // fp32: every peer's run in a slot of round_up(nnz_j, 2) floats
+    bool   sd_built64 = false, sd_built32 = false;
 };
+
+#define HIP_OK(call)                                                              \
+    do {                                                                          \
+        int rc__ = (call);                                                        \
+        ASSERT_PRINTF(rc__ == 0, "%s failed with code %d\n", #call, rc__);        \
+    } while (0)
+
+static long long up2(long long v) { return (v + 1) / 2 * 2; }
+
+// The grid-row communicator init freed: split again from the global one by the first call that needs it -- that call is
+// therefore collective over the WHOLE grid (every rank makes these calls anyway) -- and kept from then on.
+static crp_comm_t *row_comm(crp_para2d_spmm *e)
+{
+    if (e->comm_row == nullptr) e->comm_row = e->comm_glb->split(e->comm_glb->ctx, e->pi, e->pj);
+    return e->comm_row;
+}
+
+static int sum_segments(int nseg, long long len, const double *src, long long stride, double *out, void *s)
+{
+    return crp_sum_segments_f64(nseg, len, src, stride, out, s);
+}
+static int sum_segments(int nseg, long long len, const float *src, long long stride, float *out, void *s)
+{
+    return crp_sum_segments_f32(nseg, len, src, stride, out, s);
+}
+static void inner_sddmm(crp_rp_spmm_p rp, int layout, const double *X, long long ldX, const double *Y, long long ldY, double *out,
+                        int mode, void *s)
+{
+    crp_rp_spmm_sddmm_ex(rp, layout, X, ldX, Y, ldY, out, mode, s);
+}
+static void inner_sddmm(crp_rp_spmm_p rp, int layout, const float *X, long long ldX, const float *Y, long long ldY, float *out,
+                        int mode, void *s)
+{
+    crp_rp_spmm_sddmm_f32_ex(rp, layout, X, ldX, Y, ldY, out, mode, s);
+}
+
+// first SDDMM of a dtype on a grid with pn > 1: the partial buffer, the receive segments, the staging of a host `out`
+// (sized for fp64, so the fp32 call reuses them) and, for fp32, the send slots with their pad floats zeroed once
+static void build_sddmm(crp_para2d_spmm *e, bool f32)
+{
+    const long long p_nnz = e->row_off[e->pn], s_nnz = e->row_nnz[e->pj];
+    if (!e->sd_built64 && !e->sd_built32)
+    {
+        HIP_OK(crp_dev_malloc(&e->sd_part, sizeof(double) * (size_t) (p_nnz > 0 ? p_nnz : 1)));
+        HIP_OK(crp_dev_malloc(&e->sd_recv, sizeof(double) * (size_t) (s_nnz > 0 ? s_nnz * e->pn : 1)));
+        HIP_OK(crp_dev_malloc(&e->sd_out, sizeof(double) * (size_t) (s_nnz > 0 ? s_nnz : 1)));
+    }
+    if (f32 && e->sd_send32 == nullptr)
+    {
+        size_t slots = 0;
+        for (int j = 0; j < e->pn; j++) slots += (size_t) up2(e->row_nnz[j]);
+        void *d = NULL;
+        HIP_OK(crp_dev_malloc(&d, sizeof(float) * (slots > 0 ? slots : 2)));
+        HIP_OK(crp_dev_memset(d, 0, sizeof(float) * (slots > 0 ? slots : 2), NULL));
+        HIP_OK(crp_stream_sync(NULL));                     // (the caller's stream may not order against the null stream)
+        e->sd_send32 = (float *) d;
+    }
+    (f32 ? e->sd_built32 : e->sd_built64) = true;
+}
+
+template <class T>
+static void sddmm_impl(crp_para2d_spmm *e, int layout, const T *X, long long ldX, const T *Y, long long ldY, T *out, int mode, void *s)
+{
+    if (e == NULL) return;
+    if (e->pn == 1)
+    {
+        inner_sddmm(e->rp, layout, X, ldX, Y, ldY, out, mode, s);     // one grid column: the row engine's result as it is
+        return;
+    }
+    ASSERT_PRINTF(!e->plan_only, "para2d_spmm_sddmm on a plan-only engine (no device state)\n");
+    constexpr bool f32 = sizeof(T) == sizeof(float);
+    crp_comm_t *cr = row_comm(e);
+    if (!(f32 ? e->sd_built32 : e->sd_built64)) build_sddmm(e, f32);
+    const int pn = e->pn, pj = e->pj;
+    const long long s_nnz = e->row_nnz[pj];
+    int X_on_dev = 0, Y_on_dev = 0, out_on_dev = 1;
+    HIP_OK(crp_dev_ptr_is_device(X, &X_on_dev));
+    HIP_OK(crp_dev_ptr_is_device(Y, &Y_on_dev));
+    if (out != NULL) HIP_OK(crp_dev_ptr_is_device(out, &out_on_dev));
+    ASSERT_PRINTF(out != NULL || s_nnz == 0, "para2d_spmm_sddmm: NULL out\n");
+
+    // 1. partial dots over this rank's n_loc columns, in panel order
+    T *part = (T *) e->sd_part;
+    inner_sddmm(e->rp, layout, X, ldX, Y, ldY, part, mode, s);
+
+    // 2. reduce-scatter along the grid row: peer j is owed the run of its slice, this rank receives pn runs of its own
+    std::vector<long long> sc(pn), sd(pn), rc(pn), rd(pn);
+    const double *send = (const double *) part;
+    long long stride = s_nnz;                                         // of the receive segments, in elements of T
+    if (!f32)
+    {
+        for (int j = 0; j < pn; j++) { sc[j] = e->row_nnz[j]; sd[j] = e->row_off[j]; rc[j] = s_nnz; rd[j] = (long long) j * s_nnz; }
+    }
+    else
+    {
+        // fp32 runs travel inside 8-byte words: every run is first copied to a slot that starts on a word
+        stride = up2(s_nnz);
+        long long slot = 0;
+        for (int j = 0; j < pn; j++)
+        {
+            if (e->row_nnz[j] > 0)
+                HIP_OK(crp_dev_memcpy(e->sd_send32 + slot, (const float *) e->sd_part + e->row_off[j], sizeof(float) * (size_t) e->row_nnz[j], 2, s));
+            sc[j] = up2(e->row_nnz[j]) / 2; sd[j] = slot / 2; rc[j] = stride / 2; rd[j] = (long long) j * (stride / 2);
+            slot += up2(e->row_nnz[j]);
+        }
+        send = (const double *) e->sd_send32;
+    }
+    cr->alltoallv_dev_f64(cr->ctx, send, sc.data(), sd.data(), (double *) e->sd_recv, rc.data(), rd.data(), s);
+
+    // 3. the pn runs added in ascending grid column
+    if (s_nnz > 0)
+    {
+        T *outd = out_on_dev ? out : (T *) e->sd_out;
+        HIP_OK(sum_segments(pn, s_nnz, (const T *) e->sd_recv, stride, outd, s));
+        if (!out_on_dev) HIP_OK(crp_dev_memcpy(out, outd, sizeof(T) * (size_t) s_nnz, 1, s));
+    }
+    // completion as crp_rp_spmm_sddmm_ex: asynchronous only with device pointers and timing off
+    if (!out_on_dev || !X_on_dev || !Y_on_dev || crp_rp_spmm_timing(e->rp)) HIP_OK(crp_stream_sync(s));
+}
 
 extern "C" {
 
@@ -40,6 +176,7 @@ static void para2d_init_common(crp_comm_t *comm, int pm, int pn, const int *A0_r
     (void) AC_rowptr;   // implied by A0_rowptr, exactly as in the reference (:49-52)
     crp_para2d_spmm *e = new crp_para2d_spmm;
     e->comm_glb = comm;
+    e->plan_only = plan_only;
     double t0 = get_wtime_sec();
     const int r = comm->rank, pi = r / pn, pj = r % pn;
     crp_comm_t *comm_row = comm->split(comm->ctx, pi, pj);
@@ -73,6 +210,7 @@ static void para2d_init_common(crp_comm_t *comm, int pm, int pn, const int *A0_r
         comm_row->allgatherv_bytes(comm_row->ctx, A_rowptr, cnt[pj], p_rowptr.data(), cnt.data(), dsp.data());
         long long p_nnz = 0;
         for (int j = 0; j < pn; j++) p_nnz += nnzs[j];
+        e->row_nnz.assign(nnzs.begin(), nnzs.end());
         // the gathered entries are the first row pointer of every row; an empty leading slice
         // starts where the next one does, so entry 0 is already the panel's first offset
         if (p_nrow == 0) p_rowptr[0] = 0;
@@ -139,7 +277,11 @@ static void para2d_init_common(crp_comm_t *comm, int pm, int pn, const int *A0_r
         p_colidx.assign(A_colidx, A_colidx + my_nnz);
         p_val.assign(A_val, A_val + my_nnz);
         if (my_nnz == 0) { p_colidx.resize(1); p_val.resize(1); }
+        e->row_nnz.assign(1, my_nnz);
     }
+    e->pn = pn; e->pi = pi; e->pj = pj;
+    e->row_off.assign((size_t) pn + 1, 0);
+    for (int j = 0; j < pn; j++) e->row_off[j + 1] = e->row_off[j] + e->row_nnz[j];
     e->t_ag_A += get_wtime_sec() - t0;
 
     // ---- replication cost statistic: floor(1.5 * nnz(A) * (pn - 1)), nnz(A) = end of the last
@@ -195,6 +337,11 @@ void crp_para2d_spmm_free(crp_para2d_spmm_p *p)
     crp_para2d_spmm *e = *p;
     crp_rp_spmm_free(&e->rp);
     if (e->comm_col) e->comm_col->free(e->comm_col);
+    if (e->comm_row) e->comm_row->free(e->comm_row);
+    if (e->sd_part) crp_dev_free(e->sd_part);
+    if (e->sd_recv) crp_dev_free(e->sd_recv);
+    if (e->sd_out) crp_dev_free(e->sd_out);
+    if (e->sd_send32) crp_dev_free(e->sd_send32);
     delete e;
     *p = NULL;
 }
@@ -217,6 +364,53 @@ void crp_para2d_spmm_exec_f32_ex(crp_para2d_spmm_p e, int BC_layout, const float
 {
     if (e == NULL) return;
     crp_rp_spmm_exec_f32_ex(e->rp, BC_layout, B, ldB, C, ldC, stream);
+}
+
+void crp_para2d_spmm_exec_t_ex(crp_para2d_spmm_p e, int BC_layout, const double *B, long long ldB, double *C, long long ldC,
+                               void *stream)
+{
+    if (e == NULL) return;
+    crp_rp_spmm_exec_t_ex(e->rp, BC_layout, B, ldB, C, ldC, stream);
+}
+
+void crp_para2d_spmm_update_values(crp_para2d_spmm_p e, const double *A_val)
+{
+    if (e == NULL) return;
+    if (e->pn == 1)
+    {
+        crp_rp_spmm_update_values(e->rp, A_val);
+        return;
+    }
+    crp_comm_t *cr = row_comm(e);
+    const int pn = e->pn;
+    ASSERT_PRINTF(A_val != NULL || e->row_nnz[e->pj] == 0, "para2d_spmm_update_values: NULL values\n");
+    std::vector<size_t> cnt(pn), dsp(pn);
+    for (int j = 0; j < pn; j++) { cnt[j] = sizeof(double) * (size_t) e->row_nnz[j]; dsp[j] = sizeof(double) * (size_t) e->row_off[j]; }
+    e->panel_val.resize((size_t) (e->row_off[pn] > 0 ? e->row_off[pn] : 1));
+    cr->allgatherv_bytes(cr->ctx, A_val, cnt[e->pj], e->panel_val.data(), cnt.data(), dsp.data());
+    crp_rp_spmm_update_values(e->rp, e->panel_val.data());
+}
+
+void crp_para2d_spmm_sddmm_ex(crp_para2d_spmm_p e, int layout, const double *X, long long ldX, const double *Y, long long ldY,
+                              double *out, int mode, void *stream)
+{
+    sddmm_impl<double>(e, layout, X, ldX, Y, ldY, out, mode, stream);
+}
+
+void crp_para2d_spmm_sddmm_f32_ex(crp_para2d_spmm_p e, int layout, const float *X, long long ldX, const float *Y, long long ldY,
+                                  float *out, int mode, void *stream)
+{
+    sddmm_impl<float>(e, layout, X, ldX, Y, ldY, out, mode, stream);
+}
+
+int crp_para2d_spmm_sddmm_built(crp_para2d_spmm_p e) { return (e && (e->sd_built64 || e->sd_built32)) ? 1 : 0; }
+long long crp_para2d_spmm_slice_nnz(crp_para2d_spmm_p e) { return e ? e->row_nnz[e->pj] : -1; }
+int crp_para2d_spmm_row_slice_nnz(crp_para2d_spmm_p e, long long *nnz_of_pj)
+{
+    if (e == NULL) return 0;
+    if (nnz_of_pj != NULL)
+        for (int j = 0; j < e->pn; j++) nnz_of_pj[j] = e->row_nnz[j];
+    return e->pn;
 }
 
 int crp_para2d_spmm_replicated_on_device(crp_para2d_spmm_p e) { return (e && e->replicated_on_device) ? 1 : 0; }

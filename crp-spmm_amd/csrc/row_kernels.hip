@@ -348,6 +348,61 @@ hipError_t scatter_add_rows_f64(int nseg, int n, const int *seg_row, const int *
     return hipGetLastError();
 }
 
+// Sum of segments: out[p] = ((src[p] + src[stride + p]) + src[2 * stride + p]) + ..., segment after segment in ascending
+// order (the grid-row reduction of the 2D engine's SDDMM: segment j holds the partial dots grid column j formed).  One
+// thread owns a piece of VW elements of out -- VW * sizeof(T) = 16 bytes, or one element -- reads that piece of every
+// segment and adds them left to right: plain IEEE additions, element by element in the vector form too, so both instances
+// give the same bits.  No atomics, no LDS; nseg = 1 is a copy.
+template <class T, int VW>
+__global__ __launch_bounds__(256) void sum_segments_kernel(const int nseg, const int64_t npiece, const T *__restrict__ src,
+                                                           const int64_t seg_stride, T *__restrict__ out)
+{
+    typedef T tv __attribute__((ext_vector_type(VW)));
+    for (int64_t x = (int64_t) blockIdx.x * 256 + threadIdx.x; x < npiece; x += (int64_t) gridDim.x * 256)
+    {
+        const T *p = src + x * VW;
+        if constexpr (VW > 1)
+        {
+            tv acc = *reinterpret_cast<const tv *>(p);
+            for (int j = 1; j < nseg; j++) acc += *reinterpret_cast<const tv *>(p + (int64_t) j * seg_stride);
+            *reinterpret_cast<tv *>(out + x * VW) = acc;
+        }
+        else
+        {
+            T acc = *p;
+            for (int j = 1; j < nseg; j++) acc += p[(int64_t) j * seg_stride];
+            out[x] = acc;
+        }
+    }
+}
+
+// 16-byte pieces when src, out and the segment stride keep every piece 16-byte aligned; the elements that do not fill a
+// piece (and everything, when the alignment does not allow pieces) go to the element-wise instance.
+template <class T>
+static hipError_t sum_segments(int nseg, int64_t len, const T *src, int64_t seg_stride, T *out, hipStream_t s)
+{
+    if (nseg <= 0 || len <= 0) return hipSuccess;
+    constexpr int VW = 16 / (int) sizeof(T);
+    const bool vec = (((uintptr_t) src | (uintptr_t) out) % 16 == 0) && (nseg == 1 || seg_stride % VW == 0);
+    const int64_t npiece = vec ? len / VW : 0, body = npiece * VW;
+    if (npiece > 0)
+        hipLaunchKernelGGL((sum_segments_kernel<T, VW>), dim3(grid_for(npiece)), dim3(256), 0, s, nseg, npiece, src, seg_stride, out);
+    if (len > body)
+        hipLaunchKernelGGL((sum_segments_kernel<T, 1>), dim3(grid_for(len - body)), dim3(256), 0, s, nseg, len - body, src + body,
+                           seg_stride, out + body);
+    return hipGetLastError();
+}
+
+hipError_t sum_segments_f64(int nseg, int64_t len, const double *src, int64_t seg_stride, double *out, hipStream_t s)
+{
+    return sum_segments<double>(nseg, len, src, seg_stride, out, s);
+}
+
+hipError_t sum_segments_f32(int nseg, int64_t len, const float *src, int64_t seg_stride, float *out, hipStream_t s)
+{
+    return sum_segments<float>(nseg, len, src, seg_stride, out, s);
+}
+
 // fp32 copy of fp64 values (the fp32 path keeps A's values in fp64 as the caller gave them and derives its own copy)
 __global__ void convert_f64_f32_kernel(const int64_t n, const double *__restrict__ src, float *__restrict__ dst)
 {

@@ -1147,6 +1147,7 @@ void crp_rp_spmm_overlap_rows(crp_rp_spmm_p e, int *n_interior, int *n_boundary)
 }
 
 void crp_rp_spmm_set_timing(crp_rp_spmm_p e, int timing) { if (e) e->timing = timing ? 1 : 0; }
+int crp_rp_spmm_timing(crp_rp_spmm_p e) { return (e && e->timing) ? 1 : 0; }
 void crp_rp_spmm_set_variant(crp_rp_spmm_p e, int variant) { if (e) e->variant = variant; }
 void crp_rp_spmm_set_variant_f32(crp_rp_spmm_p e, int variant) { if (e) e->variant_f32 = variant; }
 

@@ -320,6 +320,8 @@ class Para2dSpmm:
         self.pm, self.pn = pm, pn
         self.pi, self.pj = comm.rank // pn, comm.rank % pn
         self.rp = RpSpmm._wrap(lib.crp_para2d_spmm_rp(self.handle), comm, lib)
+        # rows of the B / Y block: the B_rowptr block of grid row pi (the row engine's loc_B_nrow)
+        self.loc_B_nrow = int(br[self.pi + 1] - br[self.pi])
 
     def exec(self, BC_layout, B, C_out, stream=None):
         """float64 operands run the fp64 exec, float32 operands the fp32 exec (crp_para2d_spmm_exec_f32_ex)."""
@@ -330,6 +332,76 @@ class Para2dSpmm:
             stream = _current_stream(C_out)
         fn = self._lib.crp_para2d_spmm_exec_f32_ex if f32 else self._lib.crp_para2d_spmm_exec_ex
         fn(self.handle, BC_layout, bp, ldb, cp, ldc, stream)
+
+    def _check_blocks(self, layout, blocks):
+        """ValueError unless every (name, operand, rows) is a rows x n_loc block (layout 1: (n_loc, ld >= rows)): the kernels
+        index the operands by the plan's sizes, a wrong shape would be an out-of-bounds device access."""
+        for name, x, rows in blocks:
+            want = (rows, self.rp.glb_n) if layout == 0 else (self.rp.glb_n, rows)
+            got = tuple(x.shape)
+            if (layout == 0 and (got[0] < want[0] or got[1] != want[1])) or \
+               (layout == 1 and (got[0] != want[0] or got[1] < want[1])):
+                raise ValueError("%s has shape %s, the engine needs %s (layout %d)" % (name, got, want, layout))
+
+    def update_values(self, A_val):
+        """New values for the same pattern (crp_para2d_spmm_update_values): this rank's A0 slice values in the order given to
+        init.  Collective over the grid row -- the first call of an engine with pn > 1 over the whole grid."""
+        va = _f64(A_val).ravel()
+        if va.size != self.slice_nnz:
+            raise ValueError("A_val has %d entries, this rank's A0 slice %d nonzeros" % (va.size, self.slice_nnz))
+        if va.size == 0:
+            va = np.zeros(1, np.float64)
+        self._lib.crp_para2d_spmm_update_values(self.handle, _dp(va))
+
+    def exec_t(self, BC_layout, B, C_out, stream=None):
+        """C := A^T * B (crp_para2d_spmm_exec_t_ex), fp64 only: B is this rank's (panel rows) x n_loc block, C_out its
+        (B_rowptr block of grid row pi) x n_loc block; layouts and operands as ``exec``."""
+        if _operands_dtype(B, C_out) != "f64":
+            raise TypeError("exec_t is fp64 only: B and C must be float64")
+        bp, ldb, _kb = _ptr_ld(B, BC_layout)
+        cp, ldc, _kc = _ptr_ld(C_out, BC_layout)
+        self._check_blocks(BC_layout, (("B", B, self.rp.A_nrow), ("C", C_out, self.loc_B_nrow)))
+        if stream is None:
+            stream = _current_stream(C_out)
+        self._lib.crp_para2d_spmm_exec_t_ex(self.handle, BC_layout, bp, ldb, cp, ldc, stream)
+
+    def sddmm(self, BC_layout, X, Y, out, mode=0, stream=None):
+        """SDDMM over all n columns (crp_para2d_spmm_sddmm_ex / _f32_ex, by the operands' dtype): out[p] = <X[i], Y[c]> for every
+        nonzero p = (i, c) of this rank's A0 slice, in the order of the A_val given to init; mode 1: times the engine's current
+        value of p.  X is this rank's (panel rows) x n_loc block, Y its (B_rowptr block) x n_loc block, ``out`` a 1-D array or
+        tensor of ``slice_nnz`` entries of the same dtype, on the host or the device.  Collective over the grid row (the first
+        call of an engine with pn > 1 over the whole grid).  Mixed dtypes, wrong shapes, a wrong ``out`` length and a wrong
+        mode raise before the library is called."""
+        f32 = _operands_dtype(X, Y) == "f32"
+        if mode not in (0, 1):
+            raise ValueError("mode must be 0 or 1, got %r" % (mode,))
+        xp, ldx, _kx = _ptr_ld(X, BC_layout, f32)
+        yp, ldy, _ky = _ptr_ld(Y, BC_layout, f32)
+        self._check_blocks(BC_layout, (("X", X, self.rp.A_nrow), ("Y", Y, self.loc_B_nrow)))
+        op, _ko = _out_ptr(out, f32, self.slice_nnz)
+        if stream is None:
+            stream = _current_stream(out)
+        if stream is None:
+            stream = _current_stream(X)
+        fn = self._lib.crp_para2d_spmm_sddmm_f32_ex if f32 else self._lib.crp_para2d_spmm_sddmm_ex
+        fn(self.handle, BC_layout, xp, ldx, yp, ldy, op, int(mode), stream)
+
+    @property
+    def slice_nnz(self):
+        """Nonzeros of this rank's A0 slice (crp_para2d_spmm_slice_nnz)."""
+        return int(self._lib.crp_para2d_spmm_slice_nnz(self.handle))
+
+    @property
+    def row_slice_nnz(self):
+        """Nonzeros of every A0 slice of this rank's grid row, pn entries (crp_para2d_spmm_row_slice_nnz)."""
+        out = np.zeros(self.pn, np.int64)
+        self._lib.crp_para2d_spmm_row_slice_nnz(self.handle, out.ctypes.data_as(L.c_ll_p))
+        return out
+
+    @property
+    def sddmm_built(self):
+        """True once a ``sddmm`` on a grid with pn > 1 has allocated the grid-row buffers (crp_para2d_spmm_sddmm_built)."""
+        return bool(self._lib.crp_para2d_spmm_sddmm_built(self.handle))
 
     def print_stat(self):
         self._lib.crp_para2d_spmm_print_stat(self.handle)

@@ -147,6 +147,8 @@ double crp_rp_spmm_exchange_host_seconds(crp_rp_spmm_p rp_spmm);
  * or CRPSPMM_OVERLAP=0). */
 void crp_rp_spmm_overlap_rows(crp_rp_spmm_p rp_spmm, int *n_interior, int *n_boundary);
 void crp_rp_spmm_set_timing(crp_rp_spmm_p rp_spmm, int timing);
+/* the current setting (1 after init). */
+int crp_rp_spmm_timing(crp_rp_spmm_p rp_spmm);
 /* kernel variant for the local SpMM (crpspmm_hip.h: crp_spmm_variant_name). */
 void crp_rp_spmm_set_variant(crp_rp_spmm_p rp_spmm, int variant);
 /* kernel variant of the fp32 exec (crp_spmm_csr_f32): 0 auto (default), 1 row-group, 5 team kernel.  The fp32 exec
@@ -180,6 +182,44 @@ void crp_para2d_spmm_exec_ex(crp_para2d_spmm_p para2d_spmm, int BC_layout, const
 /* fp32 exec of the grid column's row engine (crp_rp_spmm_exec_f32_ex). */
 void crp_para2d_spmm_exec_f32_ex(crp_para2d_spmm_p para2d_spmm, int BC_layout, const float *B,
                                  long long ldB, float *C, long long ldC, void *stream);
+/* ---- the rest of the family on a pm x pn grid.  A NULL engine is a no-op everywhere.  The grid-row communicator, which init
+ * frees, is split again from the GLOBAL communicator (which must still be alive) by the first crp_para2d_spmm_update_values
+ * or crp_para2d_spmm_sddmm_* call of an engine with pn > 1 and kept from then on: that first call is collective over the
+ * WHOLE grid, every later one over the grid row.  An engine that makes neither call splits and allocates nothing. */
+/* New values for the same pattern: A_val is a HOST pointer to this rank's A0 slice values in the order given to init (NULL
+ * when the slice is empty).  With pn > 1 the slices are all-gathered along the grid row (allgatherv_bytes, the byte counts of
+ * init) into panel order and handed to crp_rp_spmm_update_values of the grid column's row engine, which refreshes the split
+ * matrices, the fp32 copies and, once built, the transposed matrices; with pn == 1 a plain forward.  Works on a plan-only
+ * engine (the plan's A_val is replaced). */
+void crp_para2d_spmm_update_values(crp_para2d_spmm_p e, const double *A_val);
+/* C := A^T * B (fp64) of the grid column's row engine (crp_rp_spmm_exec_t_ex): B is this rank's (panel rows) x n_loc block,
+ * C its (B_rowptr block of grid row pi) x n_loc block. */
+void crp_para2d_spmm_exec_t_ex(crp_para2d_spmm_p e, int BC_layout, const double *B, long long ldB,
+                               double *C, long long ldC, void *stream);
+/* SDDMM over all n columns: for every nonzero p = (i, c) of this rank's A0 SLICE, out[p] = < X[i][0:n], Y[c][0:n] >, times the
+ * engine's current value of p in mode 1.  X is this rank's (panel rows) x n_loc block (partitioned like C of exec), Y its
+ * (B_rowptr block) x n_loc block (like B of exec), out crp_para2d_spmm_slice_nnz entries IN THE ORDER OF THE A_val GIVEN TO
+ * INIT -- the order crp_para2d_spmm_update_values takes.  X, Y and out may each be a host or a device pointer; layout 1 as in
+ * crp_rp_spmm_sddmm_ex.  One call: (1) the row engine's SDDMM (mode passed through) gives the partial dots of the whole panel
+ * over this rank's n_loc columns -- with pn == 1 straight into out, and the call ends there, bit-identical to the row engine;
+ * (2) a reduce-scatter along the grid row through the communicator's alltoallv_dev_f64: the panel is the concatenation of
+ * the row's slices in rank order, so peer j is sent the run [off_j, off_j + nnz_j) and this rank receives pn runs of its own
+ * slice, the run of grid column j at segment j (fp32 runs travel inside 8-byte words from slots of round_up(nnz_j, 2)
+ * floats whose pad float is zero); (3) crp_sum_segments_* adds the runs in ascending grid column into out (a host out is
+ * staged).  Exchange and sum are ordered after the row engine's call on the caller's stream; completion as
+ * crp_rp_spmm_sddmm_ex (device pointers and timing off: nothing synchronises).  print_stat's lines are unchanged: exchange
+ * and sum are billed to no line, n_exec rises through the row engine's call only.  The buffers are allocated by the first
+ * SDDMM of a dtype (crp_para2d_spmm_sddmm_built: 0, then 1; always 0 with pn == 1).  For a given grid the result is
+ * bit-identical across repeated calls and timing modes; different pn cut the n columns differently, so across grids it
+ * agrees to rounding only (entrywise |out - exact| <= (max_j n_j + pn) u sum|x y|).  A plan-only engine aborts as in exec. */
+void crp_para2d_spmm_sddmm_ex(crp_para2d_spmm_p e, int layout, const double *X, long long ldX,
+                              const double *Y, long long ldY, double *out, int mode, void *stream);
+void crp_para2d_spmm_sddmm_f32_ex(crp_para2d_spmm_p e, int layout, const float *X, long long ldX,
+                                  const float *Y, long long ldY, float *out, int mode, void *stream);
+int crp_para2d_spmm_sddmm_built(crp_para2d_spmm_p e);
+/* nonzeros of this rank's A0 slice; of every slice of its grid row (pn entries written when nnz_of_pj != NULL; returns pn). */
+long long crp_para2d_spmm_slice_nnz(crp_para2d_spmm_p e);
+int crp_para2d_spmm_row_slice_nnz(crp_para2d_spmm_p e, long long *nnz_of_pj);
 void crp_para2d_spmm_print_stat(crp_para2d_spmm_p para2d_spmm);
 void crp_para2d_spmm_clear_stat(crp_para2d_spmm_p para2d_spmm);
 crp_rp_spmm_p crp_para2d_spmm_rp(crp_para2d_spmm_p para2d_spmm);

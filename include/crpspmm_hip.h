@@ -327,6 +327,15 @@ int crp_scatter_rows_f64(int layout, int nidx, int n, const int *ridx,
  * product, where one local row can come back from several peers).  seg_row / seg_ptr / seg_pos are device arrays. */
 int crp_scatter_add_rows_f64(int nseg, int n, const int *seg_row, const int *seg_ptr, const int *seg_pos,
                              const double *src, long long lds, double *dst, long long ldd, void *stream);
+/* sum of segments: out[p] = ((src[p] + src[seg_stride + p]) + src[2 * seg_stride + p]) + ... for 0 <= p < len, strictly left
+ * to right over ascending segment number (the grid-row reduction of the 2D engine's SDDMM, crp_para2d_spmm_sddmm_ex).
+ * Plain IEEE additions, no atomics and no LDS; every out[p] belongs to one thread; nseg == 1 is a copy.  Pieces of 16 bytes
+ * when src, out and seg_stride keep them aligned, single elements otherwise and for the tail, in the same order: the result
+ * does not depend on alignment, and repeated calls are bit-identical.  Asynchronous on `stream`; device pointers.  Returns 0
+ * (also for len == 0: nothing is launched), -1 for a NULL pointer, nseg < 1 or len < 0, -4 for seg_stride < len with
+ * nseg > 1, or a positive HIP error; nothing is written before the arguments have passed. */
+int crp_sum_segments_f64(int nseg, long long len, const double *src, long long seg_stride, double *out, void *stream);
+int crp_sum_segments_f32(int nseg, long long len, const float *src, long long seg_stride, float *out, void *stream);
 /* out-of-place transpose: dst[c][r] = src[r][c] for an nrow x ncol row-major
  * src (equivalently col-major <-> row-major conversion). */
 int crp_transpose_f64(int nrow, int ncol, const double *src, long long lds,
