@@ -172,6 +172,9 @@ SIGNATURES = {
     "crp_gather_rows_f64": (_I, [_I, _I, _I, _V, _V, _LL, _V, _LL, _V]),
     "crp_scatter_rows_f64": (_I, [_I, _I, _I, _V, _V, _LL, _V, _LL, _V]),
     "crp_scatter_add_rows_f64": (_I, [_I, _I, _V, _V, _V, _V, _LL, _V, _LL, _V]),
+    "crp_scatter_add_rows_f32": (_I, [_I, _I, _V, _V, _V, _V, _LL, _V, _LL, _V]),
+    "crp_gather_vals_f64": (_I, [_LL, _V, _V, _V, _V]),
+    "crp_gather_vals_f32_f64": (_I, [_LL, _V, _V, _V, _V]),
     "crp_sum_segments_f64": (_I, [_I, _LL, _V, _LL, _V, _V]),
     "crp_sum_segments_f32": (_I, [_I, _LL, _V, _LL, _V, _V]),
     "crp_transpose_f64": (_I, [_I, _I, _V, _LL, _V, _LL, _V]),
@@ -191,6 +194,7 @@ SIGNATURES = {
     "crp_rp_spmm_exec_ex": (None, [_V, _I, _V, _LL, _V, _LL, _V]),
     "crp_rp_spmm_exec_f32_ex": (None, [_V, _I, _V, _LL, _V, _LL, _V]),
     "crp_rp_spmm_exec_t_ex": (None, [_V, _I, _V, _LL, _V, _LL, _V]),
+    "crp_rp_spmm_exec_t_f32_ex": (None, [_V, _I, _V, _LL, _V, _LL, _V]),
     "crp_rp_spmm_transposed_built": (_I, [_V]),
     "crp_rp_spmm_sddmm_ex": (None, [_V, _I, _V, _LL, _V, _LL, _V, _I, _V]),
     "crp_rp_spmm_sddmm_f32_ex": (None, [_V, _I, _V, _LL, _V, _LL, _V, _I, _V]),
@@ -225,6 +229,8 @@ SIGNATURES = {
     "crp_rp_spmm_alg_bytes": (_LL, [_V]),
     "crp_rp_spmm_alg_bytes_f32": (_LL, [_V]),
     "crp_rp_spmm_update_values": (None, [_V, c_dbl_p]),
+    "crp_rp_spmm_update_values_dev": (None, [_V, _V, _I, _V]),
+    "crp_rp_spmm_host_values_stale": (_I, [_V]),
     "crp_rp_spmm_nnz": (_LL, [_V]),
     "crp_rp_spmm_dev_colidx_host": (c_int_p, [_V]),
     "crp_para2d_spmm_init": (None, [C.POINTER(CrpComm), _I, _I, c_int_p, c_int_p, c_int_p, c_int_p, c_int_p, c_int_p,
@@ -237,6 +243,8 @@ SIGNATURES = {
     "crp_para2d_spmm_exec_f32_ex": (None, [_V, _I, _V, _LL, _V, _LL, _V]),
     "crp_para2d_spmm_update_values": (None, [_V, c_dbl_p]),
     "crp_para2d_spmm_exec_t_ex": (None, [_V, _I, _V, _LL, _V, _LL, _V]),
+    "crp_para2d_spmm_exec_t_f32_ex": (None, [_V, _I, _V, _LL, _V, _LL, _V]),
+    "crp_para2d_spmm_update_values_dev": (None, [_V, _V, _I, _V]),
     "crp_para2d_spmm_sddmm_ex": (None, [_V, _I, _V, _LL, _V, _LL, _V, _I, _V]),
     "crp_para2d_spmm_sddmm_f32_ex": (None, [_V, _I, _V, _LL, _V, _LL, _V, _I, _V]),
     "crp_para2d_spmm_sddmm_built": (_I, [_V]),

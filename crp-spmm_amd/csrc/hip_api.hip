@@ -1173,6 +1173,26 @@ int crp_scatter_add_rows_f64(int nseg, int n, const int *seg_row, const int *seg
     return (int) crp::scatter_add_rows_f64(nseg, n, seg_row, seg_ptr, seg_pos, src, lds, dst, ldd, (hipStream_t) stream);
 }
 
+int crp_scatter_add_rows_f32(int nseg, int n, const int *seg_row, const int *seg_ptr, const int *seg_pos, const float *src,
+                             long long lds, float *dst, long long ldd, void *stream)
+{
+    if (nseg < 0 || n < 0) return -1;
+    if (nseg > 0 && n > 0 && (seg_row == NULL || seg_ptr == NULL || seg_pos == NULL || src == NULL || dst == NULL)) return -1;
+    return (int) crp::scatter_add_rows_f32(nseg, n, seg_row, seg_ptr, seg_pos, src, lds, dst, ldd, (hipStream_t) stream);
+}
+
+int crp_gather_vals_f64(long long n, const int *map, const double *src, double *dst, void *stream)
+{
+    if (n < 0 || (n > 0 && (src == NULL || dst == NULL))) return -1;
+    return (int) crp::gather_vals_f64(n, map, src, dst, (hipStream_t) stream);
+}
+
+int crp_gather_vals_f32_f64(long long n, const int *map, const float *src, double *dst, void *stream)
+{
+    if (n < 0 || (n > 0 && (src == NULL || dst == NULL))) return -1;
+    return (int) crp::gather_vals_f32_f64(n, map, src, dst, (hipStream_t) stream);
+}
+
 int crp_sum_segments_f64(int nseg, long long len, const double *src, long long seg_stride, double *out, void *stream)
 {
     if (src == NULL || out == NULL || nseg < 1 || len < 0) return -1;

@@ -150,9 +150,13 @@ hipError_t gather_rows_f64(int layout, int nidx, int n, const int *ridx, const d
 hipError_t scatter_rows_f64(int layout, int nidx, int n, const int *ridx, const double *src, int64_t lds,
                             double *dst, int64_t ldd, hipStream_t s);
 hipError_t scatter_vals_f64(int64_t n, const uint32_t *map, const double *src, double *dst, hipStream_t s);
-hipError_t gather_vals_f64(int64_t n, const int *map, const double *src, double *dst, hipStream_t s);      // dst[i] = src[map[i]]
+// dst[i] = (double) src[map ? map[i] : i]
+hipError_t gather_vals_f64(int64_t n, const int *map, const double *src, double *dst, hipStream_t s);
+hipError_t gather_vals_f32_f64(int64_t n, const int *map, const float *src, double *dst, hipStream_t s);
 hipError_t scatter_add_rows_f64(int nseg, int n, const int *seg_row, const int *seg_ptr, const int *seg_pos, const double *src,
                                 int64_t lds, double *dst, int64_t ldd, hipStream_t s);
+hipError_t scatter_add_rows_f32(int nseg, int n, const int *seg_row, const int *seg_ptr, const int *seg_pos, const float *src,
+                                int64_t lds, float *dst, int64_t ldd, hipStream_t s);
 // out[p] = the sum over j < nseg of src[j * seg_stride + p], added left to right (p < len)
 hipError_t sum_segments_f64(int nseg, int64_t len, const double *src, int64_t seg_stride, double *out, hipStream_t s);
 hipError_t sum_segments_f32(int nseg, int64_t len, const float *src, int64_t seg_stride, float *out, hipStream_t s);

@@ -44,6 +44,8 @@ struct crp_para2d_spmm
     void  *sd_out = nullptr;               // staging of a host `out`
     float *sd_send32 = nullptr;            // fp32: every peer's run in a slot of round_up(nnz_j, 2) floats
     bool   sd_built64 = false, sd_built32 = false;
+    void  *dv_panel = nullptr;             // update_values_dev: the panel's values as gathered (sized for fp64)
+    std::vector<char> dv_host;             // ... staged on the host when the communicator has no allgatherv_dev
 };
 
 #define HIP_OK(call)                                                              \
@@ -342,6 +344,7 @@ void crp_para2d_spmm_free(crp_para2d_spmm_p *p)
     if (e->sd_recv) crp_dev_free(e->sd_recv);
     if (e->sd_out) crp_dev_free(e->sd_out);
     if (e->sd_send32) crp_dev_free(e->sd_send32);
+    if (e->dv_panel) crp_dev_free(e->dv_panel);
     delete e;
     *p = NULL;
 }
@@ -389,6 +392,53 @@ void crp_para2d_spmm_update_values(crp_para2d_spmm_p e, const double *A_val)
     e->panel_val.resize((size_t) (e->row_off[pn] > 0 ? e->row_off[pn] : 1));
     cr->allgatherv_bytes(cr->ctx, A_val, cnt[e->pj], e->panel_val.data(), cnt.data(), dsp.data());
     crp_rp_spmm_update_values(e->rp, e->panel_val.data());
+}
+
+void crp_para2d_spmm_exec_t_f32_ex(crp_para2d_spmm_p e, int BC_layout, const float *B, long long ldB, float *C, long long ldC,
+                                   void *stream)
+{
+    if (e == NULL) return;
+    crp_rp_spmm_exec_t_f32_ex(e->rp, BC_layout, B, ldB, C, ldC, stream);
+}
+
+void crp_para2d_spmm_update_values_dev(crp_para2d_spmm_p e, const void *A_val_dev, int f32, void *stream)
+{
+    if (e == NULL) return;
+    if (e->pn == 1)
+    {
+        crp_rp_spmm_update_values_dev(e->rp, A_val_dev, f32, stream);
+        return;
+    }
+    ASSERT_PRINTF(!e->plan_only, "para2d_spmm_update_values_dev on a plan-only engine (no device state)\n");
+    ASSERT_PRINTF(f32 == 0 || f32 == 1, "para2d_spmm_update_values_dev: f32 must be 0 or 1\n");
+    crp_comm_t *cr = row_comm(e);
+    const int pn = e->pn, pj = e->pj;
+    const size_t isz = f32 ? sizeof(float) : sizeof(double);
+    ASSERT_PRINTF(A_val_dev != NULL || e->row_nnz[pj] == 0, "para2d_spmm_update_values_dev: NULL values\n");
+    const size_t p_nnz = (size_t) e->row_off[pn];
+    if (e->dv_panel == nullptr) HIP_OK(crp_dev_malloc(&e->dv_panel, sizeof(double) * (p_nnz > 0 ? p_nnz : 1)));
+    std::vector<size_t> cnt(pn), dsp(pn);
+    for (int j = 0; j < pn; j++) { cnt[j] = isz * (size_t) e->row_nnz[j]; dsp[j] = isz * (size_t) e->row_off[j]; }
+    if (cr->allgatherv_dev != NULL && !crp::knobs().replicate_host)
+        cr->allgatherv_dev(cr->ctx, A_val_dev, cnt[pj], e->dv_panel, cnt.data(), dsp.data(), stream);
+    else
+    {
+        // no device all-gather (or CRPSPMM_REPLICATE=host, as in init): the slice comes down, the panel goes up
+        e->dv_host.resize(isz * (p_nnz > 0 ? p_nnz : 1) + cnt[pj] + 1);
+        char *panel = e->dv_host.data(), *mine = panel + isz * (p_nnz > 0 ? p_nnz : 1);
+        if (cnt[pj] > 0)
+        {
+            HIP_OK(crp_dev_memcpy(mine, A_val_dev, cnt[pj], 1, stream));
+            HIP_OK(crp_stream_sync(stream));
+        }
+        cr->allgatherv_bytes(cr->ctx, mine, cnt[pj], panel, cnt.data(), dsp.data());
+        if (p_nnz > 0)
+        {
+            HIP_OK(crp_dev_memcpy(e->dv_panel, panel, isz * p_nnz, 0, stream));
+            HIP_OK(crp_stream_sync(stream));       // dv_host is reused by the next call
+        }
+    }
+    crp_rp_spmm_update_values_dev(e->rp, e->dv_panel, f32, stream);
 }
 
 void crp_para2d_spmm_sddmm_ex(crp_para2d_spmm_p e, int layout, const double *X, long long ldX, const double *Y, long long ldY,

@@ -289,63 +289,94 @@ hipError_t scatter_vals_f64(int64_t n, const uint32_t *map, const double *src, d
     return hipGetLastError();
 }
 
-// dst[i] = src[map[i]]: the values of a transposed handle from values in the original order (crp_csr_dev_update_values)
-__global__ __launch_bounds__(256) void gather_vals_kernel(const int64_t n, const int *__restrict__ map, const double *__restrict__ src,
+// dst[i] = (double) src[map ? map[i] : i]: the values of a transposed handle from values in the original order
+// (crp_csr_dev_update_values), and the parts / the transposed order of an engine's device value update (crp_gather_vals_*).
+// Widening fp32 to fp64 is exact, so the fp32 copies a handle derives from dst are the caller's fp32 bits again.
+template <class S>
+__global__ __launch_bounds__(256) void gather_vals_kernel(const int64_t n, const int *__restrict__ map, const S *__restrict__ src,
                                                           double *__restrict__ dst)
 {
-    for (int64_t i = (int64_t) blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t) gridDim.x * 256) dst[i] = src[map[i]];
+    for (int64_t i = (int64_t) blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t) gridDim.x * 256)
+        dst[i] = (double) src[map ? (int64_t) map[i] : i];
+}
+
+template <class S> static hipError_t gather_vals(int64_t n, const int *map, const S *src, double *dst, hipStream_t s)
+{
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL((gather_vals_kernel<S>), dim3(grid_for(n)), dim3(256), 0, s, n, map, src, dst);
+    return hipGetLastError();
 }
 
 hipError_t gather_vals_f64(int64_t n, const int *map, const double *src, double *dst, hipStream_t s)
 {
-    if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(gather_vals_kernel, dim3(grid_for(n)), dim3(256), 0, s, n, map, src, dst);
-    return hipGetLastError();
+    return gather_vals<double>(n, map, src, dst, s);
+}
+
+hipError_t gather_vals_f32_f64(int64_t n, const int *map, const float *src, double *dst, hipStream_t s)
+{
+    return gather_vals<float>(n, map, src, dst, s);
 }
 
 // Segmented accumulate: dst[seg_row[t]] += src[seg_pos[k]] for k = seg_ptr[t] .. seg_ptr[t + 1] - 1, in that order.  One
-// thread owns a chunk of VW doubles of one destination row and adds the segment's source rows one after the other: the
-// destination rows are distinct, so nothing races and the sum has one order.
-template <int VW>
-__global__ __launch_bounds__(256) void scatter_add_rows_kernel(const int64_t nseg, const int cpr /* chunks per row */,
+// thread owns a piece of VW elements of one destination row -- VW * sizeof(T) = 16 bytes, or one element -- and adds the
+// segment's source rows one after the other: plain IEEE additions, element by element in the vector form too, so both
+// instances give the same bits; the destination rows are distinct, so nothing races and the sum has one order.
+template <class T, int VW>
+__global__ __launch_bounds__(256) void scatter_add_rows_kernel(const int64_t nseg, const int cpr /* pieces per row */,
                                                                const int *__restrict__ seg_row, const int *__restrict__ seg_ptr,
-                                                               const int *__restrict__ seg_pos, const double *__restrict__ src,
-                                                               const int64_t lds, double *__restrict__ dst, const int64_t ldd)
+                                                               const int *__restrict__ seg_pos, const T *__restrict__ src,
+                                                               const int64_t lds, T *__restrict__ dst, const int64_t ldd)
 {
+    typedef T tv __attribute__((ext_vector_type(VW)));
     const int64_t total = nseg * (int64_t) cpr;
     for (int64_t x = (int64_t) blockIdx.x * 256 + threadIdx.x; x < total; x += (int64_t) gridDim.x * 256)
     {
         const int64_t t = x / cpr;
         const int     c = (int) (x - t * cpr) * VW;
         const int     k0 = seg_ptr[t], k1 = seg_ptr[t + 1];
-        double *out = dst + (int64_t) seg_row[t] * ldd + c;
-        if constexpr (VW == 2)
+        T *out = dst + (int64_t) seg_row[t] * ldd + c;
+        if constexpr (VW > 1)
         {
-            d2 acc = *reinterpret_cast<const d2 *>(out);
-            for (int k = k0; k < k1; k++) acc += *reinterpret_cast<const d2 *>(src + (int64_t) seg_pos[k] * lds + c);
-            *reinterpret_cast<d2 *>(out) = acc;
+            tv acc = *reinterpret_cast<const tv *>(out);
+            for (int k = k0; k < k1; k++) acc += *reinterpret_cast<const tv *>(src + (int64_t) seg_pos[k] * lds + c);
+            *reinterpret_cast<tv *>(out) = acc;
         }
         else
         {
-            double acc = *out;
+            T acc = *out;
             for (int k = k0; k < k1; k++) acc += src[(int64_t) seg_pos[k] * lds + c];
             *out = acc;
         }
     }
 }
 
+// 16-byte pieces when n, both leading dimensions and both pointers keep every piece 16-byte aligned, single elements otherwise
+template <class T>
+static hipError_t scatter_add_rows(int nseg, int n, const int *seg_row, const int *seg_ptr, const int *seg_pos, const T *src,
+                                   int64_t lds, T *dst, int64_t ldd, hipStream_t s)
+{
+    if (nseg <= 0 || n <= 0) return hipSuccess;
+    constexpr int VW = 16 / (int) sizeof(T);
+    const bool vec = (n % VW == 0) && (lds % VW == 0) && (ldd % VW == 0) && (((uintptr_t) src | (uintptr_t) dst) % 16 == 0);
+    if (vec)
+        hipLaunchKernelGGL((scatter_add_rows_kernel<T, VW>), dim3(grid_for((int64_t) nseg * (n / VW))), dim3(256), 0, s, (int64_t) nseg,
+                           n / VW, seg_row, seg_ptr, seg_pos, src, lds, dst, ldd);
+    else
+        hipLaunchKernelGGL((scatter_add_rows_kernel<T, 1>), dim3(grid_for((int64_t) nseg * n)), dim3(256), 0, s, (int64_t) nseg, n, seg_row,
+                           seg_ptr, seg_pos, src, lds, dst, ldd);
+    return hipGetLastError();
+}
+
 hipError_t scatter_add_rows_f64(int nseg, int n, const int *seg_row, const int *seg_ptr, const int *seg_pos, const double *src,
                                 int64_t lds, double *dst, int64_t ldd, hipStream_t s)
 {
-    if (nseg <= 0 || n <= 0) return hipSuccess;
-    const bool vec2 = (n % 2 == 0) && (lds % 2 == 0) && (ldd % 2 == 0) && (((uintptr_t) src | (uintptr_t) dst) % 16 == 0);
-    if (vec2)
-        hipLaunchKernelGGL((scatter_add_rows_kernel<2>), dim3(grid_for((int64_t) nseg * (n / 2))), dim3(256), 0, s, (int64_t) nseg, n / 2,
-                           seg_row, seg_ptr, seg_pos, src, lds, dst, ldd);
-    else
-        hipLaunchKernelGGL((scatter_add_rows_kernel<1>), dim3(grid_for((int64_t) nseg * n)), dim3(256), 0, s, (int64_t) nseg, n, seg_row,
-                           seg_ptr, seg_pos, src, lds, dst, ldd);
-    return hipGetLastError();
+    return scatter_add_rows<double>(nseg, n, seg_row, seg_ptr, seg_pos, src, lds, dst, ldd, s);
+}
+
+hipError_t scatter_add_rows_f32(int nseg, int n, const int *seg_row, const int *seg_ptr, const int *seg_pos, const float *src,
+                                int64_t lds, float *dst, int64_t ldd, hipStream_t s)
+{
+    return scatter_add_rows<float>(nseg, n, seg_row, seg_ptr, seg_pos, src, lds, dst, ldd, s);
 }
 
 // Sum of segments: out[p] = ((src[p] + src[stride + p]) + src[2 * stride + p]) + ..., segment after segment in ascending

@@ -75,6 +75,14 @@ struct crp_rp_spmm
     int *sd_int_pos = nullptr, *sd_bnd_pos = nullptr;
     double *sd_out = nullptr;
     size_t  sd_out_sz = 0;
+    // device value updates (crp_rp_spmm_update_values_dev), allocated by its first call: the new values as fp64 in the order the
+    // device matrices take them (A_dev: A_val's order; a split engine: A_int's nonzeros, then A_bnd's) and, once the transposed
+    // matrices exist, in theirs (through dv_t_pos, a device copy of t_src); ev_vals is recorded at the end of every update
+    bool    dv_built = false, dv_used = false;
+    double *dv_vals = nullptr, *dv_tvals = nullptr;
+    int    *dv_t_pos = nullptr;
+    void   *ev_vals = nullptr;
+    bool    host_vals_stale = false;             // A_val (host) is behind the device matrices: refreshed where it is read
     // staging (host-pointer API) and column-major temporaries, grown on demand
     double *B_stage = nullptr, *C_stage = nullptr, *B_rm = nullptr, *C_rm = nullptr;
     size_t  B_stage_sz = 0, C_stage_sz = 0, B_rm_sz = 0, C_rm_sz = 0;
@@ -366,6 +374,10 @@ void crp_rp_spmm_free(crp_rp_spmm_p *rp_spmm)
         crp_dev_free(e->sd_int_pos);
         crp_dev_free(e->sd_bnd_pos);
         crp_dev_free(e->sd_out);
+        crp_dev_free(e->dv_vals);
+        crp_dev_free(e->dv_tvals);
+        crp_dev_free(e->dv_t_pos);
+        if (e->ev_vals) crp_event_destroy(e->ev_vals);
         if (e->xstream) crp_stream_destroy(e->xstream);
         if (e->ev_packed) crp_event_destroy(e->ev_packed);
         if (e->ev_landed) crp_event_destroy(e->ev_landed);
@@ -471,6 +483,17 @@ static int spmm(crp_rp_spmm *e, crp_csr_dev_p A, int n, const float *B0, long lo
                 float *C, long long ldC, void *s)
 {
     return crp_spmm_csr_f32(A, n, B0, ldB0, B1, ldB1, C, ldC, e->variant_f32, s);
+}
+
+static int scatter_add(int nseg, int n, const int *row, const int *ptr, const int *pos, const double *src, long long lds, double *dst,
+                       long long ldd, void *s)
+{
+    return crp_scatter_add_rows_f64(nseg, n, row, ptr, pos, src, lds, dst, ldd, s);
+}
+static int scatter_add(int nseg, int n, const int *row, const int *ptr, const int *pos, const float *src, long long lds, float *dst,
+                       long long ldd, void *s)
+{
+    return crp_scatter_add_rows_f32(nseg, n, row, ptr, pos, src, lds, dst, ldd, s);
 }
 
 // The half that exec and sddmm share: pack the rows of the row-major device operand Bd that other ranks asked for, exchange them
@@ -663,11 +686,12 @@ static int sddmm(crp_csr_dev_p A, int n, const float *X, long long ldX, const fl
     return crp_sddmm_csr_f32(A, n, X, ldX, Y0, ldY0, Y1, ldY1, out, out_pos, mode, s);
 }
 
-// first SDDMM call of a split engine: the parts write through int_src / bnd_src into the order of A_val
-static void build_sddmm(crp_rp_spmm *e)
+// int_src / bnd_src of a split engine as int32 device arrays: the SDDMM's parts write through them into the order of A_val, a
+// device value update gathers the parts' values through them; whichever call comes first uploads
+static void upload_part_positions(crp_rp_spmm *e)
 {
     auto up = [&](const std::vector<long long> &src, int **dst) {
-        if (src.empty()) return;
+        if (src.empty() || *dst != nullptr) return;
         std::vector<int> pos(src.begin(), src.end());          // (positions in A_val: below 2^31, as A_rowptr is int)
         void *d = NULL;
         HIP_OK(crp_dev_malloc(&d, sizeof(int) * pos.size()));
@@ -680,7 +704,36 @@ static void build_sddmm(crp_rp_spmm *e)
         up(e->int_src, &e->sd_int_pos);
         up(e->bnd_src, &e->sd_bnd_pos);
     }
+}
+
+// first SDDMM call
+static void build_sddmm(crp_rp_spmm *e)
+{
+    upload_part_positions(e);
     e->sd_built = true;
+}
+
+// A_val (host) after device value updates: one blocking download of the values as the device matrices took them.  The engine's
+// stream is ordered after every device update (crp_rp_spmm_update_values_dev), so the copy runs there.
+static void refresh_host_values(crp_rp_spmm *e)
+{
+    if (!e->host_vals_stale) return;
+    const size_t nnz = e->A_val.size();
+    if (e->A_int != nullptr)
+    {
+        e->split_vals.resize(nnz);
+        HIP_OK(crp_dev_memcpy(e->split_vals.data(), e->dv_vals, sizeof(double) * nnz, 1, e->stream));
+        HIP_OK(crp_stream_sync(e->stream));
+        const size_t n_int = e->int_src.size();
+        for (size_t t = 0; t < n_int; t++) e->A_val[(size_t) e->int_src[t]] = e->split_vals[t];
+        for (size_t t = 0; t < e->bnd_src.size(); t++) e->A_val[(size_t) e->bnd_src[t]] = e->split_vals[n_int + t];
+    }
+    else
+    {
+        HIP_OK(crp_dev_memcpy(e->A_val.data(), e->dv_vals, sizeof(double) * nnz, 1, e->stream));
+        HIP_OK(crp_stream_sync(e->stream));
+    }
+    e->host_vals_stale = false;
 }
 
 template <class T>
@@ -772,6 +825,7 @@ static void sddmm_impl(crp_rp_spmm *e, int layout, const T *X, long long ldX, co
 // (crp_csr_transpose) and cut by rows into At_loc and At_rem; the rows that come back are grouped by the C row they add to.
 static void build_transposed(crp_rp_spmm *e)
 {
+    refresh_host_values(e);
     const int m = e->A_nrow, kb = e->loc_B_nrow, nr = (int) e->n_recv_rows;
     const long long ncol_ll = (long long) kb + nr;
     ASSERT_PRINTF(ncol_ll < INT_MAX, "rp_spmm_exec_t: %lld local + received rows pass the 32-bit row index\n", ncol_ll);
@@ -853,6 +907,7 @@ static void build_transposed(crp_rp_spmm *e)
 // new values (A_val, already copied into e->A_val) for the transposed matrices
 static void update_transposed_values(crp_rp_spmm *e)
 {
+    refresh_host_values(e);
     const size_t nnz = e->A_val.size();
     e->split_vals.resize(nnz);
     for (size_t q = 0; q < nnz; q++) e->split_vals[q] = e->A_val[(size_t) e->t_src[q]];
@@ -862,7 +917,10 @@ static void update_transposed_values(crp_rp_spmm *e)
     HIP_OK(crp_stream_sync(e->stream));
 }
 
-static void exec_t_impl(crp_rp_spmm *e, int BC_layout, const double *B, long long ldB, double *C, long long ldC, void *stream_)
+// one dtype (crp_rp_spmm_exec_t_ex / crp_rp_spmm_exec_t_f32_ex): the transposed matrices, the accumulate lists, streams and events are
+// shared, the products, the exchange buffers (exchange_of: the forward plan's, run backwards) and the accumulate are the dtype's own
+template <class T>
+static void exec_t_impl(crp_rp_spmm *e, int BC_layout, const T *B, long long ldB, T *C, long long ldC, void *stream_)
 {
     if (e == NULL) return;
     ASSERT_PRINTF(!e->plan_only, "rp_spmm_exec_t on a plan-only engine (no device state)\n");
@@ -880,49 +938,47 @@ static void exec_t_impl(crp_rp_spmm *e, int BC_layout, const double *B, long lon
     HIP_OK(crp_dev_ptr_is_device(C, &C_on_dev));
 
     // ---- operands as device-resident row-major views, staged and transposed as in exec_impl
-    const double *Bd = B;
+    const Xchg x = exchange_of(e, B);
+    const T *Bd = B;
     long long ldBd = ldB;
     if (!B_on_dev && mb > 0 && n > 0)
     {
         const size_t elems = (BC_layout == 0) ? (size_t) mb * (size_t) ldB : (size_t) n * (size_t) ldB;
-        double *stage = grow_as<double>(&e->B_stage, &e->B_stage_sz, elems);
+        T *stage = grow_as<T>(&e->B_stage, &e->B_stage_sz, elems);
         const size_t used = (BC_layout == 0) ? ((size_t) (mb - 1) * (size_t) ldB + (size_t) n) : ((size_t) (n - 1) * (size_t) ldB + (size_t) mb);
-        HIP_OK(crp_dev_memcpy(stage, B, used * sizeof(double), 0, s));
+        HIP_OK(crp_dev_memcpy(stage, B, used * sizeof(T), 0, s));
         Bd = stage;
     }
     if (BC_layout == 1 && mb > 0 && n > 0)
     {
-        double *rm = grow_as<double>(&e->B_rm, &e->B_rm_sz, (size_t) mb * (size_t) n);
+        T *rm = grow_as<T>(&e->B_rm, &e->B_rm_sz, (size_t) mb * (size_t) n);
         HIP_OK(transpose(n, mb, Bd, ldB, rm, n, s));
         Bd = rm;
         ldBd = n;
     }
-    double *Cd = C;
+    T *Cd = C;
     long long ldCd = ldC;
     if (BC_layout == 1)
     {
-        Cd = grow_as<double>(&e->C_rm, &e->C_rm_sz, (size_t) mc * (size_t) n);
+        Cd = grow_as<T>(&e->C_rm, &e->C_rm_sz, (size_t) mc * (size_t) n);
         ldCd = n;
     }
     else if (!C_on_dev && mc > 0 && n > 0)
     {
-        Cd = grow_as<double>(&e->C_stage, &e->C_stage_sz, (size_t) mc * (size_t) ldC);
+        Cd = grow_as<T>(&e->C_stage, &e->C_stage_sz, (size_t) mc * (size_t) ldC);
     }
 
     auto reverse_exchange = [&](void *xs) {
-        // the forward plan backwards: what this rank receives there it sends here, from recvbuf_dev into sendbuf_dev
+        // the forward plan backwards: what this rank receives there it sends here, from the receive into the send buffer
         const double tx0 = get_wtime_sec();
-        e->comm->alltoallv_dev_f64(e->comm->ctx, e->recvbuf_dev, e->rB_rcnts.data(), e->rB_rdispls.data(), e->sendbuf_dev,
-                                   e->rB_scnts.data(), e->rB_sdispls.data(), xs);
+        e->comm->alltoallv_dev_f64(e->comm->ctx, (const double *) x.recv, x.rc, x.rd, (double *) x.send, x.sc, x.sd, xs);
         e->t_a2a_host += get_wtime_sec() - tx0;
     };
-    auto product = [&](crp_csr_dev_p A, double *out, long long ldo) {
-        HIP_OK(crp_spmm_csr_f64(A, 0, n, Bd, ldBd, NULL, 0, out, ldo, e->variant, s));
-    };
+    auto product = [&](crp_csr_dev_p A, T *out, long long ldo) { HIP_OK(spmm(e, A, n, Bd, ldBd, (const T *) NULL, 0, out, ldo, s)); };
     auto accumulate = [&]() {
         if (e->n_acc == 0 || n == 0) return;
         const int *acc_row = e->acc_dev, *acc_ptr = acc_row + e->n_acc, *acc_pos = acc_ptr + e->n_acc + 1;
-        HIP_OK(crp_scatter_add_rows_f64(e->n_acc, n, acc_row, acc_ptr, acc_pos, e->sendbuf_dev, n, Cd, ldCd, s));
+        HIP_OK(scatter_add(e->n_acc, n, acc_row, acc_ptr, acc_pos, (const T *) x.send, x.ld, Cd, ldCd, s));
     };
 
     if (timing) { HIP_OK(crp_stream_sync(s)); }
@@ -930,7 +986,7 @@ static void exec_t_impl(crp_rp_spmm *e, int BC_layout, const double *B, long lon
     if (e->nproc > 1 && !timing)
     {
         // the exchange on its own stream beside the local product, which is enqueued first (see exec_impl)
-        if (e->At_rem != nullptr) product(e->At_rem, e->recvbuf_dev, n);
+        if (e->At_rem != nullptr) product(e->At_rem, (T *) x.recv, x.ld);
         HIP_OK(crp_event_record(e->ev_packed, s));
         product(e->At_loc, Cd, ldCd);
         HIP_OK(crp_stream_wait_event(e->xstream, e->ev_packed));
@@ -948,7 +1004,7 @@ static void exec_t_impl(crp_rp_spmm *e, int BC_layout, const double *B, long lon
             *bucket += t1 - t0;
             t0 = t1;
         };
-        if (e->At_rem != nullptr) product(e->At_rem, e->recvbuf_dev, n);
+        if (e->At_rem != nullptr) product(e->At_rem, (T *) x.recv, x.ld);
         lap(&e->t_spmm);
         if (e->nproc > 1) reverse_exchange(s);
         lap(&e->t_a2a);
@@ -959,8 +1015,8 @@ static void exec_t_impl(crp_rp_spmm *e, int BC_layout, const double *B, long lon
     }
     if (BC_layout == 1 && mc > 0 && n > 0)
     {
-        double *Ccm = C;
-        if (!C_on_dev) Ccm = grow_as<double>(&e->C_stage, &e->C_stage_sz, (size_t) n * (size_t) ldC);
+        T *Ccm = C;
+        if (!C_on_dev) Ccm = grow_as<T>(&e->C_stage, &e->C_stage_sz, (size_t) n * (size_t) ldC);
         HIP_OK(transpose(mc, n, Cd, n, Ccm, ldC, s));
         Cd = Ccm;
     }
@@ -973,7 +1029,7 @@ static void exec_t_impl(crp_rp_spmm *e, int BC_layout, const double *B, long lon
     if (!C_on_dev && mc > 0 && n > 0)
     {
         const size_t w = (BC_layout == 0) ? (size_t) n : (size_t) mc, h = (BC_layout == 0) ? (size_t) mc : (size_t) n;
-        HIP_OK(crp_dev_memcpy2d(C, (size_t) ldC * sizeof(double), Cd, (size_t) ldC * sizeof(double), w * sizeof(double), h, 1, s));
+        HIP_OK(crp_dev_memcpy2d(C, (size_t) ldC * sizeof(T), Cd, (size_t) ldC * sizeof(T), w * sizeof(T), h, 1, s));
         HIP_OK(crp_stream_sync(s));
     }
     else if (!B_on_dev || timing)
@@ -994,7 +1050,12 @@ extern "C" {
 
 void crp_rp_spmm_exec_t_ex(crp_rp_spmm_p e, int BC_layout, const double *B, long long ldB, double *C, long long ldC, void *stream_)
 {
-    exec_t_impl(e, BC_layout, B, ldB, C, ldC, stream_);
+    exec_t_impl<double>(e, BC_layout, B, ldB, C, ldC, stream_);
+}
+
+void crp_rp_spmm_exec_t_f32_ex(crp_rp_spmm_p e, int BC_layout, const float *B, long long ldB, float *C, long long ldC, void *stream_)
+{
+    exec_t_impl<float>(e, BC_layout, B, ldB, C, ldC, stream_);
 }
 
 int crp_rp_spmm_transposed_built(crp_rp_spmm_p e) { return (e && e->t_built) ? 1 : 0; }
@@ -1090,6 +1151,7 @@ void crp_rp_spmm_clear_stat(crp_rp_spmm_p e)
 void crp_rp_spmm_get_plan(crp_rp_spmm_p e, crp_rp_plan_view_t *v)
 {
     if (e == NULL || v == NULL) return;
+    refresh_host_values(e);      // A_val is a public host field: device value updates left it behind
     v->nproc = e->nproc; v->my_rank = e->my_rank; v->glb_n = e->glb_n; v->A_nrow = e->A_nrow;
     v->rB_nrow = e->rB_nrow;
     v->rB_self_src_offset = e->rB_self_src_offset;
@@ -1115,6 +1177,7 @@ void crp_rp_spmm_update_values(crp_rp_spmm_p e, const double *A_val)
     if (nnz == 0) return;
     ASSERT_PRINTF(A_val != NULL, "rp_spmm_update_values: NULL values\n");
     memcpy(e->A_val.data(), A_val, sizeof(double) * nnz);
+    e->host_vals_stale = false;  // (the engine's stream is already ordered after any device update)
     if (!e->plan_only)
     {
         if (e->exec_pending)        // kernels of an exec that returned asynchronously may still read the old values
@@ -1139,6 +1202,84 @@ void crp_rp_spmm_update_values(crp_rp_spmm_p e, const double *A_val)
         if (e->t_built) update_transposed_values(e);
     }
 }
+
+// first device value update: the scratch regions and the event; the parts' positions when the engine is split
+static void build_dev_update(crp_rp_spmm *e)
+{
+    void *d = NULL;
+    HIP_OK(crp_dev_malloc(&d, sizeof(double) * e->A_val.size()));
+    e->dv_vals = (double *) d;
+    HIP_OK(crp_event_create(&e->ev_vals));
+    upload_part_positions(e);
+    e->dv_built = true;
+}
+
+// first device value update after the transposed matrices were built: t_src on the device, the second scratch region
+static void build_dev_update_t(crp_rp_spmm *e)
+{
+    const size_t nnz = e->A_val.size();
+    void *d = NULL;
+    HIP_OK(crp_dev_malloc(&d, sizeof(double) * nnz));
+    e->dv_tvals = (double *) d;
+    HIP_OK(crp_dev_malloc(&d, sizeof(int) * nnz));
+    e->dv_t_pos = (int *) d;
+    HIP_OK(crp_dev_memcpy(e->dv_t_pos, e->t_src.data(), sizeof(int) * nnz, 0, e->stream));
+    HIP_OK(crp_stream_sync(e->stream));
+}
+
+void crp_rp_spmm_update_values_dev(crp_rp_spmm_p e, const void *A_val_dev, int f32, void *stream)
+{
+    if (e == NULL) return;
+    ASSERT_PRINTF(!e->plan_only, "rp_spmm_update_values_dev on a plan-only engine (no device state)\n");
+    ASSERT_PRINTF(f32 == 0 || f32 == 1, "rp_spmm_update_values_dev: f32 must be 0 or 1\n");
+    const size_t nnz = e->A_val.size();
+    if (nnz == 0) return;
+    ASSERT_PRINTF(A_val_dev != NULL, "rp_spmm_update_values_dev: NULL values\n");
+    if (!e->dv_built) build_dev_update(e);
+    if (e->t_built && e->dv_t_pos == nullptr) build_dev_update_t(e);
+    void *s = stream;
+    if (e->exec_pending)        // kernels of an exec that returned asynchronously may still read the old values
+    {
+        HIP_OK(crp_stream_wait_event(s, e->ev_exec));
+        e->exec_pending = false;
+    }
+    if (e->dv_used) HIP_OK(crp_stream_wait_event(s, e->ev_vals));      // the scratch of an update on another stream
+    auto gather = [&](size_t n, const int *map, double *dst) {
+        if (f32) HIP_OK(crp_gather_vals_f32_f64((long long) n, map, (const float *) A_val_dev, dst, s));
+        else HIP_OK(crp_gather_vals_f64((long long) n, map, (const double *) A_val_dev, dst, s));
+    };
+    if (e->A_int != nullptr)
+    {
+        const size_t n_int = e->int_src.size(), n_bnd = e->bnd_src.size();
+        if (n_int > 0)
+        {
+            gather(n_int, e->sd_int_pos, e->dv_vals);
+            HIP_OK(crp_csr_dev_update_values(e->A_int, e->dv_vals, s));
+        }
+        if (n_bnd > 0)
+        {
+            gather(n_bnd, e->sd_bnd_pos, e->dv_vals + n_int);
+            HIP_OK(crp_csr_dev_update_values(e->A_bnd, e->dv_vals + n_int, s));
+        }
+    }
+    else
+    {
+        gather(nnz, nullptr, e->dv_vals);       // widen or copy: the caller's buffer is free again when this has run
+        HIP_OK(crp_csr_dev_update_values(e->A_dev, e->dv_vals, s));
+    }
+    if (e->t_built)
+    {
+        gather(nnz, e->dv_t_pos, e->dv_tvals);
+        if (e->t_loc_nnz > 0) HIP_OK(crp_csr_dev_update_values(e->At_loc, e->dv_tvals, s));
+        if (e->At_rem != nullptr && nnz > e->t_loc_nnz) HIP_OK(crp_csr_dev_update_values(e->At_rem, e->dv_tvals + e->t_loc_nnz, s));
+    }
+    HIP_OK(crp_event_record(e->ev_vals, s));
+    if (s != e->stream) HIP_OK(crp_stream_wait_event(e->stream, e->ev_vals));
+    e->dv_used = true;
+    e->host_vals_stale = true;
+}
+
+int crp_rp_spmm_host_values_stale(crp_rp_spmm_p e) { return (e && e->host_vals_stale) ? 1 : 0; }
 
 void crp_rp_spmm_overlap_rows(crp_rp_spmm_p e, int *n_interior, int *n_boundary)
 {

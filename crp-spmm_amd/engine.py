@@ -95,6 +95,29 @@ def _out_ptr(out, f32, nnz):
     return out.ctypes.data or None, out
 
 
+def _f32_operands(B, C_out):
+    """TypeError unless B and C are both float32 (``exec_t_f32``), before any C call."""
+    if _operands_dtype(B, C_out) != "f32":
+        raise TypeError("exec_t_f32 is fp32 only: B and C must be float32")
+
+
+def _dev_vals(vals, nnz):
+    """(address, f32 flag, keepalive) of the 1-D contiguous float64 / float32 CUDA tensor ``update_values_dev`` takes, which must
+    hold nnz entries; TypeError for anything that is not such a tensor on the device, ValueError for a wrong length or strides."""
+    import torch
+    if not isinstance(vals, torch.Tensor):
+        raise TypeError("vals must be a torch tensor on the device (host values go to update_values)")
+    if vals.dtype not in (torch.float64, torch.float32):
+        raise TypeError("vals must be float64 or float32, got %s" % vals.dtype)
+    if vals.dim() != 1 or not vals.is_contiguous():
+        raise ValueError("vals must be 1-D and contiguous")
+    if vals.numel() != nnz:
+        raise ValueError("vals has %d entries, the engine needs %d" % (vals.numel(), nnz))
+    if not vals.is_cuda:
+        raise TypeError("vals must be on the device (host values go to update_values)")
+    return vals.data_ptr() or None, int(vals.dtype == torch.float32), vals
+
+
 def _current_stream(x):
     try:
         import torch
@@ -178,6 +201,24 @@ class RpSpmm:
             stream = _current_stream(C_out)
         self._lib.crp_rp_spmm_exec_t_ex(self.handle, BC_layout, bp, ldb, cp, ldc, stream)
 
+    def exec_t_f32(self, BC_layout, B, C_out, stream=None):
+        """C := A^T * B in fp32 (crp_rp_spmm_exec_t_f32_ex): float32 operands only, shapes and layouts as ``exec_t``.  The
+        transposed device matrices are the ones ``exec_t`` builds; whichever is called first builds them."""
+        _f32_operands(B, C_out)
+        bp, ldb, _kb = _ptr_ld(B, BC_layout, True)
+        cp, ldc, _kc = _ptr_ld(C_out, BC_layout, True)
+        for name, x, rows in (("B", B, self.A_nrow), ("C", C_out, getattr(self, "loc_B_nrow", None))):
+            if rows is None:
+                continue
+            want = (rows, self.glb_n) if BC_layout == 0 else (self.glb_n, rows)
+            got = tuple(x.shape)
+            if (BC_layout == 0 and (got[0] < want[0] or got[1] != want[1])) or \
+               (BC_layout == 1 and (got[0] != want[0] or got[1] < want[1])):
+                raise ValueError("%s has shape %s, the engine needs %s (layout %d)" % (name, got, want, BC_layout))
+        if stream is None:
+            stream = _current_stream(C_out)
+        self._lib.crp_rp_spmm_exec_t_f32_ex(self.handle, BC_layout, bp, ldb, cp, ldc, stream)
+
     def sddmm(self, BC_layout, X, Y, out, mode=0, stream=None):
         """Sampled dense-dense product over this rank's rows of A (crp_rp_spmm_sddmm_ex / _f32_ex, by the operands' dtype):
         out[p] = <X[i], Y[c]> for every local nonzero p = (i, c), in the order of the A_val given to init; mode 1: times
@@ -250,6 +291,20 @@ class RpSpmm:
     def update_values(self, A_val):
         va = _f64(A_val)
         self._lib.crp_rp_spmm_update_values(self.handle, _dp(va))
+
+    def update_values_dev(self, vals, stream=None):
+        """New values from device memory (crp_rp_spmm_update_values_dev): a 1-D contiguous float64 or float32 CUDA tensor of
+        ``nnz()`` entries in the order of the A_val given to init -- what ``sddmm`` writes.  Asynchronous on ``stream`` (default:
+        the current torch stream of the tensor's device); nothing leaves the device.  ``host_values_stale`` turns true."""
+        ptr, f32, _keep = _dev_vals(vals, self.nnz())
+        if stream is None:
+            stream = _current_stream(vals)
+        self._lib.crp_rp_spmm_update_values_dev(self.handle, ptr, f32, stream)
+
+    @property
+    def host_values_stale(self):
+        """True after ``update_values_dev`` until the host values are read (``plan``) or replaced (``update_values``)."""
+        return bool(self._lib.crp_rp_spmm_host_values_stale(self.handle))
 
     def alg_bytes(self):
         return int(self._lib.crp_rp_spmm_alg_bytes(self.handle))
@@ -364,6 +419,25 @@ class Para2dSpmm:
         if stream is None:
             stream = _current_stream(C_out)
         self._lib.crp_para2d_spmm_exec_t_ex(self.handle, BC_layout, bp, ldb, cp, ldc, stream)
+
+    def exec_t_f32(self, BC_layout, B, C_out, stream=None):
+        """C := A^T * B in fp32 (crp_para2d_spmm_exec_t_f32_ex): float32 operands only, blocks and layouts as ``exec_t``."""
+        _f32_operands(B, C_out)
+        bp, ldb, _kb = _ptr_ld(B, BC_layout, True)
+        cp, ldc, _kc = _ptr_ld(C_out, BC_layout, True)
+        self._check_blocks(BC_layout, (("B", B, self.rp.A_nrow), ("C", C_out, self.loc_B_nrow)))
+        if stream is None:
+            stream = _current_stream(C_out)
+        self._lib.crp_para2d_spmm_exec_t_f32_ex(self.handle, BC_layout, bp, ldb, cp, ldc, stream)
+
+    def update_values_dev(self, vals, stream=None):
+        """New values from device memory (crp_para2d_spmm_update_values_dev): a 1-D contiguous float64 or float32 CUDA tensor of
+        ``slice_nnz`` entries, this rank's A0 slice values in the order given to init -- what ``sddmm`` writes.  Collective like
+        ``update_values``; every rank of a grid row passes the same dtype."""
+        ptr, f32, _keep = _dev_vals(vals, self.slice_nnz)
+        if stream is None:
+            stream = _current_stream(vals)
+        self._lib.crp_para2d_spmm_update_values_dev(self.handle, ptr, f32, stream)
 
     def sddmm(self, BC_layout, X, Y, out, mode=0, stream=None):
         """SDDMM over all n columns (crp_para2d_spmm_sddmm_ex / _f32_ex, by the operands' dtype): out[p] = <X[i], Y[c]> for every

@@ -100,6 +100,18 @@ void crp_rp_spmm_exec_f32_ex(crp_rp_spmm_p rp_spmm, int BC_layout, const float *
  * transposed matrices once they exist.  A plan-only engine aborts as in exec. */
 void crp_rp_spmm_exec_t_ex(crp_rp_spmm_p rp_spmm, int BC_layout, const double *B, long long ldB,
                            double *C, long long ldC, void *stream);
+/* The fp32 form: B and C in fp32, fp32 FMAs (crp_spmm_csr_f32 with the fp32 variant) on the fp32 copies of the transposed
+ * matrices, which follow the value updates.  The transposed matrices, the accumulate lists, streams and events are the ones
+ * crp_rp_spmm_exec_t_ex builds -- whichever dtype is called first builds them, and both may be called on one engine.  The
+ * exchange is the fp32 exchange of crp_rp_spmm_exec_f32_ex run backwards: rows of ld32 = round_up(glb_n, 4) floats from the
+ * fp32 receive buffer into the fp32 send buffer, the word counts swapped; the peers' part writes glb_n columns at leading
+ * dimension ld32, so the pad columns zeroed at allocation stay zero.  The accumulate is crp_scatter_add_rows_f32: one fp32
+ * addition per returning row, in a fixed order -- repeated calls and both timing modes are bit-identical.  Entry (c, j) of C
+ * passes through at most L_c roundings (L_c: nonzeros of column c of the global A) plus one for the fp64 -> fp32 value
+ * conversion, whatever the rank count and kernel variant.  Operands, layouts, staging, statistics, completion rule, plan-only
+ * abort and NULL no-op as the fp64 form. */
+void crp_rp_spmm_exec_t_f32_ex(crp_rp_spmm_p rp_spmm, int BC_layout, const float *B, long long ldB,
+                               float *C, long long ldC, void *stream);
 int crp_rp_spmm_transposed_built(crp_rp_spmm_p rp_spmm);
 /* Sampled dense-dense product over this rank's rows of A (crp_sddmm_csr_f64 / _f32 in crpspmm_hip.h): for every local nonzero
  * p = (i, c) of the GLOBAL matrix, out[p] = < X[i][0:glb_n], Y[c][0:glb_n] >, times the engine's current value of p in mode 1
@@ -167,6 +179,22 @@ void crp_rp_spmm_kernel_info(crp_rp_spmm_p rp_spmm, int *variant, int *reordered
 /* New values for the same sparsity pattern, in the order of the A_val given to init (the
  * deprecated crpspmm_engine passes A's values on every exec: deprecated/src/crpspmm.h:108-117). */
 void crp_rp_spmm_update_values(crp_rp_spmm_p rp_spmm, const double *A_val);
+/* The same from DEVICE memory: A_val_dev holds crp_rp_spmm_nnz values in the order of the A_val given to init -- the order
+ * crp_rp_spmm_sddmm_ex writes -- as fp64 (f32 = 0) or fp32 (f32 = 1; widened exactly, so the fp32 products read the caller's
+ * fp32 bits and the result equals a host update with the widened values bit for bit).  Asynchronous on `stream` (taken
+ * literally), with no host synchronisation: it first waits for an exec that returned asynchronously; the values are widened
+ * or copied (a split engine: gathered part by part through device copies of the parts' positions in A_val, the ones the
+ * first SDDMM uploads) into an engine-owned scratch buffer, so A_val_dev is free again as soon as the stream has passed
+ * the call, and handed to crp_csr_dev_update_values of every device matrix; once the transposed matrices exist they are
+ * gathered into their order too.  The engine's own stream is made to wait for the update (an event recorded behind it), so
+ * crp_rp_spmm_exec and a later host update cannot overtake it; calls on `stream` are ordered by the stream; work on any
+ * other stream is the caller's to order.  Scratch, positions and the event are allocated by the first device update and by
+ * nothing before it (that call allocates and uploads, hence blocks).  The host values behind crp_rp_spmm_get_plan are left
+ * behind (crp_rp_spmm_host_values_stale: 1) and refreshed by one blocking download where they are read: get_plan, the
+ * first exec_t; a host crp_rp_spmm_update_values overwrites them and clears the flag.  A plan-only engine aborts as in
+ * exec; a NULL engine is a no-op (stale: 0). */
+void crp_rp_spmm_update_values_dev(crp_rp_spmm_p rp_spmm, const void *A_val_dev, int f32, void *stream);
+int crp_rp_spmm_host_values_stale(crp_rp_spmm_p rp_spmm);
 
 /* See para2d_spmm_init (src/para2d_spmm.h:22-47). Rank r sits at grid position
  * (r / pn, r % pn); A_rowptr/A_colidx/A_val is the rank's A0 slice. */
@@ -217,6 +245,18 @@ void crp_para2d_spmm_sddmm_ex(crp_para2d_spmm_p e, int layout, const double *X, 
 void crp_para2d_spmm_sddmm_f32_ex(crp_para2d_spmm_p e, int layout, const float *X, long long ldX,
                                   const float *Y, long long ldY, float *out, int mode, void *stream);
 int crp_para2d_spmm_sddmm_built(crp_para2d_spmm_p e);
+/* fp32 C := A^T * B of the grid column's row engine (crp_rp_spmm_exec_t_f32_ex). */
+void crp_para2d_spmm_exec_t_f32_ex(crp_para2d_spmm_p e, int BC_layout, const float *B, long long ldB,
+                                   float *C, long long ldC, void *stream);
+/* New values from DEVICE memory: this rank's A0 slice values in the order given to init, crp_para2d_spmm_slice_nnz entries of
+ * fp64 (f32 = 0) or fp32 (f32 = 1) -- what crp_para2d_spmm_sddmm_* writes (NULL when the slice is empty).  With pn == 1 a
+ * forward to crp_rp_spmm_update_values_dev.  With pn > 1 the slices are all-gathered along the grid-row communicator between
+ * device buffers (allgatherv_dev on `stream`, init's nonzero counts times the item size as byte counts) into an engine-owned
+ * panel buffer -- the panel is the concatenation of the slices in rank order -- which is handed to
+ * crp_rp_spmm_update_values_dev; a communicator without allgatherv_dev is served through allgatherv_bytes on host copies
+ * (a download, the gather, an upload: that path blocks).  Collective like crp_para2d_spmm_update_values: the first call
+ * of the three over the whole grid.  The panel buffer is allocated by the first device update.  A plan-only engine aborts. */
+void crp_para2d_spmm_update_values_dev(crp_para2d_spmm_p e, const void *A_val_dev, int f32, void *stream);
 /* nonzeros of this rank's A0 slice; of every slice of its grid row (pn entries written when nnz_of_pj != NULL; returns pn). */
 long long crp_para2d_spmm_slice_nnz(crp_para2d_spmm_p e);
 int crp_para2d_spmm_row_slice_nnz(crp_para2d_spmm_p e, long long *nnz_of_pj);

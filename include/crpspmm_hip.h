@@ -327,6 +327,19 @@ int crp_scatter_rows_f64(int layout, int nidx, int n, const int *ridx,
  * product, where one local row can come back from several peers).  seg_row / seg_ptr / seg_pos are device arrays. */
 int crp_scatter_add_rows_f64(int nseg, int n, const int *seg_row, const int *seg_ptr, const int *seg_pos,
                              const double *src, long long lds, double *dst, long long ldd, void *stream);
+/* the fp32 instance of the same kernel (the reduce of crp_rp_spmm_exec_t_f32_ex): plain IEEE fp32 additions in list order.
+ * Pieces of 16 bytes (4 floats; the fp64 form: 2 doubles) when n, lds, ldd and both pointers keep them aligned, single
+ * elements otherwise -- the same bits either way.  Arguments and return codes as the fp64 form: -1 for a negative count or,
+ * with work to do, a NULL pointer; 0 when nseg or n is 0 (nothing is launched); a positive HIP error. */
+int crp_scatter_add_rows_f32(int nseg, int n, const int *seg_row, const int *seg_ptr, const int *seg_pos,
+                             const float *src, long long lds, float *dst, long long ldd, void *stream);
+/* value gather: dst[i] = (double) src[map ? map[i] : i] for i < n; map (device int32, may repeat positions) == NULL is a
+ * copy / a widening.  Widening fp32 to fp64 is exact, so the fp32 copies a handle derives from dst with (float) are the
+ * caller's fp32 bits again: a device value update from fp32 values (crp_rp_spmm_update_values_dev) needs no fp32 value
+ * store in the handle.  Asynchronous on `stream`; device pointers.  Returns 0 (n == 0: nothing is launched), -1 for n < 0
+ * or, with n > 0, a NULL src or dst, or a positive HIP error. */
+int crp_gather_vals_f64(long long n, const int *map, const double *src, double *dst, void *stream);
+int crp_gather_vals_f32_f64(long long n, const int *map, const float *src, double *dst, void *stream);
 /* sum of segments: out[p] = ((src[p] + src[seg_stride + p]) + src[2 * seg_stride + p]) + ... for 0 <= p < len, strictly left
  * to right over ascending segment number (the grid-row reduction of the 2D engine's SDDMM, crp_para2d_spmm_sddmm_ex).
  * Plain IEEE additions, no atomics and no LDS; every out[p] belongs to one thread; nseg == 1 is a copy.  Pieces of 16 bytes
