@@ -620,6 +620,13 @@ static void exec_impl(crp_rp_spmm *e, int BC_layout, const T *B, long long ldB, 
         Bd = rm;
         ldBd = n;
     }
+    // A rank that owns no row of B has nothing to read there.  The caller's pointer to the empty block and its leading dimension
+    // (column-major: ldB >= 0 rows, which says nothing about n) must not reach the kernels' argument checks as a row-major view.
+    if (kb == 0)
+    {
+        Bd = nullptr;
+        ldBd = n;
+    }
     T *Cd = C;
     long long ldCd = ldC;
     if (BC_layout == 1)

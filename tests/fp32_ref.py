@@ -3,6 +3,7 @@
 fma32              an exact, vectorised emulation of one single-rounded fp32 FMA (round to nearest even)
 csr_f32_sequential the CSR row-group kernel's arithmetic (csrc/spmm_f32.hip) bit for bit
 check_f32_bound    the error bound every summation order of the fp32 path meets, against the fp64 oracle
+exact_problem32    data on which EVERY summation order, with or without FMA, gives the same fp32 bits (the twin of fp64_ref.exact_parts)
 
 Data rule of the tests that use them: values and B entries are +-2^U(-8, 1) (data_values / data_B).  Every fp32 input is then a
 multiple of 2^-31, so every exact product and partial sum is a multiple of 2^-62: a nonzero result stays far above the fp32
@@ -21,6 +22,52 @@ def data_values(rng, size):
 def data_B(rng, shape):
     """+-2^U(-8, 1) as fp32."""
     return data_values(rng, shape).astype(np.float32)
+
+
+ROW_EXP32, COL_EXP32 = 20, 10
+
+
+def exact_problem32(rowptr, colidx, k, n, rng):
+    """(val64, B32, C_exact32) for the pattern (rowptr, colidx) with k columns and an operand of n columns, on which every fp32
+    summation order, fused or not, gives C_exact32 bit for bit -- the fp32 twin of fp64_ref.exact_parts.
+
+    A = D_r A0 D_c and B = D_c^-1 B0 with power-of-two diagonals (row exponents uniform in [-20, 20], column exponents in
+    [-10, 10]); A0 and B0 hold odd integers below 2^bits_a and 2^bits_b, bits_a + bits_b + ceil(log2(longest row)) <= 24.  Then
+    val[p] * B[c][j] = a0 b0 2^(row exponent) exactly and sum_p |a0 b0| < 2^24 in every entry (asserted): every partial sum of every
+    subset of a row's products is an integer below 2^24 times 2^(row exponent) -- exact in fp32.  |val| lies in [2^-30, 2^42),
+    |B| in [2^-10, 2^22) and a nonzero |C| in [2^-20, 2^44): all normal fp32 numbers, so no result depends on the device's
+    denormal mode.  val64 holds fp32-representable numbers: the library's fp64 -> fp32 conversion of the values is exact."""
+    import oracle
+    rp = np.asarray(rowptr, dtype=np.int64)
+    ci = np.asarray(colidx, dtype=np.int64)
+    m, nnz = rp.size - 1, int(rp[-1])
+    assert nnz == 0 or (ci[:nnz].min() >= 0 and ci[:nnz].max() < k), "plain column indices (split two sources afterwards)"
+    lens = np.diff(rp)
+    longest = max(int(lens.max()) if m else 1, 1)
+    room = 24 - int(np.ceil(np.log2(longest)))
+    bits_a, bits_b = room // 2, room - room // 2
+    assert bits_a >= 2, ("rows too long for the exact fp32 budget", longest)
+
+    def odd(bits, size):
+        mag = 2 * rng.integers(0, 1 << (bits - 1), size=size, dtype=np.int64) + 1
+        return np.where(rng.integers(0, 2, size=size) == 1, mag, -mag)
+
+    A0, B0 = odd(bits_a, nnz), odd(bits_b, (k, n))
+    row_exp = rng.integers(-ROW_EXP32, ROW_EXP32 + 1, size=m)
+    col_exp = rng.integers(-COL_EXP32, COL_EXP32 + 1, size=k)
+    rows = np.repeat(np.arange(m), lens)
+    budget = oracle.spmm_csr(rowptr, colidx, np.abs(A0).astype(np.float64), np.abs(B0).astype(np.float64))
+    assert longest * float(1 << bits_a) * float(1 << bits_b) <= 2.0 ** 24 and (budget < 2.0 ** 24).all(), "exact fp32 budget exceeded"
+    val64 = np.ldexp(A0.astype(np.float64), (row_exp[rows] + col_exp[ci[:nnz]]).astype(np.int32))
+    B64 = np.ldexp(B0.astype(np.float64), (-col_exp).astype(np.int32)[:, None])
+    C0 = oracle.spmm_csr(rowptr, colidx, A0.astype(np.float64), B0.astype(np.float64))      # integers below 2^24: exact
+    C64 = np.ldexp(C0, row_exp.astype(np.int32)[:, None])
+    B32, C32 = B64.astype(np.float32), C64.astype(np.float32)
+    tiny = float(np.finfo(np.float32).tiny)
+    assert np.array_equal(val64.astype(np.float32).astype(np.float64), val64) and np.array_equal(B32.astype(np.float64), B64) \
+        and np.array_equal(C32.astype(np.float64), C64), "not exactly representable in fp32"
+    assert (np.abs(val64) >= tiny).all() and (np.abs(B64) >= tiny).all() and (np.abs(C64[C64 != 0]) >= tiny).all(), "a subnormal"
+    return val64, B32, C32
 
 
 def fma32(a, b, c):

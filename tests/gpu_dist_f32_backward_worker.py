@@ -1,7 +1,8 @@
 """Worker for tests/test_gpu_f32_backward.py: the row-parallel engine's fp32 transposed product and its device-resident value
 updates on N ranks -- sharing ONE GPU with device payloads staged through the host (the rehearsal mode of
 tests/gpu_dist_t_worker.py), or with a GPU per rank and the native RCCL exchange.  Every rank's rows of C := A^T * B meet the
-entrywise fp32 bound of tests/fp32_ref.py against the GLOBAL transpose, whatever the cut into ranks; a twin engine updated from
+entrywise fp32 bound of tests/fp32_ref.py against the GLOBAL transpose, whatever the cut into ranks, and so do its rows of the
+forward product the later checks compare with; a twin engine updated from
 the host gives the same bits as the one updated from device memory, split into interior and boundary rows or not."""
 import os
 import sys
@@ -61,6 +62,7 @@ def main():
         for n in (7, 256):
             Y32, B32 = fp32_ref.data_B(rng, (m, n)), fp32_ref.data_B(rng, (k, n))
             ref, bound = fp32_ref.f32_bound(rp_t, ci_t, va_t, Y32)
+            ref_f, bound_f = fp32_ref.f32_bound(rp, ci, va, B32)                  # the forward product, global as well
             mk = lambda: engine.RpSpmm(s, e - s, rp[s:e + 1], ci[mine], va[mine], rb, n, world)
             eng = mk()
             if P == 2 and name == "banded_fem":      # (every row of random_csr has a column of the peer's: that engine stays whole)
@@ -70,6 +72,8 @@ def main():
             # ---- lazy build: a forward fp32 exec builds nothing transposed
             fwd = run(lambda o: eng.exec(0, Bd, o), (e - s, n), torch.float32)
             assert not eng.transposed_built, tag
+            fp32_ref.check_f32_bound(rp[s:e + 1], None, None, None, fwd, what="rank %d %s n=%d forward exec" % tag,
+                                     ref_bound=(ref_f[s:e], bound_f[s:e]))
             # ---- the bound, timing on: peers' part, exchange, local part, accumulate in sequence
             seq = run(lambda o: eng.exec_t_f32(0, Yd, o), (e - s, n), torch.float32)
             assert eng.transposed_built, tag

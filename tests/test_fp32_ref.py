@@ -1,5 +1,6 @@
 """CPU checks of the fp32 references (tests/fp32_ref.py) the GPU fp32 kernel tests rely on: fma32 against exact rational
-rounding, and check_f32_bound accepting every summation order while rejecting each kind of subtle kernel bug."""
+rounding, check_f32_bound accepting every summation order while rejecting each kind of subtle kernel bug, and
+exact_problem32 giving one result in every order while a dropped nonzero or a misplaced B row shows."""
 from fractions import Fraction
 
 import numpy as np
@@ -195,3 +196,57 @@ def test_bound_nonfinite_masks(orc):
     M = C.copy(); M[fin_rows[0], 3] = np.nan
     with pytest.raises(AssertionError, match="NaN positions"):
         F.check_f32_bound(rp, ci, va, B, M, "leaked NaN")
+
+
+# ---- exact_problem32: data on which every fp32 summation order gives the same bits
+
+@pytest.fixture(scope="module")
+def exact32(orc):
+    from crp_spmm_amd import gen
+    rp, ci, _va = gen.random_csr(300, 260, 12, seed=4, empty_every=7)
+    rng = np.random.default_rng(6)
+    return (rp, ci) + F.exact_problem32(rp, ci, 260, 9, rng)
+
+
+def test_exact32_is_normal_fp32_and_hits_both_scales(exact32):
+    rp, ci, val, B, C = exact32
+    assert val.dtype == np.float64 and B.dtype == np.float32 and C.dtype == np.float32
+    assert np.array_equal(val.astype(np.float32).astype(np.float64), val)
+    tiny = np.finfo(np.float32).tiny
+    assert (np.abs(val) >= tiny).all() and (np.abs(B) >= tiny).all() and (np.abs(C[C != 0]) >= tiny).all()
+    assert (C[np.diff(rp) == 0] == 0).all() and (np.diff(rp) == 0).any()
+    mag = np.abs(C[C != 0]).astype(np.float64)
+    assert mag.max() / mag.min() > 2.0 ** 30             # rows of very different scales: what one norm cannot see
+
+
+def test_exact32_every_order_gives_the_same_bits(exact32, orc):
+    """(i) the kernel's ascending FMA chain, the same sum in reversed order and the fp64 oracle rounded to fp32."""
+    rp, ci, val, B, C = exact32
+    assert np.array_equal(_bits(F.csr_f32_sequential(rp, ci, val, B)), _bits(C))
+    assert np.array_equal(_bits(_f32_products(rp, ci, val, B, "desc")), _bits(C))
+    assert np.array_equal(_bits(_f32_products(rp, ci, val, B, "pairwise")), _bits(C))
+    assert np.array_equal(_bits(orc.spmm_csr(rp, ci, val, B.astype(np.float64)).astype(np.float32)), _bits(C))
+
+
+def test_exact32_shows_each_fault(exact32):
+    """(ii) a dropped nonzero, two B rows swapped and a B row taken from the wrong source each change at least one entry."""
+    rp, ci, val, B, C = exact32
+    lens = np.diff(rp)
+    i = int(np.nonzero(lens >= 3)[0][5])
+    p = int(rp[i]) + 1
+    dropped = val.copy(); dropped[p] = 0.0
+    M = F.csr_f32_sequential(rp, ci, dropped, B)
+    assert not np.array_equal(_bits(M), _bits(C)) and np.array_equal(_bits(np.delete(M, i, 0)), _bits(np.delete(C, i, 0)))
+    c0, c1 = int(ci[p]), int(ci[p + 1])
+    Bs = B.copy(); Bs[[c0, c1]] = Bs[[c1, c0]]                          # two received rows in each other's place
+    assert not np.array_equal(_bits(F.csr_f32_sequential(rp, ci, val, Bs)), _bits(C))
+    # two sources: columns [100, 200) local, the rest remote; the unmutated split gives C, remote position 0 read from B0 does not
+    codes, remote = F.split_two_source(ci, 260, 100, 200)
+    B0, B1 = B[100:200], B[remote]
+    assert np.array_equal(_bits(F.csr_f32_sequential(rp, codes, val, B0, B1)), _bits(C))
+    wrong = codes.copy()
+    q = int(np.nonzero(codes < 0)[0][0])
+    wrong[q] = ~codes[q]                                                # the same row number, taken from B0 instead of B1
+    assert not np.array_equal(_bits(F.csr_f32_sequential(rp, wrong, val, B0, B1)), _bits(C))
+    shifted = np.where(codes < 0, ~((~codes + 1) % remote.size), codes).astype(np.int32)   # every received row one row off
+    assert not np.array_equal(_bits(F.csr_f32_sequential(rp, shifted, val, B0, B1)), _bits(C))
