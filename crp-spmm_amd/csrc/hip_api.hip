@@ -389,10 +389,11 @@ static int sddmm_csr(crp_csr_dev *A, int n, const T *X, long long ldX, const T *
 static int sddmm_check(const crp_csr_dev *A, int n, const void *X, long long ldX, const void *Y0, long long ldY0, const void *Y1,
                        long long ldY1, const void *out, int mode)
 {
-    if (A == NULL || X == NULL || Y0 == NULL || out == NULL) return -1;
+    if (A == NULL || X == NULL || out == NULL) return -1;
     if (n < 1 || (mode != 0 && mode != 1)) return -1;
+    if (Y0 == NULL && A->b0_rows > 0) return -1;        // a column code names the first source
     if (Y1 == NULL && A->b1_rows > 0) return -1;        // a column code names the second source
-    if (ldX < n || ldY0 < n || (Y1 != NULL && ldY1 < n)) return -4;
+    if (ldX < n || (Y0 != NULL && ldY0 < n) || (Y1 != NULL && ldY1 < n)) return -4;
     return 0;
 }
 

@@ -21,6 +21,7 @@
 #include "crp_engine.h"
 #include "crpspmm_hip.h"
 #include "utils.h"
+#include "operand_view.h"      // HIP_OK
 #include "knobs.h"
 
 struct crp_para2d_spmm
@@ -48,11 +49,6 @@ struct crp_para2d_spmm
     std::vector<char> dv_host;             // ... staged on the host when the communicator has no allgatherv_dev
 };
 
-#define HIP_OK(call)                                                              \
-    do {                                                                          \
-        int rc__ = (call);                                                        \
-        ASSERT_PRINTF(rc__ == 0, "%s failed with code %d\n", #call, rc__);        \
-    } while (0)
 
 static long long up2(long long v) { return (v + 1) / 2 * 2; }
 

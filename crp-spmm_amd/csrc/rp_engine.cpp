@@ -18,6 +18,7 @@
 #include "crp_engine.h"
 #include "crpspmm_hip.h"
 #include "utils.h"
+#include "operand_view.h"
 #include "par.h"
 #include <algorithm>
 
@@ -73,8 +74,7 @@ struct crp_rp_spmm
     // as int32 device arrays; none for the unsplit engine), and the staging buffer of a host `out`
     bool sd_built = false;
     int *sd_int_pos = nullptr, *sd_bnd_pos = nullptr;
-    double *sd_out = nullptr;
-    size_t  sd_out_sz = 0;
+    crp::DevScratch sd_out;
     // device value updates (crp_rp_spmm_update_values_dev), allocated by its first call: the new values as fp64 in the order the
     // device matrices take them (A_dev: A_val's order; a split engine: A_int's nonzeros, then A_bnd's) and, once the transposed
     // matrices exist, in theirs (through dv_t_pos, a device copy of t_src); ev_vals is recorded at the end of every update
@@ -84,8 +84,7 @@ struct crp_rp_spmm
     void   *ev_vals = nullptr;
     bool    host_vals_stale = false;             // A_val (host) is behind the device matrices: refreshed where it is read
     // staging (host-pointer API) and column-major temporaries, grown on demand
-    double *B_stage = nullptr, *C_stage = nullptr, *B_rm = nullptr, *C_rm = nullptr;
-    size_t  B_stage_sz = 0, C_stage_sz = 0, B_rm_sz = 0, C_rm_sz = 0;
+    crp::DevScratch B_stage, C_stage, B_rm, C_rm;
     // the stream the last exec ran on, and an event at its end: a value update on the engine's own stream must
     // not overtake kernels of an exec that is still in flight on the caller's stream
     void *ev_exec = nullptr;
@@ -94,22 +93,6 @@ struct crp_rp_spmm
     const void *last_B = nullptr, *last_C = nullptr;
     int last_B_dev = 0, last_C_dev = 0;
 };
-
-#define HIP_OK(call)                                                              \
-    do {                                                                          \
-        int rc__ = (call);                                                        \
-        ASSERT_PRINTF(rc__ == 0, "%s failed with code %d\n", #call, rc__);        \
-    } while (0)
-
-static void grow(double **buf, size_t *cur, size_t need_elems)
-{
-    if (need_elems <= *cur) return;
-    if (*buf) HIP_OK(crp_dev_free(*buf));
-    void *p = NULL;
-    HIP_OK(crp_dev_malloc(&p, need_elems * sizeof(double)));
-    *buf = (double *) p;
-    *cur = need_elems;
-}
 
 
 // ---------------------------------------------------------------------------
@@ -373,7 +356,7 @@ void crp_rp_spmm_free(crp_rp_spmm_p *rp_spmm)
         crp_dev_free(e->acc_dev);
         crp_dev_free(e->sd_int_pos);
         crp_dev_free(e->sd_bnd_pos);
-        crp_dev_free(e->sd_out);
+        e->sd_out.release();
         crp_dev_free(e->dv_vals);
         crp_dev_free(e->dv_tvals);
         crp_dev_free(e->dv_t_pos);
@@ -387,10 +370,10 @@ void crp_rp_spmm_free(crp_rp_spmm_p *rp_spmm)
         crp_dev_free(e->sendbuf32_dev);
         crp_dev_free(e->recvbuf32_dev);
         if (e->ev_exec) crp_event_destroy(e->ev_exec);
-        crp_dev_free(e->B_stage);
-        crp_dev_free(e->C_stage);
-        crp_dev_free(e->B_rm);
-        crp_dev_free(e->C_rm);
+        e->B_stage.release();
+        e->C_stage.release();
+        e->B_rm.release();
+        e->C_rm.release();
         crp_stream_destroy(e->stream);
     }
     delete e;
@@ -404,13 +387,6 @@ void crp_rp_spmm_free(crp_rp_spmm_p *rp_spmm)
 // second B source) and carries them through the communicator's fp64 all-to-all as opaque 8-byte words: no back end does
 // arithmetic on the payload, so crp_comm_t stays as it is.
 static long long ld32_of(int n) { return ((long long) n + 3) / 4 * 4; }
-
-template <class T> static T *grow_as(double **buf, size_t *cur, size_t need_elems)
-{
-    // staging buffers and temporaries are raw device bytes shared by both dtypes (sizes kept in doubles)
-    grow(buf, cur, (need_elems * sizeof(T) + sizeof(double) - 1) / sizeof(double));
-    return (T *) *buf;
-}
 
 struct Xchg
 {
@@ -466,14 +442,6 @@ static int gather(int nidx, int n, const int *ridx, const float *src, long long 
 {
     return crp_gather_rows_f32(0, nidx, n, ridx, src, lds, dst, ldd, s);
 }
-static int transpose(int nrow, int ncol, const double *src, long long lds, double *dst, long long ldd, void *s)
-{
-    return crp_transpose_f64(nrow, ncol, src, lds, dst, ldd, s);
-}
-static int transpose(int nrow, int ncol, const float *src, long long lds, float *dst, long long ldd, void *s)
-{
-    return crp_transpose_f32(nrow, ncol, src, lds, dst, ldd, s);
-}
 static int spmm(crp_rp_spmm *e, crp_csr_dev_p A, int n, const double *B0, long long ldB0, const double *B1, long long ldB1,
                 double *C, long long ldC, void *s)
 {
@@ -494,6 +462,36 @@ static int scatter_add(int nseg, int n, const int *row, const int *ptr, const in
                        long long ldd, void *s)
 {
     return crp_scatter_add_rows_f32(nseg, n, row, ptr, pos, src, lds, dst, ldd, s);
+}
+
+// Is this pointer on the device?  The pointer-attribute query is not free: the forward exec passes the engine's cache of the last
+// operand seen in that place (last, last_dev), the other calls ask every time (last == nullptr).
+static bool on_device(const void *p, const void **last = nullptr, int *last_dev = nullptr)
+{
+    if (last != nullptr && p == *last && p != NULL) return *last_dev != 0;
+    int dev = 0;
+    HIP_OK(crp_dev_ptr_is_device(p, &dev));
+    if (last != nullptr)
+    {
+        *last = p;
+        *last_dev = dev;
+    }
+    return dev != 0;
+}
+
+// The end of an exec, exec_t or sddmm that has not synchronised yet: wait for the stream when an operand lives on the host or the
+// phases are timed, otherwise return asynchronously and remember where the call ends (crp_rp_spmm_update_values waits for it).
+static void complete(crp_rp_spmm *e, void *s, bool synced, bool must_sync)
+{
+    if (synced) return;
+    if (must_sync)
+    {
+        HIP_OK(crp_stream_sync(s));
+        return;
+    }
+    if (e->ev_exec == nullptr) HIP_OK(crp_event_create(&e->ev_exec));
+    HIP_OK(crp_event_record(e->ev_exec, s));
+    e->exec_pending = true;
 }
 
 // The half that exec and sddmm share: pack the rows of the row-major device operand Bd that other ranks asked for, exchange them
@@ -577,106 +575,23 @@ static void exec_impl(crp_rp_spmm *e, int BC_layout, const T *B, long long ldB, 
     void *s = stream_;   // taken literally: NULL is the HIP null stream (torch's default stream)
     const int n = e->glb_n, kb = e->loc_B_nrow, m = e->A_nrow;
     const bool timing = e->timing != 0;
-    double t0, t1;
+    double t0;
 
-    int B_on_dev = 0, C_on_dev = 0;
-    if (B == e->last_B && B != NULL) B_on_dev = e->last_B_dev;
-    else
-    {
-        HIP_OK(crp_dev_ptr_is_device(B, &B_on_dev));
-        e->last_B = B;
-        e->last_B_dev = B_on_dev;
-    }
-    if (C == e->last_C && C != NULL) C_on_dev = e->last_C_dev;
-    else
-    {
-        HIP_OK(crp_dev_ptr_is_device(C, &C_on_dev));
-        e->last_C = C;
-        e->last_C_dev = C_on_dev;
-    }
+    const bool B_on_dev = on_device(B, &e->last_B, &e->last_B_dev), C_on_dev = on_device(C, &e->last_C, &e->last_C_dev);
 
-    // ---- bring B to a device-resident row-major view (Bd, ldBd)
+    // ---- B as a device-resident row-major view, and where to compute C
     const Xchg x = exchange_of(e, B);
-    const T *Bd = B;
-    long long ldBd = ldB;
-    if (!B_on_dev && kb > 0 && n > 0)
-    {
-        // host operand: stage the whole local block (ld preserved)
-        const size_t elems = (BC_layout == 0) ? (size_t) kb * (size_t) ldB : (size_t) n * (size_t) ldB;
-        T *stage = grow_as<T>(&e->B_stage, &e->B_stage_sz, elems);
-        const size_t used = (BC_layout == 0) ? ((size_t) (kb - 1) * (size_t) ldB + (size_t) n)
-                                             : ((size_t) (n - 1) * (size_t) ldB + (size_t) kb);
-        // one copy straight from the caller's pageable memory: the runtime stages it through its own pinned buffers at
-        // PCIe rate (measured: 16 ms per exec for B in + C out of the pwtk-size operands; an engine-owned pinned mirror
-        // with a memcpy in front of the DMA took 46 ms, pipelined through two pinned chunks with threaded memcpy 35 ms)
-        HIP_OK(crp_dev_memcpy(stage, B, used * sizeof(T), 0, s));
-        Bd = stage;
-    }
-    if (BC_layout == 1 && kb > 0 && n > 0)
-    {
-        T *rm = grow_as<T>(&e->B_rm, &e->B_rm_sz, (size_t) kb * (size_t) n);
-        // column-major kb x n (ld ldB) == row-major n x kb; transpose to row-major kb x n
-        HIP_OK(transpose(n, kb, Bd, ldB, rm, n, s));
-        Bd = rm;
-        ldBd = n;
-    }
-    // A rank that owns no row of B has nothing to read there.  The caller's pointer to the empty block and its leading dimension
-    // (column-major: ldB >= 0 rows, which says nothing about n) must not reach the kernels' argument checks as a row-major view.
-    if (kb == 0)
-    {
-        Bd = nullptr;
-        ldBd = n;
-    }
-    T *Cd = C;
-    long long ldCd = ldC;
-    if (BC_layout == 1)
-    {
-        Cd = grow_as<T>(&e->C_rm, &e->C_rm_sz, (size_t) m * (size_t) n);
-        ldCd = n;
-    }
-    else if (!C_on_dev && m > 0 && n > 0)
-    {
-        Cd = grow_as<T>(&e->C_stage, &e->C_stage_sz, (size_t) m * (size_t) ldC);
-    }
+    const crp::InView<T> Bv = crp::operand_in(BC_layout, B, ldB, kb, n, B_on_dev, e->B_stage, e->B_rm, s);
+    const crp::OutView<T> Cv = crp::operand_out(BC_layout, C, ldC, m, n, C_on_dev, e->C_stage, e->C_rm);
 
     // ---- 1 - 3. pack, exchange, local SpMM
-    pack_exchange_run(e, x, Bd, ldBd, s, t0, [&](crp_csr_dev_p A, int) { HIP_OK(spmm(e, A, n, Bd, ldBd, (const T *) x.recv, x.ld, Cd, ldCd, s)); });
-    if (BC_layout == 1 && m > 0 && n > 0)
-    {
-        T *Ccm = C;
-        if (!C_on_dev) Ccm = grow_as<T>(&e->C_stage, &e->C_stage_sz, (size_t) n * (size_t) ldC);
-        HIP_OK(transpose(m, n, Cd, n, Ccm, ldC, s));   // row-major n x m (ld ldC) == column-major m x n
-        Cd = Ccm;
-    }
-    if (timing)
-    {
+    pack_exchange_run(e, x, Bv.p, Bv.ld, s, t0, [&](crp_csr_dev_p A, int) { HIP_OK(spmm(e, A, n, Bv.p, Bv.ld, (const T *) x.recv, x.ld, Cv.p, Cv.ld, s)); });
+    const bool synced = crp::finish(Cv, s, [&] {
+        if (!timing) return;
         HIP_OK(crp_stream_sync(s));
-        t1 = get_wtime_sec();
-        e->t_spmm += t1 - t0;
-    }
-
-    if (!C_on_dev && m > 0 && n > 0)
-    {
-        const size_t used = (BC_layout == 0) ? ((size_t) (m - 1) * (size_t) ldC + (size_t) n)
-                                             : ((size_t) (n - 1) * (size_t) ldC + (size_t) m);
-        // ONE 2D copy straight into the caller's C (round 1 issued one copy per row when ldC != n); the caller's padding
-        // between rows (columns) is never written
-        const size_t w = (BC_layout == 0) ? (size_t) n : (size_t) m, h = (BC_layout == 0) ? (size_t) m : (size_t) n;
-        (void) used;
-        HIP_OK(crp_dev_memcpy2d(C, (size_t) ldC * sizeof(T), Cd, (size_t) ldC * sizeof(T), w * sizeof(T), h, 1, s));
-        HIP_OK(crp_stream_sync(s));
-    }
-    else if (!B_on_dev || timing)
-    {
-        HIP_OK(crp_stream_sync(s));
-    }
-    else
-    {
-        // asynchronous return: remember where this exec ends (crp_rp_spmm_update_values waits for it)
-        if (e->ev_exec == nullptr) HIP_OK(crp_event_create(&e->ev_exec));
-        HIP_OK(crp_event_record(e->ev_exec, s));
-        e->exec_pending = true;
-    }
+        e->t_spmm += get_wtime_sec() - t0;
+    });
+    complete(e, s, synced, !B_on_dev || timing);
     e->t_exec += get_wtime_sec() - t_begin;
     e->n_exec++;
 }
@@ -758,48 +673,22 @@ static void sddmm_impl(crp_rp_spmm *e, int layout, const T *X, long long ldX, co
     const bool timing = e->timing != 0;
     double t0;
 
-    int X_on_dev = 0, Y_on_dev = 0, out_on_dev = 0;
-    HIP_OK(crp_dev_ptr_is_device(X, &X_on_dev));
-    HIP_OK(crp_dev_ptr_is_device(Y, &Y_on_dev));
-    HIP_OK(crp_dev_ptr_is_device(out, &out_on_dev));
+    const bool X_on_dev = on_device(X), Y_on_dev = on_device(Y), out_on_dev = on_device(out);
 
-    // ---- operands as device-resident row-major views, staged and transposed as in exec_impl: Y takes B's buffers, X takes C's
+    // ---- operands as device-resident row-major views: Y takes B's buffers, X takes C's
     const Xchg x = exchange_of(e, Y);
-    auto view = [&](const T *P, long long ld, int rows, int on_dev, double **stage, size_t *stage_sz, double **rm, size_t *rm_sz,
-                    long long *ld_out) -> const T * {
-        const T *Pd = P;
-        *ld_out = ld;
-        if (rows <= 0 || n <= 0) return Pd;
-        if (!on_dev)
-        {
-            const size_t elems = (layout == 0) ? (size_t) rows * (size_t) ld : (size_t) n * (size_t) ld;
-            T *st = grow_as<T>(stage, stage_sz, elems);
-            const size_t used = (layout == 0) ? ((size_t) (rows - 1) * (size_t) ld + (size_t) n) : ((size_t) (n - 1) * (size_t) ld + (size_t) rows);
-            HIP_OK(crp_dev_memcpy(st, P, used * sizeof(T), 0, s));
-            Pd = st;
-        }
-        if (layout == 1)
-        {
-            T *r = grow_as<T>(rm, rm_sz, (size_t) rows * (size_t) n);
-            HIP_OK(transpose(n, rows, Pd, ld, r, n, s));      // column-major rows x n (ld) == row-major n x rows
-            Pd = r;
-            *ld_out = n;
-        }
-        return Pd;
-    };
-    long long ldYd = ldY, ldXd = ldX;
-    const T *Yd = view(Y, ldY, kb, Y_on_dev, &e->B_stage, &e->B_stage_sz, &e->B_rm, &e->B_rm_sz, &ldYd);
-    const T *Xd = view(X, ldX, m, X_on_dev, &e->C_stage, &e->C_stage_sz, &e->C_rm, &e->C_rm_sz, &ldXd);
+    const crp::InView<T> Yv = crp::operand_in(layout, Y, ldY, kb, n, Y_on_dev, e->B_stage, e->B_rm, s);
+    const crp::InView<T> Xv = crp::operand_in(layout, X, ldX, m, n, X_on_dev, e->C_stage, e->C_rm, s);
     T *outd = out;
-    if (!out_on_dev && nnz > 0) outd = grow_as<T>(&e->sd_out, &e->sd_out_sz, nnz);
+    if (!out_on_dev && nnz > 0) outd = e->sd_out.grow<T>(nnz);
 
     if (n == 0 && nnz > 0) HIP_OK(crp_dev_memset(outd, 0, nnz * sizeof(T), s));      // empty dots
 
     // ---- pack Y, exchange, the kernels: the parts of a split engine write through their positions in A_val
-    pack_exchange_run(e, x, Yd, ldYd, s, t0, [&](crp_csr_dev_p A, int part) {
+    pack_exchange_run(e, x, Yv.p, Yv.ld, s, t0, [&](crp_csr_dev_p A, int part) {
         if (n == 0 || crp_csr_dev_nnz(A) == 0) return;
         const int *pos = part == 1 ? e->sd_int_pos : (part == 2 ? e->sd_bnd_pos : nullptr);
-        HIP_OK(sddmm(A, n, Xd, ldXd, Yd, ldYd, (const T *) x.recv, x.ld, outd, pos, mode, s));
+        HIP_OK(sddmm(A, n, Xv.p, Xv.ld, Yv.p, Yv.ld, (const T *) x.recv, x.ld, outd, pos, mode, s));
     });
     if (timing)
     {
@@ -807,22 +696,9 @@ static void sddmm_impl(crp_rp_spmm *e, int layout, const T *X, long long ldX, co
         e->t_spmm += get_wtime_sec() - t0;
     }
 
-    if (!out_on_dev && nnz > 0)
-    {
-        HIP_OK(crp_dev_memcpy(out, outd, nnz * sizeof(T), 1, s));
-        HIP_OK(crp_stream_sync(s));
-    }
-    else if (!X_on_dev || !Y_on_dev || timing)
-    {
-        HIP_OK(crp_stream_sync(s));
-    }
-    else
-    {
-        // asynchronous return: crp_rp_spmm_update_values waits for this call as for an exec
-        if (e->ev_exec == nullptr) HIP_OK(crp_event_create(&e->ev_exec));
-        HIP_OK(crp_event_record(e->ev_exec, s));
-        e->exec_pending = true;
-    }
+    const bool download = !out_on_dev && nnz > 0;
+    if (download) HIP_OK(crp_dev_memcpy(out, outd, nnz * sizeof(T), 1, s));
+    complete(e, s, false, download || !X_on_dev || !Y_on_dev || timing);
     e->t_exec += get_wtime_sec() - t_begin;
     e->n_exec++;
 }
@@ -940,40 +816,12 @@ static void exec_t_impl(crp_rp_spmm *e, int BC_layout, const T *B, long long ldB
     const bool timing = e->timing != 0;
     double t0, t1;
 
-    int B_on_dev = 0, C_on_dev = 0;
-    HIP_OK(crp_dev_ptr_is_device(B, &B_on_dev));
-    HIP_OK(crp_dev_ptr_is_device(C, &C_on_dev));
+    const bool B_on_dev = on_device(B), C_on_dev = on_device(C);
 
-    // ---- operands as device-resident row-major views, staged and transposed as in exec_impl
+    // ---- B as a device-resident row-major view, and where to compute C
     const Xchg x = exchange_of(e, B);
-    const T *Bd = B;
-    long long ldBd = ldB;
-    if (!B_on_dev && mb > 0 && n > 0)
-    {
-        const size_t elems = (BC_layout == 0) ? (size_t) mb * (size_t) ldB : (size_t) n * (size_t) ldB;
-        T *stage = grow_as<T>(&e->B_stage, &e->B_stage_sz, elems);
-        const size_t used = (BC_layout == 0) ? ((size_t) (mb - 1) * (size_t) ldB + (size_t) n) : ((size_t) (n - 1) * (size_t) ldB + (size_t) mb);
-        HIP_OK(crp_dev_memcpy(stage, B, used * sizeof(T), 0, s));
-        Bd = stage;
-    }
-    if (BC_layout == 1 && mb > 0 && n > 0)
-    {
-        T *rm = grow_as<T>(&e->B_rm, &e->B_rm_sz, (size_t) mb * (size_t) n);
-        HIP_OK(transpose(n, mb, Bd, ldB, rm, n, s));
-        Bd = rm;
-        ldBd = n;
-    }
-    T *Cd = C;
-    long long ldCd = ldC;
-    if (BC_layout == 1)
-    {
-        Cd = grow_as<T>(&e->C_rm, &e->C_rm_sz, (size_t) mc * (size_t) n);
-        ldCd = n;
-    }
-    else if (!C_on_dev && mc > 0 && n > 0)
-    {
-        Cd = grow_as<T>(&e->C_stage, &e->C_stage_sz, (size_t) mc * (size_t) ldC);
-    }
+    const crp::InView<T> Bv = crp::operand_in(BC_layout, B, ldB, mb, n, B_on_dev, e->B_stage, e->B_rm, s);
+    const crp::OutView<T> Cv = crp::operand_out(BC_layout, C, ldC, mc, n, C_on_dev, e->C_stage, e->C_rm);
 
     auto reverse_exchange = [&](void *xs) {
         // the forward plan backwards: what this rank receives there it sends here, from the receive into the send buffer
@@ -981,11 +829,11 @@ static void exec_t_impl(crp_rp_spmm *e, int BC_layout, const T *B, long long ldB
         e->comm->alltoallv_dev_f64(e->comm->ctx, (const double *) x.recv, x.rc, x.rd, (double *) x.send, x.sc, x.sd, xs);
         e->t_a2a_host += get_wtime_sec() - tx0;
     };
-    auto product = [&](crp_csr_dev_p A, T *out, long long ldo) { HIP_OK(spmm(e, A, n, Bd, ldBd, (const T *) NULL, 0, out, ldo, s)); };
+    auto product = [&](crp_csr_dev_p A, T *out, long long ldo) { HIP_OK(spmm(e, A, n, Bv.p, Bv.ld, (const T *) NULL, 0, out, ldo, s)); };
     auto accumulate = [&]() {
         if (e->n_acc == 0 || n == 0) return;
         const int *acc_row = e->acc_dev, *acc_ptr = acc_row + e->n_acc, *acc_pos = acc_ptr + e->n_acc + 1;
-        HIP_OK(scatter_add(e->n_acc, n, acc_row, acc_ptr, acc_pos, (const T *) x.send, x.ld, Cd, ldCd, s));
+        HIP_OK(scatter_add(e->n_acc, n, acc_row, acc_ptr, acc_pos, (const T *) x.send, x.ld, Cv.p, Cv.ld, s));
     };
 
     if (timing) { HIP_OK(crp_stream_sync(s)); }
@@ -995,7 +843,7 @@ static void exec_t_impl(crp_rp_spmm *e, int BC_layout, const T *B, long long ldB
         // the exchange on its own stream beside the local product, which is enqueued first (see exec_impl)
         if (e->At_rem != nullptr) product(e->At_rem, (T *) x.recv, x.ld);
         HIP_OK(crp_event_record(e->ev_packed, s));
-        product(e->At_loc, Cd, ldCd);
+        product(e->At_loc, Cv.p, Cv.ld);
         HIP_OK(crp_stream_wait_event(e->xstream, e->ev_packed));
         reverse_exchange(e->xstream);
         HIP_OK(crp_event_record(e->ev_landed, e->xstream));
@@ -1015,40 +863,17 @@ static void exec_t_impl(crp_rp_spmm *e, int BC_layout, const T *B, long long ldB
         lap(&e->t_spmm);
         if (e->nproc > 1) reverse_exchange(s);
         lap(&e->t_a2a);
-        product(e->At_loc, Cd, ldCd);
+        product(e->At_loc, Cv.p, Cv.ld);
         lap(&e->t_spmm);
         accumulate();
         lap(&e->t_unpack);
     }
-    if (BC_layout == 1 && mc > 0 && n > 0)
-    {
-        T *Ccm = C;
-        if (!C_on_dev) Ccm = grow_as<T>(&e->C_stage, &e->C_stage_sz, (size_t) n * (size_t) ldC);
-        HIP_OK(transpose(mc, n, Cd, n, Ccm, ldC, s));
-        Cd = Ccm;
-    }
-    if (timing)
-    {
+    const bool synced = crp::finish(Cv, s, [&] {
+        if (!timing) return;
         HIP_OK(crp_stream_sync(s));
         e->t_spmm += get_wtime_sec() - t0;
-    }
-
-    if (!C_on_dev && mc > 0 && n > 0)
-    {
-        const size_t w = (BC_layout == 0) ? (size_t) n : (size_t) mc, h = (BC_layout == 0) ? (size_t) mc : (size_t) n;
-        HIP_OK(crp_dev_memcpy2d(C, (size_t) ldC * sizeof(T), Cd, (size_t) ldC * sizeof(T), w * sizeof(T), h, 1, s));
-        HIP_OK(crp_stream_sync(s));
-    }
-    else if (!B_on_dev || timing)
-    {
-        HIP_OK(crp_stream_sync(s));
-    }
-    else
-    {
-        if (e->ev_exec == nullptr) HIP_OK(crp_event_create(&e->ev_exec));
-        HIP_OK(crp_event_record(e->ev_exec, s));
-        e->exec_pending = true;
-    }
+    });
+    complete(e, s, synced, !B_on_dev || timing);
     e->t_exec += get_wtime_sec() - t_begin;
     e->n_exec++;
 }
@@ -1102,9 +927,8 @@ void crp_rp_spmm_exec(crp_rp_spmm_p e, int BC_layout, const double *B, int ldB, 
     void *s = e ? e->stream : NULL;
     if (e != NULL && !e->plan_only)
     {
-        int bd = 0, cd = 0;
-        if (B == e->last_B && B != NULL) bd = e->last_B_dev; else crp_dev_ptr_is_device(B, &bd);
-        if (C == e->last_C && C != NULL) cd = e->last_C_dev; else crp_dev_ptr_is_device(C, &cd);
+        // (this fills the cache the exec below reads)
+        const bool bd = on_device(B, &e->last_B, &e->last_B_dev), cd = on_device(C, &e->last_C, &e->last_C_dev);
         if (bd || cd) s = NULL;
     }
     crp_rp_spmm_exec_ex(e, BC_layout, B, (long long) ldB, C, (long long) ldC, s);

@@ -118,6 +118,19 @@ def _dev_vals(vals, nnz):
     return vals.data_ptr() or None, int(vals.dtype == torch.float32), vals
 
 
+def _check_blocks(layout, n, blocks):
+    """ValueError unless every (name, operand, rows) is a rows x n block (layout 1: (n, ld >= rows)): the kernels index the
+    operands by the plan's sizes, a wrong shape would be an out-of-bounds device access.  rows None: not known, not checked."""
+    for name, x, rows in blocks:
+        if rows is None:
+            continue
+        want = (rows, n) if layout == 0 else (n, rows)
+        got = tuple(x.shape)
+        if (layout == 0 and (got[0] < want[0] or got[1] != want[1])) or \
+           (layout == 1 and (got[0] != want[0] or got[1] < want[1])):
+            raise ValueError("%s has shape %s, the engine needs %s (layout %d)" % (name, got, want, layout))
+
+
 def _current_stream(x):
     try:
         import torch
@@ -166,19 +179,19 @@ class RpSpmm:
         f32 = _operands_dtype(B, C_out) == "f32"
         bp, ldb, _kb = _ptr_ld(B, BC_layout, f32)
         cp, ldc, _kc = _ptr_ld(C_out, BC_layout, f32)
-        # the kernels index the operands by the plan's sizes: a wrong shape would be an out-of-bounds device access
-        kb = getattr(self, "loc_B_nrow", None)
-        for name, x, rows in (("B", B, kb), ("C", C_out, self.A_nrow)):
-            if rows is None:
-                continue
-            want = (rows, self.glb_n) if BC_layout == 0 else (self.glb_n, rows)
-            got = tuple(x.shape)
-            if (BC_layout == 0 and (got[0] < want[0] or got[1] != want[1])) or \
-               (BC_layout == 1 and (got[0] != want[0] or got[1] < want[1])):
-                raise ValueError("%s has shape %s, the engine needs %s (layout %d)" % (name, got, want, BC_layout))
+        _check_blocks(BC_layout, self.glb_n, (("B", B, getattr(self, "loc_B_nrow", None)), ("C", C_out, self.A_nrow)))
         if stream is None:
             stream = _current_stream(C_out)
         fn = self._lib.crp_rp_spmm_exec_f32_ex if f32 else self._lib.crp_rp_spmm_exec_ex
+        fn(self.handle, BC_layout, bp, ldb, cp, ldc, stream)
+
+    def _exec_t(self, f32, BC_layout, B, C_out, stream):
+        bp, ldb, _kb = _ptr_ld(B, BC_layout, f32)
+        cp, ldc, _kc = _ptr_ld(C_out, BC_layout, f32)
+        _check_blocks(BC_layout, self.glb_n, (("B", B, self.A_nrow), ("C", C_out, getattr(self, "loc_B_nrow", None))))
+        if stream is None:
+            stream = _current_stream(C_out)
+        fn = self._lib.crp_rp_spmm_exec_t_f32_ex if f32 else self._lib.crp_rp_spmm_exec_t_ex
         fn(self.handle, BC_layout, bp, ldb, cp, ldc, stream)
 
     def exec_t(self, BC_layout, B, C_out, stream=None):
@@ -187,37 +200,13 @@ class RpSpmm:
         ``exec``.  The first call builds the transposed device matrices (``transposed_built``)."""
         if _operands_dtype(B, C_out) != "f64":
             raise TypeError("exec_t is fp64 only: B and C must be float64")
-        bp, ldb, _kb = _ptr_ld(B, BC_layout)
-        cp, ldc, _kc = _ptr_ld(C_out, BC_layout)
-        for name, x, rows in (("B", B, self.A_nrow), ("C", C_out, getattr(self, "loc_B_nrow", None))):
-            if rows is None:
-                continue
-            want = (rows, self.glb_n) if BC_layout == 0 else (self.glb_n, rows)
-            got = tuple(x.shape)
-            if (BC_layout == 0 and (got[0] < want[0] or got[1] != want[1])) or \
-               (BC_layout == 1 and (got[0] != want[0] or got[1] < want[1])):
-                raise ValueError("%s has shape %s, the engine needs %s (layout %d)" % (name, got, want, BC_layout))
-        if stream is None:
-            stream = _current_stream(C_out)
-        self._lib.crp_rp_spmm_exec_t_ex(self.handle, BC_layout, bp, ldb, cp, ldc, stream)
+        self._exec_t(False, BC_layout, B, C_out, stream)
 
     def exec_t_f32(self, BC_layout, B, C_out, stream=None):
         """C := A^T * B in fp32 (crp_rp_spmm_exec_t_f32_ex): float32 operands only, shapes and layouts as ``exec_t``.  The
         transposed device matrices are the ones ``exec_t`` builds; whichever is called first builds them."""
         _f32_operands(B, C_out)
-        bp, ldb, _kb = _ptr_ld(B, BC_layout, True)
-        cp, ldc, _kc = _ptr_ld(C_out, BC_layout, True)
-        for name, x, rows in (("B", B, self.A_nrow), ("C", C_out, getattr(self, "loc_B_nrow", None))):
-            if rows is None:
-                continue
-            want = (rows, self.glb_n) if BC_layout == 0 else (self.glb_n, rows)
-            got = tuple(x.shape)
-            if (BC_layout == 0 and (got[0] < want[0] or got[1] != want[1])) or \
-               (BC_layout == 1 and (got[0] != want[0] or got[1] < want[1])):
-                raise ValueError("%s has shape %s, the engine needs %s (layout %d)" % (name, got, want, BC_layout))
-        if stream is None:
-            stream = _current_stream(C_out)
-        self._lib.crp_rp_spmm_exec_t_f32_ex(self.handle, BC_layout, bp, ldb, cp, ldc, stream)
+        self._exec_t(True, BC_layout, B, C_out, stream)
 
     def sddmm(self, BC_layout, X, Y, out, mode=0, stream=None):
         """Sampled dense-dense product over this rank's rows of A (crp_rp_spmm_sddmm_ex / _f32_ex, by the operands' dtype):
@@ -231,14 +220,7 @@ class RpSpmm:
             raise ValueError("mode must be 0 or 1, got %r" % (mode,))
         xp, ldx, _kx = _ptr_ld(X, BC_layout, f32)
         yp, ldy, _ky = _ptr_ld(Y, BC_layout, f32)
-        for name, x, rows in (("X", X, self.A_nrow), ("Y", Y, getattr(self, "loc_B_nrow", None))):
-            if rows is None:
-                continue
-            want = (rows, self.glb_n) if BC_layout == 0 else (self.glb_n, rows)
-            got = tuple(x.shape)
-            if (BC_layout == 0 and (got[0] < want[0] or got[1] != want[1])) or \
-               (BC_layout == 1 and (got[0] != want[0] or got[1] < want[1])):
-                raise ValueError("%s has shape %s, the engine needs %s (layout %d)" % (name, got, want, BC_layout))
+        _check_blocks(BC_layout, self.glb_n, (("X", X, self.A_nrow), ("Y", Y, getattr(self, "loc_B_nrow", None))))
         op, _ko = _out_ptr(out, f32, self.nnz())
         if stream is None:
             stream = _current_stream(out)
@@ -388,16 +370,6 @@ class Para2dSpmm:
         fn = self._lib.crp_para2d_spmm_exec_f32_ex if f32 else self._lib.crp_para2d_spmm_exec_ex
         fn(self.handle, BC_layout, bp, ldb, cp, ldc, stream)
 
-    def _check_blocks(self, layout, blocks):
-        """ValueError unless every (name, operand, rows) is a rows x n_loc block (layout 1: (n_loc, ld >= rows)): the kernels
-        index the operands by the plan's sizes, a wrong shape would be an out-of-bounds device access."""
-        for name, x, rows in blocks:
-            want = (rows, self.rp.glb_n) if layout == 0 else (self.rp.glb_n, rows)
-            got = tuple(x.shape)
-            if (layout == 0 and (got[0] < want[0] or got[1] != want[1])) or \
-               (layout == 1 and (got[0] != want[0] or got[1] < want[1])):
-                raise ValueError("%s has shape %s, the engine needs %s (layout %d)" % (name, got, want, layout))
-
     def update_values(self, A_val):
         """New values for the same pattern (crp_para2d_spmm_update_values): this rank's A0 slice values in the order given to
         init.  Collective over the grid row -- the first call of an engine with pn > 1 over the whole grid."""
@@ -408,27 +380,26 @@ class Para2dSpmm:
             va = np.zeros(1, np.float64)
         self._lib.crp_para2d_spmm_update_values(self.handle, _dp(va))
 
+    def _exec_t(self, f32, BC_layout, B, C_out, stream):
+        bp, ldb, _kb = _ptr_ld(B, BC_layout, f32)
+        cp, ldc, _kc = _ptr_ld(C_out, BC_layout, f32)
+        _check_blocks(BC_layout, self.rp.glb_n, (("B", B, self.rp.A_nrow), ("C", C_out, self.loc_B_nrow)))
+        if stream is None:
+            stream = _current_stream(C_out)
+        fn = self._lib.crp_para2d_spmm_exec_t_f32_ex if f32 else self._lib.crp_para2d_spmm_exec_t_ex
+        fn(self.handle, BC_layout, bp, ldb, cp, ldc, stream)
+
     def exec_t(self, BC_layout, B, C_out, stream=None):
         """C := A^T * B (crp_para2d_spmm_exec_t_ex), fp64 only: B is this rank's (panel rows) x n_loc block, C_out its
         (B_rowptr block of grid row pi) x n_loc block; layouts and operands as ``exec``."""
         if _operands_dtype(B, C_out) != "f64":
             raise TypeError("exec_t is fp64 only: B and C must be float64")
-        bp, ldb, _kb = _ptr_ld(B, BC_layout)
-        cp, ldc, _kc = _ptr_ld(C_out, BC_layout)
-        self._check_blocks(BC_layout, (("B", B, self.rp.A_nrow), ("C", C_out, self.loc_B_nrow)))
-        if stream is None:
-            stream = _current_stream(C_out)
-        self._lib.crp_para2d_spmm_exec_t_ex(self.handle, BC_layout, bp, ldb, cp, ldc, stream)
+        self._exec_t(False, BC_layout, B, C_out, stream)
 
     def exec_t_f32(self, BC_layout, B, C_out, stream=None):
         """C := A^T * B in fp32 (crp_para2d_spmm_exec_t_f32_ex): float32 operands only, blocks and layouts as ``exec_t``."""
         _f32_operands(B, C_out)
-        bp, ldb, _kb = _ptr_ld(B, BC_layout, True)
-        cp, ldc, _kc = _ptr_ld(C_out, BC_layout, True)
-        self._check_blocks(BC_layout, (("B", B, self.rp.A_nrow), ("C", C_out, self.loc_B_nrow)))
-        if stream is None:
-            stream = _current_stream(C_out)
-        self._lib.crp_para2d_spmm_exec_t_f32_ex(self.handle, BC_layout, bp, ldb, cp, ldc, stream)
+        self._exec_t(True, BC_layout, B, C_out, stream)
 
     def update_values_dev(self, vals, stream=None):
         """New values from device memory (crp_para2d_spmm_update_values_dev): a 1-D contiguous float64 or float32 CUDA tensor of
@@ -451,7 +422,7 @@ class Para2dSpmm:
             raise ValueError("mode must be 0 or 1, got %r" % (mode,))
         xp, ldx, _kx = _ptr_ld(X, BC_layout, f32)
         yp, ldy, _ky = _ptr_ld(Y, BC_layout, f32)
-        self._check_blocks(BC_layout, (("X", X, self.rp.A_nrow), ("Y", Y, self.loc_B_nrow)))
+        _check_blocks(BC_layout, self.rp.glb_n, (("X", X, self.rp.A_nrow), ("Y", Y, self.loc_B_nrow)))
         op, _ko = _out_ptr(out, f32, self.slice_nnz)
         if stream is None:
             stream = _current_stream(out)

@@ -286,15 +286,17 @@ int crp_spmm_variant_count(void);
  * (the fp32 form multiplies by the fp32 copy of the value, derived on first use and kept current by
  * crp_csr_dev_update_values).  Row-major operands: X has a row per row of A (row rowmap[t] for row t of a handle with a
  * row map, crp_csr_dev_set_rowmap), Y0 / Y1 are the two sources of the column code (c >= 0: row c of Y0, c < 0: row ~c
- * of Y1; Y1 may be NULL when no code is negative).  Nonzero p of the handle writes out[out_pos[p]] (out_pos: device
+ * of Y1; a source no code names may be NULL -- Y0 when every code is negative or A has no nonzero, Y1 when none is -- and
+ * its leading dimension is then not read).  Nonzero p of the handle writes out[out_pos[p]] (out_pos: device
  * int32 array of nnz entries), out[p] when out_pos is NULL: nnz entries, or the entries out_pos names, and nothing
  * else.  p counts in the handle's own CSR order -- for a handle made by crp_csr_dev_create the order of the values
  * given at create, which is the order crp_csr_dev_update_values takes, so out may be passed to it as it is; for a
  * handle made by crp_csr_dev_create_t the order of the transposed arrays.  Only pairs of the pattern are formed: a Y
  * row no column names and the X row of an empty row are never read.  All pointers are device pointers; the launch is
  * asynchronous on `stream`.  Returns 0, a HIP error (> 0), or a negative argument error, before which nothing is
- * written: -1 for a NULL handle, X, Y0 or out, for Y1 = NULL on a handle with negative codes, for n < 1 and for a mode
- * other than 0 or 1; -4 for a leading dimension below n.
+ * written: -1 for a NULL handle, X or out, for Y0 = NULL on a handle with a code >= 0, for Y1 = NULL on a handle with
+ * negative codes, for n < 1 and for a mode other than 0 or 1; -4 for a leading dimension below n (of X, or of a source
+ * that is not NULL).
  * Fixed order: column j belongs to lane (j / W) % L of a group of L lanes (W = elements per 16 bytes; L = 8, 16, 32 or
  * 64, picked from n), every lane adds its products in ascending j with FMAs, and the lanes' sums meet in the balanced
  * binary tree over the lane number.  Assignment and tree are a function of (dtype, n) ONLY -- not of operand alignment

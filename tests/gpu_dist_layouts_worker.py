@@ -2,6 +2,8 @@
 engines on N ranks, on the rank layouts no other test runs -- a rank without rows of A, a rank without rows of B, a rank that
 sends but receives nothing, a rectangular A whose B partition has nothing to do with its row partition -- with odd widths and
 padded, misaligned operands, on data whose product has ONE correct bit pattern (fp64_ref.exact_parts, fp32_ref.exact_problem32).
+On the partitions with a rank that owns no row of A or of B (b, c, d) the row-parallel engine's transposed product and SDDMM run
+too, at two widths, on exact data of their own (Data.exact_t_sets, Data.sddmm_set).
 
   (no argument)  on the GPU: N ranks sharing one card with the exchange staged through the host, or a GPU per rank and RCCL
   --plan-only    on the CPU over gloo: plan() against oracle.rp_plan_all and the emulated product of tests/dist_worker.py
@@ -19,6 +21,9 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 WIDTHS = (1, 7, 24, 33)          # scalar path; odd; a multiple of 4; odd and two 16-column pieces (fp32 ld32 != n for 1, 7, 33)
 SENT = -7.0                      # what every element around an operand holds
+T_WIDTHS = (7, 33)               # exec_t and sddmm: the widths ...
+T_LAYOUTS = ("b", "c", "d")      # ... the partitions ...
+T_FORMS = (("dev", 0, 1, 1), ("dev", 1, 3, 0), ("host", 1, 3, 0))        # ... and the operand forms they run on
 
 
 def matrices(gen):
@@ -108,6 +113,63 @@ class Data:
         """[(what, val64, B, C_exact)] -- fp64 with the wide integers in A, in B, and fp32."""
         a, b = self.exact64(n, "A"), self.exact64(n, "B")
         return [("f64 wide=A", a.val, a.B, a.C_exact), ("f64 wide=B", b.val, b.B, b.C_exact), ("f32",) + self.exact32(n)]
+
+    def transposed(self):
+        """(rowptr, colidx, order) of the transposed pattern, from a stable argsort of the column indices (np_transpose of
+        tests/gpu_dist_t_worker.py): nonzero q of the transposed pattern is nonzero order[q] of A."""
+        def make():
+            order = np.argsort(self.ci, kind="stable")
+            rows = np.repeat(np.arange(self.m, dtype=np.int32), np.diff(self.rp))
+            rp_t = np.concatenate([[0], np.cumsum(np.bincount(self.ci, minlength=self.k))]).astype(np.int32)
+            return rp_t, rows[order].astype(np.int32), order
+        return self._get("t", make)
+
+    def exact_t_sets(self, n):
+        """[(what, val64 in A's order, B (m x n), C_exact (k x n))] for C = A^T B: the exact generators run on the TRANSPOSED pattern
+        (their budgets follow its rows, A's columns), the values are carried back to A's order -- fp64 wide in A, in B, and fp32."""
+        import fp32_ref
+        import fp64_ref
+
+        def make():
+            rp_t, ci_t, order = self.transposed()
+
+            def back(v_t):
+                v = np.empty_like(v_t)
+                v[order] = v_t
+                return v
+            out = []
+            for i, wide in enumerate("AB"):
+                x = fp64_ref.exact_parts(rp_t, ci_t, self.m, n, np.random.default_rng(self.seed + 1000 * n + 11 + i), wide)
+                out.append(("exec_t f64 wide=" + wide, back(x.val), x.B, x.C_exact))
+            v, B, C = fp32_ref.exact_problem32(rp_t, ci_t, self.m, n, np.random.default_rng(self.seed + 1000 * n + 13))
+            return out + [("exec_t f32", back(v), B, C)]
+        return self._get(("xt", n), make)
+
+    def sddmm_set(self, n):
+        """(val, X (m x n), Y (k x n), out0, out1) as float64, every number exact in fp32 too: X = 2^rx X0 and Y = 2^ry Y0 by rows,
+        X0 and Y0 integers of magnitude 1 .. 255, exponents in [-8, 8], val = +-2^e with e in [-8, 8].  Every dot is an integer
+        below n 255^2 < 2^22 times a power of two -- exact in fp32 and fp64 in any order, fused or not -- and so is its product
+        with val: out0 (mode 0) and out1 (mode 1) are computed here in integers, never by the library."""
+        def make():
+            rng = np.random.default_rng(self.seed + 1000 * n + 17)
+            nnz = int(self.rp[-1])
+            ints = lambda shape: rng.integers(1, 256, size=shape) * (2 * rng.integers(0, 2, size=shape) - 1)
+            X0, Y0 = ints((self.m, n)), ints((self.k, n))
+            rx, ry = rng.integers(-8, 9, size=self.m), rng.integers(-8, 9, size=self.k)
+            val = np.ldexp((2.0 * rng.integers(0, 2, size=nnz) - 1.0), rng.integers(-8, 9, size=nnz).astype(np.int32))
+            rows, cols = np.repeat(np.arange(self.m), np.diff(self.rp)), self.ci[:nnz]
+            assert np.abs(X0).max() <= 255 and np.abs(Y0).max() <= 255 and n * 255 * 255 < 2 ** 22, "exact SDDMM budget exceeded"
+            D0 = np.einsum("pj,pj->p", X0[rows], Y0[cols])
+            assert D0.dtype == np.int64 and (np.abs(D0) < 2 ** 22).all()
+            X = np.ldexp(X0.astype(np.float64), rx.astype(np.int32)[:, None])
+            Y = np.ldexp(Y0.astype(np.float64), ry.astype(np.int32)[:, None])
+            out0 = np.ldexp(D0.astype(np.float64), (rx[rows] + ry[cols]).astype(np.int32))
+            out1 = out0 * val
+            tiny = float(np.finfo(np.float32).tiny)
+            for a in (val, X, Y, out0, out1):
+                assert np.array_equal(a.astype(np.float32).astype(np.float64), a) and (np.abs(a[a != 0]) >= tiny).all(), "not exact in fp32"
+            return val, X, Y, out0, out1
+        return self._get(("sd", n), make)
 
 
 def bits(x):
@@ -247,6 +309,38 @@ def check_exact(torch, dev, call, set_timing, form, Bl, C_want, m, n, tag, reps=
     set_timing(True)
 
 
+def check_sddmm(torch, dev, eng, form, Xl, Yl, wants, tag):
+    """One operand form of the SDDMM, timing on and off, modes 0 and 1: `out` (on the device for device operands, on the host for
+    host operands; empty on a rank without nonzeros) bit for bit wants[mode], the elements around it and X and Y untouched."""
+    n, nnz = Xl.shape[1], wants[0].size
+    ox, oy = Operands(torch, dev, form, Xl, 0, n), Operands(torch, dev, form, Yl, 0, n)
+    for timing in (True, False):
+        eng.set_timing(timing)
+        for mode in (0, 1):
+            t = tag + (form, timing, mode)
+            if form[0] == "dev":
+                buf = torch.full((nnz + 2,), SENT, dtype=ox.B_dev.dtype, device=dev)
+                out = buf[1:1 + nnz] if nnz > 0 else torch.empty(0, dtype=buf.dtype, device=dev)
+            else:
+                buf = np.full(nnz + 2, SENT, dtype=Xl.dtype)
+                out = buf[1:1 + nnz]
+            eng.sddmm(ox.layout, ox.B, oy.B, out, mode)
+            if form[0] == "dev":
+                torch.cuda.synchronize()
+                buf = buf.cpu().numpy()
+                for o in (ox, oy):
+                    assert np.array_equal(bits(o.B_dev.cpu().numpy()), bits(o.B_before)), t + ("an operand was written",)
+            else:
+                assert np.array_equal(bits(ox.B_buf), bits(ox.B_before)) and np.array_equal(bits(oy.B_buf), bits(oy.B_before)), t
+            assert buf[0] == SENT and buf[-1] == SENT, t + ("an element outside out was written",)
+            got, want = buf[1:1 + nnz], wants[mode]
+            if not np.array_equal(bits(got), bits(want)):
+                bad = np.flatnonzero(bits(got) != bits(want))
+                raise AssertionError("%r: %d of %d entries differ from the exact SDDMM, first at %d: got %r, want %r"
+                                     % (t, bad.size, nnz, bad[0], got[bad[0]], want[bad[0]]))
+    eng.set_timing(True)
+
+
 def gpu_main():
     import torch
     import torch.distributed as dist
@@ -294,6 +388,24 @@ def gpu_main():
                     Bl = np.ascontiguousarray(B[bs:be])
                     for form in forms(n):
                         check_exact(torch, dev, eng.exec, eng.set_timing, form, Bl, C_exact[s:e], e - s, n, tag)
+                # ---- the transposed product and the SDDMM where a rank owns no row of A or of B: this rank's loc_B_nrow x n block of
+                #      C = A^T B bit for bit (B has A's rows), `out` over this rank's nonzeros bit for bit; timing on once, off once
+                if letter in T_LAYOUTS and n in T_WIDTHS:
+                    for what, val, B, C_exact in data.exact_t_sets(n):
+                        eng.update_values(val[mine])
+                        call = eng.exec_t_f32 if B.dtype == np.float32 else eng.exec_t
+                        for form in T_FORMS:
+                            check_exact(torch, dev, call, eng.set_timing, form, np.ascontiguousarray(B[s:e]), C_exact[bs:be], be - bs, n,
+                                        (me, name, letter, n, what), reps=1)
+                    val, X, Y, out0, out1 = data.sddmm_set(n)
+                    eng.update_values(val[mine])
+                    # a rank without rows of B also passes what it has at hand for Y: an empty tensor, whose pointer is NULL (every rank
+                    # runs that form when one has no rows: each call is an exchange all ranks take part in)
+                    sd_forms = T_FORMS + ((("dev", 0, 0, 0),) if (np.diff(rb) == 0).any() else ())
+                    for dt in (np.float64, np.float32):
+                        for form in sd_forms:
+                            check_sddmm(torch, dev, eng, form, np.ascontiguousarray(X[s:e], dtype=dt), np.ascontiguousarray(Y[bs:be], dtype=dt),
+                                        (out0[mine].astype(dt), out1[mine].astype(dt)), (me, name, letter, n, "sddmm", np.dtype(dt).name))
                 # ---- one multi-scale rounded case per matrix and partition: every entry of the rank's rows within the derived bound
                 if n in (7, 24):
                     val, B, (ref, bound) = data.rounded64(n)

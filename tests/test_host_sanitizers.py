@@ -1,5 +1,6 @@
 """CPU: the host half of the product (format builders, team scheduler, planner, ingest) compiled with
-AddressSanitizer + UBSan and driven by tests/host_asan.cpp (GPU sanitizers are not available on the pool)."""
+AddressSanitizer + UBSan and driven by tests/host_asan.cpp, and the engines' operand layer (csrc/operand_view.h) over host stand-ins for the device ABI, driven by
+tests/host_operand_view.cpp (GPU sanitizers are not available on the pool)."""
 import os
 import shutil
 import subprocess
@@ -24,3 +25,17 @@ def test_host_code_under_asan_ubsan(tmp_path):
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", CRPSPMM_NUM_THREADS="4", CRPSPMM_SYNC_RELEASE="1")
     r = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0 and "HOST_ASAN_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
+
+
+def test_operand_view_under_asan_ubsan(tmp_path):
+    gxx = shutil.which("g++")
+    if gxx is None:
+        pytest.skip("no g++")
+    exe = str(tmp_path / "host_operand_view")
+    cmd = [gxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+           "-fno-omit-frame-pointer", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "crp-spmm_amd", "csrc"),
+           os.path.join(ROOT, "tests", "host_operand_view.cpp"), "-o", exe]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0"))
+    assert r.returncode == 0 and "HOST_OPERAND_VIEW_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
