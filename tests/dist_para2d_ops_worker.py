@@ -25,15 +25,14 @@ def _ll(a):
 
 
 def partial_dots(plan, col_comm, X_loc, Y_loc, n_loc, mode):
-    """The inner engine's SDDMM over n_loc columns (the replay of tests/dist_sddmm_worker.py): one value per panel nonzero."""
+    """The inner engine's SDDMM over n_loc columns (the replay of tests/dist_sddmm_worker.py): one value per panel nonzero.  A rank
+    whose panel has no nonzeros still serves the exchange; a block without rows or without columns (n_loc == 0) gives zeros."""
     nnz = plan["A_colidx"].size
-    if nnz == 0:
-        return np.zeros(0)
     code = plan["dev_colidx"].astype(np.int64)
     rows = np.repeat(np.arange(plan["A_nrow"]), np.diff(plan["A_rowptr"]))
+    Y1 = np.zeros((0, n_loc))
     if col_comm is None:                                         # one grid row: every column of the panel is local
         assert (code >= 0).all()
-        yrows = Y_loc[code]
     else:
         P = plan["nproc"]
         send = np.ascontiguousarray(Y_loc[plan["rB_sridxs"], :n_loc]).reshape(-1)
@@ -43,21 +42,26 @@ def partial_dots(plan, col_comm, X_loc, Y_loc, n_loc, mode):
         recv = np.full(max(nrecv, 1), np.nan)
         sc, sd, rc, rd = (np.ascontiguousarray(plan[k], dtype=np.int64) for k in ("rB_scnts", "rB_sdispls", "rB_rcnts", "rB_rdispls"))
         col_comm.struct.alltoallv_dev_f64(None, send.ctypes.data, _ll(sc), _ll(sd), recv.ctypes.data, _ll(rc), _ll(rd), None)
-        Y1 = recv[:nrecv].reshape(-1, n_loc)
-        yrows = np.where((code >= 0)[:, None], Y_loc[np.where(code >= 0, code, 0)], Y1[np.where(code < 0, ~code, 0)] if nrecv else 0.0)
+        Y1 = recv[:nrecv].reshape(nrecv // n_loc if n_loc else 0, n_loc)
+    if nnz == 0:
+        return np.zeros(0)
+    loc = code >= 0
+    yrows = np.zeros((nnz, n_loc))
+    yrows[loc] = Y_loc[code[loc]]
+    yrows[~loc] = Y1[~code[~loc]]
     out = np.einsum("ij,ij->i", X_loc[rows], yrows)
     return out * plan["A_val"] if mode else out
 
 
-def reduce_scatter(row_comm, part, row_nnz, pj):
+def reduce_scatter(row_comm, part, row_nnz, pj, starts=None):
     """Peer j is sent the run [off_j, off_j + nnz_j) of `part`; this rank receives pn runs of its own slice, added in
-    ascending grid column."""
+    ascending grid column.  starts: where the runs are read from instead of off (a negative control's wrong offsets)."""
     pn = row_nnz.size
     off = np.concatenate([[0], np.cumsum(row_nnz)]).astype(np.int64)
     mine = int(row_nnz[pj])
     recv = np.full(max(pn * mine, 1), np.nan)
     send = part if part.size else np.zeros(1)
-    sc, sd = row_nnz.astype(np.int64), off[:pn].copy()
+    sc, sd = row_nnz.astype(np.int64), (off[:pn].copy() if starts is None else np.ascontiguousarray(starts, dtype=np.int64))
     rc, rd = np.full(pn, mine, np.int64), np.arange(pn, dtype=np.int64) * mine
     row_comm.struct.alltoallv_dev_f64(None, send.ctypes.data, _ll(sc), _ll(sd), recv.ctypes.data, _ll(rc), _ll(rd), None)
     seg = recv[:pn * mine].reshape(pn, mine)
