@@ -100,8 +100,7 @@ void lattice_coords(int panel, int R, double D1, double D2, int M, int *i, int *
 // consecutive panels.  The union of the four panels' columns is stored once (tcol), with one mask
 // word per union entry: byte w = row mask of wave w (0 = wave w does not use the column).  The
 // order of the union entries is a balanced schedule, not column order (see build_teams); wave w
-// reads the 8 values of its k-th own entry from the value stream starting at entry tvoff[4g + w]
-// (tq maps every entry of the panel format to its place in the streams).
+// reads the 8 values of its k-th own entry from the value stream starting at entry tvoff[4g + w].
 struct TeamHost
 {
     int nteam = 0;
@@ -116,7 +115,6 @@ struct TeamHost
     big_vector<uint32_t>  tmask;   // union entries: row masks of waves 0..3 (complete for T = 4 only)
     std::vector<int>      torder;  // processing order of the teams
     std::vector<long long> tvoff;  // T * nteam + 1: first entry of wave w's value stream
-    std::vector<long long> tq;     // per panel-format entry: its entry index in the value streams, or -1
     big_vector<int>       tsrc;    // T per union entry: the panel-format entry of wave w behind it, or -1
     long long real_entries = 0;    // union entries before padding
     std::vector<int>      lat_key; // lattice teams: 3 per team -- team column (a, b) and position t along the teeth (team_order.h, lattice_block_order)
@@ -132,11 +130,10 @@ struct TeamSeed
     std::vector<int> team_of, slot_of;     // clustered teams: team and slot of every panel
     std::vector<int> torder;
 };
-// colpos (optional, matrices in a locality order): position of row c of A in the order the panels were built on.
 // balanced = false: the union entries of a team stay in column order (the caller orders them itself).
 // T = 4 or 8 panels per team (anything else builds teams of 4).
-void build_teams(const PanelHost &p, int nrow, const int *rowptr, const int *colidx, TeamHost *out, int T = 4, const int *colpos = nullptr,
-                 bool balanced = true, TeamSeed *seed = nullptr);
+void build_teams(const PanelHost &p, int nrow, const int *rowptr, const int *colidx, TeamHost *out, int T = 4, bool balanced = true,
+                 TeamSeed *seed = nullptr);
 
 // Team schedule for the row-panel kernel itself (no LDS sharing): the entries of every panel are
 // re-ordered to the order in which its wave meets them in the team's balanced schedule, and the

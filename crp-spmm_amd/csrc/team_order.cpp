@@ -1,6 +1,6 @@
 // team_order.cpp -- processing order of lattice teams by search against an L2 model (team_order.h).
 // (The recursive bisection of the team graph of round 3 lived here; it was removed in round 4 with the generation barrier it
-//  served -- panel_format.cpp, build_teams.)
+//  served -- team_format.cpp, build_teams.)
 #include "team_order.h"
 #include <math.h>
 #include <stdint.h>

@@ -1,6 +1,6 @@
 // Host-side format builders, planner and ingest under AddressSanitizer / UBSan (CPU only; built and
 // run by tests/test_host_sanitizers.py).  No device code is linked: everything here is the host
-// half of the product (csrc/panel_format.cpp, spmat_part.cpp, mmio_utils.cpp, host_support.cpp).
+// half of the product (the format builders of csrc/, spmat_part.cpp, mmio_utils.cpp, host_support.cpp).
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>

@@ -2,7 +2,7 @@
 """Host-side model of the B-row traffic of the team2 kernel (variant 5): replays the dispatch of a format's teams
 over the 8 XCDs (workgroup i runs on XCD i % 8, `--wgs` workgroups resident per XCD, every resident team issues one
 round of 8 rows per time step) against one LRU of `--rows` B rows per XCD, and prints the rows that miss.
-A planning tool for the team order / union order (csrc/panel_format.cpp); measured counterparts: profiles/r02_traffic.json.
+A planning tool for the team order / union order (csrc/team_format.cpp, csrc/team2_format.cpp); measured counterparts: profiles/r02_traffic.json.
 
 usage: l2sim.py [--matrix pwtk|pwtk_shell|...] [--rows 1400] [--wgs 64] [--n 256]"""
 import argparse
@@ -36,7 +36,7 @@ def team_rounds(t):
 
 
 def xcd_queues(rounds, order, nxcd=8):
-    """The launch grid of build_team2 (csrc/panel_format.cpp): the order cut into pieces of equal rounds + 4 per team."""
+    """The launch grid of build_team2 (csrc/team2_format.cpp, xcd_cuts of csrc/team_stages.h): the order cut into pieces of equal rounds + 4 per team."""
     w = [len(rounds[g]) + 4 for g in order]
     total, acc, cuts, x = sum(w), 0, [0], 1
     for i, wi in enumerate(w):
