@@ -167,6 +167,14 @@ SIGNATURES = {
     "crp_spmm_csr_f64": (_I, [_V, _I, _I, _V, _LL, _V, _LL, _V, _LL, _I, _V]),
     "crp_sddmm_csr_f64": (_I, [_V, _I, _V, _LL, _V, _LL, _V, _LL, _V, _V, _I, _V]),
     "crp_sddmm_csr_f32": (_I, [_V, _I, _V, _LL, _V, _LL, _V, _LL, _V, _V, _I, _V]),
+    "crp_row_softmax_f64": (_I, [_I, _V, _V, _V, _V]),
+    "crp_row_softmax_f32": (_I, [_I, _V, _V, _V, _V]),
+    "crp_row_softmax_bwd_f64": (_I, [_I, _V, _V, _V, _V, _V]),
+    "crp_row_softmax_bwd_f32": (_I, [_I, _V, _V, _V, _V, _V]),
+    "crp_csr_dev_row_softmax_f64": (_I, [_V, _V, _V, _V]),
+    "crp_csr_dev_row_softmax_f32": (_I, [_V, _V, _V, _V]),
+    "crp_csr_dev_row_softmax_bwd_f64": (_I, [_V, _V, _V, _V, _V]),
+    "crp_csr_dev_row_softmax_bwd_f32": (_I, [_V, _V, _V, _V, _V]),
     "crp_spmm_variant_name": (C.c_char_p, [_I]),
     "crp_spmm_variant_count": (_I, []),
     "crp_gather_rows_f64": (_I, [_I, _I, _I, _V, _V, _LL, _V, _LL, _V]),
@@ -231,6 +239,9 @@ SIGNATURES = {
     "crp_rp_spmm_update_values": (None, [_V, c_dbl_p]),
     "crp_rp_spmm_update_values_dev": (None, [_V, _V, _I, _V]),
     "crp_rp_spmm_host_values_stale": (_I, [_V]),
+    "crp_rp_spmm_row_softmax_ex": (None, [_V, _V, _V, _I, _V]),
+    "crp_rp_spmm_row_softmax_bwd_ex": (None, [_V, _V, _V, _V, _I, _V]),
+    "crp_rp_spmm_row_softmax_built": (_I, [_V]),
     "crp_rp_spmm_nnz": (_LL, [_V]),
     "crp_rp_spmm_dev_colidx_host": (c_int_p, [_V]),
     "crp_para2d_spmm_init": (None, [C.POINTER(CrpComm), _I, _I, c_int_p, c_int_p, c_int_p, c_int_p, c_int_p, c_int_p,
@@ -248,6 +259,9 @@ SIGNATURES = {
     "crp_para2d_spmm_sddmm_ex": (None, [_V, _I, _V, _LL, _V, _LL, _V, _I, _V]),
     "crp_para2d_spmm_sddmm_f32_ex": (None, [_V, _I, _V, _LL, _V, _LL, _V, _I, _V]),
     "crp_para2d_spmm_sddmm_built": (_I, [_V]),
+    "crp_para2d_spmm_row_softmax_ex": (None, [_V, _V, _V, _I, _V]),
+    "crp_para2d_spmm_row_softmax_bwd_ex": (None, [_V, _V, _V, _V, _I, _V]),
+    "crp_para2d_spmm_row_softmax_built": (_I, [_V]),
     "crp_para2d_spmm_slice_nnz": (_LL, [_V]),
     "crp_para2d_spmm_row_slice_nnz": (_I, [_V, c_ll_p]),
     "crp_para2d_spmm_print_stat": (None, [_V]),

@@ -989,6 +989,64 @@ int crp_sddmm_csr_f32(crp_csr_dev_p A, int n, const float *X, long long ldX, con
     return sddmm_csr<float>(A, n, X, ldX, Y0, ldY0, Y1, ldY1, out, out_pos, mode, A->val32, s);
 }
 
+// ---- row softmax over a CSR pattern (softmax_kernels.hip).  Every argument is checked before anything is launched.
+int crp_row_softmax_f64(int nrow, const int *rowptr, const double *s, double *y, void *stream)
+{
+    if (nrow < 0) return -1;
+    if (nrow == 0) return 0;
+    if (rowptr == NULL || s == NULL || y == NULL) return -1;
+    return (int) crp::row_softmax_f64(nrow, rowptr, s, y, (hipStream_t) stream);
+}
+
+int crp_row_softmax_f32(int nrow, const int *rowptr, const float *s, float *y, void *stream)
+{
+    if (nrow < 0) return -1;
+    if (nrow == 0) return 0;
+    if (rowptr == NULL || s == NULL || y == NULL) return -1;
+    return (int) crp::row_softmax_f32(nrow, rowptr, s, y, (hipStream_t) stream);
+}
+
+int crp_row_softmax_bwd_f64(int nrow, const int *rowptr, const double *y, const double *dy, double *ds, void *stream)
+{
+    if (nrow < 0) return -1;
+    if (nrow == 0) return 0;
+    if (rowptr == NULL || y == NULL || dy == NULL || ds == NULL) return -1;
+    return (int) crp::row_softmax_bwd_f64(nrow, rowptr, y, dy, ds, (hipStream_t) stream);
+}
+
+int crp_row_softmax_bwd_f32(int nrow, const int *rowptr, const float *y, const float *dy, float *ds, void *stream)
+{
+    if (nrow < 0) return -1;
+    if (nrow == 0) return 0;
+    if (rowptr == NULL || y == NULL || dy == NULL || ds == NULL) return -1;
+    return (int) crp::row_softmax_bwd_f32(nrow, rowptr, y, dy, ds, (hipStream_t) stream);
+}
+
+// the handle forms: the handle's own device row pointer (its CSR order, as crp_sddmm_csr_*)
+int crp_csr_dev_row_softmax_f64(crp_csr_dev_p A, const double *s, double *y, void *stream)
+{
+    if (A == NULL) return -1;
+    return crp_row_softmax_f64(A->nrow, A->rowptr, s, y, stream);
+}
+
+int crp_csr_dev_row_softmax_f32(crp_csr_dev_p A, const float *s, float *y, void *stream)
+{
+    if (A == NULL) return -1;
+    return crp_row_softmax_f32(A->nrow, A->rowptr, s, y, stream);
+}
+
+int crp_csr_dev_row_softmax_bwd_f64(crp_csr_dev_p A, const double *y, const double *dy, double *ds, void *stream)
+{
+    if (A == NULL) return -1;
+    return crp_row_softmax_bwd_f64(A->nrow, A->rowptr, y, dy, ds, stream);
+}
+
+int crp_csr_dev_row_softmax_bwd_f32(crp_csr_dev_p A, const float *y, const float *dy, float *ds, void *stream)
+{
+    if (A == NULL) return -1;
+    return crp_row_softmax_bwd_f32(A->nrow, A->rowptr, y, dy, ds, stream);
+}
+
 int crp_csr_dev_auto_variant(crp_csr_dev_p A) { return A ? A->traits.auto_variant : -1; }
 int crp_csr_dev_reordered(crp_csr_dev_p A) { return A ? (A->ord.perm.empty() ? 0 : 1) : -1; }
 int crp_csr_dev_resolved_variant(crp_csr_dev_p A, int n)      // (an aligned operand of ld = n without B1)

@@ -144,6 +144,12 @@ hipError_t spmm_rm_f32_rowgroup(const SpmmArgsF32 &a, hipStream_t s);
 hipError_t sddmm_rm_f64(const SddmmArgs<double> &a, hipStream_t s);
 hipError_t sddmm_rm_f32(const SddmmArgs<float> &a, hipStream_t s);
 
+// softmax_kernels.hip: row softmax over a CSR pattern and its Jacobian product; rowptr entries index the value arrays directly
+hipError_t row_softmax_f64(int nrow, const int *rowptr, const double *s, double *y, hipStream_t st);
+hipError_t row_softmax_f32(int nrow, const int *rowptr, const float *s, float *y, hipStream_t st);
+hipError_t row_softmax_bwd_f64(int nrow, const int *rowptr, const double *y, const double *dy, double *ds, hipStream_t st);
+hipError_t row_softmax_bwd_f32(int nrow, const int *rowptr, const float *y, const float *dy, float *ds, hipStream_t st);
+
 // row_kernels.hip
 hipError_t gather_rows_f64(int layout, int nidx, int n, const int *ridx, const double *src, int64_t lds,
                            double *dst, int64_t ldd, hipStream_t s);

@@ -47,6 +47,9 @@ struct crp_para2d_spmm
     bool   sd_built64 = false, sd_built32 = false;
     void  *dv_panel = nullptr;             // update_values_dev: the panel's values as gathered (sized for fp64)
     std::vector<char> dv_host;             // ... staged on the host when the communicator has no allgatherv_dev
+    // ---- row softmax over the slice (pn > 1): the slice's own row pointer from 0, kept by init; on the device from the first call
+    std::vector<int> slice_rowptr;
+    int   *sm_rowptr = nullptr;
 };
 
 
@@ -278,6 +281,11 @@ static void para2d_init_common(crp_comm_t *comm, int pm, int pn, const int *A0_r
         e->row_nnz.assign(1, my_nnz);
     }
     e->pn = pn; e->pi = pi; e->pj = pj;
+    if (pn > 1)
+    {
+        e->slice_rowptr.resize((size_t) my_nrow + 1);
+        for (int i = 0; i <= my_nrow; i++) e->slice_rowptr[i] = A_rowptr[i] - A_rowptr[0];
+    }
     e->row_off.assign((size_t) pn + 1, 0);
     for (int j = 0; j < pn; j++) e->row_off[j + 1] = e->row_off[j] + e->row_nnz[j];
     e->t_ag_A += get_wtime_sec() - t0;
@@ -341,6 +349,7 @@ void crp_para2d_spmm_free(crp_para2d_spmm_p *p)
     if (e->sd_out) crp_dev_free(e->sd_out);
     if (e->sd_send32) crp_dev_free(e->sd_send32);
     if (e->dv_panel) crp_dev_free(e->dv_panel);
+    if (e->sm_rowptr) crp_dev_free(e->sm_rowptr);
     delete e;
     *p = NULL;
 }
@@ -447,6 +456,61 @@ void crp_para2d_spmm_sddmm_f32_ex(crp_para2d_spmm_p e, int layout, const float *
                                   float *out, int mode, void *stream)
 {
     sddmm_impl<float>(e, layout, X, ldX, Y, ldY, out, mode, stream);
+}
+
+// row softmax over the slice on a grid with pn > 1: the slice is a run of whole rows, so neither the panel nor a communicator
+// is involved; false when the slice holds no nonzero (nothing to upload or launch)
+static bool row_softmax_ready(crp_para2d_spmm *e, const char *what, int f32)
+{
+    ASSERT_PRINTF(!e->plan_only, "%s on a plan-only engine (no device state)\n", what);
+    ASSERT_PRINTF(f32 == 0 || f32 == 1, "%s: f32 must be 0 or 1\n", what);
+    if (e->row_nnz[e->pj] == 0) return false;
+    if (e->sm_rowptr == nullptr)
+    {
+        const size_t rb = sizeof(int) * e->slice_rowptr.size();
+        void *d = NULL;
+        HIP_OK(crp_dev_malloc(&d, rb));
+        HIP_OK(crp_dev_memcpy(d, e->slice_rowptr.data(), rb, 0, NULL));
+        HIP_OK(crp_stream_sync(NULL));
+        e->sm_rowptr = (int *) d;
+    }
+    return true;
+}
+
+void crp_para2d_spmm_row_softmax_ex(crp_para2d_spmm_p e, const void *s, void *y, int f32, void *stream)
+{
+    if (e == NULL) return;
+    if (e->pn == 1)
+    {
+        crp_rp_spmm_row_softmax_ex(e->rp, s, y, f32, stream);
+        return;
+    }
+    if (!row_softmax_ready(e, "para2d_spmm_row_softmax", f32)) return;
+    ASSERT_PRINTF(s != NULL && y != NULL, "para2d_spmm_row_softmax: NULL values\n");
+    const int nrow = (int) e->slice_rowptr.size() - 1;
+    if (f32) HIP_OK(crp_row_softmax_f32(nrow, e->sm_rowptr, (const float *) s, (float *) y, stream));
+    else HIP_OK(crp_row_softmax_f64(nrow, e->sm_rowptr, (const double *) s, (double *) y, stream));
+}
+
+void crp_para2d_spmm_row_softmax_bwd_ex(crp_para2d_spmm_p e, const void *y, const void *dy, void *ds, int f32, void *stream)
+{
+    if (e == NULL) return;
+    if (e->pn == 1)
+    {
+        crp_rp_spmm_row_softmax_bwd_ex(e->rp, y, dy, ds, f32, stream);
+        return;
+    }
+    if (!row_softmax_ready(e, "para2d_spmm_row_softmax_bwd", f32)) return;
+    ASSERT_PRINTF(y != NULL && dy != NULL && ds != NULL, "para2d_spmm_row_softmax_bwd: NULL values\n");
+    const int nrow = (int) e->slice_rowptr.size() - 1;
+    if (f32) HIP_OK(crp_row_softmax_bwd_f32(nrow, e->sm_rowptr, (const float *) y, (const float *) dy, (float *) ds, stream));
+    else HIP_OK(crp_row_softmax_bwd_f64(nrow, e->sm_rowptr, (const double *) y, (const double *) dy, (double *) ds, stream));
+}
+
+int crp_para2d_spmm_row_softmax_built(crp_para2d_spmm_p e)
+{
+    if (e == NULL) return 0;
+    return e->pn == 1 ? crp_rp_spmm_row_softmax_built(e->rp) : (e->sm_rowptr ? 1 : 0);
 }
 
 int crp_para2d_spmm_sddmm_built(crp_para2d_spmm_p e) { return (e && (e->sd_built64 || e->sd_built32)) ? 1 : 0; }

@@ -83,6 +83,8 @@ struct crp_rp_spmm
     int    *dv_t_pos = nullptr;
     void   *ev_vals = nullptr;
     bool    host_vals_stale = false;             // A_val (host) is behind the device matrices: refreshed where it is read
+    // row softmax (crp_rp_spmm_row_softmax_ex), uploaded by its first call: A_rowptr as a device array
+    int *sm_rowptr = nullptr;
     // staging (host-pointer API) and column-major temporaries, grown on demand
     crp::DevScratch B_stage, C_stage, B_rm, C_rm;
     // the stream the last exec ran on, and an event at its end: a value update on the engine's own stream must
@@ -360,6 +362,7 @@ void crp_rp_spmm_free(crp_rp_spmm_p *rp_spmm)
         crp_dev_free(e->dv_vals);
         crp_dev_free(e->dv_tvals);
         crp_dev_free(e->dv_t_pos);
+        crp_dev_free(e->sm_rowptr);
         if (e->ev_vals) crp_event_destroy(e->ev_vals);
         if (e->xstream) crp_stream_destroy(e->xstream);
         if (e->ev_packed) crp_event_destroy(e->ev_packed);
@@ -1109,6 +1112,44 @@ void crp_rp_spmm_update_values_dev(crp_rp_spmm_p e, const void *A_val_dev, int f
     e->dv_used = true;
     e->host_vals_stale = true;
 }
+
+// ---- row softmax over this rank's rows (crp_row_softmax_*): the values are the caller's, in A_val's order, so init's row pointer
+// addresses them as it is, split engine or not
+static bool row_softmax_ready(crp_rp_spmm *e, const char *what, int f32)
+{
+    ASSERT_PRINTF(!e->plan_only, "%s on a plan-only engine (no device state)\n", what);
+    ASSERT_PRINTF(f32 == 0 || f32 == 1, "%s: f32 must be 0 or 1\n", what);
+    if (e->sm_rowptr == nullptr)
+    {
+        const size_t rb = sizeof(int) * ((size_t) e->A_nrow + 1);
+        void *d = NULL;
+        HIP_OK(crp_dev_malloc(&d, rb));
+        HIP_OK(crp_dev_memcpy(d, e->A_rowptr.data(), rb, 0, e->stream));
+        HIP_OK(crp_stream_sync(e->stream));
+        e->sm_rowptr = (int *) d;
+    }
+    return !e->A_val.empty();       // rows without a nonzero: nothing to launch, the pointers may be NULL
+}
+
+void crp_rp_spmm_row_softmax_ex(crp_rp_spmm_p e, const void *s, void *y, int f32, void *stream)
+{
+    if (e == NULL) return;
+    if (!row_softmax_ready(e, "rp_spmm_row_softmax", f32)) return;
+    ASSERT_PRINTF(s != NULL && y != NULL, "rp_spmm_row_softmax: NULL values\n");
+    if (f32) HIP_OK(crp_row_softmax_f32(e->A_nrow, e->sm_rowptr, (const float *) s, (float *) y, stream));
+    else HIP_OK(crp_row_softmax_f64(e->A_nrow, e->sm_rowptr, (const double *) s, (double *) y, stream));
+}
+
+void crp_rp_spmm_row_softmax_bwd_ex(crp_rp_spmm_p e, const void *y, const void *dy, void *ds, int f32, void *stream)
+{
+    if (e == NULL) return;
+    if (!row_softmax_ready(e, "rp_spmm_row_softmax_bwd", f32)) return;
+    ASSERT_PRINTF(y != NULL && dy != NULL && ds != NULL, "rp_spmm_row_softmax_bwd: NULL values\n");
+    if (f32) HIP_OK(crp_row_softmax_bwd_f32(e->A_nrow, e->sm_rowptr, (const float *) y, (const float *) dy, (float *) ds, stream));
+    else HIP_OK(crp_row_softmax_bwd_f64(e->A_nrow, e->sm_rowptr, (const double *) y, (const double *) dy, (double *) ds, stream));
+}
+
+int crp_rp_spmm_row_softmax_built(crp_rp_spmm_p e) { return (e && e->sm_rowptr) ? 1 : 0; }
 
 int crp_rp_spmm_host_values_stale(crp_rp_spmm_p e) { return (e && e->host_vals_stale) ? 1 : 0; }
 

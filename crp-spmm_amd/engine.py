@@ -12,6 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
+from .hip import _check_dev_vectors, _softmax_vecs
 
 
 def _i32(a):
@@ -103,18 +104,10 @@ def _f32_operands(B, C_out):
 
 def _dev_vals(vals, nnz):
     """(address, f32 flag, keepalive) of the 1-D contiguous float64 / float32 CUDA tensor ``update_values_dev`` takes, which must
-    hold nnz entries; TypeError for anything that is not such a tensor on the device, ValueError for a wrong length or strides."""
+    hold nnz entries; TypeError for anything that is not such a tensor on the device, ValueError for a wrong length or strides
+    (hip._check_dev_vectors, the checker the row softmax shares)."""
     import torch
-    if not isinstance(vals, torch.Tensor):
-        raise TypeError("vals must be a torch tensor on the device (host values go to update_values)")
-    if vals.dtype not in (torch.float64, torch.float32):
-        raise TypeError("vals must be float64 or float32, got %s" % vals.dtype)
-    if vals.dim() != 1 or not vals.is_contiguous():
-        raise ValueError("vals must be 1-D and contiguous")
-    if vals.numel() != nnz:
-        raise ValueError("vals has %d entries, the engine needs %d" % (vals.numel(), nnz))
-    if not vals.is_cuda:
-        raise TypeError("vals must be on the device (host values go to update_values)")
+    _check_dev_vectors((("vals", vals),), nnz)
     return vals.data_ptr() or None, int(vals.dtype == torch.float32), vals
 
 
@@ -283,6 +276,34 @@ class RpSpmm:
             stream = _current_stream(vals)
         self._lib.crp_rp_spmm_update_values_dev(self.handle, ptr, f32, stream)
 
+    def row_softmax(self, s, out=None, stream=None):
+        """Row softmax over this rank's rows of A (crp_rp_spmm_row_softmax_ex): out[p] = exp(s[p] - max) / sum over every row's
+        nonzeros.  ``s`` is a 1-D contiguous float64 or float32 CUDA tensor of ``nnz()`` entries in the order of the A_val given to
+        init -- what ``sddmm`` writes and ``update_values_dev`` takes; ``out`` one like it (allocated when None; ``out is s`` is
+        allowed).  Asynchronous on ``stream`` (default: the current torch stream), no communication, not collective; -inf entries
+        are masked edges.  Every argument is checked before the library is called.  Returns ``out``."""
+        s, out = _softmax_vecs((("s", s),), out, self.nnz())
+        if stream is None:
+            stream = _current_stream(out)
+        f32 = int(s.dtype.itemsize == 4)
+        self._lib.crp_rp_spmm_row_softmax_ex(self.handle, s.data_ptr() or None, out.data_ptr() or None, f32, stream)
+        return out
+
+    def row_softmax_bwd(self, y, dy, out=None, stream=None):
+        """The Jacobian product of ``row_softmax`` (crp_rp_spmm_row_softmax_bwd_ex): out[p] = y[p] * (dy[p] - D), D = the row's
+        sum of y * dy.  Tensors as in ``row_softmax``, one dtype; ``out`` may be ``dy`` or ``y``.  Returns ``out``."""
+        y, dy, out = _softmax_vecs((("y", y), ("dy", dy)), out, self.nnz())
+        if stream is None:
+            stream = _current_stream(out)
+        f32 = int(y.dtype.itemsize == 4)
+        self._lib.crp_rp_spmm_row_softmax_bwd_ex(self.handle, y.data_ptr() or None, dy.data_ptr() or None, out.data_ptr() or None, f32, stream)
+        return out
+
+    @property
+    def row_softmax_built(self):
+        """True once a ``row_softmax`` / ``row_softmax_bwd`` has uploaded the row pointer (crp_rp_spmm_row_softmax_built)."""
+        return bool(self._lib.crp_rp_spmm_row_softmax_built(self.handle))
+
     @property
     def host_values_stale(self):
         """True after ``update_values_dev`` until the host values are read (``plan``) or replaced (``update_values``)."""
@@ -409,6 +430,35 @@ class Para2dSpmm:
         if stream is None:
             stream = _current_stream(vals)
         self._lib.crp_para2d_spmm_update_values_dev(self.handle, ptr, f32, stream)
+
+    def row_softmax(self, s, out=None, stream=None):
+        """Row softmax over this rank's A0 slice (crp_para2d_spmm_row_softmax_ex): out[p] = exp(s[p] - max) / sum over every row's
+        nonzeros.  ``s`` is a 1-D contiguous float64 or float32 CUDA tensor of ``slice_nnz`` entries in the order of the A_val given to
+        init -- what ``sddmm`` writes and ``update_values_dev`` takes; ``out`` one like it (allocated when None; ``out is s`` is
+        allowed).  Asynchronous on ``stream`` (default: the current torch stream), no communication, not collective; -inf entries
+        are masked edges.  Every argument is checked before the library is called.  Returns ``out``."""
+        s, out = _softmax_vecs((("s", s),), out, self.slice_nnz)
+        if stream is None:
+            stream = _current_stream(out)
+        f32 = int(s.dtype.itemsize == 4)
+        self._lib.crp_para2d_spmm_row_softmax_ex(self.handle, s.data_ptr() or None, out.data_ptr() or None, f32, stream)
+        return out
+
+    def row_softmax_bwd(self, y, dy, out=None, stream=None):
+        """The Jacobian product of ``row_softmax`` (crp_para2d_spmm_row_softmax_bwd_ex): out[p] = y[p] * (dy[p] - D), D = the row's
+        sum of y * dy.  Tensors as in ``row_softmax``, one dtype; ``out`` may be ``dy`` or ``y``.  Returns ``out``."""
+        y, dy, out = _softmax_vecs((("y", y), ("dy", dy)), out, self.slice_nnz)
+        if stream is None:
+            stream = _current_stream(out)
+        f32 = int(y.dtype.itemsize == 4)
+        self._lib.crp_para2d_spmm_row_softmax_bwd_ex(self.handle, y.data_ptr() or None, dy.data_ptr() or None, out.data_ptr() or None, f32, stream)
+        return out
+
+    @property
+    def row_softmax_built(self):
+        """True once a ``row_softmax`` / ``row_softmax_bwd`` has uploaded the row pointer (crp_para2d_spmm_row_softmax_built); with
+        pn > 1 an empty slice uploads nothing and stays False."""
+        return bool(self._lib.crp_para2d_spmm_row_softmax_built(self.handle))
 
     def sddmm(self, BC_layout, X, Y, out, mode=0, stream=None):
         """SDDMM over all n columns (crp_para2d_spmm_sddmm_ex / _f32_ex, by the operands' dtype): out[p] = <X[i], Y[c]> for every

@@ -157,6 +157,30 @@ class CsrDev:
                 fn.__name__)
         return out
 
+    def row_softmax(self, s, out=None, stream=None):
+        """Row softmax over this matrix's pattern (crp_csr_dev_row_softmax_f64 / _f32, by the dtype of ``s``): for every row,
+        out[p] = exp(s[p] - max) / sum over the row's nonzeros p, which count in the handle's CSR order -- what ``sddmm``
+        writes.  ``s`` is a 1-D contiguous float64 or float32 cuda tensor of nnz entries; ``out`` one like it (allocated when
+        None; ``out is s`` is allowed).  -inf entries are masked edges (exactly 0).  Returns ``out``."""
+        s, out = _softmax_vecs((("s", s),), out, self.nnz)
+        if self.nnz == 0:
+            return out
+        import torch
+        fn = self._lib.crp_csr_dev_row_softmax_f64 if s.dtype == torch.float64 else self._lib.crp_csr_dev_row_softmax_f32
+        L.check(fn(self.handle, s.data_ptr(), out.data_ptr(), _stream(out) if stream is None else stream), fn.__name__)
+        return out
+
+    def row_softmax_bwd(self, y, dy, out=None, stream=None):
+        """The Jacobian product of ``row_softmax`` (crp_csr_dev_row_softmax_bwd_f64 / _f32): out[p] = y[p] * (dy[p] - D) with
+        D = the row's sum of y * dy.  ``y``, ``dy`` and ``out`` as in ``row_softmax``, one dtype; ``out`` may be ``dy`` or ``y``."""
+        y, dy, out = _softmax_vecs((("y", y), ("dy", dy)), out, self.nnz)
+        if self.nnz == 0:
+            return out
+        import torch
+        fn = self._lib.crp_csr_dev_row_softmax_bwd_f64 if y.dtype == torch.float64 else self._lib.crp_csr_dev_row_softmax_bwd_f32
+        L.check(fn(self.handle, y.data_ptr(), dy.data_ptr(), out.data_ptr(), _stream(out) if stream is None else stream), fn.__name__)
+        return out
+
     def resolved_variant(self, n):
         """crp_csr_dev_resolved_variant: what a variant-0 product of n columns launches on this matrix."""
         return int(self._lib.crp_csr_dev_resolved_variant(self.handle, int(n)))
@@ -196,6 +220,83 @@ class CsrDev:
 def _stream(t):
     import torch
     return torch.cuda.current_stream(t.device).cuda_stream
+
+
+def _check_dev_vectors(named, nnz):
+    """The one checker of value vectors that live on the device (``update_values_dev``, the row softmax), run before any
+    library call: every (name, tensor) of ``named`` a 1-D contiguous float64 / float32 CUDA tensor of nnz entries (nnz None: as
+    many as the first holds), all of one dtype and device.  TypeError for anything that is not a torch tensor, for another
+    dtype and for mixed dtypes; then ValueError for a wrong dimension, strides or length; then TypeError for a tensor that is
+    not on the device."""
+    import torch
+    head, first = named[0]
+    for name, t in named:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s must be a torch tensor on the device (host values go to update_values)" % name)
+        if t.dtype not in (torch.float64, torch.float32):
+            raise TypeError("%s must be float64 or float32, got %s" % (name, t.dtype))
+        if t.dtype != first.dtype:
+            raise TypeError("%s and %s must share one dtype (%s, %s)" % (head, name, first.dtype, t.dtype))
+    for name, t in named:
+        if t.dim() != 1 or not t.is_contiguous():
+            raise ValueError("%s must be 1-D and contiguous" % name)
+        want = first.numel() if nnz is None else nnz
+        if t.numel() != want:
+            raise ValueError("%s has %d entries, the call needs %d" % (name, t.numel(), want))
+    for name, t in named:
+        if not t.is_cuda or t.device != first.device:
+            raise TypeError("%s must be on the device%s (host values go to update_values)" % (name, "" if t is first else ", with " + head))
+
+
+def _softmax_vecs(named, out, nnz):
+    """The value tensors of a row softmax call through ``_check_dev_vectors``; ``out`` is allocated like the first when None.
+    Returns the tensors, out last."""
+    import torch
+    _check_dev_vectors(tuple(named) + ((("out", out),) if out is not None else ()), nnz)
+    if out is None:
+        out = torch.empty_like(named[0][1])
+    return tuple(t for _, t in named) + (out,)
+
+
+def _softmax_rowptr(rowptr, like):
+    import torch
+    if not isinstance(rowptr, torch.Tensor) or rowptr.dtype != torch.int32:
+        raise TypeError("rowptr must be an int32 torch tensor on the device")
+    if rowptr.dim() != 1 or not rowptr.is_contiguous() or rowptr.numel() < 1:
+        raise ValueError("rowptr must be 1-D and contiguous, with nrow + 1 entries")
+    if not rowptr.is_cuda or rowptr.device != like.device:
+        raise TypeError("rowptr must be on the device, with the values")
+    return rowptr.numel() - 1
+
+
+def row_softmax(rowptr, s, out=None, stream=None):
+    """Row softmax over a CSR pattern (crp_row_softmax_f64 / _f32, by the dtype of ``s``): ``rowptr`` is an int32 cuda tensor
+    of nrow + 1 non-decreasing entries that index ``s`` and ``out`` directly (rowptr[0] need not be 0: a slice ``rowptr[r0:r1]``
+    addresses a row subset of the same tensors; the entries must lie inside ``s``, which cannot be checked without a
+    download).  ``s`` is a 1-D contiguous float64 or float32 cuda tensor, ``out`` one of the same length (allocated when None;
+    only the entries the rows name are written; ``out is s`` is allowed).  Returns ``out``."""
+    import torch
+    s, out = _softmax_vecs((("s", s),), out, None)
+    nrow = _softmax_rowptr(rowptr, s)
+    if nrow == 0 or s.numel() == 0:
+        return out
+    fn = L.load().crp_row_softmax_f64 if s.dtype == torch.float64 else L.load().crp_row_softmax_f32
+    L.check(fn(nrow, rowptr.data_ptr(), s.data_ptr(), out.data_ptr(), _stream(out) if stream is None else stream), fn.__name__)
+    return out
+
+
+def row_softmax_bwd(rowptr, y, dy, out=None, stream=None):
+    """The Jacobian product of ``row_softmax`` (crp_row_softmax_bwd_f64 / _f32): out[p] = y[p] * (dy[p] - D), D = the row's sum
+    of y * dy.  Arguments as ``row_softmax``; ``out`` may be ``dy`` or ``y``."""
+    import torch
+    y, dy, out = _softmax_vecs((("y", y), ("dy", dy)), out, None)
+    nrow = _softmax_rowptr(rowptr, y)
+    if nrow == 0 or y.numel() == 0:
+        return out
+    fn = L.load().crp_row_softmax_bwd_f64 if y.dtype == torch.float64 else L.load().crp_row_softmax_bwd_f32
+    L.check(fn(nrow, rowptr.data_ptr(), y.data_ptr(), dy.data_ptr(), out.data_ptr(), _stream(out) if stream is None else stream),
+            fn.__name__)
+    return out
 
 
 def spmm_csr(A, B0, C_out, n=None, layout=0, B1=None, variant=0, stream=None):

@@ -195,6 +195,21 @@ void crp_rp_spmm_update_values(crp_rp_spmm_p rp_spmm, const double *A_val);
  * exec; a NULL engine is a no-op (stale: 0). */
 void crp_rp_spmm_update_values_dev(crp_rp_spmm_p rp_spmm, const void *A_val_dev, int f32, void *stream);
 int crp_rp_spmm_host_values_stale(crp_rp_spmm_p rp_spmm);
+/* Row softmax over this rank's rows of A and its Jacobian product (crp_row_softmax_* in crpspmm_hip.h: definition, special
+ * cases, fixed order, aliasing rule and error bounds) -- the step between crp_rp_spmm_sddmm_ex and
+ * crp_rp_spmm_update_values_dev, and its backward.  s / y (y / dy / ds) are DEVICE pointers to crp_rp_spmm_nnz entries IN THE
+ * ORDER OF THE A_val GIVEN TO INIT, as fp64 (f32 = 0) or fp32 (f32 = 1); the rows are the rank's A_nrow rows with init's
+ * A_rowptr.  Every row of A is whole on one rank, so the call needs no communication and is not collective; a split engine
+ * needs no per-part work (the order is A_val's, not the parts').  Asynchronous on `stream` (taken literally), with no host
+ * synchronisation; it reads nothing of the engine's values, so it needs no ordering against exec beyond the caller's stream.
+ * The first call uploads the row pointer as a device array, and nothing before it does (crp_rp_spmm_row_softmax_built: 0, then
+ * 1; that one call blocks).  A rank whose rows hold no nonzero uploads its (one-entry or all-equal) row pointer like any other
+ * and then returns without a launch; its pointers may be NULL.  Because the summation order is fixed per row, a rank's result is bit-identical to
+ * the same rows of a one-GPU call on the whole matrix, for any rank count.  A plan-only engine aborts as
+ * crp_rp_spmm_update_values_dev does; a NULL engine is a no-op (_built: 0). */
+void crp_rp_spmm_row_softmax_ex(crp_rp_spmm_p e, const void *s, void *y, int f32, void *stream);
+void crp_rp_spmm_row_softmax_bwd_ex(crp_rp_spmm_p e, const void *y, const void *dy, void *ds, int f32, void *stream);
+int  crp_rp_spmm_row_softmax_built(crp_rp_spmm_p e);
 
 /* See para2d_spmm_init (src/para2d_spmm.h:22-47). Rank r sits at grid position
  * (r / pn, r % pn); A_rowptr/A_colidx/A_val is the rank's A0 slice. */
@@ -257,6 +272,16 @@ void crp_para2d_spmm_exec_t_f32_ex(crp_para2d_spmm_p e, int BC_layout, const flo
  * (a download, the gather, an upload: that path blocks).  Collective like crp_para2d_spmm_update_values: the first call
  * of the three over the whole grid.  The panel buffer is allocated by the first device update.  A plan-only engine aborts. */
 void crp_para2d_spmm_update_values_dev(crp_para2d_spmm_p e, const void *A_val_dev, int f32, void *stream);
+/* Row softmax over this rank's A0 SLICE and its Jacobian product (crp_rp_spmm_row_softmax_ex): crp_para2d_spmm_slice_nnz
+ * entries in the order given to init, device pointers, with the slice's own row pointer (a host copy kept by init, uploaded by
+ * the first call on a slice with nonzeros: crp_para2d_spmm_row_softmax_built 0, then 1; that call blocks).  The slice is a run of
+ * whole rows of the panel, so with pn > 1 the call neither splits the grid-row communicator nor touches the panel, and it is
+ * not collective; with pn == 1 it forwards to the row engine (_built is then the row engine's).  An empty slice takes NULL
+ * pointers and returns without an upload or a launch: _built stays 0.  Bit-identical to the same rows of a one-GPU call on
+ * the whole matrix, on any grid.  A plan-only engine aborts; a NULL engine is a no-op (_built: 0). */
+void crp_para2d_spmm_row_softmax_ex(crp_para2d_spmm_p e, const void *s, void *y, int f32, void *stream);
+void crp_para2d_spmm_row_softmax_bwd_ex(crp_para2d_spmm_p e, const void *y, const void *dy, void *ds, int f32, void *stream);
+int  crp_para2d_spmm_row_softmax_built(crp_para2d_spmm_p e);
 /* nonzeros of this rank's A0 slice; of every slice of its grid row (pn entries written when nnz_of_pj != NULL; returns pn). */
 long long crp_para2d_spmm_slice_nnz(crp_para2d_spmm_p e);
 int crp_para2d_spmm_row_slice_nnz(crp_para2d_spmm_p e, long long *nnz_of_pj);

@@ -311,6 +311,44 @@ int crp_sddmm_csr_f32(crp_csr_dev_p A, int n, const float *X, long long ldX,
                       const float *Y0, long long ldY0, const float *Y1, long long ldY1,
                       float *out, const int *out_pos, int mode, void *stream);
 
+/* ---- row softmax over A's pattern (edge softmax) and its Jacobian product ------
+ * For every row r with entries p in [rowptr[r], rowptr[r + 1]):
+ *   forward :  m = max_p s[p],  e_p = exp(s[p] - m),  y[p] = e_p / sum_q e_q
+ *   backward:  D = sum_q y[q] * dy[q] (accumulated with FMAs),  ds[p] = y[p] * (dy[p] - D)
+ * -- the step between crp_sddmm_csr_* (which writes s) and a value update (which takes y), and its backward.  exp / expf are
+ * the device library's functions, the division is IEEE.  No atomics, no LDS, no partial result in memory.
+ * Raw forms: rowptr is a device int32 array of nrow + 1 non-decreasing entries that index s / y (dy, ds) directly;
+ * rowptr[0] need not be 0, so `rowptr + r0` with fewer rows addresses a row subset of the same arrays.  Only the entries
+ * rowptr[0] .. rowptr[nrow] - 1 are read or written.  Handle forms: the handle's own device row pointer; p counts in the
+ * handle's CSR order, as for crp_sddmm_csr_* (a crp_csr_dev_create_t handle: the transposed order).  All pointers are
+ * device pointers; the launch is asynchronous on `stream`.
+ * Special cases: an empty row reads and writes nothing; a row of one finite entry gives exactly 1.0; an entry of -inf is a
+ * masked edge, its y is exactly 0; a row whose entries are all -inf gives all zeros, not NaN; a row that holds NaN or +inf
+ * has unspecified outputs for that row only -- other rows are unaffected and nothing faults.
+ * Fixed order: both sums are formed from 64 strided partials -- partial k adds entries k, k + 64, k + 128, ... of the row in
+ * ascending order, starting from +0 -- which meet in the balanced binary tree over k (k with k ^ 1, then k ^ 2, ... k ^ 32),
+ * every node one IEEE addition.  The order is a function of the dtype ONLY: not of the row's position, the row pointer's
+ * first value, pointer alignment, the kernel instance (a group of 8, 16, 32 or 64 lanes per row, which the kernel picks
+ * from the launch's mean row length (rowptr[nrow] - rowptr[0]) / nrow) or the other rows of the call.  Repeated calls are
+ * bit-identical, and a row subset reproduces the full call's entries bit for bit.
+ * Aliasing: exact aliasing is allowed (y == s; ds == dy or ds == y), partial overlap is not.  Every element is read and
+ * later written by the same lane; a row of up to 8 entries per lane of its group is read entirely before its first write,
+ * in a longer row every element's last read precedes its own write.
+ * Error bounds (u = 2^-53 / 2^-24; L = the row's length, T = max_p (m - s[p]) over its finite entries; against the exact
+ * result of the dtype-rounded inputs, results away from the subnormal range):
+ *   |y - ref|  <= 1.01 (L + 2 T + 8) u ref                      (exp within 2 ulp)
+ *   |ds - ref| <= 1.01 u |y_p| ((L + 2) S + 2 |dy_p|),  S = sum_q |y_q dy_q|.
+ * Return: 0 on success -- also for nrow == 0, for which nothing is launched; -1 for nrow < 0, a NULL handle, or a NULL
+ * pointer when nrow > 0; a positive HIP error otherwise.  Nothing is written before the arguments have passed. */
+int crp_row_softmax_f64(int nrow, const int *rowptr, const double *s, double *y, void *stream);
+int crp_row_softmax_f32(int nrow, const int *rowptr, const float *s, float *y, void *stream);
+int crp_row_softmax_bwd_f64(int nrow, const int *rowptr, const double *y, const double *dy, double *ds, void *stream);
+int crp_row_softmax_bwd_f32(int nrow, const int *rowptr, const float *y, const float *dy, float *ds, void *stream);
+int crp_csr_dev_row_softmax_f64(crp_csr_dev_p A, const double *s, double *y, void *stream);
+int crp_csr_dev_row_softmax_f32(crp_csr_dev_p A, const float *s, float *y, void *stream);
+int crp_csr_dev_row_softmax_bwd_f64(crp_csr_dev_p A, const double *y, const double *dy, double *ds, void *stream);
+int crp_csr_dev_row_softmax_bwd_f32(crp_csr_dev_p A, const float *y, const float *dy, float *ds, void *stream);
+
 /* ---- row gather / scatter (pack / unpack of the B exchange) ----------------
  * gather : dst[i][0:n] = src[ridx[i]][0:n]   (i < nidx)
  * scatter: dst[ridx[i]][0:n] = src[i][0:n]
