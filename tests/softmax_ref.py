@@ -18,8 +18,10 @@ Data rule: no result near the subnormal range; T <= 60 (fp32) and <= 600 (fp64),
 
 replay_fwd / replay_bwd repeat the kernel's FIXED ORDER in numpy: 64 strided partials per row (partial k adds entries k,
 k + 64, ... in ascending order from +0), then the balanced binary tree over k (k ^ 1, k ^ 2, ... k ^ 32).  numpy has no FMA:
-the backward's is emulated in the next wider format (exact product, one extra rounding in rare cases), and numpy's exp is
-not the device's -- the replay shows that the ORDER meets the bounds, it does not predict the device's bits."""
+the backward's is emulated with one rounding (fma: fp32 exactly, through the exact fp64 product and a tie correction; fp64 by
+an error-free product and sum, whose one approximation shows in about one operation in 2^50), so replay_bwd gives the bits of
+any IEEE device for the same y and dy.  numpy's exp is not the device's: with it replay_fwd shows that the ORDER meets the
+bounds and does not predict the device's bits; given the device library's exp (its `exp` argument) it does."""
 import functools
 
 import numpy as np
@@ -90,10 +92,46 @@ def bound_bwd(y, dy, L, S, dtype):
     return 1.01 * U[np.dtype(dtype)] * yl * ((L + 2) * S + 2 * gl)
 
 
+def _two_sum(a, b):
+    """(s, e): s = fl(a + b) and a + b = s + e exactly"""
+    s = a + b
+    bb = s - a
+    return s, (a - (s - bb)) + (b - bb)
+
+
+def fma(a, b, c):
+    """fl(a * b + c) with ONE rounding, elementwise, for float32 or float64 arrays of one dtype (no overflow, no subnormal
+    product).  float32: the product is exact in float64 and so is the sum but for one rounding to 53 bits; where that lands
+    exactly half way between two float32 numbers the sign of its error decides, as it would have for the exact sum.  float64:
+    Dekker's error-free product ph + pl and Knuth's error-free sum s + e of ph and c; the result is fl(s + fl(e + pl))."""
+    a, b, c = np.broadcast_arrays(np.asarray(a), np.asarray(b), np.asarray(c))
+    dt = a.dtype
+    assert dt == b.dtype == c.dtype and dt in U, (a.dtype, b.dtype, c.dtype)
+    if dt == np.float32:
+        p = a.astype(np.float64) * b.astype(np.float64)
+        s, e = _two_sum(p, c.astype(np.float64))
+        r = s.astype(np.float32)
+        d = s - r.astype(np.float64)
+        up, dn = np.nextafter(r, np.float32(np.inf)), np.nextafter(r, np.float32(-np.inf))
+        with np.errstate(invalid="ignore", over="ignore"):
+            go_up = (d > 0) & (2 * d == up.astype(np.float64) - r) & (e > 0)
+            go_dn = (d < 0) & (-2 * d == r.astype(np.float64) - dn) & (e < 0)
+        return np.where(go_up, up, np.where(go_dn, dn, r))
+    split = 134217729.0                                     # 2^27 + 1
+    ph = a * b
+    t = a * split
+    ah = t - (t - a)
+    t = b * split
+    bh = t - (t - b)
+    al, bl = a - ah, b - bh
+    pl = ((ah * bh - ph) + ah * bl + al * bh) + al * bl
+    s, e = _two_sum(ph, c)
+    return s + (e + pl)
+
+
 def _fixed_order_sums(rp, a, b=None):
     """per row, the sum of a (b None) or of a * b with FMAs, in the kernel's order; a, b are views of the rows' entries"""
     dt = a.dtype
-    wide = np.float64 if dt == np.float32 else np.longdouble
     lens = np.diff(rp).astype(np.int64)
     off = (rp[:-1] - rp[0]).astype(np.int64)
     out = np.zeros(lens.size, dt)
@@ -110,15 +148,18 @@ def _fixed_order_sums(rp, a, b=None):
             if B is None:
                 acc = acc + A[:, k, :]
             else:
-                acc = (acc.astype(wide) + A[:, k, :].astype(wide) * B[:, k, :].astype(wide)).astype(dt)
+                acc = fma(A[:, k, :], B[:, k, :], acc)
         for step in (1, 2, 4, 8, 16, 32):
             acc = acc + acc[:, _LANE ^ step]
         out[rows] = acc[:, 0]
     return out
 
 
-def replay_fwd(rp, s):
-    """the rows' softmax in the dtype of s, in the kernel's order (an array of rp[-1] - rp[0] entries)"""
+def replay_fwd(rp, s, exp=np.exp):
+    """the rows' softmax in the dtype of s, in the kernel's order (an array of rp[-1] - rp[0] entries).  exp: the exponential,
+    on an array of the dtype holding 0, negative numbers and -inf; numpy's by default, which is not the device library's in
+    the last bit -- a GPU test that wants the device's bits passes an exp evaluated by that library (outside the code under
+    test), and the subtraction, the order of the sum and the division stay this function's"""
     x = _view(rp, s)
     dt = x.dtype
     nrow = rp.size - 1
@@ -129,7 +170,7 @@ def replay_fwd(rp, s):
         m[ne] = np.maximum.reduceat(x, starts)
     live = np.isfinite(m)[rows]
     with np.errstate(invalid="ignore"):
-        e = np.where(live, np.exp(np.where(live, x - m[rows], 0).astype(dt)), 0).astype(dt)
+        e = np.where(live, np.asarray(exp(np.where(live, x - m[rows], 0).astype(dt))), 0).astype(dt)
     tot = _fixed_order_sums(rp, e)
     with np.errstate(invalid="ignore", divide="ignore"):
         return np.where(live, e / tot[rows], 0).astype(dt)

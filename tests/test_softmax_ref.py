@@ -60,3 +60,48 @@ def test_a_row_subset_replays_to_the_same_bits():
     full = R.replay_fwd(rp, s)
     sub = rp[40:90]
     assert np.array_equal(R.replay_fwd(sub, s), full[sub[0]:sub[-1]])
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_the_replays_fma_rounds_once(dtype):
+    """softmax_ref.fma against exact rational arithmetic: random operands, cancelling ones, and sums that land exactly half way
+    between two numbers of the dtype after the wider rounding (the cases a product-then-sum emulation gets wrong)."""
+    from fractions import Fraction
+    dt = np.dtype(dtype)
+    bits = 53 if dt == np.float64 else 24
+    rng = np.random.default_rng(9)
+    n = 4000
+    a = rng.standard_normal(n).astype(dt)
+    b = rng.standard_normal(n).astype(dt)
+    c = (rng.standard_normal(n) * np.exp2(rng.integers(-30, 31, n))).astype(dt)
+    c[:500] = -(a[:500] * b[:500])                                       # cancellation: the low half of the product survives
+    # ties: c = 1 + one ulp (odd last bit), a * b = half an ulp less 2^-2j of it, too little for the wider format to keep: the
+    # wider sum lands exactly half way and goes to the even neighbour above, the exact sum lies below the half
+    j = rng.integers(15, 24, 500).astype(np.float64)
+    a[500:1000] = (np.ldexp(1.0, -(bits // 2)) * (1 + np.exp2(-j))).astype(dt)
+    b[500:1000] = (np.ldexp(1.0, -(bits - bits // 2)) * (1 - np.exp2(-j))).astype(dt)
+    c[500:1000] = np.asarray(1 + np.ldexp(1.0, 1 - bits), dt)
+    a[750:1000], c[750:1000] = -a[750:1000], -c[750:1000]
+    got = R.fma(a, b, c)
+    assert got.dtype == dt
+
+    def exact(x, y, z):
+        v = Fraction(float(x)) * Fraction(float(y)) + Fraction(float(z))
+        if v == 0:
+            return dt.type(0.0)
+        if dt == np.float64:
+            return np.float64(float(v))                                  # int / int division of a Fraction rounds correctly
+        sign, v = (-1, -v) if v < 0 else (1, v)
+        e = v.numerator.bit_length() - v.denominator.bit_length()
+        e = e if v >= Fraction(2) ** e else e - 1
+        q = v / Fraction(2) ** (e - bits + 1)                           # 2^(bits - 1) <= q < 2^bits
+        fl = q.numerator // q.denominator
+        rem = q - fl
+        fl += 1 if rem > Fraction(1, 2) or (rem == Fraction(1, 2) and fl % 2 == 1) else 0
+        return np.float32(sign * float(fl) * 2.0 ** (e - bits + 1))
+
+    want = np.array([exact(x, y, z) for x, y, z in zip(a, b, c)], dt)
+    assert np.array_equal(got, want), int((got != want).sum())
+    naive = (a.astype(np.longdouble) * b.astype(np.longdouble) + c.astype(np.longdouble)).astype(dt) if dt == np.float64 else \
+        (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(dt)
+    assert (naive != want).any()                                         # the data holds cases that need the single rounding
