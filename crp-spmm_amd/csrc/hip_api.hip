@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <cmath>
 #include <new>
 #include <memory>
 #include <algorithm>
@@ -394,6 +395,34 @@ static int sddmm_check(const crp_csr_dev *A, int n, const void *X, long long ldX
     if (Y0 == NULL && A->b0_rows > 0) return -1;        // a column code names the first source
     if (Y1 == NULL && A->b1_rows > 0) return -1;        // a column code names the second source
     if (ldX < n || (Y0 != NULL && ldY0 < n) || (Y1 != NULL && ldY1 < n)) return -4;
+    return 0;
+}
+
+static hipError_t attention_launch(const crp::AttnArgs<double> &a, hipStream_t s) { return crp::attention_rm_f64(a, s); }
+static hipError_t attention_launch(const crp::AttnArgs<float> &a, hipStream_t s) { return crp::attention_rm_f32(a, s); }
+// O = softmax_row(scale (Q K^T)|pattern(A) (+ A's values)) V (attention_kernels.hip), one dtype; val: the values in T, or nullptr
+template <class T>
+static int attention_csr(crp_csr_dev *A, int nk, int nv, double scale, const T *val, const T *Q, long long ldQ, const T *K0,
+                         long long ldK0, const T *K1, long long ldK1, const T *V0, long long ldV0, const T *V1, long long ldV1, T *O,
+                         long long ldO, T *lse, T *p_out, const int *out_pos, hipStream_t s)
+{
+    crp::AttnArgs<T> a;
+    a.nrow = A->nrow; a.nk = nk; a.nv = nv; a.rowptr = A->rowptr; a.colidx = A->colidx; a.val = val; a.scale = (T) scale;
+    a.Q = Q; a.ldQ = ldQ; a.K0 = K0; a.ldK0 = ldK0; a.K1 = K1; a.ldK1 = ldK1; a.V0 = V0; a.ldV0 = ldV0; a.V1 = V1; a.ldV1 = ldV1;
+    a.O = O; a.ldO = ldO; a.lse = lse; a.p_out = p_out; a.rowmap = A->rowmap; a.out_pos = out_pos;
+    return (int) attention_launch(a, s);
+}
+// every argument is checked before anything is launched or allocated: a negative return has written nothing
+static int attention_check(const crp_csr_dev *A, int nk, int nv, double scale, int bias, const void *Q, long long ldQ, const void *K0,
+                           long long ldK0, const void *K1, long long ldK1, const void *V0, long long ldV0, const void *V1, long long ldV1,
+                           const void *O, long long ldO)
+{
+    if (A == NULL || Q == NULL || O == NULL) return -1;
+    if (nk < 1 || nv < 1 || (bias != 0 && bias != 1) || !std::isfinite(scale)) return -1;
+    if ((K0 == NULL || V0 == NULL) && A->b0_rows > 0) return -1;        // a column code names the first source
+    if ((K1 == NULL || V1 == NULL) && A->b1_rows > 0) return -1;        // a column code names the second source
+    if (ldQ < nk || ldO < nv) return -4;
+    if ((K0 != NULL && ldK0 < nk) || (K1 != NULL && ldK1 < nk) || (V0 != NULL && ldV0 < nv) || (V1 != NULL && ldV1 < nv)) return -4;
     return 0;
 }
 
@@ -987,6 +1016,33 @@ int crp_sddmm_csr_f32(crp_csr_dev_p A, int n, const float *X, long long ldX, con
         CRP_TRY(crp::convert_f64_f32(A->nnz, A->val, A->val32, s));
     }
     return sddmm_csr<float>(A, n, X, ldX, Y0, ldY0, Y1, ldY1, out, out_pos, mode, A->val32, s);
+}
+
+// ---- fused sparse attention over A's pattern (attention_kernels.hip)
+int crp_attention_csr_f64(crp_csr_dev_p A, int nk, int nv, double scale, int bias, const double *Q, long long ldQ, const double *K0,
+                          long long ldK0, const double *K1, long long ldK1, const double *V0, long long ldV0, const double *V1,
+                          long long ldV1, double *O, long long ldO, double *lse, double *p_out, const int *out_pos, void *stream)
+{
+    const int rc = attention_check(A, nk, nv, scale, bias, Q, ldQ, K0, ldK0, K1, ldK1, V0, ldV0, V1, ldV1, O, ldO);
+    if (rc != 0 || A->nrow == 0) return rc;
+    return attention_csr<double>(A, nk, nv, scale, bias ? (const double *) A->val : nullptr, Q, ldQ, K0, ldK0, K1, ldK1, V0, ldV0, V1, ldV1,
+                                 O, ldO, lse, p_out, out_pos, (hipStream_t) stream);
+}
+
+int crp_attention_csr_f32(crp_csr_dev_p A, int nk, int nv, double scale, int bias, const float *Q, long long ldQ, const float *K0,
+                          long long ldK0, const float *K1, long long ldK1, const float *V0, long long ldV0, const float *V1,
+                          long long ldV1, float *O, long long ldO, float *lse, float *p_out, const int *out_pos, void *stream)
+{
+    const int rc = attention_check(A, nk, nv, scale, bias, Q, ldQ, K0, ldK0, K1, ldK1, V0, ldV0, V1, ldV1, O, ldO);
+    if (rc != 0 || A->nrow == 0) return rc;
+    const hipStream_t s = (hipStream_t) stream;
+    if (bias == 1 && A->nnz > 0 && A->val32 == nullptr)     // the fp32 copy of the values, as crp_sddmm_csr_f32 mode 1 derives it
+    {
+        CRP_TRY(A->val32.alloc(sizeof(float) * (size_t) A->nnz));
+        CRP_TRY(crp::convert_f64_f32(A->nnz, A->val, A->val32, s));
+    }
+    return attention_csr<float>(A, nk, nv, scale, (bias && A->nnz > 0) ? (const float *) A->val32 : nullptr, Q, ldQ, K0, ldK0, K1, ldK1, V0,
+                                ldV0, V1, ldV1, O, ldO, lse, p_out, out_pos, s);
 }
 
 // ---- row softmax over a CSR pattern (softmax_kernels.hip).  Every argument is checked before anything is launched.

@@ -106,6 +106,33 @@ template <typename T> struct SddmmArgs     // sddmm_kernels.hip: out[p] = < X[ro
     int        mode;        // 0: the dot, 1: the dot times val[p]
 };
 
+template <typename T> struct AttnArgs      // attention_kernels.hip: O[i] = sum_p softmax_p(scale <Q[i], K[c_p]> (+ val[p])) V[c_p]
+{
+    int nrow;
+    int nk;                 // columns of Q and K
+    int nv;                 // columns of V and O
+    const int *rowptr;
+    const int *colidx;
+    const T   *val;         // the values in T (bias), or nullptr
+    T          scale;
+    const T   *Q;
+    int64_t    ldQ;
+    const T   *K0;
+    int64_t    ldK0;
+    const T   *K1;
+    int64_t    ldK1;
+    const T   *V0;
+    int64_t    ldV0;
+    const T   *V1;
+    int64_t    ldV1;
+    T         *O;
+    int64_t    ldO;
+    T         *lse;         // nullptr, or one entry per row (indexed like the rows of O)
+    T         *p_out;       // nullptr, or the probabilities per nonzero
+    const int *rowmap;      // nullptr, or the Q / O row of every row (row-subset matrices)
+    const int *out_pos;     // nullptr, or where nonzero p writes: p_out[out_pos[p]]
+};
+
 // The instance every SpMM launcher names at its hipLaunchKernelGGL, from its own template arguments ("rowgroup<16,2,1>",
 // "panel<8,2,2,a32,b1>", "team2<f64,NV1,b0,compact>", ...): a string with static storage, per host thread.  hip_api.hip copies
 // it into the handle after the product (crp_csr_dev_last_kernel); nothing else reads it.
@@ -143,6 +170,10 @@ hipError_t spmm_rm_f32_rowgroup(const SpmmArgsF32 &a, hipStream_t s);
 // sddmm_kernels.hip: row-major operands, any width and alignment, both sources
 hipError_t sddmm_rm_f64(const SddmmArgs<double> &a, hipStream_t s);
 hipError_t sddmm_rm_f32(const SddmmArgs<float> &a, hipStream_t s);
+
+// attention_kernels.hip: fused scores, online row softmax and product with V; row-major operands, any widths and alignment
+hipError_t attention_rm_f64(const AttnArgs<double> &a, hipStream_t s);
+hipError_t attention_rm_f32(const AttnArgs<float> &a, hipStream_t s);
 
 // softmax_kernels.hip: row softmax over a CSR pattern and its Jacobian product; rowptr entries index the value arrays directly
 hipError_t row_softmax_f64(int nrow, const int *rowptr, const double *s, double *y, hipStream_t st);

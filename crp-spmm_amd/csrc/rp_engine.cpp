@@ -85,6 +85,12 @@ struct crp_rp_spmm
     bool    host_vals_stale = false;             // A_val (host) is behind the device matrices: refreshed where it is read
     // row softmax (crp_rp_spmm_row_softmax_ex), uploaded by its first call: A_rowptr as a device array
     int *sm_rowptr = nullptr;
+    // fused attention (crp_rp_spmm_attention_ex), allocated by its first call of a dtype: the receive buffer of V's rows -- K's land
+    // in the forward exchange's -- and the scratch of host operands (Q, V, lse; a host p_out takes sd_out)
+    bool    at_built = false, at_ready64 = false, at_ready32 = false;
+    double *at_recv_dev = nullptr;
+    float  *at_recv32_dev = nullptr;
+    crp::DevScratch Q_stage, Q_rm, V_stage, V_rm, at_lse;
     // staging (host-pointer API) and column-major temporaries, grown on demand
     crp::DevScratch B_stage, C_stage, B_rm, C_rm;
     // the stream the last exec ran on, and an event at its end: a value update on the engine's own stream must
@@ -252,6 +258,8 @@ static void build_device_matrices(crp_rp_spmm *e, const double *A_val_dev)
             HIP_OK(crp_csr_dev_create(m, e->loc_B_nrow, e->A_rowptr.data(), e->dev_colidx_host.data(), e->A_val.data(), &e->A_dev));
         return;
     }
+    // (a row's entries keep A_val's order inside its part: the fused attention's online softmax adds them in CSR order, and its
+    //  bit-identity across rank counts rests on that)
     auto make = [&](const std::vector<int> &rows, std::vector<long long> &src, crp_csr_dev_p *out) {
         std::vector<int> rp(rows.size() + 1, 0), ci, start(rows.size(), 0);
         std::vector<double> va;
@@ -363,6 +371,13 @@ void crp_rp_spmm_free(crp_rp_spmm_p *rp_spmm)
         crp_dev_free(e->dv_tvals);
         crp_dev_free(e->dv_t_pos);
         crp_dev_free(e->sm_rowptr);
+        crp_dev_free(e->at_recv_dev);
+        crp_dev_free(e->at_recv32_dev);
+        e->Q_stage.release();
+        e->Q_rm.release();
+        e->V_stage.release();
+        e->V_rm.release();
+        e->at_lse.release();
         if (e->ev_vals) crp_event_destroy(e->ev_vals);
         if (e->xstream) crp_stream_destroy(e->xstream);
         if (e->ev_packed) crp_event_destroy(e->ev_packed);
@@ -706,6 +721,157 @@ static void sddmm_impl(crp_rp_spmm *e, int layout, const T *X, long long ldX, co
     e->n_exec++;
 }
 
+// ---- O = softmax_row(scale (Q K^T)|pattern(A) (+ A's values)) V over this rank's rows of A (crp_rp_spmm_attention_ex / _f32_ex) ----
+static int attention(crp_csr_dev_p A, int n, double scale, int bias, const double *Q, long long ldQ, const double *K0, long long ldK0,
+                     const double *K1, long long ldK1, const double *V0, long long ldV0, const double *V1, long long ldV1, double *O,
+                     long long ldO, double *lse, double *p_out, const int *out_pos, void *s)
+{
+    return crp_attention_csr_f64(A, n, n, scale, bias, Q, ldQ, K0, ldK0, K1, ldK1, V0, ldV0, V1, ldV1, O, ldO, lse, p_out, out_pos, s);
+}
+static int attention(crp_csr_dev_p A, int n, double scale, int bias, const float *Q, long long ldQ, const float *K0, long long ldK0,
+                     const float *K1, long long ldK1, const float *V0, long long ldV0, const float *V1, long long ldV1, float *O,
+                     long long ldO, float *lse, float *p_out, const int *out_pos, void *s)
+{
+    return crp_attention_csr_f32(A, n, n, scale, bias, Q, ldQ, K0, ldK0, K1, ldK1, V0, ldV0, V1, ldV1, O, ldO, lse, p_out, out_pos, s);
+}
+
+// first attention call of a dtype: the second receive buffer (rows of x.ld elements, zeroed once: the fp32 rows' pad columns are
+// never written again), and the parts' positions in A_val; blocks
+template <class T>
+static T *attention_recv(crp_rp_spmm *e, const Xchg &x, T **buf, bool *ready)
+{
+    if (!*ready)
+    {
+        upload_part_positions(e);
+        if (e->n_recv_rows > 0 && x.ld > 0)
+        {
+            const size_t bytes = sizeof(T) * (size_t) e->n_recv_rows * (size_t) x.ld;
+            void *p = NULL;
+            HIP_OK(crp_dev_malloc(&p, bytes));
+            *buf = (T *) p;
+            HIP_OK(crp_dev_memset(p, 0, bytes, NULL));
+            HIP_OK(crp_stream_sync(NULL));
+        }
+        *ready = true;
+        e->at_built = true;
+    }
+    return *buf;
+}
+static double *attention_recv(crp_rp_spmm *e, const Xchg &x, const double *) { return attention_recv(e, x, &e->at_recv_dev, &e->at_ready64); }
+static float *attention_recv(crp_rp_spmm *e, const Xchg &x, const float *) { return attention_recv(e, x, &e->at_recv32_dev, &e->at_ready32); }
+
+// pack_exchange_run for two operands partitioned like B: the rows of Kd travel into x.recv, then those of Vd into recv2, both
+// through x.send, which is reused in stream order.  With timing off and a split engine the interior part is enqueued on s first and
+// both packs and both exchanges run beside it on the engine's second stream, from the point of s where the operands are ready; the
+// boundary part follows on s after the second exchange has landed.  Otherwise everything runs on s in sequence and, with timing
+// on, bills to t_pack and t_a2a (t0 is left at the start of the kernels).
+template <class T, class F>
+static void pack_exchange_run2(crp_rp_spmm *e, const Xchg &x, void *recv2, const T *Kd, long long ldKd, const T *Vd, long long ldVd, void *s,
+                               double &t0, F &&product)
+{
+    const int n = e->glb_n;
+    const bool timing = e->timing != 0;
+    const bool split = (e->A_int != nullptr);
+    auto pack = [&](const T *Bd, long long ldBd, void *st) {
+        if (e->n_send_rows > 0 && n > 0) HIP_OK(gather((int) e->n_send_rows, n, e->sridxs_dev, Bd, ldBd, (T *) x.send, x.ld, st));
+    };
+    auto exchange = [&](void *recv, void *st) {
+        const double tx0 = get_wtime_sec();
+        e->comm->alltoallv_dev_f64(e->comm->ctx, (const double *) x.send, x.sc, x.sd, (double *) recv, x.rc, x.rd, st);
+        e->t_a2a_host += get_wtime_sec() - tx0;
+    };
+    if (timing) { HIP_OK(crp_stream_sync(s)); }
+    t0 = get_wtime_sec();
+    if (split && !timing)
+    {
+        HIP_OK(crp_event_record(e->ev_packed, s));          // (here: the operands are ready)
+        product(e->A_int, 1);
+        HIP_OK(crp_stream_wait_event(e->xstream, e->ev_packed));
+        pack(Kd, ldKd, e->xstream);
+        exchange(x.recv, e->xstream);
+        pack(Vd, ldVd, e->xstream);
+        exchange(recv2, e->xstream);
+        HIP_OK(crp_event_record(e->ev_landed, e->xstream));
+        HIP_OK(crp_stream_wait_event(s, e->ev_landed));
+        product(e->A_bnd, 2);
+        return;
+    }
+    for (int op = 0; op < 2; op++)
+    {
+        pack(op == 0 ? Kd : Vd, op == 0 ? ldKd : ldVd, s);
+        if (timing)
+        {
+            HIP_OK(crp_stream_sync(s));
+            const double t1 = get_wtime_sec();
+            e->t_pack += t1 - t0;
+            t0 = t1;
+        }
+        if (e->nproc > 1) exchange(op == 0 ? x.recv : recv2, s);
+        if (timing)
+        {
+            HIP_OK(crp_stream_sync(s));
+            const double t1 = get_wtime_sec();
+            e->t_a2a += t1 - t0;
+            t0 = t1;
+        }
+    }
+    if (split)
+    {
+        product(e->A_int, 1);
+        product(e->A_bnd, 2);
+    }
+    else product(e->A_dev, 0);
+}
+
+template <class T>
+static void attention_impl(crp_rp_spmm *e, int layout, double scale, int bias, const T *Q, long long ldQ, const T *K, long long ldK,
+                           const T *V, long long ldV, T *O, long long ldO, T *lse, T *p_out, void *stream_)
+{
+    if (e == NULL) return;
+    ASSERT_PRINTF(!e->plan_only, "rp_spmm_attention on a plan-only engine (no device state)\n");
+    ASSERT_PRINTF(layout == 0 || layout == 1, "layout must be 0 or 1\n");
+    ASSERT_PRINTF(bias == 0 || bias == 1, "bias must be 0 or 1\n");
+    ASSERT_PRINTF(scale - scale == 0.0, "scale must be finite\n");
+    const double t_begin = get_wtime_sec();
+    void *s = stream_;
+    const int n = e->glb_n, kb = e->loc_B_nrow, m = e->A_nrow;
+    const size_t nnz = e->A_val.size();
+    const bool timing = e->timing != 0;
+    double t0;
+
+    const bool Q_on_dev = on_device(Q), K_on_dev = on_device(K), V_on_dev = on_device(V), O_on_dev = on_device(O);
+    const bool lse_host = lse != NULL && m > 0 && !on_device(lse), p_host = p_out != NULL && nnz > 0 && !on_device(p_out);
+
+    // ---- operands as device-resident row-major views: K takes B's buffers and the forward exchange, O takes C's
+    const Xchg x = exchange_of(e, K);
+    T *recv2 = attention_recv(e, x, K);
+    const crp::InView<T> Kv = crp::operand_in(layout, K, ldK, kb, n, K_on_dev, e->B_stage, e->B_rm, s);
+    const crp::InView<T> Vv = crp::operand_in(layout, V, ldV, kb, n, V_on_dev, e->V_stage, e->V_rm, s);
+    const crp::InView<T> Qv = crp::operand_in(layout, Q, ldQ, m, n, Q_on_dev, e->Q_stage, e->Q_rm, s);
+    const crp::OutView<T> Ov = crp::operand_out(layout, O, ldO, m, n, O_on_dev, e->C_stage, e->C_rm);
+    T *lsed = lse_host ? e->at_lse.grow<T>((size_t) m) : lse;
+    T *pd = p_host ? e->sd_out.grow<T>(nnz) : p_out;
+
+    // ---- pack and exchange K, then V; the kernels: the parts of a split engine write O and lse through their row maps and p_out
+    // through their positions in A_val
+    pack_exchange_run2(e, x, recv2, Kv.p, Kv.ld, Vv.p, Vv.ld, s, t0, [&](crp_csr_dev_p A, int part) {
+        if (n == 0 || crp_csr_dev_nrow(A) == 0) return;
+        const int *pos = part == 1 ? e->sd_int_pos : (part == 2 ? e->sd_bnd_pos : nullptr);
+        HIP_OK(attention(A, n, scale, bias, Qv.p, Qv.ld, Kv.p, Kv.ld, (const T *) x.recv, x.ld, Vv.p, Vv.ld, (const T *) recv2, x.ld, Ov.p,
+                         Ov.ld, lsed, pd, pos, s));
+    });
+    if (lse_host) HIP_OK(crp_dev_memcpy(lse, lsed, (size_t) m * sizeof(T), 1, s));
+    if (p_host) HIP_OK(crp_dev_memcpy(p_out, pd, nnz * sizeof(T), 1, s));
+    const bool synced = crp::finish(Ov, s, [&] {
+        if (!timing) return;
+        HIP_OK(crp_stream_sync(s));
+        e->t_spmm += get_wtime_sec() - t0;
+    });
+    complete(e, s, synced, lse_host || p_host || !Q_on_dev || !K_on_dev || !V_on_dev || timing);
+    e->t_exec += get_wtime_sec() - t_begin;
+    e->n_exec++;
+}
+
 // ---- C := A^T * B (crp_rp_spmm_exec_t_ex) --------------------------------------------------------------------------------------
 // First call: the two-source local matrix, its remote columns renumbered behind the local ones, is transposed on the device
 // (crp_csr_transpose) and cut by rows into At_loc and At_rem; the rows that come back are grouped by the C row they add to.
@@ -908,6 +1074,22 @@ void crp_rp_spmm_sddmm_f32_ex(crp_rp_spmm_p e, int layout, const float *X, long 
 }
 
 int crp_rp_spmm_sddmm_built(crp_rp_spmm_p e) { return (e && e->sd_built) ? 1 : 0; }
+
+void crp_rp_spmm_attention_ex(crp_rp_spmm_p e, int layout, double scale, int bias, const double *Q, long long ldQ, const double *K,
+                              long long ldK, const double *V, long long ldV, double *O, long long ldO, double *lse, double *p_out,
+                              void *stream_)
+{
+    attention_impl<double>(e, layout, scale, bias, Q, ldQ, K, ldK, V, ldV, O, ldO, lse, p_out, stream_);
+}
+
+void crp_rp_spmm_attention_f32_ex(crp_rp_spmm_p e, int layout, double scale, int bias, const float *Q, long long ldQ, const float *K,
+                                  long long ldK, const float *V, long long ldV, float *O, long long ldO, float *lse, float *p_out,
+                                  void *stream_)
+{
+    attention_impl<float>(e, layout, scale, bias, Q, ldQ, K, ldK, V, ldV, O, ldO, lse, p_out, stream_);
+}
+
+int crp_rp_spmm_attention_built(crp_rp_spmm_p e) { return (e && e->at_built) ? 1 : 0; }
 
 void crp_rp_spmm_exec_ex(crp_rp_spmm_p e, int BC_layout, const double *B, long long ldB, double *C,
                          long long ldC, void *stream_)

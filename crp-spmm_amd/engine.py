@@ -96,6 +96,29 @@ def _out_ptr(out, f32, nnz):
     return out.ctypes.data or None, out
 
 
+def _vec_ptr(name, x, f32, count):
+    """(address, keepalive) of an optional 1-D contiguous float64 (f32: float32) result of ``attention`` with ``count`` entries,
+    on the host or the device; (None, None) for None."""
+    if x is None:
+        return None, None
+    dname = "float32" if f32 else "float64"
+    try:
+        import torch
+        if isinstance(x, torch.Tensor):
+            if x.dtype != (torch.float32 if f32 else torch.float64) or x.dim() != 1:
+                raise TypeError("%s must be 1-D %s, like the operands" % (name, dname))
+            if not x.is_contiguous() or x.numel() != count:
+                raise ValueError("%s must be contiguous with %d entries" % (name, count))
+            return x.data_ptr() or None, x
+    except ImportError:
+        pass
+    if not isinstance(x, np.ndarray) or x.dtype != np.dtype(dname) or x.ndim != 1:
+        raise TypeError("%s must be a 1-D %s torch tensor or numpy array, like the operands" % (name, dname))
+    if not x.flags.c_contiguous or not x.flags.writeable or x.size != count:
+        raise ValueError("%s must be contiguous and writeable with %d entries" % (name, count))
+    return x.ctypes.data or None, x
+
+
 def _f32_operands(B, C_out):
     """TypeError unless B and C are both float32 (``exec_t_f32``), before any C call."""
     if _operands_dtype(B, C_out) != "f32":
@@ -226,6 +249,41 @@ class RpSpmm:
     def sddmm_built(self):
         """True once a ``sddmm`` has uploaded the positions its row parts write through (crp_rp_spmm_sddmm_built)."""
         return bool(self._lib.crp_rp_spmm_sddmm_built(self.handle))
+
+    def attention(self, layout, Q, K, V, out, scale=1.0, bias=False, lse=None, p_out=None, stream=None):
+        """Fused sparse attention over this rank's rows of A (crp_rp_spmm_attention_ex / _f32_ex, by the operands' dtype):
+        out[i] = sum_p softmax_p(scale * <Q[i], K[c_p]> (+ the engine's current value of p with ``bias``)) * V[c_p] over the
+        nonzeros p = (i, c_p) of row i.  Q and ``out`` are this rank's A_nrow x glb_n blocks, K and V its loc_B_nrow x glb_n
+        blocks (layouts and operands as ``exec``); ``lse`` (A_nrow entries) and ``p_out`` (nnz entries in the order of the A_val
+        given to init) are optional 1-D arrays or tensors of the same dtype, on the host or the device.  The engine's values
+        are not changed.  Mixed dtypes, wrong shapes and wrong lengths raise before the library is called."""
+        dt = _operands_dtype(Q, K)
+        if _operands_dtype(V, out) != dt:
+            raise TypeError("Q, K, V and out must have the same dtype")
+        f32 = dt == "f32"
+        if bias not in (False, True, 0, 1):
+            raise ValueError("bias must be a bool, got %r" % (bias,))
+        scale = float(scale)
+        if not np.isfinite(scale):
+            raise ValueError("scale must be finite, got %r" % (scale,))
+        qp, ldq, _kq = _ptr_ld(Q, layout, f32)
+        kp, ldk, _kk = _ptr_ld(K, layout, f32)
+        vp, ldv, _kv = _ptr_ld(V, layout, f32)
+        op, ldo, _ko = _ptr_ld(out, layout, f32)
+        kb = getattr(self, "loc_B_nrow", None)
+        _check_blocks(layout, self.glb_n, (("Q", Q, self.A_nrow), ("K", K, kb), ("V", V, kb), ("out", out, self.A_nrow)))
+        lp, _kl = _vec_ptr("lse", lse, f32, self.A_nrow)
+        pp, _kp = _vec_ptr("p_out", p_out, f32, self.nnz())
+        if stream is None:
+            stream = _current_stream(out)
+        if stream is None:
+            stream = _current_stream(Q)
+        fn = self._lib.crp_rp_spmm_attention_f32_ex if f32 else self._lib.crp_rp_spmm_attention_ex
+        fn(self.handle, layout, scale, int(bool(bias)), qp, ldq, kp, ldk, vp, ldv, op, ldo, lp, pp, stream)
+
+    def attention_built(self):
+        """True once an ``attention`` has allocated V's receive buffer (crp_rp_spmm_attention_built)."""
+        return bool(self._lib.crp_rp_spmm_attention_built(self.handle))
 
     @property
     def transposed_built(self):

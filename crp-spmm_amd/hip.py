@@ -157,6 +157,93 @@ class CsrDev:
                 fn.__name__)
         return out
 
+    def attention(self, Q, K0, V0, K1=None, V1=None, scale=1.0, bias=False, out=None, lse=None, p_out=None, out_pos=None,
+                  stream=None):
+        """Fused sparse attention over this matrix's pattern (crp_attention_csr_f64 / _f32, by the operands' dtype):
+        out[i] = sum_p softmax_p(scale * <Q[i], K[c_p]> (+ the matrix's value of p with ``bias``)) * V[c_p] over the nonzeros
+        p = (i, c_p) of row i; c >= 0 reads row c of K0 / V0, c < 0 row ~c of K1 / V1.  Q, K0, K1 are 2-D row-major float64 or
+        float32 cuda tensors of nk columns, V0, V1 of nv columns, all of one dtype; ``out`` a 2-D tensor of nv columns with a
+        row per row of Q (allocated when None).  Optional outputs: ``lse`` a 1-D contiguous tensor with an entry per row of
+        ``out``, ``p_out`` a 1-D contiguous tensor of nnz entries for the probabilities -- nonzero p writes p_out[out_pos[p]]
+        when ``out_pos`` (int32, nnz entries) is given.  The matrix's values are not changed.  Returns ``out``.  Mixed
+        dtypes, wrong shapes and tensors that are not on the device raise before the library is called."""
+        import torch
+        if (K1 is None) != (V1 is None):
+            raise ValueError("K1 and V1 come together")
+        kops = [("Q", Q), ("K0", K0)] + ([("K1", K1)] if K1 is not None else [])
+        vops = [("V0", V0)] + ([("V1", V1)] if V1 is not None else []) + ([("out", out)] if out is not None else [])
+        for name, t in kops + vops:
+            if not (isinstance(t, torch.Tensor) and t.dim() == 2):
+                raise TypeError("%s must be a 2-D torch tensor on the device" % name)
+            if t.dtype not in (torch.float64, torch.float32):
+                raise TypeError("%s must be float64 or float32, got %s" % (name, t.dtype))
+            if t.dtype != Q.dtype:
+                raise TypeError("the operands must have one dtype (Q is %s, %s is %s)" % (Q.dtype, name, t.dtype))
+            if t.shape[1] > 1 and t.stride(1) != 1:
+                raise ValueError("%s must be contiguous along its rows" % name)
+        for name, t in (("lse", lse), ("p_out", p_out)):
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor):
+                raise TypeError("%s must be a torch tensor on the device" % name)
+            if t.dtype != Q.dtype:
+                raise TypeError("%s must have the operands' dtype (%s is %s, Q is %s)" % (name, name, t.dtype, Q.dtype))
+        if bias not in (False, True, 0, 1):
+            raise ValueError("bias must be a bool, got %r" % (bias,))
+        scale = float(scale)
+        if not np.isfinite(scale):
+            raise ValueError("scale must be finite, got %r" % (scale,))
+        nk, nv = int(Q.shape[1]), int(V0.shape[1])
+        if nk < 1 or nv < 1:
+            raise ValueError("the operands need at least one column")
+        for name, t in kops[1:]:
+            if t.shape[1] != nk:
+                raise ValueError("%s has %d columns, Q has %d" % (name, t.shape[1], nk))
+        for name, t in vops[1:]:
+            if t.shape[1] != nv:
+                raise ValueError("%s has %d columns, V0 has %d" % (name, t.shape[1], nv))
+        x_nrow = getattr(self, "_x_nrow", self.nrow)
+        if Q.shape[0] < x_nrow:
+            raise ValueError("Q has %d rows, the matrix needs %d" % (Q.shape[0], x_nrow))
+        for name, t in (("K0", K0), ("V0", V0)):
+            if t.shape[0] < self.ncol:
+                raise ValueError("%s has %d rows, the matrix has %d columns" % (name, t.shape[0], self.ncol))
+        if K1 is not None and V1.shape[0] != K1.shape[0]:
+            raise ValueError("K1 has %d rows, V1 %d" % (K1.shape[0], V1.shape[0]))
+        if out is not None and out.shape[0] < x_nrow:
+            raise ValueError("out has %d rows, the matrix needs %d" % (out.shape[0], x_nrow))
+        nnz = self.nnz
+        if lse is not None and (lse.dim() != 1 or not lse.is_contiguous() or lse.numel() < x_nrow):
+            raise ValueError("lse must be 1-D and contiguous with %d entries" % x_nrow)
+        if out_pos is not None:
+            if not (isinstance(out_pos, torch.Tensor) and out_pos.dtype == torch.int32 and out_pos.dim() == 1
+                    and out_pos.is_contiguous()):
+                raise TypeError("out_pos must be a contiguous 1-D int32 torch tensor on the device")
+            if out_pos.numel() != nnz:
+                raise ValueError("out_pos has %d entries, the matrix %d nonzeros" % (out_pos.numel(), nnz))
+            if p_out is None:
+                raise ValueError("out_pos needs a p_out to write into")
+        if p_out is not None:
+            if p_out.dim() != 1 or not p_out.is_contiguous():
+                raise ValueError("p_out must be 1-D and contiguous")
+            if out_pos is None and p_out.numel() < nnz:
+                raise ValueError("p_out has %d entries, the matrix %d nonzeros" % (p_out.numel(), nnz))
+        named = kops + vops + [(n_, t) for n_, t in (("lse", lse), ("p_out", p_out), ("out_pos", out_pos)) if t is not None]
+        for name, t in named:
+            if not t.is_cuda or t.device != Q.device:
+                raise TypeError("%s must be on the device, with Q" % name)      # (all pointers are device pointers)
+        if out is None:
+            out = torch.empty((x_nrow, nv), dtype=Q.dtype, device=Q.device)
+        if self.nrow == 0:
+            return out
+        fn = self._lib.crp_attention_csr_f64 if Q.dtype == torch.float64 else self._lib.crp_attention_csr_f32
+        k1p, ldk1, v1p, ldv1 = (K1.data_ptr(), K1.stride(0), V1.data_ptr(), V1.stride(0)) if K1 is not None else (None, 0, None, 0)
+        ptr = lambda t: (t.data_ptr() or None) if t is not None else None
+        L.check(fn(self.handle, nk, nv, scale, int(bool(bias)), Q.data_ptr(), Q.stride(0), ptr(K0), K0.stride(0), k1p, ldk1,
+                   ptr(V0), V0.stride(0), v1p, ldv1, out.data_ptr(), out.stride(0), ptr(lse), ptr(p_out), ptr(out_pos),
+                   _stream(out) if stream is None else stream), fn.__name__)
+        return out
+
     def row_softmax(self, s, out=None, stream=None):
         """Row softmax over this matrix's pattern (crp_csr_dev_row_softmax_f64 / _f32, by the dtype of ``s``): for every row,
         out[p] = exp(s[p] - max) / sum over the row's nonzeros p, which count in the handle's CSR order -- what ``sddmm``

@@ -134,6 +134,32 @@ void crp_rp_spmm_sddmm_ex(crp_rp_spmm_p rp_spmm, int layout, const double *X, lo
 void crp_rp_spmm_sddmm_f32_ex(crp_rp_spmm_p rp_spmm, int layout, const float *X, long long ldX,
                               const float *Y, long long ldY, float *out, int mode, void *stream);
 int crp_rp_spmm_sddmm_built(crp_rp_spmm_p rp_spmm);
+/* Fused sparse attention over this rank's rows of A (crp_attention_csr_f64 / _f32 in crpspmm_hip.h, with nk = nv = glb_n): for
+ * every local row i with nonzeros p = (i, c_p) of the GLOBAL matrix, s_p = scale * < Q[i], K[c_p] > (+ the engine's current
+ * value of p when bias = 1) and O[i] = sum_p softmax_p(s) * V[c_p].  Q and O are this rank's A_nrow x glb_n blocks (partitioned
+ * like A's rows), K and V its loc_B_nrow x glb_n blocks (partitioned like B); lse (A_nrow entries) and p_out (one value per
+ * local nonzero IN THE ORDER OF THE A_val GIVEN TO INIT, what crp_rp_spmm_update_values_dev and the row softmax's backward take)
+ * are optional (NULL: skipped).  Every pointer may be a host or a device pointer.  The engine's values are not changed: an
+ * exec before and after the call gives the same bits.
+ * The call needs the rows of K and of V that exec needs of B: it runs the forward exchange twice, K into the forward
+ * exchange's receive buffer and then V into a second one (per dtype, rows padded as the fp32 exchange pads them), which the
+ * first call of a dtype allocates and nothing before it does (crp_rp_spmm_attention_built: 0, then 1; that call blocks); the
+ * send buffer is reused in stream order.  With timing off and a split engine the interior rows' kernel is enqueued on the
+ * caller's stream beside both packs and exchanges, which run on the engine's second stream, and the boundary rows' kernel
+ * after both have landed; with timing on the phases run in sequence.  The parts of a split engine write O and lse through their
+ * row maps and p_out through the positions crp_rp_spmm_sddmm_ex uses.  A row's entries keep A_val's order inside the parts,
+ * and a row's bits depend on its entries in that order only (crpspmm_hip.h), so O, lse and p_out are bit-identical across
+ * rank counts, timing modes and repeated calls, and equal crp_attention_csr_* on the whole matrix.  Layout 1, staging,
+ * streams, statistics (pack, redistribution and SpMM time; n_exec counts these calls too) and the completion rule as
+ * crp_rp_spmm_sddmm_ex: with device pointers and timing off nothing synchronises.  glb_n = 0 computes nothing.  A plan-only
+ * engine aborts as in exec, as do a layout or a bias other than 0 or 1 and a non-finite scale; a NULL engine is a no-op. */
+void crp_rp_spmm_attention_ex(crp_rp_spmm_p rp_spmm, int layout, double scale, int bias, const double *Q, long long ldQ,
+                              const double *K, long long ldK, const double *V, long long ldV, double *O, long long ldO,
+                              double *lse, double *p_out, void *stream);
+void crp_rp_spmm_attention_f32_ex(crp_rp_spmm_p rp_spmm, int layout, double scale, int bias, const float *Q, long long ldQ,
+                                  const float *K, long long ldK, const float *V, long long ldV, float *O, long long ldO,
+                                  float *lse, float *p_out, void *stream);
+int crp_rp_spmm_attention_built(crp_rp_spmm_p rp_spmm);
 void crp_rp_spmm_print_stat(crp_rp_spmm_p rp_spmm);
 void crp_rp_spmm_clear_stat(crp_rp_spmm_p rp_spmm);
 /* rp_spmm_init for a caller that ALSO holds the values in device memory, in the order of A_val (A_val_dev: the panel a

@@ -311,6 +311,49 @@ int crp_sddmm_csr_f32(crp_csr_dev_p A, int n, const float *X, long long ldX,
                       const float *Y0, long long ldY0, const float *Y1, long long ldY1,
                       float *out, const int *out_pos, int mode, void *stream);
 
+/* ---- fused sparse attention over A's pattern -----------------------------------
+ * For every row i of the handle with entries p = (i, c_p), p in the handle's CSR order:
+ *   s_p = scale * < Q[i][0:nk], K[c_p][0:nk] >      (bias = 1: + A's current value of p; the fp32 form adds the fp32 copy
+ *                                                    of the value that crp_sddmm_csr_f32 mode 1 uses)
+ *   O[i][0:nv] = sum_p softmax_p(s) * V[c_p][0:nv]
+ * -- crp_sddmm_csr_*, a scale, crp_row_softmax_*, a value update and crp_spmm_csr_* in one trip over the row, without the
+ * nnz-sized intermediates and without touching A's values.  Row-major operands: Q and O have a row per row of A (row
+ * rowmap[t] for row t of a handle with a row map); K0 / V0 and K1 / V1 are the two sources of the column code, as Y0 / Y1
+ * of the SDDMM (a source no code names may be NULL).  The fp32 form takes scale as a double and rounds it to float once.
+ * Optional outputs, each skipped when NULL: lse[i] = m + log(l) per row, indexed like the rows of O (m = the row's maximum
+ * score, l = sum_p exp(s_p - m)); p_out = the probabilities exp(s_p - m) / l, nonzero p written to p_out[out_pos[p]]
+ * (p_out[p] when out_pos is NULL), as the SDDMM writes -- the order crp_csr_dev_update_values and crp_row_softmax_bwd_*
+ * take, so the existing calls form the backward pass from it.  Only what is named is written: O[i][0:nv] of every row,
+ * lse of every row, the nnz entries of p_out.  All pointers are device pointers; the launch is asynchronous on `stream`.
+ * Special cases: an empty row writes +0 to O[i][0:nv] and lse = -inf; a one-entry row with a finite score gives O[i] =
+ * V[c] bit for bit; a score of -inf (a bias value or a product) is a masked edge that contributes exactly nothing, p_out =
+ * 0 (its V row may still be read; V is taken to be finite); an all-masked row gives zeros, lse = -inf; a row with NaN or
+ * +inf among its scores has unspecified outputs in that row only.
+ * Fixed order: a group of L lanes owns a row; with W = elements per 16 bytes and G(n) = 8, 16, 32 or 64 for n <= 8 W, 16 W,
+ * 32 W, else, L = max(G(nk), G(nv)); column j of Q / K and of V / O belongs to lane (j / W) % L.  The dot of an entry is
+ * formed as crp_sddmm_csr_* forms it for (dtype, nk), so the bits before `* scale` are the SDDMM's; s = dot * scale (one
+ * rounding; bias: + value, one more).  The row goes in batches of 8 entries in ascending p with an online softmax:
+ * m' = max(m, batch), f = exp(m - m'), e_u = exp(s_u - m'); l = l * f, then l = l + e_u in ascending u; acc[j] = acc[j] * f,
+ * then acc[j] = fma(e_u, V[c_u][j], acc[j]) in ascending u; after the row O = acc / l (IEEE).  The maximum is never
+ * deferred.  A row's bits depend on (dtype, nk, nv, scale, bias) and the row's entries in CSR order ONLY: not on alignment,
+ * leading dimensions (operands that cannot be accessed in 16-byte pieces are accessed by elements in the same assignment),
+ * the source a K / V row comes from, the handle (full matrix or row subset), the optional outputs or the other rows.
+ * Error bound: DESIGN.md 5j.
+ * Returns 0 (also for a handle without rows, for which nothing is launched), a HIP error (> 0), or a negative argument
+ * error, before which nothing is written: -1 for a NULL handle, Q or O, for a NULL K or V source that a code names, for
+ * nk < 1 or nv < 1, for a bias other than 0 or 1 and for a non-finite scale; -4 for a leading dimension below its width
+ * (nk for Q and K, nv for V and O; of a source that is not NULL). */
+int crp_attention_csr_f64(crp_csr_dev_p A, int nk, int nv, double scale, int bias,
+                          const double *Q, long long ldQ,
+                          const double *K0, long long ldK0, const double *K1, long long ldK1,
+                          const double *V0, long long ldV0, const double *V1, long long ldV1,
+                          double *O, long long ldO, double *lse, double *p_out, const int *out_pos, void *stream);
+int crp_attention_csr_f32(crp_csr_dev_p A, int nk, int nv, double scale, int bias,
+                          const float *Q, long long ldQ,
+                          const float *K0, long long ldK0, const float *K1, long long ldK1,
+                          const float *V0, long long ldV0, const float *V1, long long ldV1,
+                          float *O, long long ldO, float *lse, float *p_out, const int *out_pos, void *stream);
+
 /* ---- row softmax over A's pattern (edge softmax) and its Jacobian product ------
  * For every row r with entries p in [rowptr[r], rowptr[r + 1]):
  *   forward :  m = max_p s[p],  e_p = exp(s[p] - m),  y[p] = e_p / sum_q e_q
