@@ -2,7 +2,8 @@
 //
 // The engines' entry points take B, C, X and Y on the host or on the device, row-major (layout 0: rows x n, ld >= n) or
 // column-major (layout 1: n x rows as stored, ld >= rows), while the kernels read and write row-major device memory.  This
-// layer is the one copy of that conversion.  It holds no engine state: the caller owns the scratch buffers and the stream.
+// layer is the one copy of that conversion.  It holds no engine state: the scratch buffers (crp::DevScratch, dev_owned.h) and the stream
+// are the caller's, and the buffers release themselves with the engine that holds them.
 //   operand_in    a source operand:  stage the used span with ONE copy if it is on the host, transpose if it is column-major
 //   operand_out   a result operand:  where to compute (the caller's memory, a row-major temporary or a host image)
 //   finish        transpose the temporary back and, for a host result, ONE 2D copy that never writes the caller's padding
@@ -14,53 +15,10 @@
 #ifndef CRP_OPERAND_VIEW_H
 #define CRP_OPERAND_VIEW_H
 
-#include "crpspmm_hip.h"
-#include "utils.h"
-
-#define HIP_OK(call)                                                              \
-    do {                                                                          \
-        int rc__ = (call);                                                        \
-        ASSERT_PRINTF(rc__ == 0, "%s failed with code %d\n", #call, rc__);        \
-    } while (0)
+#include "dtype_calls.h"      // HIP_OK, DevScratch, transpose
 
 namespace crp
 {
-
-// grow-only device scratch: raw bytes shared by both dtypes, its size kept in doubles
-struct DevScratch
-{
-    double *p = nullptr;
-    size_t  sz = 0;
-
-    template <class T> T *grow(size_t need_elems)
-    {
-        const size_t need = (need_elems * sizeof(T) + sizeof(double) - 1) / sizeof(double);
-        if (need > sz)
-        {
-            if (p) HIP_OK(crp_dev_free(p));
-            void *q = NULL;
-            HIP_OK(crp_dev_malloc(&q, need * sizeof(double)));
-            p = (double *) q;
-            sz = need;
-        }
-        return (T *) p;
-    }
-    void release()
-    {
-        crp_dev_free(p);
-        p = nullptr;
-        sz = 0;
-    }
-};
-
-static inline int transpose(int nrow, int ncol, const double *src, long long lds, double *dst, long long ldd, void *s)
-{
-    return crp_transpose_f64(nrow, ncol, src, lds, dst, ldd, s);
-}
-static inline int transpose(int nrow, int ncol, const float *src, long long lds, float *dst, long long ldd, void *s)
-{
-    return crp_transpose_f32(nrow, ncol, src, lds, dst, ldd, s);
-}
 
 // elements a rows x n operand spans from its first to its last element
 static inline size_t used_span(int layout, int rows, int n, long long ld)

@@ -21,14 +21,25 @@
 #include "crp_engine.h"
 #include "crpspmm_hip.h"
 #include "utils.h"
-#include "operand_view.h"      // HIP_OK
+#include "dtype_calls.h"       // HIP_OK, the owners (dev_owned.h), sum_segments, inner_sddmm, the row softmax
 #include "knobs.h"
 
+// the inner row engine, released with crp_rp_spmm_free
+struct RpEngine
+{
+    crp_rp_spmm_p p = nullptr;
+    RpEngine() = default;
+    RpEngine(const RpEngine &) = delete;
+    RpEngine &operator=(const RpEngine &) = delete;
+    ~RpEngine() { if (p) crp_rp_spmm_free(&p); }
+    operator crp_rp_spmm_p() const { return p; }
+};
+
+// crp_para2d_spmm_free is `delete`: members are released in REVERSE order of declaration -- the inner row engine first, then the
+// two communicators it and the grid row use, then this engine's own device buffers, which is why those come first here.
 struct crp_para2d_spmm
 {
-    crp_rp_spmm_p rp = nullptr;
-    crp_comm_t   *comm_glb = nullptr;   // not owned
-    crp_comm_t   *comm_col = nullptr;   // owned
+    crp_comm_t *comm_glb = nullptr;        // not owned
     size_t rA_cost = 0;
     double t_init = 0.0, t_ag_A = 0.0;
     int    value_uploads = 1;              // times the panel's values went host -> device (0: filled from the device all-gather)
@@ -37,19 +48,21 @@ struct crp_para2d_spmm
     int    pn = 1, pi = 0, pj = 0;
     std::vector<long long> row_nnz;        // pn: nonzeros of the grid row's A0 slices
     std::vector<long long> row_off;        // pn + 1: their prefix sums = where every slice starts in the panel
-    // ---- state of update_values / sddmm on a grid with pn > 1: nothing below exists before the first such call
-    crp_comm_t *comm_row = nullptr;        // owned; split again from comm_glb by the first update_values / sddmm
-    std::vector<double> panel_val;         // update_values: the panel's values as gathered
-    void  *sd_part = nullptr;              // partial dots of the panel: row_off[pn] entries (these three are sized for fp64, used by both dtypes)
-    void  *sd_recv = nullptr;              // the pn runs received: fp64 stride slice nnz, fp32 stride round_up(slice nnz, 2)
-    void  *sd_out = nullptr;               // staging of a host `out`
-    float *sd_send32 = nullptr;            // fp32: every peer's run in a slot of round_up(nnz_j, 2) floats
-    bool   sd_built64 = false, sd_built32 = false;
-    void  *dv_panel = nullptr;             // update_values_dev: the panel's values as gathered (sized for fp64)
-    std::vector<char> dv_host;             // ... staged on the host when the communicator has no allgatherv_dev
     // ---- row softmax over the slice (pn > 1): the slice's own row pointer from 0, kept by init; on the device from the first call
     std::vector<int> slice_rowptr;
-    int   *sm_rowptr = nullptr;
+    crp::DevArray<int> sm_rowptr;
+    // ---- state of update_values / sddmm on a grid with pn > 1: nothing below exists before the first such call
+    std::vector<double> panel_val;         // update_values: the panel's values as gathered
+    crp::DevArray<double> dv_panel;        // update_values_dev: the panel's values as gathered (sized for fp64)
+    std::vector<char> dv_host;             // ... staged on the host when the communicator has no allgatherv_dev
+    crp::DevArray<float>  sd_send32;       // fp32: every peer's run in a slot of round_up(nnz_j, 2) floats
+    crp::DevArray<double> sd_out;          // staging of a host `out` (these three are sized for fp64, used by both dtypes)
+    crp::DevArray<double> sd_recv;         // the pn runs received: fp64 stride slice nnz, fp32 stride round_up(slice nnz, 2)
+    crp::DevArray<double> sd_part;         // partial dots of the panel: row_off[pn] entries
+    bool sd_built64 = false, sd_built32 = false;
+    crp::OwnedComm comm_row;               // split again from comm_glb by the first update_values / sddmm
+    crp::OwnedComm comm_col;               // the grid column's, the inner engine's communicator
+    RpEngine rp;
 };
 
 
@@ -59,27 +72,8 @@ static long long up2(long long v) { return (v + 1) / 2 * 2; }
 // therefore collective over the WHOLE grid (every rank makes these calls anyway) -- and kept from then on.
 static crp_comm_t *row_comm(crp_para2d_spmm *e)
 {
-    if (e->comm_row == nullptr) e->comm_row = e->comm_glb->split(e->comm_glb->ctx, e->pi, e->pj);
+    if (e->comm_row == nullptr) e->comm_row = crp::OwnedComm(e->comm_glb->split(e->comm_glb->ctx, e->pi, e->pj));
     return e->comm_row;
-}
-
-static int sum_segments(int nseg, long long len, const double *src, long long stride, double *out, void *s)
-{
-    return crp_sum_segments_f64(nseg, len, src, stride, out, s);
-}
-static int sum_segments(int nseg, long long len, const float *src, long long stride, float *out, void *s)
-{
-    return crp_sum_segments_f32(nseg, len, src, stride, out, s);
-}
-static void inner_sddmm(crp_rp_spmm_p rp, int layout, const double *X, long long ldX, const double *Y, long long ldY, double *out,
-                        int mode, void *s)
-{
-    crp_rp_spmm_sddmm_ex(rp, layout, X, ldX, Y, ldY, out, mode, s);
-}
-static void inner_sddmm(crp_rp_spmm_p rp, int layout, const float *X, long long ldX, const float *Y, long long ldY, float *out,
-                        int mode, void *s)
-{
-    crp_rp_spmm_sddmm_f32_ex(rp, layout, X, ldX, Y, ldY, out, mode, s);
 }
 
 // first SDDMM of a dtype on a grid with pn > 1: the partial buffer, the receive segments, the staging of a host `out`
@@ -89,19 +83,15 @@ static void build_sddmm(crp_para2d_spmm *e, bool f32)
     const long long p_nnz = e->row_off[e->pn], s_nnz = e->row_nnz[e->pj];
     if (!e->sd_built64 && !e->sd_built32)
     {
-        HIP_OK(crp_dev_malloc(&e->sd_part, sizeof(double) * (size_t) (p_nnz > 0 ? p_nnz : 1)));
-        HIP_OK(crp_dev_malloc(&e->sd_recv, sizeof(double) * (size_t) (s_nnz > 0 ? s_nnz * e->pn : 1)));
-        HIP_OK(crp_dev_malloc(&e->sd_out, sizeof(double) * (size_t) (s_nnz > 0 ? s_nnz : 1)));
+        e->sd_part.alloc((size_t) (p_nnz > 0 ? p_nnz : 1));
+        e->sd_recv.alloc((size_t) (s_nnz > 0 ? s_nnz * e->pn : 1));
+        e->sd_out.alloc((size_t) (s_nnz > 0 ? s_nnz : 1));
     }
     if (f32 && e->sd_send32 == nullptr)
     {
         size_t slots = 0;
         for (int j = 0; j < e->pn; j++) slots += (size_t) up2(e->row_nnz[j]);
-        void *d = NULL;
-        HIP_OK(crp_dev_malloc(&d, sizeof(float) * (slots > 0 ? slots : 2)));
-        HIP_OK(crp_dev_memset(d, 0, sizeof(float) * (slots > 0 ? slots : 2), NULL));
-        HIP_OK(crp_stream_sync(NULL));                     // (the caller's stream may not order against the null stream)
-        e->sd_send32 = (float *) d;
+        e->sd_send32.zeroed(slots > 0 ? slots : 2);
     }
     (f32 ? e->sd_built32 : e->sd_built64) = true;
 }
@@ -112,7 +102,7 @@ static void sddmm_impl(crp_para2d_spmm *e, int layout, const T *X, long long ldX
     if (e == NULL) return;
     if (e->pn == 1)
     {
-        inner_sddmm(e->rp, layout, X, ldX, Y, ldY, out, mode, s);     // one grid column: the row engine's result as it is
+        crp::inner_sddmm(e->rp, layout, X, ldX, Y, ldY, out, mode, s);     // one grid column: the row engine's result as it is
         return;
     }
     ASSERT_PRINTF(!e->plan_only, "para2d_spmm_sddmm on a plan-only engine (no device state)\n");
@@ -128,8 +118,8 @@ static void sddmm_impl(crp_para2d_spmm *e, int layout, const T *X, long long ldX
     ASSERT_PRINTF(out != NULL || s_nnz == 0, "para2d_spmm_sddmm: NULL out\n");
 
     // 1. partial dots over this rank's n_loc columns, in panel order
-    T *part = (T *) e->sd_part;
-    inner_sddmm(e->rp, layout, X, ldX, Y, ldY, part, mode, s);
+    T *part = (T *) e->sd_part.get();
+    crp::inner_sddmm(e->rp, layout, X, ldX, Y, ldY, part, mode, s);
 
     // 2. reduce-scatter along the grid row: peer j is owed the run of its slice, this rank receives pn runs of its own
     std::vector<long long> sc(pn), sd(pn), rc(pn), rd(pn);
@@ -147,19 +137,19 @@ static void sddmm_impl(crp_para2d_spmm *e, int layout, const T *X, long long ldX
         for (int j = 0; j < pn; j++)
         {
             if (e->row_nnz[j] > 0)
-                HIP_OK(crp_dev_memcpy(e->sd_send32 + slot, (const float *) e->sd_part + e->row_off[j], sizeof(float) * (size_t) e->row_nnz[j], 2, s));
+                HIP_OK(crp_dev_memcpy(e->sd_send32 + slot, (const float *) part + e->row_off[j], sizeof(float) * (size_t) e->row_nnz[j], 2, s));
             sc[j] = up2(e->row_nnz[j]) / 2; sd[j] = slot / 2; rc[j] = stride / 2; rd[j] = (long long) j * (stride / 2);
             slot += up2(e->row_nnz[j]);
         }
-        send = (const double *) e->sd_send32;
+        send = (const double *) e->sd_send32.get();
     }
-    cr->alltoallv_dev_f64(cr->ctx, send, sc.data(), sd.data(), (double *) e->sd_recv, rc.data(), rd.data(), s);
+    cr->alltoallv_dev_f64(cr->ctx, send, sc.data(), sd.data(), e->sd_recv, rc.data(), rd.data(), s);
 
     // 3. the pn runs added in ascending grid column
     if (s_nnz > 0)
     {
-        T *outd = out_on_dev ? out : (T *) e->sd_out;
-        HIP_OK(sum_segments(pn, s_nnz, (const T *) e->sd_recv, stride, outd, s));
+        T *outd = out_on_dev ? out : (T *) e->sd_out.get();
+        HIP_OK(crp::sum_segments(pn, s_nnz, (const T *) e->sd_recv.get(), stride, outd, s));
         if (!out_on_dev) HIP_OK(crp_dev_memcpy(out, outd, sizeof(T) * (size_t) s_nnz, 1, s));
     }
     // completion as crp_rp_spmm_sddmm_ex: asynchronous only with device pointers and timing off
@@ -180,8 +170,8 @@ static void para2d_init_common(crp_comm_t *comm, int pm, int pn, const int *A0_r
     e->plan_only = plan_only;
     double t0 = get_wtime_sec();
     const int r = comm->rank, pi = r / pn, pj = r % pn;
-    crp_comm_t *comm_row = comm->split(comm->ctx, pi, pj);
-    e->comm_col = comm->split(comm->ctx, pj, pi);
+    crp::OwnedComm comm_row(comm->split(comm->ctx, pi, pj));       // for the replication only: released on return
+    e->comm_col = crp::OwnedComm(comm->split(comm->ctx, pj, pi));
     e->t_init += get_wtime_sec() - t0;
 
     // ---- replicate the row panel inside the grid row (reference :49-99)
@@ -192,7 +182,7 @@ static void para2d_init_common(crp_comm_t *comm, int pm, int pn, const int *A0_r
     const int p_nrow  = A0_rowptr[(pi + 1) * pn] - p_srow;
     std::vector<int>    p_rowptr((size_t) p_nrow + 1, 0), p_colidx;
     std::vector<double> p_val;
-    void *panel_val_dev = NULL;                    // the panel's values in HBM, when the replication left them there
+    crp::DevArray<double> panel_val_dev;           // the panel's values in HBM, when the replication left them there
     if (pn > 1)
     {
         std::vector<size_t> cnt(pn), dsp(pn);
@@ -234,17 +224,17 @@ static void para2d_init_common(crp_comm_t *comm, int pm, int pn, const int *A0_r
             // host field of the engine (struct rowpara_spmm::A_val, /root/reference/src/rowpara_spmm.h:8-40), so the copy
             // down is owed to the API.  The gathered VALUES stay in HBM until the 1D engine has been built: its device
             // matrices are filled from them (crp_rp_spmm_init_dv), not uploaded a second time.
-            void *s_i = NULL, *s_v = NULL, *d_ci = NULL, *d_va = NULL, *d_ci_all = NULL, *d_va_all = NULL, *h_ci = NULL, *h_va = NULL;
-            int rc = crp_stream_create(&s_i);
-            if (rc == 0) rc = crp_stream_create(&s_v);
-            if (rc == 0) rc = crp_dev_malloc(&d_ci_all, sizeof(int) * (size_t) p_nnz);
-            if (rc == 0) rc = crp_dev_malloc(&d_va_all, sizeof(double) * (size_t) p_nnz);
-            if (rc == 0) rc = crp_host_malloc(&h_ci, sizeof(int) * (size_t) p_nnz);
-            if (rc == 0) rc = crp_host_malloc(&h_va, sizeof(double) * (size_t) p_nnz);
-            ASSERT_PRINTF(rc == 0, "para2d_spmm_init: device buffers for the panel replication (%d)\n", rc);
+            crp::DevStream s_i, s_v;
+            crp::DevArray<int> ci_all;
+            crp::HostPinned h_ci, h_va;
+            s_i.ensure();
+            s_v.ensure();
+            void *d_ci_all = ci_all.alloc((size_t) p_nnz), *d_va_all = panel_val_dev.alloc((size_t) p_nnz);
+            h_ci.alloc(sizeof(int) * (size_t) p_nnz);
+            h_va.alloc(sizeof(double) * (size_t) p_nnz);
             // own slice straight into its place of the gathered arrays (send == recv + displacement: no extra copy)
-            d_ci = (char *) d_ci_all + dsp_i[pj];
-            d_va = (char *) d_va_all + dsp_v[pj];
+            void *d_ci = (char *) d_ci_all + dsp_i[pj], *d_va = (char *) d_va_all + dsp_v[pj];
+            int rc = 0;
             if (my_nnz > 0)
             {
                 rc = crp_dev_memcpy(d_ci, A_colidx, cnt_i[pj], 0, s_i);
@@ -253,17 +243,13 @@ static void para2d_init_common(crp_comm_t *comm, int pm, int pn, const int *A0_r
             }
             comm_row->allgatherv_dev(comm_row->ctx, d_ci, cnt_i[pj], d_ci_all, cnt_i.data(), dsp_i.data(), s_i);
             comm_row->allgatherv_dev(comm_row->ctx, d_va, cnt_v[pj], d_va_all, cnt_v.data(), dsp_v.data(), s_v);
-            rc = crp_dev_memcpy(h_ci, d_ci_all, sizeof(int) * (size_t) p_nnz, 1, s_i);
-            if (rc == 0) rc = crp_dev_memcpy(h_va, d_va_all, sizeof(double) * (size_t) p_nnz, 1, s_v);
+            rc = crp_dev_memcpy(h_ci.p, d_ci_all, sizeof(int) * (size_t) p_nnz, 1, s_i);
+            if (rc == 0) rc = crp_dev_memcpy(h_va.p, d_va_all, sizeof(double) * (size_t) p_nnz, 1, s_v);
             if (rc == 0) rc = crp_stream_sync(s_i);
             if (rc == 0) rc = crp_stream_sync(s_v);
             ASSERT_PRINTF(rc == 0, "para2d_spmm_init: panel replication on the device (%d)\n", rc);
-            memcpy(p_colidx.data(), h_ci, sizeof(int) * (size_t) p_nnz);
-            memcpy(p_val.data(), h_va, sizeof(double) * (size_t) p_nnz);
-            crp_host_free(h_ci); crp_host_free(h_va);
-            crp_dev_free(d_ci_all);
-            panel_val_dev = d_va_all;              // (freed below, after crp_rp_spmm_init_dv)
-            crp_stream_destroy(s_i); crp_stream_destroy(s_v);
+            memcpy(p_colidx.data(), h_ci.p, sizeof(int) * (size_t) p_nnz);
+            memcpy(p_val.data(), h_va.p, sizeof(double) * (size_t) p_nnz);
             e->replicated_on_device = true;
         }
         else
@@ -307,19 +293,18 @@ static void para2d_init_common(crp_comm_t *comm, int pm, int pn, const int *A0_r
     const int n_loc = BC_colptr[pj + 1] - BC_colptr[pj];
     if (plan_only)
         crp_rp_spmm_init_plan_only(p_srow, p_nrow, p_rowptr.data(), p_colidx.data(), p_val.data(), B_rowptr, n_loc,
-                                   e->comm_col, &e->rp);
-    else if (panel_val_dev != NULL)
+                                   e->comm_col, &e->rp.p);
+    else if (panel_val_dev != nullptr)
     {
-        crp_rp_spmm_init_dv(p_srow, p_nrow, p_rowptr.data(), p_colidx.data(), p_val.data(), (const double *) panel_val_dev, B_rowptr, n_loc,
-                            e->comm_col, &e->rp);
+        crp_rp_spmm_init_dv(p_srow, p_nrow, p_rowptr.data(), p_colidx.data(), p_val.data(), panel_val_dev, B_rowptr, n_loc, e->comm_col,
+                            &e->rp.p);
         e->value_uploads = 0;
     }
     else
         crp_rp_spmm_init(p_srow, p_nrow, p_rowptr.data(), p_colidx.data(), p_val.data(), B_rowptr, n_loc,
-                         e->comm_col, &e->rp);
-    if (panel_val_dev != NULL) crp_dev_free(panel_val_dev);
+                         e->comm_col, &e->rp.p);
+    panel_val_dev.reset();
     e->t_init += get_wtime_sec() - t0;
-    comm_row->free(comm_row);
     *out = e;
 }
 
@@ -340,17 +325,7 @@ void crp_para2d_spmm_init_plan_only(crp_comm_t *comm, int pm, int pn, const int 
 void crp_para2d_spmm_free(crp_para2d_spmm_p *p)
 {
     if (p == NULL || *p == NULL) return;
-    crp_para2d_spmm *e = *p;
-    crp_rp_spmm_free(&e->rp);
-    if (e->comm_col) e->comm_col->free(e->comm_col);
-    if (e->comm_row) e->comm_row->free(e->comm_row);
-    if (e->sd_part) crp_dev_free(e->sd_part);
-    if (e->sd_recv) crp_dev_free(e->sd_recv);
-    if (e->sd_out) crp_dev_free(e->sd_out);
-    if (e->sd_send32) crp_dev_free(e->sd_send32);
-    if (e->dv_panel) crp_dev_free(e->dv_panel);
-    if (e->sm_rowptr) crp_dev_free(e->sm_rowptr);
-    delete e;
+    delete *p;       // every device resource, the communicators and the inner engine are members that release themselves
     *p = NULL;
 }
 
@@ -421,7 +396,7 @@ void crp_para2d_spmm_update_values_dev(crp_para2d_spmm_p e, const void *A_val_de
     const size_t isz = f32 ? sizeof(float) : sizeof(double);
     ASSERT_PRINTF(A_val_dev != NULL || e->row_nnz[pj] == 0, "para2d_spmm_update_values_dev: NULL values\n");
     const size_t p_nnz = (size_t) e->row_off[pn];
-    if (e->dv_panel == nullptr) HIP_OK(crp_dev_malloc(&e->dv_panel, sizeof(double) * (p_nnz > 0 ? p_nnz : 1)));
+    if (e->dv_panel == nullptr) e->dv_panel.alloc(p_nnz > 0 ? p_nnz : 1);
     std::vector<size_t> cnt(pn), dsp(pn);
     for (int j = 0; j < pn; j++) { cnt[j] = isz * (size_t) e->row_nnz[j]; dsp[j] = isz * (size_t) e->row_off[j]; }
     if (cr->allgatherv_dev != NULL && !crp::knobs().replicate_host)
@@ -462,19 +437,9 @@ void crp_para2d_spmm_sddmm_f32_ex(crp_para2d_spmm_p e, int layout, const float *
 // is involved; false when the slice holds no nonzero (nothing to upload or launch)
 static bool row_softmax_ready(crp_para2d_spmm *e, const char *what, int f32)
 {
-    ASSERT_PRINTF(!e->plan_only, "%s on a plan-only engine (no device state)\n", what);
-    ASSERT_PRINTF(f32 == 0 || f32 == 1, "%s: f32 must be 0 or 1\n", what);
-    if (e->row_nnz[e->pj] == 0) return false;
-    if (e->sm_rowptr == nullptr)
-    {
-        const size_t rb = sizeof(int) * e->slice_rowptr.size();
-        void *d = NULL;
-        HIP_OK(crp_dev_malloc(&d, rb));
-        HIP_OK(crp_dev_memcpy(d, e->slice_rowptr.data(), rb, 0, NULL));
-        HIP_OK(crp_stream_sync(NULL));
-        e->sm_rowptr = (int *) d;
-    }
-    return true;
+    const bool any = e->row_nnz[e->pj] != 0;
+    crp::row_softmax_ready(what, e->plan_only, f32, any, e->sm_rowptr, e->slice_rowptr, NULL);
+    return any;
 }
 
 void crp_para2d_spmm_row_softmax_ex(crp_para2d_spmm_p e, const void *s, void *y, int f32, void *stream)
@@ -487,9 +452,7 @@ void crp_para2d_spmm_row_softmax_ex(crp_para2d_spmm_p e, const void *s, void *y,
     }
     if (!row_softmax_ready(e, "para2d_spmm_row_softmax", f32)) return;
     ASSERT_PRINTF(s != NULL && y != NULL, "para2d_spmm_row_softmax: NULL values\n");
-    const int nrow = (int) e->slice_rowptr.size() - 1;
-    if (f32) HIP_OK(crp_row_softmax_f32(nrow, e->sm_rowptr, (const float *) s, (float *) y, stream));
-    else HIP_OK(crp_row_softmax_f64(nrow, e->sm_rowptr, (const double *) s, (double *) y, stream));
+    crp::row_softmax((int) e->slice_rowptr.size() - 1, e->sm_rowptr, f32, s, y, stream);
 }
 
 void crp_para2d_spmm_row_softmax_bwd_ex(crp_para2d_spmm_p e, const void *y, const void *dy, void *ds, int f32, void *stream)
@@ -502,9 +465,7 @@ void crp_para2d_spmm_row_softmax_bwd_ex(crp_para2d_spmm_p e, const void *y, cons
     }
     if (!row_softmax_ready(e, "para2d_spmm_row_softmax_bwd", f32)) return;
     ASSERT_PRINTF(y != NULL && dy != NULL && ds != NULL, "para2d_spmm_row_softmax_bwd: NULL values\n");
-    const int nrow = (int) e->slice_rowptr.size() - 1;
-    if (f32) HIP_OK(crp_row_softmax_bwd_f32(nrow, e->sm_rowptr, (const float *) y, (const float *) dy, (float *) ds, stream));
-    else HIP_OK(crp_row_softmax_bwd_f64(nrow, e->sm_rowptr, (const double *) y, (const double *) dy, (double *) ds, stream));
+    crp::row_softmax_bwd((int) e->slice_rowptr.size() - 1, e->sm_rowptr, f32, y, dy, ds, stream);
 }
 
 int crp_para2d_spmm_row_softmax_built(crp_para2d_spmm_p e)
@@ -571,7 +532,7 @@ void crp_para2d_spmm_clear_stat(crp_para2d_spmm_p e)
     crp_rp_spmm_clear_stat(e->rp);
 }
 
-crp_rp_spmm_p crp_para2d_spmm_rp(crp_para2d_spmm_p e) { return e ? e->rp : NULL; }
+crp_rp_spmm_p crp_para2d_spmm_rp(crp_para2d_spmm_p e) { return e ? e->rp.p : NULL; }
 size_t crp_para2d_spmm_rA_cost(crp_para2d_spmm_p e) { return e ? e->rA_cost : 0; }
 double crp_para2d_spmm_t_ag_A(crp_para2d_spmm_p e) { return e ? e->t_ag_A : 0.0; }
 

@@ -39,69 +39,70 @@ struct crp_rp_spmm
     double t_a2a_host = 0;           // host time inside the exchange CALL (issuing the sends / receives), whatever the timing mode
     crp_comm_t *comm = nullptr;
 
-    // ---- device side
+    // ---- device side.  Every device resource is a member that releases itself (dev_owned.h) and crp_rp_spmm_free is `delete`:
+    // members go in REVERSE order of declaration, so the streams come first here, then the events, then the matrices and buffers
+    // -- those are released before the events, and the events before the streams, as the hand-written free did.  A plan-only
+    // engine holds empty owners only: its delete calls nothing on the device.
     bool plan_only = false;
     int  timing = 1, variant = 0;
     int  variant_f32 = 0;                        // the fp32 exec's kernel variant (crp_spmm_csr_f32: 0, 1, 5)
     int  loc_B_nrow = 0;
     long long n_send_rows = 0, n_recv_rows = 0, n_needed_rows = 0;
     std::vector<int> dev_colidx_host;
-    crp_csr_dev_p A_dev = nullptr;
-    // exchange / compute overlap (nproc > 1): rows with no remote column ("interior") run while the
-    // B rows travel, the rest ("boundary") after they have landed; A_dev then stays unset
-    crp_csr_dev_p A_int = nullptr, A_bnd = nullptr;
-    std::vector<long long> int_src, bnd_src;     // position in A_val of every nonzero of the two parts
-    std::vector<double>    split_vals;
-    void *xstream = nullptr, *ev_packed = nullptr, *ev_landed = nullptr;
-    int    *sridxs_dev = nullptr;
-    double *sendbuf_dev = nullptr, *recvbuf_dev = nullptr;
-    // fp32 exchange, set up by the first fp32 exec: rows of round_up(glb_n, 4) floats, counts in 8-byte words
-    bool   x32_ready = false;
-    float *sendbuf32_dev = nullptr, *recvbuf32_dev = nullptr;
+    crp::DevStream stream;                       // the engine's own stream
+    crp::DevStream xstream;                      // the exchange's (nproc > 1: a split engine, or the first exec_t)
+    // ev_exec: the end of the last exec that returned asynchronously -- a value update on the engine's own stream must not overtake
+    // kernels of an exec that is still in flight on the caller's stream; ev_packed / ev_landed: with xstream; ev_vals: recorded at
+    // the end of every device value update
+    crp::DevEvent ev_exec, ev_landed, ev_packed, ev_vals;
+    bool exec_pending = false;
+    // staging (host-pointer API) and column-major temporaries, grown on demand
+    crp::DevScratch C_rm, B_rm, C_stage, B_stage;
+    // the forward exchange; the fp32 one is set up by the first fp32 exec: rows of round_up(glb_n, 4) floats, counts in 8-byte words
+    crp::DevArray<float>  recvbuf32_dev, sendbuf32_dev;
+    crp::DevArray<double> recvbuf_dev, sendbuf_dev;
+    crp::DevArray<int>    sridxs_dev;
+    bool x32_ready = false;
     std::vector<long long> x32_scnts, x32_sdispls, x32_rcnts, x32_rdispls;
-    void   *stream = nullptr;
+    // fused attention (crp_rp_spmm_attention_ex), allocated by its first call of a dtype: the receive buffer of V's rows -- K's land
+    // in the forward exchange's -- and the scratch of host operands (Q, V, lse; a host p_out takes sd_out)
+    bool at_built = false, at_ready64 = false, at_ready32 = false;
+    crp::DevScratch at_lse, V_rm, V_stage, Q_rm, Q_stage;
+    crp::DevArray<float>  at_recv32_dev;
+    crp::DevArray<double> at_recv_dev;
+    // row softmax (crp_rp_spmm_row_softmax_ex), uploaded by its first call: A_rowptr as a device array
+    crp::DevArray<int> sm_rowptr;
+    // device value updates (crp_rp_spmm_update_values_dev), allocated by its first call: the new values as fp64 in the order the
+    // device matrices take them (A_dev: A_val's order; a split engine: A_int's nonzeros, then A_bnd's) and, once the transposed
+    // matrices exist, in theirs (through dv_t_pos, a device copy of t_src)
+    bool dv_built = false, dv_used = false;
+    crp::DevArray<int>    dv_t_pos;
+    crp::DevArray<double> dv_tvals, dv_vals;
+    bool host_vals_stale = false;                // A_val (host) is behind the device matrices: refreshed where it is read
+    // SDDMM (crp_rp_spmm_sddmm_ex), uploaded by its first call: where the nonzeros of A_int / A_bnd sit in A_val (int_src / bnd_src
+    // as int32 device arrays; none for the unsplit engine), and the staging buffer of a host `out`
+    bool sd_built = false;
+    crp::DevScratch sd_out;
+    crp::DevArray<int> sd_bnd_pos, sd_int_pos;
     // transposed product (crp_rp_spmm_exec_t_ex), built by its first call: the transpose of the two-source local matrix cut by
     // rows -- At_loc writes this rank's C block, At_rem the rows owed to peers (into recvbuf_dev, in the forward plan's peer order)
     bool t_built = false;
-    crp_csr_dev_p At_loc = nullptr, At_rem = nullptr;
     std::vector<int> t_src;                      // position in A_val of every nonzero of At_loc, then of At_rem
     size_t t_loc_nnz = 0;
     // the rows that come back (one per row this rank sends in the forward exchange), grouped by the C row they add to:
     // acc_dev = rows[n_acc] | ptr[n_acc + 1] | positions in sendbuf_dev[n_send_rows], ascending inside a group
     int  n_acc = 0;
-    int *acc_dev = nullptr;
-    // SDDMM (crp_rp_spmm_sddmm_ex), uploaded by its first call: where the nonzeros of A_int / A_bnd sit in A_val (int_src / bnd_src
-    // as int32 device arrays; none for the unsplit engine), and the staging buffer of a host `out`
-    bool sd_built = false;
-    int *sd_int_pos = nullptr, *sd_bnd_pos = nullptr;
-    crp::DevScratch sd_out;
-    // device value updates (crp_rp_spmm_update_values_dev), allocated by its first call: the new values as fp64 in the order the
-    // device matrices take them (A_dev: A_val's order; a split engine: A_int's nonzeros, then A_bnd's) and, once the transposed
-    // matrices exist, in theirs (through dv_t_pos, a device copy of t_src); ev_vals is recorded at the end of every update
-    bool    dv_built = false, dv_used = false;
-    double *dv_vals = nullptr, *dv_tvals = nullptr;
-    int    *dv_t_pos = nullptr;
-    void   *ev_vals = nullptr;
-    bool    host_vals_stale = false;             // A_val (host) is behind the device matrices: refreshed where it is read
-    // row softmax (crp_rp_spmm_row_softmax_ex), uploaded by its first call: A_rowptr as a device array
-    int *sm_rowptr = nullptr;
-    // fused attention (crp_rp_spmm_attention_ex), allocated by its first call of a dtype: the receive buffer of V's rows -- K's land
-    // in the forward exchange's -- and the scratch of host operands (Q, V, lse; a host p_out takes sd_out)
-    bool    at_built = false, at_ready64 = false, at_ready32 = false;
-    double *at_recv_dev = nullptr;
-    float  *at_recv32_dev = nullptr;
-    crp::DevScratch Q_stage, Q_rm, V_stage, V_rm, at_lse;
-    // staging (host-pointer API) and column-major temporaries, grown on demand
-    crp::DevScratch B_stage, C_stage, B_rm, C_rm;
-    // the stream the last exec ran on, and an event at its end: a value update on the engine's own stream must
-    // not overtake kernels of an exec that is still in flight on the caller's stream
-    void *ev_exec = nullptr;
-    bool  exec_pending = false;
-    // last operands seen and where they live (the pointer-attribute query is not free)
+    crp::DevArray<int> acc_dev;
+    crp::DevCsr At_rem, At_loc;
+    // exchange / compute overlap (nproc > 1): rows with no remote column ("interior") run while the
+    // B rows travel, the rest ("boundary") after they have landed; A_dev then stays unset
+    std::vector<long long> int_src, bnd_src;     // position in A_val of every nonzero of the two parts
+    std::vector<double>    split_vals;
+    crp::DevCsr A_bnd, A_int, A_dev;
+    // last operands seen and where they live (the pointer-attribute query is not free); not owned
     const void *last_B = nullptr, *last_C = nullptr;
     int last_B_dev = 0, last_C_dev = 0;
 };
-
 
 // ---------------------------------------------------------------------------
 static void build_plan(crp_rp_spmm *e, int A_nrow, const int *A_rowptr, const int *A_colidx,
@@ -253,9 +254,9 @@ static void build_device_matrices(crp_rp_spmm *e, const double *A_val_dev)
     if (rows_int.size() < (size_t) m / 16 || rows_bnd.empty())
     {
         if (A_val_dev != nullptr && !e->A_val.empty())
-            HIP_OK(crp_csr_dev_create_dv(m, e->loc_B_nrow, e->A_rowptr.data(), e->dev_colidx_host.data(), e->A_val.data(), A_val_dev, nullptr, &e->A_dev));
+            HIP_OK(crp_csr_dev_create_dv(m, e->loc_B_nrow, e->A_rowptr.data(), e->dev_colidx_host.data(), e->A_val.data(), A_val_dev, nullptr, e->A_dev.out()));
         else
-            HIP_OK(crp_csr_dev_create(m, e->loc_B_nrow, e->A_rowptr.data(), e->dev_colidx_host.data(), e->A_val.data(), &e->A_dev));
+            HIP_OK(crp_csr_dev_create(m, e->loc_B_nrow, e->A_rowptr.data(), e->dev_colidx_host.data(), e->A_val.data(), e->A_dev.out()));
         return;
     }
     // (a row's entries keep A_val's order inside its part: the fused attention's online softmax adds them in CSR order, and its
@@ -284,11 +285,11 @@ static void build_device_matrices(crp_rp_spmm *e, const double *A_val_dev)
             HIP_OK(crp_csr_dev_create((int) rows.size(), e->loc_B_nrow, rp.data(), ci.data(), va.data(), out));
         HIP_OK(crp_csr_dev_set_rowmap(*out, rows.data(), m));
     };
-    make(rows_int, e->int_src, &e->A_int);
-    make(rows_bnd, e->bnd_src, &e->A_bnd);
-    HIP_OK(crp_stream_create(&e->xstream));
-    HIP_OK(crp_event_create(&e->ev_packed));
-    HIP_OK(crp_event_create(&e->ev_landed));
+    make(rows_int, e->int_src, e->A_int.out());
+    make(rows_bnd, e->bnd_src, e->A_bnd.out());
+    e->xstream.ensure();
+    e->ev_packed.ensure();
+    e->ev_landed.ensure();
 }
 
 static void rp_init_common(int A_nrow, const int *A_rowptr, const int *A_colidx, const double *A_val,
@@ -305,21 +306,13 @@ static void rp_init_common(int A_nrow, const int *A_rowptr, const int *A_colidx,
     {
         build_device_matrices(e, A_val_dev);
         e->vals_from_device = (A_val_dev != nullptr);
-        HIP_OK(crp_stream_create(&e->stream));
-        void *p = NULL;
+        e->stream.ensure();
         if (e->n_send_rows > 0)
         {
-            HIP_OK(crp_dev_malloc(&p, sizeof(int) * (size_t) e->n_send_rows));
-            e->sridxs_dev = (int *) p;
-            HIP_OK(crp_dev_memcpy(e->sridxs_dev, e->rB_sridxs.data(), sizeof(int) * (size_t) e->n_send_rows, 0, NULL));
-            HIP_OK(crp_dev_malloc(&p, sizeof(double) * (size_t) e->n_send_rows * (size_t) glb_n));
-            e->sendbuf_dev = (double *) p;
+            e->sridxs_dev.upload(e->rB_sridxs.data(), (size_t) e->n_send_rows, NULL);
+            e->sendbuf_dev.alloc((size_t) e->n_send_rows * (size_t) glb_n);
         }
-        if (e->n_recv_rows > 0)
-        {
-            HIP_OK(crp_dev_malloc(&p, sizeof(double) * (size_t) e->n_recv_rows * (size_t) glb_n));
-            e->recvbuf_dev = (double *) p;
-        }
+        if (e->n_recv_rows > 0) e->recvbuf_dev.alloc((size_t) e->n_recv_rows * (size_t) glb_n);
         HIP_OK(crp_stream_sync(NULL));
     }
     e->t_init = get_wtime_sec() - t0;
@@ -355,46 +348,7 @@ void crp_rp_spmm_init_plan_only(int A_srow, int A_nrow, const int *A_rowptr, con
 void crp_rp_spmm_free(crp_rp_spmm_p *rp_spmm)
 {
     if (rp_spmm == NULL || *rp_spmm == NULL) return;
-    crp_rp_spmm *e = *rp_spmm;
-    if (!e->plan_only)
-    {
-        crp_csr_dev_destroy(&e->A_dev);
-        crp_csr_dev_destroy(&e->A_int);
-        crp_csr_dev_destroy(&e->A_bnd);
-        crp_csr_dev_destroy(&e->At_loc);
-        crp_csr_dev_destroy(&e->At_rem);
-        crp_dev_free(e->acc_dev);
-        crp_dev_free(e->sd_int_pos);
-        crp_dev_free(e->sd_bnd_pos);
-        e->sd_out.release();
-        crp_dev_free(e->dv_vals);
-        crp_dev_free(e->dv_tvals);
-        crp_dev_free(e->dv_t_pos);
-        crp_dev_free(e->sm_rowptr);
-        crp_dev_free(e->at_recv_dev);
-        crp_dev_free(e->at_recv32_dev);
-        e->Q_stage.release();
-        e->Q_rm.release();
-        e->V_stage.release();
-        e->V_rm.release();
-        e->at_lse.release();
-        if (e->ev_vals) crp_event_destroy(e->ev_vals);
-        if (e->xstream) crp_stream_destroy(e->xstream);
-        if (e->ev_packed) crp_event_destroy(e->ev_packed);
-        if (e->ev_landed) crp_event_destroy(e->ev_landed);
-        crp_dev_free(e->sridxs_dev);
-        crp_dev_free(e->sendbuf_dev);
-        crp_dev_free(e->recvbuf_dev);
-        crp_dev_free(e->sendbuf32_dev);
-        crp_dev_free(e->recvbuf32_dev);
-        if (e->ev_exec) crp_event_destroy(e->ev_exec);
-        e->B_stage.release();
-        e->C_stage.release();
-        e->B_rm.release();
-        e->C_rm.release();
-        crp_stream_destroy(e->stream);
-    }
-    delete e;
+    delete *rp_spmm;       // every device resource is a member that releases itself
     *rp_spmm = NULL;
 }
 
@@ -435,31 +389,14 @@ static Xchg exchange_of(crp_rp_spmm *e, const float *)
         words(e->rB_rcnts, e->x32_rcnts);
         words(e->rB_rdispls, e->x32_rdispls);
         // the pad columns are zeroed here and never written again: no uninitialised byte crosses a link
-        auto alloc = [&](long long rows, float **buf) {
-            if (rows <= 0 || ld <= 0) return;
-            const size_t bytes = sizeof(float) * (size_t) rows * (size_t) ld;
-            void *p = NULL;
-            HIP_OK(crp_dev_malloc(&p, bytes));
-            *buf = (float *) p;
-            HIP_OK(crp_dev_memset(p, 0, bytes, NULL));
-        };
-        alloc(e->n_send_rows, &e->sendbuf32_dev);
-        alloc(e->n_recv_rows, &e->recvbuf32_dev);
-        HIP_OK(crp_stream_sync(NULL));
+        if (e->n_send_rows > 0 && ld > 0) e->sendbuf32_dev.zeroed((size_t) e->n_send_rows * (size_t) ld);
+        if (e->n_recv_rows > 0 && ld > 0) e->recvbuf32_dev.zeroed((size_t) e->n_recv_rows * (size_t) ld);
         e->x32_ready = true;
     }
     return Xchg{e->sendbuf32_dev, e->recvbuf32_dev, ld, e->x32_scnts.data(), e->x32_sdispls.data(), e->x32_rcnts.data(),
                 e->x32_rdispls.data()};
 }
 
-static int gather(int nidx, int n, const int *ridx, const double *src, long long lds, double *dst, long long ldd, void *s)
-{
-    return crp_gather_rows_f64(0, nidx, n, ridx, src, lds, dst, ldd, s);
-}
-static int gather(int nidx, int n, const int *ridx, const float *src, long long lds, float *dst, long long ldd, void *s)
-{
-    return crp_gather_rows_f32(0, nidx, n, ridx, src, lds, dst, ldd, s);
-}
 static int spmm(crp_rp_spmm *e, crp_csr_dev_p A, int n, const double *B0, long long ldB0, const double *B1, long long ldB1,
                 double *C, long long ldC, void *s)
 {
@@ -469,17 +406,6 @@ static int spmm(crp_rp_spmm *e, crp_csr_dev_p A, int n, const float *B0, long lo
                 float *C, long long ldC, void *s)
 {
     return crp_spmm_csr_f32(A, n, B0, ldB0, B1, ldB1, C, ldC, e->variant_f32, s);
-}
-
-static int scatter_add(int nseg, int n, const int *row, const int *ptr, const int *pos, const double *src, long long lds, double *dst,
-                       long long ldd, void *s)
-{
-    return crp_scatter_add_rows_f64(nseg, n, row, ptr, pos, src, lds, dst, ldd, s);
-}
-static int scatter_add(int nseg, int n, const int *row, const int *ptr, const int *pos, const float *src, long long lds, float *dst,
-                       long long ldd, void *s)
-{
-    return crp_scatter_add_rows_f32(nseg, n, row, ptr, pos, src, lds, dst, ldd, s);
 }
 
 // Is this pointer on the device?  The pointer-attribute query is not free: the forward exec passes the engine's cache of the last
@@ -507,38 +433,62 @@ static void complete(crp_rp_spmm *e, void *s, bool synced, bool must_sync)
         HIP_OK(crp_stream_sync(s));
         return;
     }
-    if (e->ev_exec == nullptr) HIP_OK(crp_event_create(&e->ev_exec));
-    HIP_OK(crp_event_record(e->ev_exec, s));
+    HIP_OK(crp_event_record(e->ev_exec.ensure(), s));
     e->exec_pending = true;
 }
 
+// ---- the pieces pack_exchange_run and pack_exchange_run2 share ---------------------------------------------------------------------
+// pack the rows of the row-major device operand Bd that other ranks asked for into x.send, on st (reference :232-262)
+template <class T>
+static void pack_rows(crp_rp_spmm *e, const Xchg &x, const T *Bd, long long ldBd, void *st)
+{
+    if (e->n_send_rows > 0 && e->glb_n > 0) HIP_OK(crp::gather((int) e->n_send_rows, e->glb_n, e->sridxs_dev, Bd, ldBd, (T *) x.send, x.ld, st));
+}
+
+// the exchange call on st (reference :275-309), its host time billed to t_a2a_host; the received rows land in recv in final order
+static void exchange_rows(crp_rp_spmm *e, const Xchg &x, void *recv, void *st)
+{
+    const double tx0 = get_wtime_sec();
+    e->comm->alltoallv_dev_f64(e->comm->ctx, (const double *) x.send, x.sc, x.sd, (double *) recv, x.rc, x.rd, st);
+    e->t_a2a_host += get_wtime_sec() - tx0;
+}
+
+// with timing on: wait for s and bill the time since t0 to *bucket
+static void lap(crp_rp_spmm *e, void *s, double &t0, double *bucket)
+{
+    if (!e->timing) return;
+    HIP_OK(crp_stream_sync(s));
+    const double t1 = get_wtime_sec();
+    *bucket += t1 - t0;
+    t0 = t1;
+}
+
+// the local kernels after the exchange (reference :388-408): product(A, part) once for A_dev (part 0), or for A_int (1) and A_bnd (2)
+template <class F>
+static void run_parts(crp_rp_spmm *e, F &&product)
+{
+    if (e->A_int != nullptr)
+    {
+        product(e->A_int, 1);
+        product(e->A_bnd, 2);
+    }
+    else product(e->A_dev, 0);
+}
+
 // The half that exec and sddmm share: pack the rows of the row-major device operand Bd that other ranks asked for, exchange them
-// (the received rows land in x.recv in final order), and run the local kernels -- product(A, part) once for A_dev (part 0), or for
-// A_int (1) and A_bnd (2).  With timing off and a split engine the interior part is enqueued on s beside the exchange, which runs
-// on the engine's second stream, and the boundary part after the rows have landed; with timing on the phases run in sequence and
-// bill to t_pack and t_a2a (t0 is left at the start of the kernels, which the caller bills).
+// (the received rows land in x.recv in final order), and run the local kernels.  With timing off and a split engine the interior
+// part is enqueued on s beside the exchange, which runs on the engine's second stream, and the boundary part after the rows have
+// landed; with timing on the phases run in sequence and bill to t_pack and t_a2a (t0 is left at the start of the kernels, which
+// the caller bills).
 template <class T, class F>
 static void pack_exchange_run(crp_rp_spmm *e, const Xchg &x, const T *Bd, long long ldBd, void *s, double &t0, F &&product)
 {
-    const int n = e->glb_n;
     const bool timing = e->timing != 0;
-    double t1;
-    // ---- 1. pack the rows other ranks asked for (reference :232-262)
     if (timing) { HIP_OK(crp_stream_sync(s)); }
     t0 = get_wtime_sec();
-    if (e->n_send_rows > 0 && n > 0)
-        HIP_OK(gather((int) e->n_send_rows, n, e->sridxs_dev, Bd, ldBd, (T *) x.send, x.ld, s));
-    if (timing)
-    {
-        HIP_OK(crp_stream_sync(s));
-        t1 = get_wtime_sec();
-        e->t_pack += t1 - t0;
-        t0 = t1;
-    }
-
-    // ---- 2. exchange (reference :275-309); received rows land in final order
-    const bool split = (e->A_int != nullptr);
-    if (split && !timing)
+    pack_rows(e, x, Bd, ldBd, s);
+    lap(e, s, t0, &e->t_pack);
+    if (e->A_int != nullptr && !timing)
     {
         // The exchange runs on its own stream beside the interior rows' product.  The product is ENQUEUED FIRST: it does not
         // depend on the exchange, and issuing a group of sends / receives can hold the host for a while (a non-blocking RCCL
@@ -547,39 +497,15 @@ static void pack_exchange_run(crp_rp_spmm *e, const Xchg &x, const T *Bd, long l
         HIP_OK(crp_event_record(e->ev_packed, s));
         product(e->A_int, 1);
         HIP_OK(crp_stream_wait_event(e->xstream, e->ev_packed));
-        {
-            const double tx0 = get_wtime_sec();
-            e->comm->alltoallv_dev_f64(e->comm->ctx, (const double *) x.send, x.sc, x.sd, (double *) x.recv, x.rc, x.rd, e->xstream);
-            e->t_a2a_host += get_wtime_sec() - tx0;
-        }
+        exchange_rows(e, x, x.recv, e->xstream);
         HIP_OK(crp_event_record(e->ev_landed, e->xstream));
         HIP_OK(crp_stream_wait_event(s, e->ev_landed));
         product(e->A_bnd, 2);
+        return;
     }
-    else
-    {
-        if (e->nproc > 1)
-        {
-            const double tx0 = get_wtime_sec();
-            e->comm->alltoallv_dev_f64(e->comm->ctx, (const double *) x.send, x.sc, x.sd, (double *) x.recv, x.rc, x.rd, s);
-            e->t_a2a_host += get_wtime_sec() - tx0;
-        }
-        if (timing)
-        {
-            HIP_OK(crp_stream_sync(s));
-            t1 = get_wtime_sec();
-            e->t_a2a += t1 - t0;
-            t0 = t1;
-        }
-
-        // ---- 3. the local kernels (reference :388-408)
-        if (split)
-        {
-            product(e->A_int, 1);
-            product(e->A_bnd, 2);
-        }
-        else product(e->A_dev, 0);
-    }
+    if (e->nproc > 1) exchange_rows(e, x, x.recv, s);
+    lap(e, s, t0, &e->t_a2a);
+    run_parts(e, product);
 }
 
 // C := A * B on this rank, one dtype (crp_rp_spmm_exec_ex / crp_rp_spmm_exec_f32_ex)
@@ -604,53 +530,27 @@ static void exec_impl(crp_rp_spmm *e, int BC_layout, const T *B, long long ldB, 
 
     // ---- 1 - 3. pack, exchange, local SpMM
     pack_exchange_run(e, x, Bv.p, Bv.ld, s, t0, [&](crp_csr_dev_p A, int) { HIP_OK(spmm(e, A, n, Bv.p, Bv.ld, (const T *) x.recv, x.ld, Cv.p, Cv.ld, s)); });
-    const bool synced = crp::finish(Cv, s, [&] {
-        if (!timing) return;
-        HIP_OK(crp_stream_sync(s));
-        e->t_spmm += get_wtime_sec() - t0;
-    });
+    const bool synced = crp::finish(Cv, s, [&] { lap(e, s, t0, &e->t_spmm); });
     complete(e, s, synced, !B_on_dev || timing);
     e->t_exec += get_wtime_sec() - t_begin;
     e->n_exec++;
 }
 
 // ---- out[p] = < X[row(p)], Y[col(p)] > over this rank's rows of A (crp_rp_spmm_sddmm_ex / _f32_ex) --------------------------------
-static int sddmm(crp_csr_dev_p A, int n, const double *X, long long ldX, const double *Y0, long long ldY0, const double *Y1, long long ldY1,
-                 double *out, const int *out_pos, int mode, void *s)
-{
-    return crp_sddmm_csr_f64(A, n, X, ldX, Y0, ldY0, Y1, ldY1, out, out_pos, mode, s);
-}
-static int sddmm(crp_csr_dev_p A, int n, const float *X, long long ldX, const float *Y0, long long ldY0, const float *Y1, long long ldY1,
-                 float *out, const int *out_pos, int mode, void *s)
-{
-    return crp_sddmm_csr_f32(A, n, X, ldX, Y0, ldY0, Y1, ldY1, out, out_pos, mode, s);
-}
-
 // int_src / bnd_src of a split engine as int32 device arrays: the SDDMM's parts write through them into the order of A_val, a
 // device value update gathers the parts' values through them; whichever call comes first uploads
 static void upload_part_positions(crp_rp_spmm *e)
 {
-    auto up = [&](const std::vector<long long> &src, int **dst) {
-        if (src.empty() || *dst != nullptr) return;
+    auto up = [&](const std::vector<long long> &src, crp::DevArray<int> &dst) {
+        if (src.empty() || dst != nullptr) return;
         std::vector<int> pos(src.begin(), src.end());          // (positions in A_val: below 2^31, as A_rowptr is int)
-        void *d = NULL;
-        HIP_OK(crp_dev_malloc(&d, sizeof(int) * pos.size()));
-        *dst = (int *) d;
-        HIP_OK(crp_dev_memcpy(*dst, pos.data(), sizeof(int) * pos.size(), 0, e->stream));
-        HIP_OK(crp_stream_sync(e->stream));
+        dst.upload(pos.data(), pos.size(), e->stream);
     };
     if (e->A_int != nullptr)
     {
-        up(e->int_src, &e->sd_int_pos);
-        up(e->bnd_src, &e->sd_bnd_pos);
+        up(e->int_src, e->sd_int_pos);
+        up(e->bnd_src, e->sd_bnd_pos);
     }
-}
-
-// first SDDMM call
-static void build_sddmm(crp_rp_spmm *e)
-{
-    upload_part_positions(e);
-    e->sd_built = true;
 }
 
 // A_val (host) after device value updates: one blocking download of the values as the device matrices took them.  The engine's
@@ -684,7 +584,11 @@ static void sddmm_impl(crp_rp_spmm *e, int layout, const T *X, long long ldX, co
     ASSERT_PRINTF(layout == 0 || layout == 1, "layout must be 0 or 1\n");
     ASSERT_PRINTF(mode == 0 || mode == 1, "mode must be 0 or 1\n");
     const double t_begin = get_wtime_sec();
-    if (!e->sd_built) build_sddmm(e);
+    if (!e->sd_built)
+    {
+        upload_part_positions(e);
+        e->sd_built = true;
+    }
     void *s = stream_;
     const int n = e->glb_n, kb = e->loc_B_nrow, m = e->A_nrow;
     const size_t nnz = e->A_val.size();
@@ -705,14 +609,10 @@ static void sddmm_impl(crp_rp_spmm *e, int layout, const T *X, long long ldX, co
     // ---- pack Y, exchange, the kernels: the parts of a split engine write through their positions in A_val
     pack_exchange_run(e, x, Yv.p, Yv.ld, s, t0, [&](crp_csr_dev_p A, int part) {
         if (n == 0 || crp_csr_dev_nnz(A) == 0) return;
-        const int *pos = part == 1 ? e->sd_int_pos : (part == 2 ? e->sd_bnd_pos : nullptr);
-        HIP_OK(sddmm(A, n, Xv.p, Xv.ld, Yv.p, Yv.ld, (const T *) x.recv, x.ld, outd, pos, mode, s));
+        const int *pos = part == 1 ? e->sd_int_pos.get() : (part == 2 ? e->sd_bnd_pos.get() : nullptr);
+        HIP_OK(crp::sddmm(A, n, Xv.p, Xv.ld, Yv.p, Yv.ld, (const T *) x.recv, x.ld, outd, pos, mode, s));
     });
-    if (timing)
-    {
-        HIP_OK(crp_stream_sync(s));
-        e->t_spmm += get_wtime_sec() - t0;
-    }
+    lap(e, s, t0, &e->t_spmm);
 
     const bool download = !out_on_dev && nnz > 0;
     if (download) HIP_OK(crp_dev_memcpy(out, outd, nnz * sizeof(T), 1, s));
@@ -722,43 +622,22 @@ static void sddmm_impl(crp_rp_spmm *e, int layout, const T *X, long long ldX, co
 }
 
 // ---- O = softmax_row(scale (Q K^T)|pattern(A) (+ A's values)) V over this rank's rows of A (crp_rp_spmm_attention_ex / _f32_ex) ----
-static int attention(crp_csr_dev_p A, int n, double scale, int bias, const double *Q, long long ldQ, const double *K0, long long ldK0,
-                     const double *K1, long long ldK1, const double *V0, long long ldV0, const double *V1, long long ldV1, double *O,
-                     long long ldO, double *lse, double *p_out, const int *out_pos, void *s)
-{
-    return crp_attention_csr_f64(A, n, n, scale, bias, Q, ldQ, K0, ldK0, K1, ldK1, V0, ldV0, V1, ldV1, O, ldO, lse, p_out, out_pos, s);
-}
-static int attention(crp_csr_dev_p A, int n, double scale, int bias, const float *Q, long long ldQ, const float *K0, long long ldK0,
-                     const float *K1, long long ldK1, const float *V0, long long ldV0, const float *V1, long long ldV1, float *O,
-                     long long ldO, float *lse, float *p_out, const int *out_pos, void *s)
-{
-    return crp_attention_csr_f32(A, n, n, scale, bias, Q, ldQ, K0, ldK0, K1, ldK1, V0, ldV0, V1, ldV1, O, ldO, lse, p_out, out_pos, s);
-}
-
 // first attention call of a dtype: the second receive buffer (rows of x.ld elements, zeroed once: the fp32 rows' pad columns are
 // never written again), and the parts' positions in A_val; blocks
 template <class T>
-static T *attention_recv(crp_rp_spmm *e, const Xchg &x, T **buf, bool *ready)
+static T *attention_recv(crp_rp_spmm *e, const Xchg &x, crp::DevArray<T> &buf, bool *ready)
 {
     if (!*ready)
     {
         upload_part_positions(e);
-        if (e->n_recv_rows > 0 && x.ld > 0)
-        {
-            const size_t bytes = sizeof(T) * (size_t) e->n_recv_rows * (size_t) x.ld;
-            void *p = NULL;
-            HIP_OK(crp_dev_malloc(&p, bytes));
-            *buf = (T *) p;
-            HIP_OK(crp_dev_memset(p, 0, bytes, NULL));
-            HIP_OK(crp_stream_sync(NULL));
-        }
+        if (e->n_recv_rows > 0 && x.ld > 0) buf.zeroed((size_t) e->n_recv_rows * (size_t) x.ld);
         *ready = true;
         e->at_built = true;
     }
-    return *buf;
+    return buf;
 }
-static double *attention_recv(crp_rp_spmm *e, const Xchg &x, const double *) { return attention_recv(e, x, &e->at_recv_dev, &e->at_ready64); }
-static float *attention_recv(crp_rp_spmm *e, const Xchg &x, const float *) { return attention_recv(e, x, &e->at_recv32_dev, &e->at_ready32); }
+static double *attention_recv(crp_rp_spmm *e, const Xchg &x, const double *) { return attention_recv(e, x, e->at_recv_dev, &e->at_ready64); }
+static float *attention_recv(crp_rp_spmm *e, const Xchg &x, const float *) { return attention_recv(e, x, e->at_recv32_dev, &e->at_ready32); }
 
 // pack_exchange_run for two operands partitioned like B: the rows of Kd travel into x.recv, then those of Vd into recv2, both
 // through x.send, which is reused in stream order.  With timing off and a split engine the interior part is enqueued on s first and
@@ -769,28 +648,18 @@ template <class T, class F>
 static void pack_exchange_run2(crp_rp_spmm *e, const Xchg &x, void *recv2, const T *Kd, long long ldKd, const T *Vd, long long ldVd, void *s,
                                double &t0, F &&product)
 {
-    const int n = e->glb_n;
     const bool timing = e->timing != 0;
-    const bool split = (e->A_int != nullptr);
-    auto pack = [&](const T *Bd, long long ldBd, void *st) {
-        if (e->n_send_rows > 0 && n > 0) HIP_OK(gather((int) e->n_send_rows, n, e->sridxs_dev, Bd, ldBd, (T *) x.send, x.ld, st));
-    };
-    auto exchange = [&](void *recv, void *st) {
-        const double tx0 = get_wtime_sec();
-        e->comm->alltoallv_dev_f64(e->comm->ctx, (const double *) x.send, x.sc, x.sd, (double *) recv, x.rc, x.rd, st);
-        e->t_a2a_host += get_wtime_sec() - tx0;
-    };
     if (timing) { HIP_OK(crp_stream_sync(s)); }
     t0 = get_wtime_sec();
-    if (split && !timing)
+    if (e->A_int != nullptr && !timing)
     {
         HIP_OK(crp_event_record(e->ev_packed, s));          // (here: the operands are ready)
         product(e->A_int, 1);
         HIP_OK(crp_stream_wait_event(e->xstream, e->ev_packed));
-        pack(Kd, ldKd, e->xstream);
-        exchange(x.recv, e->xstream);
-        pack(Vd, ldVd, e->xstream);
-        exchange(recv2, e->xstream);
+        pack_rows(e, x, Kd, ldKd, e->xstream);
+        exchange_rows(e, x, x.recv, e->xstream);
+        pack_rows(e, x, Vd, ldVd, e->xstream);
+        exchange_rows(e, x, recv2, e->xstream);
         HIP_OK(crp_event_record(e->ev_landed, e->xstream));
         HIP_OK(crp_stream_wait_event(s, e->ev_landed));
         product(e->A_bnd, 2);
@@ -798,29 +667,12 @@ static void pack_exchange_run2(crp_rp_spmm *e, const Xchg &x, void *recv2, const
     }
     for (int op = 0; op < 2; op++)
     {
-        pack(op == 0 ? Kd : Vd, op == 0 ? ldKd : ldVd, s);
-        if (timing)
-        {
-            HIP_OK(crp_stream_sync(s));
-            const double t1 = get_wtime_sec();
-            e->t_pack += t1 - t0;
-            t0 = t1;
-        }
-        if (e->nproc > 1) exchange(op == 0 ? x.recv : recv2, s);
-        if (timing)
-        {
-            HIP_OK(crp_stream_sync(s));
-            const double t1 = get_wtime_sec();
-            e->t_a2a += t1 - t0;
-            t0 = t1;
-        }
+        pack_rows(e, x, op == 0 ? Kd : Vd, op == 0 ? ldKd : ldVd, s);
+        lap(e, s, t0, &e->t_pack);
+        if (e->nproc > 1) exchange_rows(e, x, op == 0 ? x.recv : recv2, s);
+        lap(e, s, t0, &e->t_a2a);
     }
-    if (split)
-    {
-        product(e->A_int, 1);
-        product(e->A_bnd, 2);
-    }
-    else product(e->A_dev, 0);
+    run_parts(e, product);
 }
 
 template <class T>
@@ -856,17 +708,13 @@ static void attention_impl(crp_rp_spmm *e, int layout, double scale, int bias, c
     // through their positions in A_val
     pack_exchange_run2(e, x, recv2, Kv.p, Kv.ld, Vv.p, Vv.ld, s, t0, [&](crp_csr_dev_p A, int part) {
         if (n == 0 || crp_csr_dev_nrow(A) == 0) return;
-        const int *pos = part == 1 ? e->sd_int_pos : (part == 2 ? e->sd_bnd_pos : nullptr);
-        HIP_OK(attention(A, n, scale, bias, Qv.p, Qv.ld, Kv.p, Kv.ld, (const T *) x.recv, x.ld, Vv.p, Vv.ld, (const T *) recv2, x.ld, Ov.p,
+        const int *pos = part == 1 ? e->sd_int_pos.get() : (part == 2 ? e->sd_bnd_pos.get() : nullptr);
+        HIP_OK(crp::attention(A, n, scale, bias, Qv.p, Qv.ld, Kv.p, Kv.ld, (const T *) x.recv, x.ld, Vv.p, Vv.ld, (const T *) recv2, x.ld, Ov.p,
                          Ov.ld, lsed, pd, pos, s));
     });
     if (lse_host) HIP_OK(crp_dev_memcpy(lse, lsed, (size_t) m * sizeof(T), 1, s));
     if (p_host) HIP_OK(crp_dev_memcpy(p_out, pd, nnz * sizeof(T), 1, s));
-    const bool synced = crp::finish(Ov, s, [&] {
-        if (!timing) return;
-        HIP_OK(crp_stream_sync(s));
-        e->t_spmm += get_wtime_sec() - t0;
-    });
+    const bool synced = crp::finish(Ov, s, [&] { lap(e, s, t0, &e->t_spmm); });
     complete(e, s, synced, lse_host || p_host || !Q_on_dev || !K_on_dev || !V_on_dev || timing);
     e->t_exec += get_wtime_sec() - t_begin;
     e->n_exec++;
@@ -894,9 +742,8 @@ static void build_transposed(crp_rp_spmm *e)
     {
         // device temporaries: val | val_t | rowptr | rowptr_t | col | col_t | tmap
         const size_t vb = sizeof(double) * n1, ib = sizeof(int) * n1, rb = sizeof(int) * ((size_t) m + 1), tb = sizeof(int) * ((size_t) ncol + 1);
-        void *d = NULL;
-        HIP_OK(crp_dev_malloc(&d, 2 * vb + rb + tb + 3 * ib));
-        char *b = (char *) d;
+        crp::DevArray<char> tmp;
+        char *b = tmp.alloc(2 * vb + rb + tb + 3 * ib);
         double *d_val = (double *) b, *d_val_t = (double *) (b + vb);
         int *d_rp = (int *) (b + 2 * vb), *d_rp_t = (int *) (b + 2 * vb + rb), *d_col = (int *) (b + 2 * vb + rb + tb), *d_col_t = d_col + n1,
             *d_tmap = d_col_t + n1;
@@ -909,17 +756,16 @@ static void build_transposed(crp_rp_spmm *e)
         HIP_OK(crp_dev_memcpy(va_t.data(), d_val_t, vb, 1, e->stream));
         HIP_OK(crp_dev_memcpy(e->t_src.data(), d_tmap, ib, 1, e->stream));
         HIP_OK(crp_stream_sync(e->stream));
-        HIP_OK(crp_dev_free(d));
     }
     e->t_loc_nnz = (size_t) rp_t[(size_t) kb];
-    HIP_OK(crp_csr_dev_create(kb, m, rp_t.data(), ci_t.data(), va_t.data(), &e->At_loc));
+    HIP_OK(crp_csr_dev_create(kb, m, rp_t.data(), ci_t.data(), va_t.data(), e->At_loc.out()));
     if (nr > 0)
     {
         std::vector<int> rp_r((size_t) nr + 1);
         for (int i = 0; i <= nr; i++) rp_r[(size_t) i] = rp_t[(size_t) kb + (size_t) i] - (int) e->t_loc_nnz;
         // (an empty part still gets valid pointers: the arrays hold at least one element)
         const size_t off = e->t_loc_nnz < n1 ? e->t_loc_nnz : 0;
-        HIP_OK(crp_csr_dev_create(nr, m, rp_r.data(), ci_t.data() + off, va_t.data() + off, &e->At_rem));
+        HIP_OK(crp_csr_dev_create(nr, m, rp_r.data(), ci_t.data() + off, va_t.data() + off, e->At_rem.out()));
     }
     if (e->n_send_rows > 0)
     {
@@ -941,17 +787,13 @@ static void build_transposed(crp_rp_spmm *e)
         std::vector<int> all(rows);
         all.insert(all.end(), ptr.begin(), ptr.end());
         all.insert(all.end(), pos.begin(), pos.end());
-        void *d = NULL;
-        HIP_OK(crp_dev_malloc(&d, sizeof(int) * all.size()));
-        e->acc_dev = (int *) d;
-        HIP_OK(crp_dev_memcpy(e->acc_dev, all.data(), sizeof(int) * all.size(), 0, e->stream));
-        HIP_OK(crp_stream_sync(e->stream));
+        e->acc_dev.upload(all.data(), all.size(), e->stream);
     }
     if (e->nproc > 1)
     {
-        if (e->xstream == nullptr) HIP_OK(crp_stream_create(&e->xstream));
-        if (e->ev_packed == nullptr) HIP_OK(crp_event_create(&e->ev_packed));
-        if (e->ev_landed == nullptr) HIP_OK(crp_event_create(&e->ev_landed));
+        e->xstream.ensure();
+        e->ev_packed.ensure();
+        e->ev_landed.ensure();
     }
     e->t_built = true;
 }
@@ -983,7 +825,7 @@ static void exec_t_impl(crp_rp_spmm *e, int BC_layout, const T *B, long long ldB
     // B has A's rows, C the rows of this rank's block of the forward operand
     const int n = e->glb_n, mb = e->A_nrow, mc = e->loc_B_nrow;
     const bool timing = e->timing != 0;
-    double t0, t1;
+    double t0;
 
     const bool B_on_dev = on_device(B), C_on_dev = on_device(C);
 
@@ -1002,7 +844,7 @@ static void exec_t_impl(crp_rp_spmm *e, int BC_layout, const T *B, long long ldB
     auto accumulate = [&]() {
         if (e->n_acc == 0 || n == 0) return;
         const int *acc_row = e->acc_dev, *acc_ptr = acc_row + e->n_acc, *acc_pos = acc_ptr + e->n_acc + 1;
-        HIP_OK(scatter_add(e->n_acc, n, acc_row, acc_ptr, acc_pos, (const T *) x.send, x.ld, Cv.p, Cv.ld, s));
+        HIP_OK(crp::scatter_add(e->n_acc, n, acc_row, acc_ptr, acc_pos, (const T *) x.send, x.ld, Cv.p, Cv.ld, s));
     };
 
     if (timing) { HIP_OK(crp_stream_sync(s)); }
@@ -1021,27 +863,16 @@ static void exec_t_impl(crp_rp_spmm *e, int BC_layout, const T *B, long long ldB
     }
     else
     {
-        auto lap = [&](double *bucket) {
-            if (!timing) return;
-            HIP_OK(crp_stream_sync(s));
-            t1 = get_wtime_sec();
-            *bucket += t1 - t0;
-            t0 = t1;
-        };
         if (e->At_rem != nullptr) product(e->At_rem, (T *) x.recv, x.ld);
-        lap(&e->t_spmm);
+        lap(e, s, t0, &e->t_spmm);
         if (e->nproc > 1) reverse_exchange(s);
-        lap(&e->t_a2a);
+        lap(e, s, t0, &e->t_a2a);
         product(e->At_loc, Cv.p, Cv.ld);
-        lap(&e->t_spmm);
+        lap(e, s, t0, &e->t_spmm);
         accumulate();
-        lap(&e->t_unpack);
+        lap(e, s, t0, &e->t_unpack);
     }
-    const bool synced = crp::finish(Cv, s, [&] {
-        if (!timing) return;
-        HIP_OK(crp_stream_sync(s));
-        e->t_spmm += get_wtime_sec() - t0;
-    });
+    const bool synced = crp::finish(Cv, s, [&] { lap(e, s, t0, &e->t_spmm); });
     complete(e, s, synced, !B_on_dev || timing);
     e->t_exec += get_wtime_sec() - t_begin;
     e->n_exec++;
@@ -1109,7 +940,7 @@ void crp_rp_spmm_exec(crp_rp_spmm_p e, int BC_layout, const double *B, int ldB, 
     // stream.  Device operands were produced, and will be consumed, by work the caller enqueued somewhere the engine
     // cannot know -- by HIP's rules the null stream orders against that (every blocking stream, and the null stream
     // itself), the engine's non-blocking stream would not: device operands run on the null stream.
-    void *s = e ? e->stream : NULL;
+    void *s = e ? e->stream.h : NULL;
     if (e != NULL && !e->plan_only)
     {
         // (this fills the cache the exec below reads)
@@ -1222,25 +1053,10 @@ void crp_rp_spmm_update_values(crp_rp_spmm_p e, const double *A_val)
 // first device value update: the scratch regions and the event; the parts' positions when the engine is split
 static void build_dev_update(crp_rp_spmm *e)
 {
-    void *d = NULL;
-    HIP_OK(crp_dev_malloc(&d, sizeof(double) * e->A_val.size()));
-    e->dv_vals = (double *) d;
-    HIP_OK(crp_event_create(&e->ev_vals));
+    e->dv_vals.alloc(e->A_val.size());
+    e->ev_vals.ensure();
     upload_part_positions(e);
     e->dv_built = true;
-}
-
-// first device value update after the transposed matrices were built: t_src on the device, the second scratch region
-static void build_dev_update_t(crp_rp_spmm *e)
-{
-    const size_t nnz = e->A_val.size();
-    void *d = NULL;
-    HIP_OK(crp_dev_malloc(&d, sizeof(double) * nnz));
-    e->dv_tvals = (double *) d;
-    HIP_OK(crp_dev_malloc(&d, sizeof(int) * nnz));
-    e->dv_t_pos = (int *) d;
-    HIP_OK(crp_dev_memcpy(e->dv_t_pos, e->t_src.data(), sizeof(int) * nnz, 0, e->stream));
-    HIP_OK(crp_stream_sync(e->stream));
 }
 
 void crp_rp_spmm_update_values_dev(crp_rp_spmm_p e, const void *A_val_dev, int f32, void *stream)
@@ -1252,7 +1068,11 @@ void crp_rp_spmm_update_values_dev(crp_rp_spmm_p e, const void *A_val_dev, int f
     if (nnz == 0) return;
     ASSERT_PRINTF(A_val_dev != NULL, "rp_spmm_update_values_dev: NULL values\n");
     if (!e->dv_built) build_dev_update(e);
-    if (e->t_built && e->dv_t_pos == nullptr) build_dev_update_t(e);
+    if (e->t_built && e->dv_t_pos == nullptr)      // the first one after the transposed matrices were built: the second scratch region,
+    {                                               // t_src on the device (nnz > 0 here: the pointer says "built")
+        e->dv_tvals.alloc(nnz);
+        e->dv_t_pos.upload(e->t_src.data(), nnz, e->stream);
+    }
     void *s = stream;
     if (e->exec_pending)        // kernels of an exec that returned asynchronously may still read the old values
     {
@@ -1299,17 +1119,7 @@ void crp_rp_spmm_update_values_dev(crp_rp_spmm_p e, const void *A_val_dev, int f
 // addresses them as it is, split engine or not
 static bool row_softmax_ready(crp_rp_spmm *e, const char *what, int f32)
 {
-    ASSERT_PRINTF(!e->plan_only, "%s on a plan-only engine (no device state)\n", what);
-    ASSERT_PRINTF(f32 == 0 || f32 == 1, "%s: f32 must be 0 or 1\n", what);
-    if (e->sm_rowptr == nullptr)
-    {
-        const size_t rb = sizeof(int) * ((size_t) e->A_nrow + 1);
-        void *d = NULL;
-        HIP_OK(crp_dev_malloc(&d, rb));
-        HIP_OK(crp_dev_memcpy(d, e->A_rowptr.data(), rb, 0, e->stream));
-        HIP_OK(crp_stream_sync(e->stream));
-        e->sm_rowptr = (int *) d;
-    }
+    crp::row_softmax_ready(what, e->plan_only, f32, true, e->sm_rowptr, e->A_rowptr, e->stream);
     return !e->A_val.empty();       // rows without a nonzero: nothing to launch, the pointers may be NULL
 }
 
@@ -1318,8 +1128,7 @@ void crp_rp_spmm_row_softmax_ex(crp_rp_spmm_p e, const void *s, void *y, int f32
     if (e == NULL) return;
     if (!row_softmax_ready(e, "rp_spmm_row_softmax", f32)) return;
     ASSERT_PRINTF(s != NULL && y != NULL, "rp_spmm_row_softmax: NULL values\n");
-    if (f32) HIP_OK(crp_row_softmax_f32(e->A_nrow, e->sm_rowptr, (const float *) s, (float *) y, stream));
-    else HIP_OK(crp_row_softmax_f64(e->A_nrow, e->sm_rowptr, (const double *) s, (double *) y, stream));
+    crp::row_softmax(e->A_nrow, e->sm_rowptr, f32, s, y, stream);
 }
 
 void crp_rp_spmm_row_softmax_bwd_ex(crp_rp_spmm_p e, const void *y, const void *dy, void *ds, int f32, void *stream)
@@ -1327,8 +1136,7 @@ void crp_rp_spmm_row_softmax_bwd_ex(crp_rp_spmm_p e, const void *y, const void *
     if (e == NULL) return;
     if (!row_softmax_ready(e, "rp_spmm_row_softmax_bwd", f32)) return;
     ASSERT_PRINTF(y != NULL && dy != NULL && ds != NULL, "rp_spmm_row_softmax_bwd: NULL values\n");
-    if (f32) HIP_OK(crp_row_softmax_bwd_f32(e->A_nrow, e->sm_rowptr, (const float *) y, (const float *) dy, (float *) ds, stream));
-    else HIP_OK(crp_row_softmax_bwd_f64(e->A_nrow, e->sm_rowptr, (const double *) y, (const double *) dy, (double *) ds, stream));
+    crp::row_softmax_bwd(e->A_nrow, e->sm_rowptr, f32, y, dy, ds, stream);
 }
 
 int crp_rp_spmm_row_softmax_built(crp_rp_spmm_p e) { return (e && e->sm_rowptr) ? 1 : 0; }

@@ -1,6 +1,7 @@
 """CPU: the host half of the product (format builders, team scheduler, planner, ingest) compiled with
 AddressSanitizer + UBSan and driven by tests/host_asan.cpp, and the engines' operand layer (csrc/operand_view.h) over host stand-ins for the device ABI, driven by
-tests/host_operand_view.cpp (GPU sanitizers are not available on the pool)."""
+tests/host_operand_view.cpp, and the two engines with the owners of their device resources (csrc/dev_owned.h) over such stand-ins, driven by
+tests/host_engine_resources.cpp (GPU sanitizers are not available on the pool)."""
 import os
 import shutil
 import subprocess
@@ -39,3 +40,25 @@ def test_operand_view_under_asan_ubsan(tmp_path):
     assert r.returncode == 0, r.stderr[-3000:]
     r = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0"))
     assert r.returncode == 0 and "HOST_OPERAND_VIEW_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
+
+
+def test_engine_resources_under_asan_ubsan(tmp_path):
+    """Every device block, stream, event and matrix handle the engines create is released exactly once by crp_*_spmm_free, a plan-only
+    engine touches no device function, and the owners release what they hold once (tests/host_engine_resources.cpp)."""
+    gxx = shutil.which("g++")
+    if gxx is None:
+        pytest.skip("no g++")
+    src = os.path.join(ROOT, "crp-spmm_amd", "csrc")
+    files = [os.path.join(src, f) for f in ("rp_engine.cpp", "para2d_engine.cpp", "knobs.cpp", "host_support.cpp")]
+    exe = str(tmp_path / "host_engine_resources")
+    cmd = [gxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+           "-fno-omit-frame-pointer", "-pthread", "-I" + os.path.join(ROOT, "include"), "-I" + src,
+           os.path.join(ROOT, "tests", "host_engine_resources.cpp"), *files, "-o", exe]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0 and "HOST_ENGINE_RESOURCES_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
+    t = subprocess.run([exe, "--trace"], capture_output=True, text=True, timeout=600, env=env)
+    names = t.stdout.split()
+    assert t.returncode == 0 and len(names) > 1000 and "dev_free(null)" not in names and "csr_dev_destroy(null)" not in names
