@@ -133,6 +133,67 @@ template <typename T> struct AttnArgs      // attention_kernels.hip: O[i] = sum_
     const int *out_pos;     // nullptr, or where nonzero p writes: p_out[out_pos[p]]
 };
 
+// attention_bwd_kernels.hip, row side: dQ[i] = scale sum_p dS_p K[c_p], delta[i] = <dO[i], O[i]>, ds_out[p] = dS_p over A's rows
+template <typename T> struct AttnBwdQArgs
+{
+    int nrow;
+    int nk;                 // columns of Q, K and dQ
+    int nv;                 // columns of V, O and dO
+    const int *rowptr;
+    const int *colidx;
+    const T   *val;         // the values in T (bias), or nullptr
+    T          scale;
+    const T   *Q;
+    int64_t    ldQ;
+    const T   *K0;
+    int64_t    ldK0;
+    const T   *K1;
+    int64_t    ldK1;
+    const T   *V0;
+    int64_t    ldV0;
+    const T   *V1;
+    int64_t    ldV1;
+    const T   *O;
+    int64_t    ldO;
+    const T   *dO;
+    int64_t    lddO;
+    const T   *lse;         // one entry per row, as the forward wrote it (indexed like the rows of O)
+    T         *dQ;
+    int64_t    lddQ;
+    T         *delta;       // one entry per row, indexed like lse
+    T         *ds_out;      // nullptr, or dS per nonzero
+    const int *rowmap;      // nullptr, or the Q / O / dO / dQ / lse / delta row of every row (row-subset matrices)
+    const int *out_pos;     // nullptr, or where nonzero p writes: ds_out[out_pos[p]]
+};
+
+// attention_bwd_kernels.hip, column side, over a handle of A^T (row c = column c of A, entries = the rows i of A that hold c):
+// dK[c] = scale sum_p dS_p Q[i_p], dV[c] = sum_p p_p dO[i_p]
+template <typename T> struct AttnBwdKVArgs
+{
+    int nrow;               // rows of the transposed handle
+    int nk;
+    int nv;
+    const int *rowptr;
+    const int *colidx;      // rows of Q / dO / lse / delta (one source: no negative code)
+    const T   *val;         // the transposed handle's values in T (bias), or nullptr
+    T          scale;
+    const T   *K;
+    int64_t    ldK;
+    const T   *V;
+    int64_t    ldV;
+    const T   *Q;
+    int64_t    ldQ;
+    const T   *dO;
+    int64_t    lddO;
+    const T   *lse;
+    const T   *delta;
+    T         *dK;          // may be K exactly (a group reads its row whole before it writes it)
+    int64_t    lddK;
+    T         *dV;          // may be V exactly
+    int64_t    lddV;
+    const int *rowmap;      // nullptr, or the K / V / dK / dV row of every row (row-subset matrices)
+};
+
 // The instance every SpMM launcher names at its hipLaunchKernelGGL, from its own template arguments ("rowgroup<16,2,1>",
 // "panel<8,2,2,a32,b1>", "team2<f64,NV1,b0,compact>", ...): a string with static storage, per host thread.  hip_api.hip copies
 // it into the handle after the product (crp_csr_dev_last_kernel); nothing else reads it.
@@ -174,6 +235,13 @@ hipError_t sddmm_rm_f32(const SddmmArgs<float> &a, hipStream_t s);
 // attention_kernels.hip: fused scores, online row softmax and product with V; row-major operands, any widths and alignment
 hipError_t attention_rm_f64(const AttnArgs<double> &a, hipStream_t s);
 hipError_t attention_rm_f32(const AttnArgs<float> &a, hipStream_t s);
+
+// attention_bwd_kernels.hip: the fused backward of attention_rm_*; nk and nv at most ATTN_BWD_MAX_PIECES * 64 * (16 / sizeof(T))
+constexpr int ATTN_BWD_MAX_PIECES = 4;
+hipError_t attention_bwd_q_f64(const AttnBwdQArgs<double> &a, hipStream_t s);
+hipError_t attention_bwd_q_f32(const AttnBwdQArgs<float> &a, hipStream_t s);
+hipError_t attention_bwd_kv_f64(const AttnBwdKVArgs<double> &a, hipStream_t s);
+hipError_t attention_bwd_kv_f32(const AttnBwdKVArgs<float> &a, hipStream_t s);
 
 // softmax_kernels.hip: row softmax over a CSR pattern and its Jacobian product; rowptr entries index the value arrays directly
 hipError_t row_softmax_f64(int nrow, const int *rowptr, const double *s, double *y, hipStream_t st);

@@ -285,6 +285,54 @@ class RpSpmm:
         """True once an ``attention`` has allocated V's receive buffer (crp_rp_spmm_attention_built)."""
         return bool(self._lib.crp_rp_spmm_attention_built(self.handle))
 
+    def attention_bwd(self, Q, K, V, O, dO, lse, dQ, dK, dV, scale=1.0, bias=False, ds_out=None, stream=None):
+        """The fused backward of ``attention`` over this rank's rows of A (crp_rp_spmm_attention_bwd_ex / _f32_ex, by the operands'
+        dtype): with ``O`` and ``lse`` as the forward wrote them and the upstream gradient ``dO``, writes dQ (A_nrow x glb_n), dK
+        and dV (loc_B_nrow x glb_n) and optionally ``ds_out`` (nnz entries in A_val's order: the gradient of the bias).  Every
+        operand is a row-major torch tensor on the device; host arrays and layout 1 are not offered.  glb_n is at most 512
+        (float64) / 1024 (float32).  Wrong types, dtypes, shapes and devices raise before the library is called."""
+        import torch
+        two_d = (("Q", Q, self.A_nrow), ("O", O, self.A_nrow), ("dO", dO, self.A_nrow), ("dQ", dQ, self.A_nrow),
+                 ("K", K, getattr(self, "loc_B_nrow", None)), ("V", V, getattr(self, "loc_B_nrow", None)),
+                 ("dK", dK, getattr(self, "loc_B_nrow", None)), ("dV", dV, getattr(self, "loc_B_nrow", None)))
+        vecs = (("lse", lse, self.A_nrow),) + ((("ds_out", ds_out, self.nnz()),) if ds_out is not None else ())
+        for name, t, _ in two_d + vecs:
+            if not isinstance(t, torch.Tensor):
+                raise TypeError("%s must be a torch tensor on the device" % name)
+            if t.dtype not in (torch.float64, torch.float32) or t.dtype != Q.dtype:
+                raise TypeError("the operands must be float64 or float32, all alike (%s is %s)" % (name, t.dtype))
+        for name, t, rows in two_d:
+            if t.dim() != 2:
+                raise TypeError("%s must be 2-D" % name)
+            if t.shape[1] != self.glb_n or (rows is not None and t.shape[0] != rows):
+                raise ValueError("%s is %s, this rank needs (%s, %d)" % (name, tuple(t.shape), rows, self.glb_n))
+            if t.shape[1] > 1 and t.stride(1) != 1:
+                raise ValueError("%s must be contiguous along its rows" % name)
+        for name, t, count in vecs:
+            if t.dim() != 1 or not t.is_contiguous() or t.numel() != count:
+                raise ValueError("%s must be 1-D and contiguous with %d entries" % (name, count))
+        if bias not in (False, True, 0, 1):
+            raise ValueError("bias must be a bool, got %r" % (bias,))
+        scale = float(scale)
+        if not np.isfinite(scale):
+            raise ValueError("scale must be finite, got %r" % (scale,))
+        cap = 512 if Q.dtype == torch.float64 else 1024
+        if self.glb_n > cap:
+            raise ValueError("the fused backward takes at most %d columns in %s, this engine has %d" % (cap, Q.dtype, self.glb_n))
+        for name, t, _ in two_d + vecs:
+            if not t.is_cuda or t.device != Q.device:
+                raise TypeError("%s must be on the device, with Q" % name)
+        if stream is None:
+            stream = _current_stream(dQ)
+        ptr = lambda t: (t.data_ptr() or None) if t is not None else None
+        fn = self._lib.crp_rp_spmm_attention_bwd_f32_ex if Q.dtype == torch.float32 else self._lib.crp_rp_spmm_attention_bwd_ex
+        fn(self.handle, scale, int(bool(bias)), ptr(Q), Q.stride(0), ptr(K), K.stride(0), ptr(V), V.stride(0), ptr(O), O.stride(0), ptr(dO),
+           dO.stride(0), ptr(lse), ptr(dQ), dQ.stride(0), ptr(dK), dK.stride(0), ptr(dV), dV.stride(0), ptr(ds_out), stream)
+
+    def attention_bwd_built(self):
+        """True once an ``attention_bwd`` has allocated the engine's delta (crp_rp_spmm_attention_bwd_built)."""
+        return bool(self._lib.crp_rp_spmm_attention_bwd_built(self.handle))
+
     @property
     def transposed_built(self):
         """True once an ``exec_t`` has built the transposed device matrices (crp_rp_spmm_transposed_built)."""

@@ -244,6 +244,96 @@ class CsrDev:
                    _stream(out) if stream is None else stream), fn.__name__)
         return out
 
+    def attention_bwd_q(self, Q, K0, V0, O, dO, lse, K1=None, V1=None, scale=1.0, bias=False, dQ=None, delta=None, ds_out=None,
+                        out_pos=None, stream=None):
+        """The row side of the fused backward of ``attention`` (crp_attention_bwd_q_csr_f64 / _f32, by the operands' dtype), on
+        the handle the forward ran on: with ``O`` and ``lse`` as the forward wrote them and the upstream gradient ``dO``,
+        dQ[i] = scale * sum_p dS_p K[c_p] and delta[i] = <dO[i], O[i]> for every row, dS_p = p_p (<dO[i], V[c_p]> - delta[i]),
+        p_p = exp(s_p - lse[i]).  Q, K0, K1, dQ have nk columns, V0, V1, O, dO nv; ``lse`` and ``delta`` are 1-D contiguous with
+        an entry per row of Q; ``ds_out`` (optional, 1-D contiguous, nnz entries) receives dS_p -- at ds_out[out_pos[p]] when
+        ``out_pos`` is given -- the gradient of the bias, in the order ``update_values`` takes.  ``dQ`` and ``delta`` are
+        allocated when None.  No output may alias an input.  Widths over 512 (float64) / 1024 (float32) raise ValueError: the
+        chain of ``row_softmax_bwd`` and the products serves those.  Returns (dQ, delta).  Every error is raised before the
+        library is called."""
+        import torch
+        if (K1 is None) != (V1 is None):
+            raise ValueError("K1 and V1 come together")
+        kops = [("Q", Q), ("K0", K0)] + ([("K1", K1)] if K1 is not None else []) + ([("dQ", dQ)] if dQ is not None else [])
+        vops = [("V0", V0)] + ([("V1", V1)] if V1 is not None else []) + [("O", O), ("dO", dO)]
+        vecs = [("lse", lse)] + [(n_, t) for n_, t in (("delta", delta), ("ds_out", ds_out)) if t is not None]
+        nk, nv, scale, bias = _bwd_operands(kops, vops, vecs, scale, bias)
+        x_nrow = getattr(self, "_x_nrow", self.nrow)
+        for name, t in (("Q", Q), ("O", O), ("dO", dO), ("dQ", dQ)):
+            if t is not None and t.shape[0] < x_nrow:
+                raise ValueError("%s has %d rows, the matrix needs %d" % (name, t.shape[0], x_nrow))
+        for name, t in (("K0", K0), ("V0", V0)):
+            if t.shape[0] < self.ncol:
+                raise ValueError("%s has %d rows, the matrix has %d columns" % (name, t.shape[0], self.ncol))
+        if K1 is not None and V1.shape[0] != K1.shape[0]:
+            raise ValueError("K1 has %d rows, V1 %d" % (K1.shape[0], V1.shape[0]))
+        for name, t in (("lse", lse), ("delta", delta)):
+            if t is not None and t.numel() < x_nrow:
+                raise ValueError("%s must hold %d entries" % (name, x_nrow))
+        nnz = self.nnz
+        if out_pos is not None:
+            if not (isinstance(out_pos, torch.Tensor) and out_pos.dtype == torch.int32 and out_pos.dim() == 1
+                    and out_pos.is_contiguous()):
+                raise TypeError("out_pos must be a contiguous 1-D int32 torch tensor on the device")
+            if out_pos.numel() != nnz:
+                raise ValueError("out_pos has %d entries, the matrix %d nonzeros" % (out_pos.numel(), nnz))
+            if ds_out is None:
+                raise ValueError("out_pos needs a ds_out to write into")
+        elif ds_out is not None and ds_out.numel() < nnz:
+            raise ValueError("ds_out has %d entries, the matrix %d nonzeros" % (ds_out.numel(), nnz))
+        _bwd_on_device(kops + vops + vecs + ([("out_pos", out_pos)] if out_pos is not None else []))
+        if dQ is None:
+            dQ = torch.empty((x_nrow, nk), dtype=Q.dtype, device=Q.device)
+        if delta is None:
+            delta = torch.empty((x_nrow,), dtype=Q.dtype, device=Q.device)
+        if self.nrow == 0:
+            return dQ, delta
+        fn = self._lib.crp_attention_bwd_q_csr_f64 if Q.dtype == torch.float64 else self._lib.crp_attention_bwd_q_csr_f32
+        k1p, ldk1, v1p, ldv1 = (K1.data_ptr(), K1.stride(0), V1.data_ptr(), V1.stride(0)) if K1 is not None else (None, 0, None, 0)
+        ptr = lambda t: (t.data_ptr() or None) if t is not None else None
+        L.check(fn(self.handle, nk, nv, scale, bias, Q.data_ptr(), Q.stride(0), ptr(K0), K0.stride(0), k1p, ldk1, ptr(V0), V0.stride(0),
+                   v1p, ldv1, O.data_ptr(), O.stride(0), dO.data_ptr(), dO.stride(0), lse.data_ptr(), dQ.data_ptr(), dQ.stride(0),
+                   delta.data_ptr(), ptr(ds_out), ptr(out_pos), _stream(dQ) if stream is None else stream), fn.__name__)
+        return dQ, delta
+
+    def attention_bwd_kv(self, K, V, Q, dO, lse, delta, scale=1.0, bias=False, dK=None, dV=None, stream=None):
+        """The column side of the fused backward of ``attention`` (crp_attention_bwd_kv_csr_f64 / _f32), on a handle of A^T
+        (``from_transpose``): dK[c] = scale * sum_p dS_p Q[i_p] and dV[c] = sum_p p_p dO[i_p] over the entries of column c of A,
+        with ``lse`` from the forward and ``delta`` from ``attention_bwd_q``.  K, Q, dK have nk columns, V, dO, dV nv; K, V, dK,
+        dV a row per row of this handle, Q, dO, lse, delta one per column.  With ``bias`` the value added to a score is this
+        handle's own.  ``dK is K`` and ``dV is V`` are allowed (same tensor); both are allocated when None.  Widths over 512
+        (float64) / 1024 (float32) raise ValueError.  Returns (dK, dV).  Every error is raised before the library is called."""
+        import torch
+        kops = [("K", K), ("Q", Q)] + ([("dK", dK)] if dK is not None else [])
+        vops = [("V", V), ("dO", dO)] + ([("dV", dV)] if dV is not None else [])
+        nk, nv, scale, bias = _bwd_operands(kops, vops, [("lse", lse), ("delta", delta)], scale, bias)
+        x_nrow = getattr(self, "_x_nrow", self.nrow)
+        for name, t in (("K", K), ("V", V), ("dK", dK), ("dV", dV)):
+            if t is not None and t.shape[0] < x_nrow:
+                raise ValueError("%s has %d rows, the matrix needs %d" % (name, t.shape[0], x_nrow))
+        for name, t in (("Q", Q), ("dO", dO)):
+            if t.shape[0] < self.ncol:
+                raise ValueError("%s has %d rows, the matrix has %d columns" % (name, t.shape[0], self.ncol))
+        for name, t in (("lse", lse), ("delta", delta)):
+            if t.numel() < self.ncol:
+                raise ValueError("%s must hold %d entries" % (name, self.ncol))
+        _bwd_on_device(kops + vops + [("lse", lse), ("delta", delta)])
+        if dK is None:
+            dK = torch.empty((x_nrow, nk), dtype=K.dtype, device=K.device)
+        if dV is None:
+            dV = torch.empty((x_nrow, nv), dtype=K.dtype, device=K.device)
+        if self.nrow == 0:
+            return dK, dV
+        fn = self._lib.crp_attention_bwd_kv_csr_f64 if K.dtype == torch.float64 else self._lib.crp_attention_bwd_kv_csr_f32
+        L.check(fn(self.handle, nk, nv, scale, bias, K.data_ptr(), K.stride(0), V.data_ptr(), V.stride(0), Q.data_ptr() or None,
+                   Q.stride(0), dO.data_ptr() or None, dO.stride(0), lse.data_ptr() or None, delta.data_ptr() or None, dK.data_ptr(),
+                   dK.stride(0), dV.data_ptr(), dV.stride(0), _stream(dK) if stream is None else stream), fn.__name__)
+        return dK, dV
+
     def row_softmax(self, s, out=None, stream=None):
         """Row softmax over this matrix's pattern (crp_csr_dev_row_softmax_f64 / _f32, by the dtype of ``s``): for every row,
         out[p] = exp(s[p] - max) / sum over the row's nonzeros p, which count in the handle's CSR order -- what ``sddmm``
@@ -335,6 +425,56 @@ def _check_dev_vectors(named, nnz):
             raise TypeError("%s must be on the device%s (host values go to update_values)" % (name, "" if t is first else ", with " + head))
 
 
+BWD_WIDTH_CAP = {8: 512, 4: 1024}       # widest nk / nv of the fused attention backward, by the element size
+
+
+def _bwd_operands(kops, vops, vecs, scale, bias):
+    """The operands of the fused attention backward, checked before any library call: kops 2-D of one width nk, vops 2-D of one
+    width nv, vecs 1-D and contiguous, all float64 or float32 of the first's dtype.  Returns (nk, nv, scale,
+    bias) as the C call takes them; the device is checked by _bwd_on_device."""
+    import torch
+    head, first = kops[0]
+    for name, t in kops + vops + vecs:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s must be a torch tensor on the device" % name)
+        if t.dtype not in (torch.float64, torch.float32):
+            raise TypeError("%s must be float64 or float32, got %s" % (name, t.dtype))
+        if t.dtype != first.dtype:
+            raise TypeError("the operands must have one dtype (%s is %s, %s is %s)" % (head, first.dtype, name, t.dtype))
+    for name, t in kops + vops:
+        if t.dim() != 2:
+            raise TypeError("%s must be a 2-D torch tensor on the device" % name)
+        if t.shape[1] > 1 and t.stride(1) != 1:
+            raise ValueError("%s must be contiguous along its rows" % name)
+    for name, t in vecs:
+        if t.dim() != 1 or not t.is_contiguous():
+            raise ValueError("%s must be 1-D and contiguous" % name)
+    if bias not in (False, True, 0, 1):
+        raise ValueError("bias must be a bool, got %r" % (bias,))
+    scale = float(scale)
+    if not np.isfinite(scale):
+        raise ValueError("scale must be finite, got %r" % (scale,))
+    nk, nv = int(first.shape[1]), int(vops[0][1].shape[1])
+    if nk < 1 or nv < 1:
+        raise ValueError("the operands need at least one column")
+    for (ops, n) in ((kops, nk), (vops, nv)):
+        for name, t in ops[1:]:
+            if t.shape[1] != n:
+                raise ValueError("%s has %d columns, %s has %d" % (name, t.shape[1], ops[0][0], n))
+    cap = BWD_WIDTH_CAP[first.element_size()]
+    if nk > cap or nv > cap:
+        raise ValueError("the fused backward takes at most %d columns in %s (nk = %d, nv = %d)" % (cap, first.dtype, nk, nv))
+    return nk, nv, scale, int(bool(bias))
+
+
+def _bwd_on_device(named):
+    """... and, after every shape check, all of them on the first's device (all pointers are device pointers)"""
+    head, first = named[0]
+    for name, t in named:
+        if not t.is_cuda or t.device != first.device:
+            raise TypeError("%s must be on the device, with %s" % (name, head))
+
+
 def _softmax_vecs(named, out, nnz):
     """The value tensors of a row softmax call through ``_check_dev_vectors``; ``out`` is allocated like the first when None.
     Returns the tensors, out last."""
@@ -384,6 +524,52 @@ def row_softmax_bwd(rowptr, y, dy, out=None, stream=None):
     L.check(fn(nrow, rowptr.data_ptr(), y.data_ptr(), dy.data_ptr(), out.data_ptr(), _stream(out) if stream is None else stream),
             fn.__name__)
     return out
+
+
+def sparse_attention(A, At, Q, K, V, scale=1.0, bias=False):
+    """softmax_row(scale * (Q K^T)|pattern(A) (+ A's values with ``bias``)) V as a differentiable function of Q, K and V: ``A`` is
+    the ``CsrDev`` of the pattern, ``At`` the ``CsrDev.from_transpose`` of the same CSR (with ``bias`` both hold the same
+    values).  The forward is ``A.attention``, which keeps O and lse; the backward is ``A.attention_bwd_q`` and
+    ``At.attention_bwd_kv``.  Nothing nnz-sized is stored between the two.  2-D row-major cuda tensors of one dtype.  The
+    matrix's values are constants here: with ``bias`` they enter the scores and get no gradient (``attention_bwd_q`` with
+    ``ds_out`` forms it).  ``At`` must be the transpose of ``A``: its shape and nonzero count are checked, its pattern is not."""
+    if At.nrow != A.ncol or At.ncol != A.nrow or At.nnz != A.nnz:
+        raise ValueError("At is %d x %d with %d nonzeros: not the transpose of A (%d x %d, %d)"
+                         % (At.nrow, At.ncol, At.nnz, A.nrow, A.ncol, A.nnz))
+    return _sparse_attention_fn().apply(Q, K, V, A, At, float(scale), bool(bias))
+
+
+_SPARSE_ATTENTION_FN = None
+
+
+def _sparse_attention_fn():
+    """the autograd.Function behind ``sparse_attention``, made on first use (this module imports torch only where it is used)"""
+    global _SPARSE_ATTENTION_FN
+    if _SPARSE_ATTENTION_FN is not None:
+        return _SPARSE_ATTENTION_FN
+    import torch
+
+    class SparseAttention(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, Q, K, V, A, At, scale, bias):
+            Q, K, V = (t if t.stride(-1) == 1 else t.contiguous() for t in (Q.detach(), K.detach(), V.detach()))
+            lse = torch.empty((Q.shape[0],), dtype=Q.dtype, device=Q.device)
+            O = A.attention(Q, K, V, scale=scale, bias=bias, lse=lse)
+            ctx.save_for_backward(Q, K, V, O, lse)
+            ctx.handles = (A, At, scale, bias)
+            return O
+
+        @staticmethod
+        def backward(ctx, dO):
+            Q, K, V, O, lse = ctx.saved_tensors
+            A, At, scale, bias = ctx.handles
+            dO = dO if dO.stride(-1) == 1 else dO.contiguous()
+            dQ, delta = A.attention_bwd_q(Q, K, V, O, dO, lse, scale=scale, bias=bias)
+            dK, dV = At.attention_bwd_kv(K, V, Q, dO, lse, delta, scale=scale, bias=bias)
+            return dQ, dK, dV, None, None, None, None
+
+    _SPARSE_ATTENTION_FN = SparseAttention
+    return SparseAttention
 
 
 def spmm_csr(A, B0, C_out, n=None, layout=0, B1=None, variant=0, stream=None):

@@ -160,6 +160,39 @@ void crp_rp_spmm_attention_f32_ex(crp_rp_spmm_p rp_spmm, int layout, double scal
                                   const float *K, long long ldK, const float *V, long long ldV, float *O, long long ldO,
                                   float *lse, float *p_out, void *stream);
 int crp_rp_spmm_attention_built(crp_rp_spmm_p rp_spmm);
+/* The fused backward of crp_rp_spmm_attention_ex over this rank's rows of A (crpspmm_hip.h, crp_attention_bwd_q_csr_* and
+ * crp_attention_bwd_kv_csr_*; nk = nv = glb_n): with O and lse as the forward wrote them and the upstream gradient dO,
+ *   dQ[i] = scale sum_p dS_p K[c_p],   dK[c] = scale sum_p dS_p Q[i_p],   dV[c] = sum_p p_p dO[i_p],   ds_out[p] = dS_p (optional: the
+ * gradient of the bias, in A_val's order) -- without the stored probabilities, the value updates and the products of the chain of
+ * existing calls; A's values are not touched.  Every operand is a DEVICE pointer to row-major data (anything else aborts, like the
+ * engine's other argument errors; host operands and layout 1 are not offered): Q, O, dO, dQ and lse have this rank's A_nrow rows,
+ * K, V, dK and dV its rows of B (B_row_displs).  glb_n is at most 512 (fp64) / 1024 (fp32): a wider engine aborts here and keeps
+ * the chain.
+ * Data flow: the forward exchange of K then V, exactly as crp_rp_spmm_attention_ex does it; the row side on the engine's parts
+ * (dQ, an engine-owned delta, ds_out through the positions crp_rp_spmm_sddmm_ex uses); the transposed matrices of
+ * crp_rp_spmm_exec_t_ex, built by the first call that needs them -- the rows owed to peers are computed in place over the received
+ * K and V rows, this rank's own go to dK and dV; then the forward plan runs backwards twice, as exec_t runs it once, each followed
+ * by the accumulate into dK, then dV, through the shared send buffer in stream order.  With timing off and nproc > 1 the first
+ * reverse exchange runs on the engine's second stream beside the local column kernel; with timing on everything runs in sequence
+ * and bills to the pack, redistribution, SpMM and unpack time; n_exec counts these calls too.  With bias = 1 the transposed
+ * matrices hold the engine's current values whichever of crp_rp_spmm_update_values / _dev came before or after they were built.
+ * The first call allocates delta (crp_rp_spmm_attention_bwd_built: 0, then 1) and whatever of the forward attention's and
+ * exec_t's state does not exist yet; an engine that never calls it allocates nothing.
+ * dQ and ds_out are bit-identical across rank counts, timing modes and repeated calls and equal the handle call on the whole
+ * matrix; dK and dV are bit-identical across repeated calls and timing modes for one rank layout, equal the handle call at one
+ * rank, and agree to rounding across rank counts (a column's sum is formed per rank and the ranks' sums are added, as in exec_t).
+ * A plan-only engine aborts; a NULL engine is a no-op. */
+void crp_rp_spmm_attention_bwd_ex(crp_rp_spmm_p rp_spmm, double scale, int bias, const double *Q, long long ldQ,
+                                  const double *K, long long ldK, const double *V, long long ldV, const double *O, long long ldO,
+                                  const double *dO, long long lddO, const double *lse,
+                                  double *dQ, long long lddQ, double *dK, long long lddK, double *dV, long long lddV,
+                                  double *ds_out, void *stream);
+void crp_rp_spmm_attention_bwd_f32_ex(crp_rp_spmm_p rp_spmm, double scale, int bias, const float *Q, long long ldQ,
+                                      const float *K, long long ldK, const float *V, long long ldV, const float *O, long long ldO,
+                                      const float *dO, long long lddO, const float *lse,
+                                      float *dQ, long long lddQ, float *dK, long long lddK, float *dV, long long lddV,
+                                      float *ds_out, void *stream);
+int crp_rp_spmm_attention_bwd_built(crp_rp_spmm_p rp_spmm);
 void crp_rp_spmm_print_stat(crp_rp_spmm_p rp_spmm);
 void crp_rp_spmm_clear_stat(crp_rp_spmm_p rp_spmm);
 /* rp_spmm_init for a caller that ALSO holds the values in device memory, in the order of A_val (A_val_dev: the panel a

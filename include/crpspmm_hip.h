@@ -354,6 +354,68 @@ int crp_attention_csr_f32(crp_csr_dev_p A, int nk, int nv, double scale, int bia
                           const float *V0, long long ldV0, const float *V1, long long ldV1,
                           float *O, long long ldO, float *lse, float *p_out, const int *out_pos, void *stream);
 
+/* ---- the fused backward of crp_attention_csr_* ------------------------------------
+ * Inputs: Q, K, V, scale and bias as in the forward, O and lse as the forward wrote them, and the upstream gradient dO (a row
+ * per row of O).  For every nonzero p = (i, c):
+ *   s_p  = scale * < Q[i][0:nk], K[c][0:nk] >      (bias = 1: + the handle's current value of p, as the forward forms it)
+ *   p_p  = exp(s_p - lse[i]),   dP_p = < dO[i][0:nv], V[c][0:nv] >,   D_i = < dO[i][0:nv], O[i][0:nv] >,   dS_p = p_p (dP_p - D_i)
+ *   dQ[i] = scale * sum over row i of dS_p K[c_p]
+ *   dK[c] = scale * sum over column c of dS_p Q[i_p],     dV[c] = sum over column c of p_p dO[i_p]
+ * in two calls that re-form the probabilities from lse instead of reading stored ones.  Nothing nnz-sized is written unless
+ * ds_out is given, and the handles' values are not touched.
+ *   crp_attention_bwd_q_csr_*, over a handle of A (two-source column codes for K and V, a row map selects the Q / O / dO / dQ /
+ *   lse / delta row, all as in the forward): writes dQ[i][0:nk] and delta[i] = D_i of every row -- delta is required, one entry
+ *   per row, indexed like lse -- and, when ds_out is not NULL, ds_out[out_pos[p]] = dS_p (ds_out[p] when out_pos is NULL): the
+ *   gradient of the bias, i.e. of A's values, in the order crp_csr_dev_update_values takes.
+ *   crp_attention_bwd_kv_csr_*, over a handle of A^T (crp_csr_dev_create_t: its rows are A's columns, its entries the rows of A
+ *   in the stable transposed order; a row map selects the K / V / dK / dV row): one source -- a handle whose codes name a second
+ *   source returns -1.  Takes delta as the row side wrote it and writes dK[c][0:nk], dV[c][0:nv] of every row of the handle.
+ *   With bias = 1 the value added to s_p is this handle's own current value of the entry.
+ * Width cap: a lane keeps the whole of K[c] and V[c], so nk and nv are at most 4 * 64 * W columns each (W = elements per 16
+ * bytes): 512 in fp64, 1024 in fp32.  Wider operands return CRP_ATTN_BWD_EWIDTH with nothing written; the chain of the existing
+ * calls (p_out, crp_row_softmax_bwd_*, value updates and products) serves those widths.
+ * Aliasing: bwd_kv allows dK == K and dV == V exactly (same pointer, same leading dimension): a lane group reads its row of K
+ * and V whole before it writes it, and no other group reads that row.  bwd_q allows no output to alias an input.
+ * Special cases: lse[i] = -inf (an empty or all-masked row) makes every p and dS of that row +0 and dQ[i] = +0; s_p = -inf
+ * gives p = dS = +0 exactly; an empty row of either handle writes +0 to its outputs (delta[i] is still written: a plain dot);
+ * NaN or +inf among a row's scores leaves that row's outputs unspecified, and for bwd_kv those of the columns it touches.
+ * Fixed order: the lane group and the column-to-lane assignment are the forward's, L = max(G(nk), G(nv)); both dots of an entry
+ * and D_i are formed as crp_sddmm_csr_* forms them for (dtype, nk) and (dtype, nv), on both sides, so s, p, dP and dS have the
+ * same bits in both calls; s = dot * scale (+ value), p = exp(s - lse), dS = p * (dP - D) (p == 0: +0); entries go in batches
+ * of 8 in the handle's CSR order with acc[j] = fma(dS_u, K[c_u][j], acc[j]) (kv: fma(dS_u, Q[i_u][j], .) and fma(p_u,
+ * dO[i_u][j], .)) from +0, and dQ = acc * scale (dK likewise; dV = acc).  A row's bits depend on (dtype, nk, nv, scale, bias)
+ * and its entries in the handle's CSR order ONLY: not on alignment or leading dimensions, the source a row comes from, the
+ * handle (full matrix or row subset), the optional output or the other rows.  Error bound: DESIGN.md 5l.
+ * The fp32 forms take scale as a double and round it to float once.  All pointers are device pointers; the launches are
+ * asynchronous on `stream`.  Returns 0 (also for a handle without rows, for which nothing is launched), a HIP error (> 0), or
+ * a negative argument error, before which nothing is written: -1 for a NULL handle or a NULL required pointer (bwd_q: Q, O, dO,
+ * lse, dQ, delta and a K or V source that a code names; bwd_kv: K, V, dK, dV, and Q, dO, lse, delta when the handle has a
+ * nonzero), for nk < 1 or nv < 1, a bias other than 0 or 1, a non-finite scale, and for bwd_kv on a handle with negative
+ * codes; -4 for a leading dimension below its width; CRP_ATTN_BWD_EWIDTH for nk or nv over the cap. */
+#define CRP_ATTN_BWD_EWIDTH (-6)   /* nk or nv above 4 * 64 * (elements per 16 bytes) */
+int crp_attention_bwd_q_csr_f64(crp_csr_dev_p A, int nk, int nv, double scale, int bias,
+                                const double *Q, long long ldQ,
+                                const double *K0, long long ldK0, const double *K1, long long ldK1,
+                                const double *V0, long long ldV0, const double *V1, long long ldV1,
+                                const double *O, long long ldO, const double *dO, long long lddO, const double *lse,
+                                double *dQ, long long lddQ, double *delta, double *ds_out, const int *out_pos, void *stream);
+int crp_attention_bwd_q_csr_f32(crp_csr_dev_p A, int nk, int nv, double scale, int bias,
+                                const float *Q, long long ldQ,
+                                const float *K0, long long ldK0, const float *K1, long long ldK1,
+                                const float *V0, long long ldV0, const float *V1, long long ldV1,
+                                const float *O, long long ldO, const float *dO, long long lddO, const float *lse,
+                                float *dQ, long long lddQ, float *delta, float *ds_out, const int *out_pos, void *stream);
+int crp_attention_bwd_kv_csr_f64(crp_csr_dev_p At, int nk, int nv, double scale, int bias,
+                                 const double *K, long long ldK, const double *V, long long ldV,
+                                 const double *Q, long long ldQ, const double *dO, long long lddO,
+                                 const double *lse, const double *delta,
+                                 double *dK, long long lddK, double *dV, long long lddV, void *stream);
+int crp_attention_bwd_kv_csr_f32(crp_csr_dev_p At, int nk, int nv, double scale, int bias,
+                                 const float *K, long long ldK, const float *V, long long ldV,
+                                 const float *Q, long long ldQ, const float *dO, long long lddO,
+                                 const float *lse, const float *delta,
+                                 float *dK, long long lddK, float *dV, long long lddV, void *stream);
+
 /* ---- row softmax over A's pattern (edge softmax) and its Jacobian product ------
  * For every row r with entries p in [rowptr[r], rowptr[r + 1]):
  *   forward :  m = max_p s[p],  e_p = exp(s[p] - m),  y[p] = e_p / sum_q e_q
