@@ -198,6 +198,21 @@ static void drop_skeleton_when_done(crp_csr_dev *A)
         if (e__ != hipSuccess) return (int) e__;      \
     } while (0)
 
+// State that a call builds on a handle is COMPLETE ON RETURN (include/crpspmm_hip.h, "Streams"): whatever the building call
+// enqueued on its stream is waited for once, so that a later call on any other stream finds it ready.
+// The fp32 copy of the values (the fp32 products, the fp32 SDDMM in mode 1, the fp32 attention calls with bias), built by the
+// first call that needs it and kept current by crp_csr_dev_update_values.
+static int ensure_val32(crp_csr_dev *A, hipStream_t s)
+{
+    if (A->val32 != nullptr) return 0;
+    DevBuf<float> v;
+    CRP_TRY(v.alloc(sizeof(float) * (size_t) (A->nnz > 0 ? A->nnz : 1)));
+    CRP_TRY(crp::convert_f64_f32(A->nnz, A->val, v, s));
+    CRP_TRY(hipStreamSynchronize(s));
+    A->val32 = std::move(v);
+    return 0;
+}
+
 // Build (once) and upload the row-panel format with R = 4 (idx 0) or 8 (idx 1). Blocking.  (A failed upload leaves the format unbuilt.)
 static int ensure_panel(crp_csr_dev *A, int idx, hipStream_t stream)
 {
@@ -255,7 +270,11 @@ static int ensure_panel(crp_csr_dev *A, int idx, hipStream_t stream)
         }
     }
     if (e != hipSuccess) return (int) e;
-    if (A->host_vals_stale && A->nnz > 0) CRP_TRY(scatter_values(A, d, stream));
+    if (A->host_vals_stale && A->nnz > 0)
+    {
+        CRP_TRY(scatter_values(A, d, stream));
+        CRP_TRY(hipStreamSynchronize(stream));      // complete on return, for callers on other streams
+    }
     d.built = true;
     A->pan[idx] = std::move(d);
     return 0;
@@ -442,11 +461,8 @@ template <> int attention_bias_values<float>(crp_csr_dev *A, int bias, hipStream
 {
     *val = nullptr;
     if (bias != 1 || A->nnz == 0) return 0;
-    if (A->val32 == nullptr)
-    {
-        CRP_TRY(A->val32.alloc(sizeof(float) * (size_t) A->nnz));
-        CRP_TRY(crp::convert_f64_f32(A->nnz, A->val, A->val32, s));
-    }
+    const int rc = ensure_val32(A, s);
+    if (rc != 0) return rc;
     *val = (const float *) A->val32;
     return 0;
 }
@@ -991,6 +1007,7 @@ static int spmm_csr_f64(crp_csr_dev_p A, int layout, int n, const double *B0, lo
             if (d.rows_epoch != A->rowmap_epoch || d.rows_map != a.rowmap)      // the C rows of the panels, once per row map
             {
                 CRP_TRY(crp::team2r_fill_rows(t, a, s));
+                CRP_TRY(hipStreamSynchronize(s));       // complete on return: a product on another stream reads these rows
                 d.rows_epoch = A->rowmap_epoch;
                 d.rows_map = a.rowmap;
             }
@@ -1032,10 +1049,9 @@ static int spmm_csr_f32(crp_csr_dev_p A, int n, const float *B0, long long ldB0,
     if (C == NULL || (B0 == NULL && B1 == NULL && A->nnz > 0)) return -1;
     if (ldC < n || (B0 && ldB0 < n) || (B1 && ldB1 < n)) return -4;
     const hipStream_t s = (hipStream_t) stream;
-    if (A->val32 == nullptr)
     {
-        CRP_TRY(A->val32.alloc(sizeof(float) * (size_t) (A->nnz > 0 ? A->nnz : 1)));
-        CRP_TRY(crp::convert_f64_f32(A->nnz, A->val, A->val32, s));
+        const int rc = ensure_val32(A, s);
+        if (rc != 0) return rc;
     }
     crp::SpmmArgsF32 a;
     a.nrow = A->nrow; a.n = n; a.rowptr = A->rowptr; a.colidx = A->colidx; a.val = A->val32;
@@ -1047,9 +1063,12 @@ static int spmm_csr_f32(crp_csr_dev_p A, int n, const float *B0, long long ldB0,
     Team2Dev &d = A->team2;
     if (d.tval32 == nullptr)
     {
-        CRP_TRY(d.tval32.alloc(sizeof(float) * ((size_t) d.value_entries + 1024)));
-        CRP_TRY(hipMemsetAsync(d.tval32, 0, sizeof(float) * ((size_t) d.value_entries + 1024), s));
-        CRP_TRY(crp::convert_f64_f32(d.value_entries, d.tval, d.tval32, s));
+        DevBuf<float> v;
+        CRP_TRY(v.alloc(sizeof(float) * ((size_t) d.value_entries + 1024)));
+        CRP_TRY(hipMemsetAsync(v, 0, sizeof(float) * ((size_t) d.value_entries + 1024), s));
+        CRP_TRY(crp::convert_f64_f32(d.value_entries, d.tval, v, s));
+        CRP_TRY(hipStreamSynchronize(s));           // complete on return, for callers on other streams
+        d.tval32 = std::move(v);
     }
     if (A->rowmap_fmt != nullptr) a.rowmap = A->rowmap_fmt;
     crp::Team2Args t;
@@ -1080,10 +1099,10 @@ int crp_sddmm_csr_f32(crp_csr_dev_p A, int n, const float *X, long long ldX, con
     const int rc = sddmm_check(A, n, X, ldX, Y0, ldY0, Y1, ldY1, out, mode);
     if (rc != 0 || A->nnz == 0) return rc;
     const hipStream_t s = (hipStream_t) stream;
-    if (mode == 1 && A->val32 == nullptr)               // the fp32 copy of the values, as crp_spmm_csr_f32 derives it
+    if (mode == 1)                                      // the fp32 copy of the values, as crp_spmm_csr_f32 derives it
     {
-        CRP_TRY(A->val32.alloc(sizeof(float) * (size_t) A->nnz));
-        CRP_TRY(crp::convert_f64_f32(A->nnz, A->val, A->val32, s));
+        const int rc1 = ensure_val32(A, s);
+        if (rc1 != 0) return rc1;
     }
     return sddmm_csr<float>(A, n, X, ldX, Y0, ldY0, Y1, ldY1, out, out_pos, mode, A->val32, s);
 }
@@ -1106,10 +1125,10 @@ int crp_attention_csr_f32(crp_csr_dev_p A, int nk, int nv, double scale, int bia
     const int rc = attention_check(A, nk, nv, scale, bias, Q, ldQ, K0, ldK0, K1, ldK1, V0, ldV0, V1, ldV1, O, ldO);
     if (rc != 0 || A->nrow == 0) return rc;
     const hipStream_t s = (hipStream_t) stream;
-    if (bias == 1 && A->nnz > 0 && A->val32 == nullptr)     // the fp32 copy of the values, as crp_sddmm_csr_f32 mode 1 derives it
+    if (bias == 1 && A->nnz > 0)                            // the fp32 copy of the values, as crp_sddmm_csr_f32 mode 1 derives it
     {
-        CRP_TRY(A->val32.alloc(sizeof(float) * (size_t) A->nnz));
-        CRP_TRY(crp::convert_f64_f32(A->nnz, A->val, A->val32, s));
+        const int rc1 = ensure_val32(A, s);
+        if (rc1 != 0) return rc1;
     }
     return attention_csr<float>(A, nk, nv, scale, (bias && A->nnz > 0) ? (const float *) A->val32 : nullptr, Q, ldQ, K0, ldK0, K1, ldK1, V0,
                                 ldV0, V1, ldV1, O, ldO, lse, p_out, out_pos, s);

@@ -209,7 +209,8 @@ void crp_rp_spmm_get_plan(crp_rp_spmm_p rp_spmm, crp_rp_plan_view_t *view);
 double crp_rp_spmm_exchange_host_seconds(crp_rp_spmm_p rp_spmm);
 /* timing = 1 (default): every phase is bracketed by stream synchronisation and
  * billed to t_pack / t_a2a / t_unpack / t_spmm like the reference; 0: fully
- * asynchronous exec, only t_exec (host enqueue time) is accumulated. */
+ * asynchronous exec, only t_exec (host enqueue time) is accumulated.  With timing on every call waits for its
+ * stream. */
 /* Exchange / compute overlap: with more than one rank the rows of A are split at init into
  * "interior" rows (no column owned by a peer) and "boundary" rows; with timing off, exec runs the
  * B exchange on a second stream beside the interior rows' product and the boundary rows' product

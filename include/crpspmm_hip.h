@@ -24,6 +24,23 @@
  * caller's local B block (B0, leading dimension ldB0); c < 0 addresses row
  * (~c) of the compact buffer of rows received from peers (B1, ldB1).  With
  * one rank every index is >= 0 and B1 may be NULL.
+ *
+ * Streams.  Every call that takes a `stream` is asynchronous on that stream, taken literally (NULL = the null
+ * stream): in steady state it enqueues all of its device work there and nowhere else, allocates nothing, waits
+ * for nothing and touches no other stream, so it may be captured into a graph on that stream.  The calls that
+ * may block are these and no others:
+ *   - The first call that builds state on a handle blocks: what it builds is complete on return.  State a handle
+ *     builds lazily -- a derived format (row panels, team streams, the row-owner kernel's C rows after a new row
+ *     map) and the fp32 copies of the values -- is built by the first call that needs it, on that call's stream,
+ *     and the call waits once for what it enqueued there.  Later calls on ANY stream therefore find it complete;
+ *     they never wait, and the library keeps no event for it.  Such a first call is not capturable.
+ *   - With a host pointer crp_csr_dev_update_values blocks until the values have left the caller's array.  With
+ *     a device pointer it is asynchronous and refreshes every format and copy built so far on `stream`.
+ *   - crp_csr_transpose with device pointers (it sizes its work from counts it reads back), and the calls marked
+ *     Blocking below.
+ * Two calls on one handle that run on different streams are the caller's to order whenever one of them writes
+ * the handle's values (crp_csr_dev_update_values) or a row map; calls that only read the handle -- the products,
+ * the SDDMM, the attention calls, the row softmax -- need no ordering among themselves.
  */
 #ifndef CRPSPMM_HIP_H
 #define CRPSPMM_HIP_H

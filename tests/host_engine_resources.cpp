@@ -4,291 +4,9 @@
 // something that is not live ends the program.  The engines run over crp_comm_self() on a tiny matrix and on one without
 // nonzeros; afterwards every create has its destroy and nothing is live.  `--trace` prints the names of the ABI calls in order.
 // NOT reached here (only a communicator of several ranks builds them): the interior / boundary split, xstream with ev_packed and
-// ev_landed, the parts' position arrays, the second receive buffer, and the 2D engine's state for pn > 1.
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include <map>
-#include <set>
-#include <string>
-#include <utility>
-#include <vector>
-#include "crp_engine.h"
-#include "crpspmm_hip.h"
-#if __has_include("dev_owned.h")
-#include "dev_owned.h"
-#define HAVE_OWNERS 1
-#endif
-
-#define CHECK(cond, ...)                                                         \
-    do {                                                                         \
-        if (!(cond)) {                                                           \
-            fprintf(stderr, "%s:%d: CHECK(%s) failed: ", __FILE__, __LINE__, #cond); \
-            fprintf(stderr, __VA_ARGS__);                                        \
-            fprintf(stderr, "\n");                                               \
-            exit(1);                                                             \
-        }                                                                        \
-    } while (0)
-
-// ---- stand-ins ------------------------------------------------------------------------------------------------------------------
-struct crp_csr_dev { int nrow; long long nnz; };
-
-static std::map<const char *, size_t> g_dev;          // live "device" blocks: start -> bytes
-static std::set<void *> g_pinned, g_streams, g_events, g_csr;
-static std::map<std::string, long> g_calls;
-static bool g_trace = false;
-
-static int hit(const char *name)
-{
-    g_calls[name]++;
-    if (g_trace) printf("%s\n", name);
-    return 0;
-}
-static long calls(const char *name) { return g_calls.count(name) ? g_calls[name] : 0; }
-static long total_calls()
-{
-    long t = 0;
-    for (auto &kv : g_calls) t += kv.second;
-    return t;
-}
-static bool in_device(const void *p, size_t bytes)
-{
-    auto it = g_dev.upper_bound((const char *) p);
-    if (it == g_dev.begin()) return false;
-    --it;
-    return (const char *) p + bytes <= it->first + it->second;
-}
-static void live_stream(void *s) { CHECK(s == NULL || g_streams.count(s), "a stream that is not live"); }
-static void live_csr(crp_csr_dev_p A) { CHECK(A != NULL && g_csr.count(A), "a matrix handle that is not live"); }
-static int kernel(const char *name, void *stream)
-{
-    live_stream(stream);
-    return hit(name);
-}
-static int csr_create(const char *name, int nrow, const int *rowptr, crp_csr_dev_p *out)
-{
-    crp_csr_dev *A = new crp_csr_dev{nrow, rowptr[nrow]};
-    g_csr.insert(A);
-    *out = A;
-    return hit(name);
-}
-
-extern "C" {
-int crp_dev_malloc(void **p, size_t bytes)
-{
-    *p = NULL;
-    if (bytes == 0) return hit("dev_malloc(0)");      // NULL, as the device ABI gives it: nothing to free
-    *p = calloc(bytes, 1);
-    g_dev[(const char *) *p] = bytes;
-    return hit("dev_malloc");
-}
-int crp_dev_free(void *p)
-{
-    if (p == NULL) return hit("dev_free(null)");
-    CHECK(g_dev.erase((const char *) p) == 1, "crp_dev_free of a block that is not live");
-    free(p);
-    return hit("dev_free");
-}
-int crp_dev_memset(void *p, int v, size_t bytes, void *stream)
-{
-    live_stream(stream);
-    CHECK(bytes == 0 || in_device(p, bytes), "memset outside a live block");
-    if (bytes) memset(p, v, bytes);
-    return hit("dev_memset");
-}
-int crp_dev_memcpy(void *dst, const void *src, size_t bytes, int kind, void *stream)
-{
-    live_stream(stream);
-    if (bytes)
-    {
-        CHECK(kind == 1 || in_device(dst, bytes), "copy into something that is no live block");
-        CHECK(kind == 0 || in_device(src, bytes), "copy out of something that is no live block");
-        memcpy(dst, src, bytes);
-    }
-    return hit("dev_memcpy");
-}
-int crp_dev_memcpy2d(void *dst, size_t dpitch, const void *src, size_t spitch, size_t width_bytes, size_t height, int kind, void *stream)
-{
-    live_stream(stream);
-    for (size_t r = 0; r < height && width_bytes > 0; r++)
-    {
-        CHECK(kind == 1 || in_device((char *) dst + r * dpitch, width_bytes), "2D copy into something that is no live block");
-        CHECK(kind == 0 || in_device((const char *) src + r * spitch, width_bytes), "2D copy out of something that is no live block");
-        memcpy((char *) dst + r * dpitch, (const char *) src + r * spitch, width_bytes);
-    }
-    return hit("dev_memcpy2d");
-}
-int crp_host_malloc(void **p, size_t bytes)
-{
-    *p = calloc(bytes ? bytes : 1, 1);
-    g_pinned.insert(*p);
-    return hit("host_malloc");
-}
-int crp_host_free(void *p)
-{
-    CHECK(g_pinned.erase(p) == 1, "crp_host_free of a block that is not live");
-    free(p);
-    return hit("host_free");
-}
-int crp_dev_ptr_is_device(const void *p, int *is_dev)
-{
-    *is_dev = (p != NULL && in_device(p, 1)) ? 1 : 0;
-    return 0;      // (a query: neither counted nor traced)
-}
-int crp_stream_create(void **s)
-{
-    *s = malloc(1);
-    g_streams.insert(*s);
-    return hit("stream_create");
-}
-int crp_stream_destroy(void *s)
-{
-    CHECK(g_streams.erase(s) == 1, "crp_stream_destroy of a stream that is not live");
-    free(s);
-    return hit("stream_destroy");
-}
-int crp_stream_sync(void *s) { return kernel("stream_sync", s); }
-int crp_event_create(void **ev)
-{
-    *ev = malloc(1);
-    g_events.insert(*ev);
-    return hit("event_create");
-}
-int crp_event_destroy(void *ev)
-{
-    CHECK(g_events.erase(ev) == 1, "crp_event_destroy of an event that is not live");
-    free(ev);
-    return hit("event_destroy");
-}
-int crp_event_record(void *ev, void *s)
-{
-    CHECK(g_events.count(ev), "record of an event that is not live");
-    return kernel("event_record", s);
-}
-int crp_stream_wait_event(void *s, void *ev)
-{
-    CHECK(g_events.count(ev), "wait for an event that is not live");
-    return kernel("stream_wait_event", s);
-}
-int crp_csr_dev_create(int nrow, int, const int *rowptr, const int *, const double *, crp_csr_dev_p *out)
-{
-    return csr_create("csr_dev_create", nrow, rowptr, out);
-}
-int crp_csr_dev_create_dv(int nrow, int, const int *rowptr, const int *, const double *, const double *, const int *, crp_csr_dev_p *out)
-{
-    return csr_create("csr_dev_create_dv", nrow, rowptr, out);
-}
-int crp_csr_dev_destroy(crp_csr_dev_p *A)
-{
-    if (A == NULL || *A == NULL) return hit("csr_dev_destroy(null)");
-    CHECK(g_csr.erase(*A) == 1, "crp_csr_dev_destroy of a handle that is not live");
-    delete *A;
-    *A = NULL;
-    return hit("csr_dev_destroy");
-}
-int crp_csr_dev_update_values(crp_csr_dev_p A, const double *, void *s) { live_csr(A); return kernel("csr_dev_update_values", s); }
-int crp_csr_dev_set_rowmap(crp_csr_dev_p A, const int *, int) { live_csr(A); return hit("csr_dev_set_rowmap"); }
-int crp_csr_dev_nrow(crp_csr_dev_p A) { live_csr(A); return A->nrow; }
-long long crp_csr_dev_nnz(crp_csr_dev_p A) { live_csr(A); return A->nnz; }
-int crp_csr_dev_last_variant(crp_csr_dev_p) { return 0; }
-int crp_csr_dev_resolved_variant(crp_csr_dev_p, int) { return 1; }
-int crp_csr_dev_reordered(crp_csr_dev_p) { return 0; }
-int crp_csr_dev_lattice(crp_csr_dev_p) { return 0; }
-int crp_csr_transpose(int nrow, int ncol, const int *rowptr, const int *, const double *, int *rowptr_t, int *colidx_t, double *val_t,
-                      int *tmap, void *s)
-{
-    // zeros: every entry in row 0 of the transpose's first ncol rows is a legal, if wrong, answer for code that only moves it about
-    CHECK(in_device(rowptr, sizeof(int) * ((size_t) nrow + 1)) && in_device(rowptr_t, sizeof(int) * ((size_t) ncol + 1)), "transpose outside live blocks");
-    const size_t nnz = (size_t) rowptr[nrow];
-    memset(rowptr_t, 0, sizeof(int) * ((size_t) ncol + 1));
-    CHECK(nnz == 0 || (in_device(colidx_t, sizeof(int) * nnz) && in_device(val_t, sizeof(double) * nnz) && in_device(tmap, sizeof(int) * nnz)),
-          "transpose outside live blocks");
-    if (nnz) { memset(colidx_t, 0, sizeof(int) * nnz); memset(val_t, 0, sizeof(double) * nnz); memset(tmap, 0, sizeof(int) * nnz); }
-    return kernel("csr_transpose", s);
-}
-int crp_spmm_csr_f64(crp_csr_dev_p A, int, int, const double *, long long, const double *, long long, double *, long long, int, void *s)
-{
-    live_csr(A);
-    return kernel("spmm_csr_f64", s);
-}
-int crp_spmm_csr_f32(crp_csr_dev_p A, int, const float *, long long, const float *, long long, float *, long long, int, void *s)
-{
-    live_csr(A);
-    return kernel("spmm_csr_f32", s);
-}
-int crp_sddmm_csr_f64(crp_csr_dev_p A, int, const double *, long long, const double *, long long, const double *, long long, double *,
-                      const int *, int, void *s)
-{
-    live_csr(A);
-    return kernel("sddmm_csr_f64", s);
-}
-int crp_sddmm_csr_f32(crp_csr_dev_p A, int, const float *, long long, const float *, long long, const float *, long long, float *, const int *,
-                      int, void *s)
-{
-    live_csr(A);
-    return kernel("sddmm_csr_f32", s);
-}
-int crp_attention_csr_f64(crp_csr_dev_p A, int, int, double, int, const double *, long long, const double *, long long, const double *,
-                          long long, const double *, long long, const double *, long long, double *, long long, double *, double *,
-                          const int *, void *s)
-{
-    live_csr(A);
-    return kernel("attention_csr_f64", s);
-}
-int crp_attention_csr_f32(crp_csr_dev_p A, int, int, double, int, const float *, long long, const float *, long long, const float *, long long,
-                          const float *, long long, const float *, long long, float *, long long, float *, float *, const int *, void *s)
-{
-    live_csr(A);
-    return kernel("attention_csr_f32", s);
-}
-int crp_row_softmax_f64(int, const int *rp, const double *, double *, void *s) { CHECK(in_device(rp, 4), "row pointer"); return kernel("row_softmax_f64", s); }
-int crp_row_softmax_f32(int, const int *rp, const float *, float *, void *s) { CHECK(in_device(rp, 4), "row pointer"); return kernel("row_softmax_f32", s); }
-int crp_row_softmax_bwd_f64(int, const int *rp, const double *, const double *, double *, void *s)
-{
-    CHECK(in_device(rp, 4), "row pointer");
-    return kernel("row_softmax_bwd_f64", s);
-}
-int crp_row_softmax_bwd_f32(int, const int *rp, const float *, const float *, float *, void *s)
-{
-    CHECK(in_device(rp, 4), "row pointer");
-    return kernel("row_softmax_bwd_f32", s);
-}
-int crp_gather_rows_f64(int, int, int, const int *, const double *, long long, double *, long long, void *s) { return kernel("gather_rows_f64", s); }
-int crp_gather_rows_f32(int, int, int, const int *, const float *, long long, float *, long long, void *s) { return kernel("gather_rows_f32", s); }
-int crp_scatter_add_rows_f64(int, int, const int *, const int *, const int *, const double *, long long, double *, long long, void *s)
-{
-    return kernel("scatter_add_rows_f64", s);
-}
-int crp_scatter_add_rows_f32(int, int, const int *, const int *, const int *, const float *, long long, float *, long long, void *s)
-{
-    return kernel("scatter_add_rows_f32", s);
-}
-int crp_gather_vals_f64(long long n, const int *, const double *, double *dst, void *s)
-{
-    CHECK(in_device(dst, sizeof(double) * (size_t) n), "value gather outside a live block");
-    return kernel("gather_vals_f64", s);
-}
-int crp_gather_vals_f32_f64(long long n, const int *, const float *, double *dst, void *s)
-{
-    CHECK(in_device(dst, sizeof(double) * (size_t) n), "value gather outside a live block");
-    return kernel("gather_vals_f32_f64", s);
-}
-int crp_sum_segments_f64(int, long long, const double *, long long, double *, void *s) { return kernel("sum_segments_f64", s); }
-int crp_sum_segments_f32(int, long long, const float *, long long, float *, void *s) { return kernel("sum_segments_f32", s); }
-int crp_transpose_f64(int, int, const double *, long long, double *, long long, void *s) { return kernel("transpose_f64", s); }
-int crp_transpose_f32(int, int, const float *, long long, float *, long long, void *s) { return kernel("transpose_f32", s); }
-}
-
-static void check_balanced(const char *what)
-{
-    CHECK(calls("dev_malloc") == calls("dev_free"), "%s: %ld allocations, %ld frees", what, calls("dev_malloc"), calls("dev_free"));
-    CHECK(g_dev.empty(), "%s: %zu device blocks are still live", what, g_dev.size());
-    CHECK(g_pinned.empty() && calls("host_malloc") == calls("host_free"), "%s: pinned blocks are still live", what);
-    CHECK(g_streams.empty() && calls("stream_create") == calls("stream_destroy"), "%s: %zu streams are still live", what, g_streams.size());
-    CHECK(g_events.empty() && calls("event_create") == calls("event_destroy"), "%s: %zu events are still live", what, g_events.size());
-    CHECK(g_csr.empty() && calls("csr_dev_create") + calls("csr_dev_create_dv") == calls("csr_dev_destroy"), "%s: %zu matrices are still live", what,
-          g_csr.size());
-}
+// ev_landed, the parts' position arrays, the second receive buffer, and the 2D engine's state for pn > 1 (the split engine and its
+// streams: tests/host_engine_streams.cpp, over the same stand-ins, tests/host_device_standins.h).
+#include "host_device_standins.h"
 
 // ---- the owners by themselves ------------------------------------------------------------------------------------------------------
 #ifdef HAVE_OWNERS

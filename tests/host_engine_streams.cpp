@@ -1,0 +1,219 @@
+// The ORDER of the row-parallel engine's device work across streams (csrc/rp_engine.cpp, csrc/rp_attention_bwd.cpp), checked on the
+// CPU under AddressSanitizer / UBSan; built and run by tests/test_host_sanitizers.py.  The device ABI is the set of host stand-ins of
+// tests/host_device_standins.h, which log every call as (call, stream, buffers read, buffers written) and every event record and wait.
+// A single-threaded fake communicator plays rank 0 of 2: it answers the plan's alltoall_i32 / alltoallv_i32 with fabricated but
+// valid requests from the peer and logs alltoallv_dev_f64 as "read send, write recv" on its stream -- so the engine is SPLIT into
+// interior and boundary rows and takes the xstream / ev_packed / ev_landed paths that one rank never reaches.  The caller's stream is
+// a token of its own, distinct from the engine's streams and from the null stream.
+//
+// The log is replayed with vector clocks.  Ordering edges: the order of a stream's own work, event record -> wait, and a stream
+// synchronisation (the host has seen everything on that stream; what it enqueues afterwards comes later).  Asserted: every read of
+// a buffer is ordered after its last write, every write after all earlier reads and writes.  A buffer is a whole live block or a
+// matrix handle (its values), so the check is conservative.  Negative control: the same checker on the same log with one
+// stream_wait_event removed must report a race.  This is the only place the overlap path's order can be checked without several
+// devices; it says nothing about what a real transport does inside alltoallv_dev_f64.
+#include "host_device_standins.h"
+
+// ---- rank 0 of 2 -------------------------------------------------------------------------------------------------------------
+struct FakeCtx { int lo, hi, wanted; };      // my block of B rows, and how many of them the peer asks for
+
+static void f_alltoall(void *ctx, const int *send, int *recv, int count)
+{
+    CHECK(count == 1, "alltoall_i32 with count %d", count);
+    recv[0] = send[0];
+    recv[1] = ((FakeCtx *) ctx)->wanted;
+}
+static void f_alltoallv(void *ctx, const int *send, const int *scnts, const int *sdispls, int *recv, const int *rcnts, const int *rdispls)
+{
+    const FakeCtx *c = (const FakeCtx *) ctx;
+    for (int i = 0; i < rcnts[0]; i++) recv[rdispls[0] + i] = send[sdispls[0] + i];
+    CHECK(scnts[0] == rcnts[0] && rcnts[1] == c->wanted && rcnts[1] <= c->hi - c->lo, "the plan's counts");
+    for (int i = 0; i < rcnts[1]; i++) recv[rdispls[1] + i] = c->hi - 1 - i;      // the peer wants my last rows
+}
+static void f_allgatherv(void *, const void *send, size_t sbytes, void *recv, const size_t *, const size_t *rdispls)
+{
+    if (sbytes) memcpy((char *) recv + rdispls[0], send, sbytes);
+}
+static void f_barrier(void *) {}
+static void f_reduce_f64(void *, const double *in, double *out, int count, int) { memcpy(out, in, sizeof(double) * (size_t) count); }
+static void f_reduce_u64(void *, const uint64_t *in, uint64_t *out, int count, int) { memcpy(out, in, sizeof(uint64_t) * (size_t) count); }
+static void f_exchange(void *, const double *send_dev, const long long *scnts, const long long *, double *recv_dev, const long long *rcnts,
+                       const long long *, void *stream)
+{
+    live_stream(stream);
+    log_op(OP_WORK, "alltoallv_dev_f64", stream, NULL, {R{scnts[1] > 0 ? send_dev : NULL}}, {W{rcnts[1] > 0 ? recv_dev : NULL}});
+    hit("alltoallv_dev_f64");
+}
+static void f_free(crp_comm_t *) {}
+
+// ---- the replay ----------------------------------------------------------------------------------------------------------------
+typedef std::map<void *, long> Clock;      // stream -> count of its operations that have happened
+static void join(Clock &a, const Clock &b)
+{
+    for (auto &kv : b)
+        if (a[kv.first] < kv.second) a[kv.first] = kv.second;
+}
+struct Access { void *stream; long tick; const char *call; size_t index; };
+static bool before(const Access &a, const Clock &now)
+{
+    auto it = now.find(a.stream);
+    return it != now.end() && a.tick <= it->second;
+}
+struct Race { size_t first, second; const void *buffer; };
+
+// every pair of conflicting accesses that the log does not order; skip_wait: the index of a wait to leave out (the negative control)
+static std::vector<Race> races(const std::vector<Op> &log, size_t skip_wait = (size_t) -1)
+{
+    std::map<void *, Clock> at;                  // the clock of every stream (key NULL: the null stream)
+    std::map<void *, Clock> recorded;            // the clock an event was last recorded at
+    Clock host;                                  // what the host has waited for
+    std::map<const void *, Access> last_write;
+    std::map<const void *, std::vector<Access>> reads_since;
+    std::vector<Race> out;
+    for (size_t i = 0; i < log.size(); i++)
+    {
+        const Op &op = log[i];
+        if (op.kind == OP_FORGET)
+        {
+            for (const void *b : op.writes) { last_write.erase(b); reads_since.erase(b); }
+            continue;
+        }
+        Clock &c = at[op.stream];
+        join(c, host);                           // enqueued now: after everything the host has waited for
+        if (op.kind == OP_SYNC) { join(host, c); continue; }
+        if (op.kind == OP_WAIT)
+        {
+            if (i != skip_wait && recorded.count(op.event)) join(c, recorded[op.event]);
+            continue;
+        }
+        const long tick = ++c[op.stream];
+        if (op.kind == OP_RECORD) { recorded[op.event] = c; continue; }
+        const Access me{op.stream, tick, op.call, i};
+        for (const void *b : op.reads)
+            if (last_write.count(b) && !before(last_write[b], c)) out.push_back(Race{last_write[b].index, i, b});
+        for (const void *b : op.writes)
+        {
+            if (last_write.count(b) && !before(last_write[b], c)) out.push_back(Race{last_write[b].index, i, b});
+            for (const Access &r : reads_since[b])
+                if (r.index != i && !before(r, c)) out.push_back(Race{r.index, i, b});
+        }
+        for (const void *b : op.reads) reads_since[b].push_back(me);
+        for (const void *b : op.writes) { last_write[b] = me; reads_since[b].clear(); }
+    }
+    return out;
+}
+
+// ---- the engine's calls ----------------------------------------------------------------------------------------------------------
+template <class T> struct Dev      // a caller's device array
+{
+    T *p = nullptr;
+    explicit Dev(size_t n) { void *d; crp_dev_malloc(&d, sizeof(T) * (n ? n : 1)); p = (T *) d; }
+    ~Dev() { crp_dev_free(p); }
+};
+
+int main()
+{
+    // 4 of 8 rows on rank 0, B rows 0 .. 3 here and 4 .. 7 on the peer; rows 0 and 1 name local columns only (interior), rows 2 and 3
+    // name columns of the peer (boundary)
+    const int m = 4, N = 3, displs[3] = {0, 4, 8};
+    const std::vector<int> rp{0, 2, 4, 7, 9}, ci{0, 1, 1, 3, 2, 4, 6, 0, 7};
+    const std::vector<double> va{1, 2, 3, 4, 5, 6, 7, 8, 9};
+    const size_t nnz = va.size();
+    FakeCtx fc{0, 4, 2};
+    crp_comm_t comm;
+    memset(&comm, 0, sizeof(comm));
+    comm.ctx = &fc; comm.nproc = 2; comm.rank = 0;
+    comm.alltoall_i32 = f_alltoall; comm.alltoallv_i32 = f_alltoallv; comm.allgatherv_bytes = f_allgatherv; comm.barrier = f_barrier;
+    comm.reduce_f64 = f_reduce_f64; comm.reduce_u64 = f_reduce_u64; comm.alltoallv_dev_f64 = f_exchange; comm.free = f_free;
+
+    g_logging = true;
+    crp_rp_spmm_p e = NULL;
+    crp_rp_spmm_init(0, m, rp.data(), ci.data(), va.data(), displs, N, &comm, &e);
+    int n_int = 0, n_bnd = 0;
+    crp_rp_spmm_overlap_rows(e, &n_int, &n_bnd);
+    CHECK(n_int == 2 && n_bnd == 2, "the engine is not split: %d interior, %d boundary rows", n_int, n_bnd);
+    crp_rp_spmm_set_timing(e, 0);
+    void *caller = NULL, *caller2 = NULL;
+    crp_stream_create(&caller);
+    crp_stream_create(&caller2);
+    {
+        Dev<double> B((size_t) m * N), C((size_t) m * N), X((size_t) m * N), Ct((size_t) m * N), out(nnz), Q((size_t) m * N), K((size_t) m * N),
+            V((size_t) m * N), O((size_t) m * N), lse(m), p(nnz), dO((size_t) m * N), dQ((size_t) m * N), dK((size_t) m * N), dV((size_t) m * N),
+            ds(nnz), vals(nnz), vals2(nnz);
+        Dev<float> Bf((size_t) m * N), Cf((size_t) m * N), Xf((size_t) m * N), outf(nnz), valsf(nnz);
+        // what the caller wrote before: on the caller's stream (the engine must order its other streams after it)
+        for (double *b : {B.p, X.p, Q.p, K.p, V.p, dO.p, vals.p}) crp_dev_memset(b, 0, 8, caller);
+        for (float *b : {Bf.p, Xf.p, valsf.p}) crp_dev_memset(b, 0, 4, caller);
+        auto round_of_calls = [&](void *s) {
+            crp_rp_spmm_exec_ex(e, 0, B.p, N, C.p, N, s);
+            crp_rp_spmm_exec_f32_ex(e, 0, Bf.p, N, Cf.p, N, s);
+            crp_rp_spmm_exec_t_ex(e, 0, X.p, N, Ct.p, N, s);
+            crp_rp_spmm_exec_t_f32_ex(e, 0, Xf.p, N, Cf.p, N, s);
+            crp_rp_spmm_sddmm_ex(e, 0, X.p, N, B.p, N, out.p, 1, s);
+            crp_rp_spmm_sddmm_f32_ex(e, 0, Xf.p, N, Bf.p, N, outf.p, 1, s);
+            crp_rp_spmm_attention_ex(e, 0, 0.5, 1, Q.p, N, K.p, N, V.p, N, O.p, N, lse.p, p.p, s);
+            crp_rp_spmm_attention_bwd_ex(e, 0.5, 1, Q.p, N, K.p, N, V.p, N, O.p, N, dO.p, N, lse.p, dQ.p, N, dK.p, N, dV.p, N, ds.p, s);
+        };
+        round_of_calls(caller);                                  // the first calls build what they need
+        round_of_calls(caller);                                  // steady state
+        crp_rp_spmm_update_values(e, va.data());                 // a host update behind execs in flight on the caller's stream
+        round_of_calls(caller);
+        crp_rp_spmm_update_values_dev(e, vals.p, 0, caller);     // a device update on the caller's stream, then more work there
+        crp_rp_spmm_update_values_dev(e, valsf.p, 1, caller);
+        round_of_calls(caller);
+        crp_rp_spmm_update_values(e, va.data());                 // ... and a host update behind the device update
+        round_of_calls(caller);
+        // a second caller stream: the caller orders its own buffers (it waits for the first), the engine orders its values
+        crp_stream_sync(caller);
+        crp_dev_memset(vals2.p, 0, 8, caller2);
+        crp_rp_spmm_update_values_dev(e, vals2.p, 0, caller2);
+        round_of_calls(caller2);
+        crp_stream_sync(caller2);
+        crp_rp_spmm_update_values_dev(e, vals.p, 0, caller);     // ... and back: after an update on another stream
+        round_of_calls(caller);
+        crp_stream_sync(caller);
+        crp_stream_sync(caller2);
+    }
+    crp_rp_spmm_free(&e);
+    crp_stream_destroy(caller);
+    crp_stream_destroy(caller2);
+    g_logging = false;
+    check_balanced("split row engine");
+
+    // ---- the log reached the overlap path, and it is ordered
+    std::set<void *> work_streams;
+    long exchanges = 0, waits = 0;
+    for (const Op &op : g_log)
+    {
+        if (op.kind == OP_WORK) work_streams.insert(op.stream);
+        if (op.kind == OP_WORK && strcmp(op.call, "alltoallv_dev_f64") == 0 && op.stream != caller && op.stream != caller2) exchanges++;
+        if (op.kind == OP_WAIT) waits++;
+    }
+    CHECK(work_streams.count(caller) && work_streams.count(caller2) && work_streams.size() >= 4, "work on %zu streams only", work_streams.size());
+    CHECK(exchanges > 0 && waits > 0, "no exchange on the engine's second stream (%ld) or no wait (%ld)", exchanges, waits);
+    const std::vector<Race> found = races(g_log);
+    for (size_t i = 0; i < found.size() && i < 10; i++)
+        fprintf(stderr, "race: #%zu %s (stream %p) and #%zu %s (stream %p) on buffer %p\n", found[i].first, g_log[found[i].first].call,
+                g_log[found[i].first].stream, found[i].second, g_log[found[i].second].call, g_log[found[i].second].stream, found[i].buffer);
+    CHECK(found.empty(), "%zu unordered pairs of conflicting accesses", found.size());
+
+    // ---- negative control: without its first wait for the exchange stream, the caller's stream races with the exchange
+    std::map<void *, void *> recorded_on;
+    size_t victim = (size_t) -1;
+    long needed = 0, cross = 0;
+    for (size_t i = 0; i < g_log.size(); i++)
+    {
+        const Op &op = g_log[i];
+        if (op.kind == OP_RECORD) recorded_on[op.event] = op.stream;
+        if (op.kind != OP_WAIT || !recorded_on.count(op.event) || recorded_on[op.event] == op.stream) continue;
+        cross++;
+        if (!races(g_log, i).empty()) needed++;
+        if (victim == (size_t) -1 && op.stream == caller && recorded_on[op.event] != caller2) victim = i;
+    }
+    CHECK(victim != (size_t) -1, "the caller's stream never waits for an engine stream");
+    const std::vector<Race> broken = races(g_log, victim);
+    CHECK(!broken.empty(), "the checker does not see the race of a log without wait #%zu", victim);
+    printf("HOST_ENGINE_STREAMS_OK ops=%zu streams=%zu exchanges=%ld cross_stream_waits=%ld needed=%ld control_races=%zu\n", g_log.size(),
+           work_streams.size(), exchanges, cross, needed, broken.size());
+    return 0;
+}

@@ -1,7 +1,8 @@
 """CPU: the host half of the product (format builders, team scheduler, planner, ingest) compiled with
 AddressSanitizer + UBSan and driven by tests/host_asan.cpp, and the engines' operand layer (csrc/operand_view.h) over host stand-ins for the device ABI, driven by
 tests/host_operand_view.cpp, and the two engines with the owners of their device resources (csrc/dev_owned.h) over such stand-ins, driven by
-tests/host_engine_resources.cpp (GPU sanitizers are not available on the pool)."""
+tests/host_engine_resources.cpp, and the row engine's cross-stream ORDER on a split engine, replayed with vector clocks from the stand-ins' log by
+tests/host_engine_streams.cpp (GPU sanitizers are not available on the pool)."""
 import os
 import shutil
 import subprocess
@@ -62,3 +63,26 @@ def test_engine_resources_under_asan_ubsan(tmp_path):
     t = subprocess.run([exe, "--trace"], capture_output=True, text=True, timeout=600, env=env)
     names = t.stdout.split()
     assert t.returncode == 0 and len(names) > 1000 and "dev_free(null)" not in names and "csr_dev_destroy(null)" not in names
+
+
+def test_engine_stream_order_under_asan_ubsan(tmp_path):
+    """The split row engine (a fake communicator of 2 ranks) orders every conflicting pair of device accesses across the caller's
+    stream, its own stream and the exchange stream -- exec, exec_t, sddmm, attention, attention_bwd, update_values and
+    update_values_dev, on two caller streams -- and the same checker reports a race once one stream_wait_event is taken out of
+    the log (tests/host_engine_streams.cpp)."""
+    gxx = shutil.which("g++")
+    if gxx is None:
+        pytest.skip("no g++")
+    src = os.path.join(ROOT, "crp-spmm_amd", "csrc")
+    files = [os.path.join(src, f) for f in ("rp_engine.cpp", "rp_attention_bwd.cpp", "knobs.cpp", "host_support.cpp")]
+    exe = str(tmp_path / "host_engine_streams")
+    cmd = [gxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+           "-fno-omit-frame-pointer", "-pthread", "-I" + os.path.join(ROOT, "include"), "-I" + src,
+           os.path.join(ROOT, "tests", "host_engine_streams.cpp"), *files, "-o", exe]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0 and "HOST_ENGINE_STREAMS_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
+    stats = dict(kv.split("=") for kv in r.stdout.split()[1:])
+    assert int(stats["streams"]) >= 4 and int(stats["exchanges"]) > 0 and int(stats["needed"]) > 0 and int(stats["control_races"]) > 0, r.stdout
