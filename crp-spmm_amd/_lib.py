@@ -173,6 +173,13 @@ SIGNATURES = {
     "crp_attention_bwd_q_csr_f32": (_I, [_V, _I, _I, C.c_double, _I, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _V, _LL, _V, _V, _V, _V]),
     "crp_attention_bwd_kv_csr_f64": (_I, [_V, _I, _I, C.c_double, _I, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _V, _V, _LL, _V, _LL, _V]),
     "crp_attention_bwd_kv_csr_f32": (_I, [_V, _I, _I, C.c_double, _I, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _V, _V, _LL, _V, _LL, _V]),
+    # ... multi-head: (heads, dk, dv) in place of (nk, nv)
+    "crp_attention_mh_csr_f64": (_I, [_V, _I, _I, _I, C.c_double, _I, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _V, _V, _V]),
+    "crp_attention_mh_csr_f32": (_I, [_V, _I, _I, _I, C.c_double, _I, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _V, _V, _V]),
+    "crp_attention_bwd_q_mh_csr_f64": (_I, [_V, _I, _I, _I, C.c_double, _I, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _V, _LL, _V, _V, _V, _V]),
+    "crp_attention_bwd_q_mh_csr_f32": (_I, [_V, _I, _I, _I, C.c_double, _I, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _V, _LL, _V, _V, _V, _V]),
+    "crp_attention_bwd_kv_mh_csr_f64": (_I, [_V, _I, _I, _I, C.c_double, _I, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _V, _V, _LL, _V, _LL, _V]),
+    "crp_attention_bwd_kv_mh_csr_f32": (_I, [_V, _I, _I, _I, C.c_double, _I, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _V, _V, _LL, _V, _LL, _V]),
     "crp_row_softmax_f64": (_I, [_I, _V, _V, _V, _V]),
     "crp_row_softmax_f32": (_I, [_I, _V, _V, _V, _V]),
     "crp_row_softmax_bwd_f64": (_I, [_I, _V, _V, _V, _V, _V]),
@@ -219,6 +226,11 @@ SIGNATURES = {
     "crp_rp_spmm_attention_bwd_ex": (None, [_V, C.c_double, _I, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _V, _LL, _V, _LL, _V, _LL, _V, _V]),
     "crp_rp_spmm_attention_bwd_f32_ex": (None, [_V, C.c_double, _I, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _V, _LL, _V, _LL, _V, _LL, _V, _V]),
     "crp_rp_spmm_attention_bwd_built": (_I, [_V]),
+    # ... multi-head: heads after the layout (forward) / the engine (backward)
+    "crp_rp_spmm_attention_mh_ex": (None, [_V, _I, _I, C.c_double, _I, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _V, _V]),
+    "crp_rp_spmm_attention_mh_f32_ex": (None, [_V, _I, _I, C.c_double, _I, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _V, _V]),
+    "crp_rp_spmm_attention_bwd_mh_ex": (None, [_V, _I, C.c_double, _I, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _V, _LL, _V, _LL, _V, _LL, _V, _V]),
+    "crp_rp_spmm_attention_bwd_mh_f32_ex": (None, [_V, _I, C.c_double, _I, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _V, _LL, _V, _LL, _V, _LL, _V, _V]),
     "crp_rp_spmm_print_stat": (None, [_V]),
     "crp_rp_spmm_clear_stat": (None, [_V]),
     "crp_rp_spmm_get_plan": (None, [_V, C.POINTER(RpPlanView)]),

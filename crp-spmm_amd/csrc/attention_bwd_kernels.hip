@@ -34,6 +34,13 @@
 // ALIASING.  bwd_kv: dK == K and dV == V (exactly) are legal: a group reads its K and V row whole before it writes them, and no
 // other group reads them.  bwd_q: no output may alias an input.
 //
+// MULTI-HEAD (the MH instances, attention_bwd_q_mh_* / attention_bwd_kv_mh_*).  a.heads = H heads of nk / nv columns each, side by
+// side in every operand, as in the forward: a group owns the unit (row, head) = (u / H, u % H) -- bwd_kv: (column c, head h) -- and
+// works on the column views of its head, so head h's bits are the single-head instance's.  lse and delta are (rows of A, H)
+// row-major, ds_out (nnz, H); val[p] is shared by the heads.  dK == K and dV == V stay legal: a group reads its own slice of the row
+// whole before it writes it, and no other group reads that slice.  The cap applies to one head's widths.  The single-head
+// instances (MH = false) compile none of this.
+//
 // LOADS IN FLIGHT.  Per batch, the gathers of a step (per lane two 16-byte pieces, or one piece by elements, of each of the 8 K
 // rows and of the 8 V rows; kv: Q and dO rows) are all issued before the step's FMAs.
 #include <hip/hip_runtime.h>
@@ -255,7 +262,9 @@ __device__ __forceinline__ void ab_entry(const T dot, const T dp, const T scale,
 }
 
 // LPR lanes per row; PK / PV pieces per lane of the nk- / nv-wide rows.  VEC: 16-byte accesses; else single elements.
-template <typename T, int LPR, int PK, int PV, bool VEC>
+// MH: a group owns the unit (row, head) = (u / heads, u % heads), nk and nv are the widths of one head, and head h's slices start
+// at column h * nk and h * nv; lse and delta are (rows, heads), ds_out is (nnz, heads).  Without MH none of it is compiled.
+template <typename T, int LPR, int PK, int PV, bool VEC, bool MH = false>
 __global__ __launch_bounds__(256) void attention_bwd_q_kernel(const AttnBwdQArgs<T> a)
 {
     constexpr int VW  = AbPiece<T>::VW;
@@ -263,22 +272,37 @@ __global__ __launch_bounds__(256) void attention_bwd_q_kernel(const AttnBwdQArgs
     constexpr int UNR = AB_UNR;
     constexpr int CK  = ab_ch<PK, VEC>;
     const int lir = threadIdx.x % LPR;                  // lane in row group
-    const int row = blockIdx.x * RPB + threadIdx.x / LPR;
-    if (row >= a.nrow) return;
+    int row = blockIdx.x * RPB + threadIdx.x / LPR;
+    int64_t nh = 1, h = 0;                              // heads, and this group's
+    if constexpr (MH)
+    {
+        const int64_t u = (int64_t) blockIdx.x * RPB + threadIdx.x / LPR;
+        nh = a.heads;
+        if (u >= (int64_t) a.nrow * nh) return;
+        row = (int) (u / nh);
+        h = u % nh;
+    }
+    else if (row >= a.nrow) return;
     int pb = a.rowptr[row];
     const int pe = a.rowptr[row + 1];
     if constexpr (LPR == 64) pb = __builtin_amdgcn_readfirstlane(pb);
     const int nk = a.nk, nv = a.nv;
     const int64_t orow = a.rowmap ? a.rowmap[row] : row;
+    const int64_t hk = h * nk, hv = h * nv;             // the head's first column (MH; else 0)
+    const int64_t srow = MH ? orow * nh + h : orow;     // the unit's entry of lse and delta
+    auto ppos = [&](const int pos) {                    // where nonzero position pos of this unit lies in ds_out
+        if constexpr (MH) return pos * nh + h;
+        else return pos;
+    };
     const T ninf = ab_ninf<T>();
 
     // D = < dO[i], O[i] >, the SDDMM's dot for (dtype, nv); every lane of the group ends with the same bits
     T xd[PV][VW];
-    ab_load_row<T, LPR, PV, VEC>(xd, a.dO + orow * a.lddO, nv, lir);
+    ab_load_row<T, LPR, PV, VEC>(xd, a.dO + orow * a.lddO + hv, nv, lir);
     T delta = (T) 0;
     {
         T xo[PV][VW];
-        ab_load_row<T, LPR, PV, VEC>(xo, a.O + orow * a.ldO, nv, lir);
+        ab_load_row<T, LPR, PV, VEC>(xo, a.O + orow * a.ldO + hv, nv, lir);
 #pragma unroll
         for (int v = 0; v < PV; v++)
 #pragma unroll
@@ -287,24 +311,24 @@ __global__ __launch_bounds__(256) void attention_bwd_q_kernel(const AttnBwdQArgs
 #pragma unroll
         for (int mask = 1; mask < LPR; mask <<= 1) delta = delta + __shfl_xor(delta, mask, LPR);
     }
-    if (lir == 0) a.delta[orow] = delta;
+    if (lir == 0) a.delta[srow] = delta;
 
     T acc[PK][VW];
 #pragma unroll
     for (int v = 0; v < PK; v++)
 #pragma unroll
         for (int w = 0; w < VW; w++) acc[v][w] = (T) 0;
-    T *const dqrow = a.dQ + orow * a.lddQ;
-    const T lse = a.lse[orow];
+    T *const dqrow = a.dQ + orow * a.lddQ + hk;
+    const T lse = a.lse[srow];
     if (pb >= pe || lse == ninf)                        // an empty or all-masked row: +0 everywhere; no Q row is read
     {
         ab_store_row<T, LPR, PK, VEC>(acc, dqrow, nk, lir);
         if (a.ds_out != nullptr)
-            for (int p = pb + lir; p < pe; p += LPR) a.ds_out[a.out_pos ? a.out_pos[p] : p] = (T) 0;
+            for (int p = pb + lir; p < pe; p += LPR) a.ds_out[ppos(a.out_pos ? a.out_pos[p] : p)] = (T) 0;
         return;
     }
     T xq[PK][VW];
-    ab_load_row<T, LPR, PK, VEC>(xq, a.Q + orow * a.ldQ, nk, lir);
+    ab_load_row<T, LPR, PK, VEC>(xq, a.Q + orow * a.ldQ + hk, nk, lir);
     const T scale = a.scale;
     const int again = ab_again<VW>(a.nk);
 
@@ -321,8 +345,8 @@ __global__ __launch_bounds__(256) void attention_bwd_q_kernel(const AttnBwdQArgs
             for (int u = 0; u < UNR; u++)
             {
                 const int cj = ab_bcast_i<LPR>(c, min(j + u, cnt - 1));
-                krow[u] = (cj >= 0) ? (a.K0 + (int64_t) cj * a.ldK0) : (a.K1 + (int64_t) (~cj) * a.ldK1);
-                vrow[u] = (cj >= 0) ? (a.V0 + (int64_t) cj * a.ldV0) : (a.V1 + (int64_t) (~cj) * a.ldV1);
+                krow[u] = ((cj >= 0) ? (a.K0 + (int64_t) cj * a.ldK0) : (a.K1 + (int64_t) (~cj) * a.ldK1)) + hk;
+                vrow[u] = ((cj >= 0) ? (a.V0 + (int64_t) cj * a.ldV0) : (a.V1 + (int64_t) (~cj) * a.ldV1)) + hv;
             }
             T ps[UNR], pp[UNR];
             ab_dots2<T, LPR, PK, PV, VEC>(ps, xq, krow, nk, pp, xd, vrow, nv, lir);
@@ -334,7 +358,7 @@ __global__ __launch_bounds__(256) void attention_bwd_q_kernel(const AttnBwdQArgs
             {
                 const int p = p0 + mine;
                 ab_entry<T>(rs, rp, scale, a.val, p, lse, delta, false, &prob, &ds);
-                if (a.ds_out != nullptr && lir < UNR) a.ds_out[a.out_pos ? a.out_pos[p] : p] = ds;
+                if (a.ds_out != nullptr && lir < UNR) a.ds_out[ppos(a.out_pos ? a.out_pos[p] : p)] = ds;
             }
             T coef[UNR];
 #pragma unroll
@@ -356,7 +380,8 @@ __global__ __launch_bounds__(256) void attention_bwd_q_kernel(const AttnBwdQArgs
     ab_store_row<T, LPR, PK, VEC>(acc, dqrow, nk, lir);
 }
 
-template <typename T, int LPR, int PK, int PV, bool VEC>
+// MH: the unit is (column c, head h); lse and delta of row i of A are read at i * heads + h
+template <typename T, int LPR, int PK, int PV, bool VEC, bool MH = false>
 __global__ __launch_bounds__(256) void attention_bwd_kv_kernel(const AttnBwdKVArgs<T> a)
 {
     constexpr int VW  = AbPiece<T>::VW;
@@ -364,16 +389,26 @@ __global__ __launch_bounds__(256) void attention_bwd_kv_kernel(const AttnBwdKVAr
     constexpr int UNR = AB_UNR;
     constexpr int CK  = ab_ch<PK, VEC>, CV = ab_ch<PV, VEC>, PM = PK > PV ? PK : PV;
     const int lir = threadIdx.x % LPR;
-    const int row = blockIdx.x * RPB + threadIdx.x / LPR;
-    if (row >= a.nrow) return;
+    int row = blockIdx.x * RPB + threadIdx.x / LPR;
+    int64_t nh = 1, h = 0;                              // heads, and this group's
+    if constexpr (MH)
+    {
+        const int64_t u = (int64_t) blockIdx.x * RPB + threadIdx.x / LPR;
+        nh = a.heads;
+        if (u >= (int64_t) a.nrow * nh) return;
+        row = (int) (u / nh);
+        h = u % nh;
+    }
+    else if (row >= a.nrow) return;
     int pb = a.rowptr[row];
     const int pe = a.rowptr[row + 1];
     if constexpr (LPR == 64) pb = __builtin_amdgcn_readfirstlane(pb);
     const int nk = a.nk, nv = a.nv;
     const int64_t crow = a.rowmap ? a.rowmap[row] : row;
     const T ninf = ab_ninf<T>();
-    T *const dkrow = a.dK + crow * a.lddK;
-    T *const dvrow = a.dV + crow * a.lddV;
+    const int64_t hk = h * nk, hv = h * nv;             // the head's first column (MH; else 0)
+    T *const dkrow = a.dK + crow * a.lddK + hk;
+    T *const dvrow = a.dV + crow * a.lddV + hv;
 
     T accK[PK][VW], accV[PV][VW];
 #pragma unroll
@@ -392,8 +427,8 @@ __global__ __launch_bounds__(256) void attention_bwd_kv_kernel(const AttnBwdKVAr
     }
     // K[c] and V[c] whole, before anything of this row is written (dK == K, dV == V)
     T xk[PK][VW], xv[PV][VW];
-    ab_load_row<T, LPR, PK, VEC>(xk, a.K + crow * a.ldK, nk, lir);
-    ab_load_row<T, LPR, PV, VEC>(xv, a.V + crow * a.ldV, nv, lir);
+    ab_load_row<T, LPR, PK, VEC>(xk, a.K + crow * a.ldK + hk, nk, lir);
+    ab_load_row<T, LPR, PV, VEC>(xv, a.V + crow * a.ldV + hv, nv, lir);
     const T scale = a.scale;
     const int again = ab_again<VW>(a.nk);
 
@@ -409,8 +444,8 @@ __global__ __launch_bounds__(256) void attention_bwd_kv_kernel(const AttnBwdKVAr
             for (int u = 0; u < UNR; u++)
             {
                 const int ij = ab_bcast_i<LPR>(c, min(j + u, cnt - 1));
-                qrow[u] = a.Q + (int64_t) ij * a.ldQ;
-                drow[u] = a.dO + (int64_t) ij * a.lddO;
+                qrow[u] = a.Q + (int64_t) ij * a.ldQ + hk;
+                drow[u] = a.dO + (int64_t) ij * a.lddO + hv;
             }
             T ps[UNR], pp[UNR];
             ab_dots2<T, LPR, PK, PV, VEC>(ps, xk, qrow, nk, pp, xv, drow, nv, lir);
@@ -420,8 +455,12 @@ __global__ __launch_bounds__(256) void attention_bwd_kv_kernel(const AttnBwdKVAr
             T prob = (T) 0, ds = (T) 0;
             if (mine < cnt)
             {
-                const T lse = a.lse[im];
-                ab_entry<T>(rs, rp, scale, a.val, p0 + mine, lse, a.delta[im], lse == ninf, &prob, &ds);
+                auto sidx = [&](const int i) {                                  // row i's entry of lse and delta
+                    if constexpr (MH) return i * nh + h;
+                    else return i;
+                };
+                const T lse = a.lse[sidx(im)];
+                ab_entry<T>(rs, rp, scale, a.val, p0 + mine, lse, a.delta[sidx(im)], lse == ninf, &prob, &ds);
             }
             T cs[UNR], cp[UNR];
 #pragma unroll
@@ -459,7 +498,7 @@ static inline bool ab_aligned(std::initializer_list<const void *> ptrs, std::ini
     return ok;
 }
 
-template <typename T, int LPR, int PK, int PV>
+template <typename T, int LPR, int PK, int PV, bool MH>
 static hipError_t launch_bwd(const AttnBwdQArgs<T> &a, hipStream_t s)
 {
     constexpr int VW = AbPiece<T>::VW, RPB = 256 / LPR;
@@ -467,51 +506,75 @@ static hipError_t launch_bwd(const AttnBwdQArgs<T> &a, hipStream_t s)
     const bool vec = ab_aligned({a.Q, a.K0, a.K1, a.V0, a.V1, a.O, a.dO, a.dQ},
                                 {a.nk, a.nv, a.ldQ, a.ldO, a.lddO, a.lddQ, a.K0 ? a.ldK0 : 0, a.K0 ? a.ldV0 : 0, a.K1 ? a.ldK1 : 0,
                                  a.K1 ? a.ldV1 : 0}, VW);
+    if constexpr (MH)
+    {
+        // (nk % VW == 0 and nv % VW == 0 above keep every head's slice on a 16-byte boundary)
+        const int64_t blocks = ((int64_t) a.nrow * a.heads + RPB - 1) / RPB;
+        if (blocks > INT32_MAX) return hipErrorInvalidValue;            // before anything is written
+        const dim3 grid((unsigned) blocks), block(256);
+        if (vec) hipLaunchKernelGGL((attention_bwd_q_kernel<T, LPR, PK, PV, true, true>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((attention_bwd_q_kernel<T, LPR, PK, PV, false, true>), grid, block, 0, s, a);
+        return hipGetLastError();
+    }
     const dim3 grid((a.nrow + RPB - 1) / RPB), block(256);
     if (vec) hipLaunchKernelGGL((attention_bwd_q_kernel<T, LPR, PK, PV, true>), grid, block, 0, s, a);
     else hipLaunchKernelGGL((attention_bwd_q_kernel<T, LPR, PK, PV, false>), grid, block, 0, s, a);
     return hipGetLastError();
 }
 
-template <typename T, int LPR, int PK, int PV>
+template <typename T, int LPR, int PK, int PV, bool MH>
 static hipError_t launch_bwd(const AttnBwdKVArgs<T> &a, hipStream_t s)
 {
     constexpr int VW = AbPiece<T>::VW, RPB = 256 / LPR;
     const bool vec = ab_aligned({a.K, a.V, a.Q, a.dO, a.dK, a.dV}, {a.nk, a.nv, a.ldK, a.ldV, a.ldQ, a.lddO, a.lddK, a.lddV}, VW);
+    if constexpr (MH)
+    {
+        // (nk % VW == 0 and nv % VW == 0 above keep every head's slice on a 16-byte boundary)
+        const int64_t blocks = ((int64_t) a.nrow * a.heads + RPB - 1) / RPB;
+        if (blocks > INT32_MAX) return hipErrorInvalidValue;            // before anything is written
+        const dim3 grid((unsigned) blocks), block(256);
+        if (vec) hipLaunchKernelGGL((attention_bwd_kv_kernel<T, LPR, PK, PV, true, true>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((attention_bwd_kv_kernel<T, LPR, PK, PV, false, true>), grid, block, 0, s, a);
+        return hipGetLastError();
+    }
     const dim3 grid((a.nrow + RPB - 1) / RPB), block(256);
     if (vec) hipLaunchKernelGGL((attention_bwd_kv_kernel<T, LPR, PK, PV, true>), grid, block, 0, s, a);
     else hipLaunchKernelGGL((attention_bwd_kv_kernel<T, LPR, PK, PV, false>), grid, block, 0, s, a);
     return hipGetLastError();
 }
 
-template <typename T, int PK, class Args>
+template <typename T, int PK, bool MH, class Args>
 static hipError_t bwd_wave(const Args &a, hipStream_t s)
 {
     constexpr int W = 16 / (int) sizeof(T);
-    if (a.nv <= 64 * W)  return launch_bwd<T, 64, PK, 1>(a, s);
-    if (a.nv <= 128 * W) return launch_bwd<T, 64, PK, 2>(a, s);
-    return launch_bwd<T, 64, PK, 4>(a, s);
+    if (a.nv <= 64 * W)  return launch_bwd<T, 64, PK, 1, MH>(a, s);
+    if (a.nv <= 128 * W) return launch_bwd<T, 64, PK, 2, MH>(a, s);
+    return launch_bwd<T, 64, PK, 4, MH>(a, s);
 }
 
-// The instance, from (dtype, nk, nv) alone (the rule is stated at the top of this file)
-template <typename T, class Args>
+// The instance, from (dtype, nk, nv) alone (the rule is stated at the top of this file); MH: from the widths of one head
+template <typename T, bool MH, class Args>
 static hipError_t attention_bwd(const Args &a, hipStream_t s)
 {
     constexpr int W = 16 / (int) sizeof(T), CAP = ATTN_BWD_MAX_PIECES * 64 * W;
     if (a.nk > CAP || a.nv > CAP) return hipErrorInvalidValue;         // (the entry points refuse these before they come here)
     if (a.nrow <= 0) return hipSuccess;
     const int wide = a.nk > a.nv ? a.nk : a.nv;
-    if (wide <= 8 * W)  return launch_bwd<T, 8, 1, 1>(a, s);
-    if (wide <= 16 * W) return launch_bwd<T, 16, 1, 1>(a, s);
-    if (wide <= 32 * W) return launch_bwd<T, 32, 1, 1>(a, s);
-    if (a.nk <= 64 * W)  return bwd_wave<T, 1>(a, s);
-    if (a.nk <= 128 * W) return bwd_wave<T, 2>(a, s);
-    return bwd_wave<T, 4>(a, s);
+    if (wide <= 8 * W)  return launch_bwd<T, 8, 1, 1, MH>(a, s);
+    if (wide <= 16 * W) return launch_bwd<T, 16, 1, 1, MH>(a, s);
+    if (wide <= 32 * W) return launch_bwd<T, 32, 1, 1, MH>(a, s);
+    if (a.nk <= 64 * W)  return bwd_wave<T, 1, MH>(a, s);
+    if (a.nk <= 128 * W) return bwd_wave<T, 2, MH>(a, s);
+    return bwd_wave<T, 4, MH>(a, s);
 }
 
-hipError_t attention_bwd_q_f64(const AttnBwdQArgs<double> &a, hipStream_t s) { return attention_bwd<double>(a, s); }
-hipError_t attention_bwd_q_f32(const AttnBwdQArgs<float> &a, hipStream_t s) { return attention_bwd<float>(a, s); }
-hipError_t attention_bwd_kv_f64(const AttnBwdKVArgs<double> &a, hipStream_t s) { return attention_bwd<double>(a, s); }
-hipError_t attention_bwd_kv_f32(const AttnBwdKVArgs<float> &a, hipStream_t s) { return attention_bwd<float>(a, s); }
+hipError_t attention_bwd_q_f64(const AttnBwdQArgs<double> &a, hipStream_t s) { return attention_bwd<double, false>(a, s); }
+hipError_t attention_bwd_q_mh_f64(const AttnBwdQArgs<double> &a, hipStream_t s) { return attention_bwd<double, true>(a, s); }
+hipError_t attention_bwd_q_f32(const AttnBwdQArgs<float> &a, hipStream_t s) { return attention_bwd<float, false>(a, s); }
+hipError_t attention_bwd_q_mh_f32(const AttnBwdQArgs<float> &a, hipStream_t s) { return attention_bwd<float, true>(a, s); }
+hipError_t attention_bwd_kv_f64(const AttnBwdKVArgs<double> &a, hipStream_t s) { return attention_bwd<double, false>(a, s); }
+hipError_t attention_bwd_kv_mh_f64(const AttnBwdKVArgs<double> &a, hipStream_t s) { return attention_bwd<double, true>(a, s); }
+hipError_t attention_bwd_kv_f32(const AttnBwdKVArgs<float> &a, hipStream_t s) { return attention_bwd<float, false>(a, s); }
+hipError_t attention_bwd_kv_mh_f32(const AttnBwdKVArgs<float> &a, hipStream_t s) { return attention_bwd<float, true>(a, s); }
 
 }  // namespace crp

@@ -36,6 +36,15 @@
 // taken to be finite: 0 * V must be 0).  An all-masked row keeps m == -inf and writes zeros, lse = -inf, p_out = 0.  A row with
 // NaN or +inf among its scores has unspecified outputs in that row only.
 //
+// MULTI-HEAD (the MH instances, attention_mh_rm_*).  a.heads = H heads of nk / nv columns each lie side by side in every operand:
+// head h owns columns [h nk, (h + 1) nk) of Q / K and [h nv, (h + 1) nv) of V / O.  A group owns the unit u = row * H + h
+// (row = u / H, h = u % H in 64 bits), so consecutive groups of a wave hold consecutive heads of one row, share its column
+// indices and gather adjacent slices of the same K / V row.  Everything above holds per unit with the operand bases advanced by
+// h nk / h nv: head h's bits are the single-head instance's on the column views of head h.  lse is (rows, H) row-major, p_out
+// (nnz, H): entry (pos, h) at pos * H + h; val[p] (bias) is shared by the heads.  The 16-byte path needs nk % W == 0 and
+// nv % W == 0 as before, which now keeps every head's slice aligned.  The grid is ceil(nrow * H / RPB) in 64 bits.  The
+// single-head instances (MH = false) compile none of this.
+//
 // p_out: the lanes 0 .. 7 of the group that hold a batch's scores store them raw (through out_pos); after the row the same lanes
 // -- entry p of a row that starts at pb belongs to lane (p - pb) % 8 -- read their own stores back and overwrite them with the
 // probabilities.  No lane ever reads what another lane wrote.
@@ -65,7 +74,9 @@ __device__ __forceinline__ int at_bcast_i(int v, int j)
 
 // LPR lanes per row; PK pieces of Q per lane in registers (0: any nk); PV pieces of the accumulator per lane and V block.
 // VEC: 16-byte accesses; else single elements.  Every column slot is checked against its width.
-template <typename T, int LPR, int PK, int PV, bool VEC>
+// MH: a group owns the unit (row, head) = (u / heads, u % heads), nk and nv are the widths of one head, and head h's slices start
+// at column h * nk of Q / K and h * nv of V / O; lse is (rows, heads), p_out is (nnz, heads).  Without MH none of it is compiled.
+template <typename T, int LPR, int PK, int PV, bool VEC, bool MH = false>
 __global__ __launch_bounds__(256) void attention_rm_kernel(const AttnArgs<T> a)
 {
     typedef typename AtPiece<T>::type PT;
@@ -77,15 +88,30 @@ __global__ __launch_bounds__(256) void attention_rm_kernel(const AttnArgs<T> a)
     constexpr int VC  = PV < 4 ? PV : 4;                // pieces of V per load chunk (8 VC pieces in flight)
     constexpr int VBW = LPR * VW * PV;                  // columns of a V block
     const int lir = threadIdx.x % LPR;                  // lane in row group
-    const int row = blockIdx.x * RPB + threadIdx.x / LPR;
-    if (row >= a.nrow) return;
+    int row = blockIdx.x * RPB + threadIdx.x / LPR;
+    int64_t nh = 1, h = 0;                              // heads, and this group's
+    if constexpr (MH)
+    {
+        const int64_t u = (int64_t) blockIdx.x * RPB + threadIdx.x / LPR;
+        nh = a.heads;
+        if (u >= (int64_t) a.nrow * nh) return;
+        row = (int) (u / nh);
+        h = u % nh;
+    }
+    else if (row >= a.nrow) return;
     int pb = a.rowptr[row];
     const int pe = a.rowptr[row + 1];
     if constexpr (LPR == 64) pb = __builtin_amdgcn_readfirstlane(pb);
     const int nk = a.nk, nv = a.nv;
     const int64_t orow = a.rowmap ? a.rowmap[row] : row;        // rowmap: the Q and O row of every row of a row-subset matrix
     const T ninf = at_ninf<T>();
-    T *const orp = a.O + orow * a.ldO;
+    const int64_t hk = h * nk, hv = h * nv;             // the head's first column (MH; else 0)
+    const int64_t srow = MH ? orow * nh + h : orow;     // the unit's entry of lse
+    T *const orp = a.O + orow * a.ldO + hv;
+    auto ppos = [&](const int pos) {                    // where nonzero position pos of this unit lies in p_out
+        if constexpr (MH) return pos * nh + h;
+        else return pos;
+    };
 
     // this lane's piece v of block vb of O[orow]
     auto store_o = [&](const T (*acc)[VW], const int vb) {
@@ -117,10 +143,10 @@ __global__ __launch_bounds__(256) void attention_rm_kernel(const AttnArgs<T> a)
 #pragma unroll
             for (int w = 0; w < VW; w++) z[v][w] = (T) 0;
         for (int vb = 0; vb < nv; vb += VBW) store_o(z, vb);
-        if (a.lse != nullptr && lir == 0) a.lse[orow] = ninf;
+        if (a.lse != nullptr && lir == 0) a.lse[srow] = ninf;
         return;
     }
-    const T *qrow = a.Q + orow * a.ldQ;
+    const T *qrow = a.Q + orow * a.ldQ + hk;
 
     // this lane's pieces piece0 .. piece0 + np - 1 of Q[orow]: piece q starts at column (q * LPR + lir) * VW
     auto load_q = [&](T (*x)[VW], const int piece0, const int np) {
@@ -229,8 +255,8 @@ __global__ __launch_bounds__(256) void attention_rm_kernel(const AttnArgs<T> a)
                 for (int u = 0; u < UNR; u++)
                 {
                     const int cj = at_bcast_i<LPR>(c, min(j + u, cnt - 1));
-                    krow[u] = (cj >= 0) ? (a.K0 + (int64_t) cj * a.ldK0) : (a.K1 + (int64_t) (~cj) * a.ldK1);
-                    vrow[u] = (cj >= 0) ? (a.V0 + (int64_t) cj * a.ldV0) : (a.V1 + (int64_t) (~cj) * a.ldV1);
+                    krow[u] = ((cj >= 0) ? (a.K0 + (int64_t) cj * a.ldK0) : (a.K1 + (int64_t) (~cj) * a.ldK1)) + hk;
+                    vrow[u] = ((cj >= 0) ? (a.V0 + (int64_t) cj * a.ldV0) : (a.V1 + (int64_t) (~cj) * a.ldV1)) + hv;
                 }
                 T part[UNR];
 #pragma unroll
@@ -281,7 +307,7 @@ __global__ __launch_bounds__(256) void attention_rm_kernel(const AttnArgs<T> a)
                     if (first && a.p_out != nullptr && lir < UNR)
                     {
                         const int p = p0 + mine;
-                        a.p_out[a.out_pos ? a.out_pos[p] : p] = s;
+                        a.p_out[ppos(a.out_pos ? a.out_pos[p] : p)] = s;
                     }
                 }
                 T bm = fmax(s, __shfl_xor(s, 1, LPR));
@@ -331,11 +357,11 @@ __global__ __launch_bounds__(256) void attention_rm_kernel(const AttnArgs<T> a)
         store_o(acc, vb);
         if (first)
         {
-            if (a.lse != nullptr && lir == 0) a.lse[orow] = masked ? ninf : m + at_log(l);
+            if (a.lse != nullptr && lir == 0) a.lse[srow] = masked ? ninf : m + at_log(l);
             if (a.p_out != nullptr && lir < UNR)
                 for (int p = pb + lir; p < pe; p += UNR)        // this lane's own stores
                 {
-                    const int pos = a.out_pos ? a.out_pos[p] : p;
+                    const auto pos = ppos(a.out_pos ? a.out_pos[p] : p);
                     const T sv = a.p_out[pos];
                     a.p_out[pos] = masked ? (T) 0 : at_exp(sv - m) / l;
                 }
@@ -343,7 +369,7 @@ __global__ __launch_bounds__(256) void attention_rm_kernel(const AttnArgs<T> a)
     }
 }
 
-template <typename T, int LPR, int PK, int PV>
+template <typename T, int LPR, int PK, int PV, bool MH>
 static hipError_t launch_attention(const AttnArgs<T> &a, hipStream_t s)
 {
     constexpr int VW = 16 / (int) sizeof(T), RPB = 256 / LPR;
@@ -351,39 +377,51 @@ static hipError_t launch_attention(const AttnArgs<T> &a, hipStream_t s)
                      (a.K0 == nullptr || (a.ldK0 % VW == 0 && a.ldV0 % VW == 0)) &&
                      (a.K1 == nullptr || (a.ldK1 % VW == 0 && a.ldV1 % VW == 0)) &&
                      (((uintptr_t) a.Q | (uintptr_t) a.O | (uintptr_t) a.K0 | (uintptr_t) a.K1 | (uintptr_t) a.V0 | (uintptr_t) a.V1) % 16 == 0);
+    if constexpr (MH)
+    {
+        // (nk % VW == 0 and nv % VW == 0 above keep every head's slice on a 16-byte boundary)
+        const int64_t blocks = ((int64_t) a.nrow * a.heads + RPB - 1) / RPB;
+        if (blocks > INT32_MAX) return hipErrorInvalidValue;            // before anything is written
+        const dim3 grid((unsigned) blocks), block(256);
+        if (vec) hipLaunchKernelGGL((attention_rm_kernel<T, LPR, PK, PV, true, true>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((attention_rm_kernel<T, LPR, PK, PV, false, true>), grid, block, 0, s, a);
+        return hipGetLastError();
+    }
     const dim3 grid((a.nrow + RPB - 1) / RPB), block(256);
     if (vec) hipLaunchKernelGGL((attention_rm_kernel<T, LPR, PK, PV, true>), grid, block, 0, s, a);
     else hipLaunchKernelGGL((attention_rm_kernel<T, LPR, PK, PV, false>), grid, block, 0, s, a);
     return hipGetLastError();
 }
 
-template <typename T, int PK>
+template <typename T, int PK, bool MH>
 static hipError_t attention_wave(const AttnArgs<T> &a, hipStream_t s)
 {
     constexpr int W = 16 / (int) sizeof(T);
-    if (a.nv <= 64 * W)  return launch_attention<T, 64, PK, 1>(a, s);
-    if (a.nv <= 128 * W) return launch_attention<T, 64, PK, 2>(a, s);
-    if (a.nv <= 256 * W) return launch_attention<T, 64, PK, 4>(a, s);
-    return launch_attention<T, 64, PK, 8>(a, s);
+    if (a.nv <= 64 * W)  return launch_attention<T, 64, PK, 1, MH>(a, s);
+    if (a.nv <= 128 * W) return launch_attention<T, 64, PK, 2, MH>(a, s);
+    if (a.nv <= 256 * W) return launch_attention<T, 64, PK, 4, MH>(a, s);
+    return launch_attention<T, 64, PK, 8, MH>(a, s);
 }
 
-// The instance, from (dtype, nk, nv) alone (the rule is stated at the top of this file)
-template <typename T>
+// The instance, from (dtype, nk, nv) alone (the rule is stated at the top of this file); MH: from the widths of one head
+template <typename T, bool MH>
 static hipError_t attention_rm(const AttnArgs<T> &a, hipStream_t s)
 {
     constexpr int W = 16 / (int) sizeof(T);
     if (a.nrow <= 0) return hipSuccess;
     const int wide = a.nk > a.nv ? a.nk : a.nv;
-    if (wide <= 8 * W)  return launch_attention<T, 8, 1, 1>(a, s);
-    if (wide <= 16 * W) return launch_attention<T, 16, 1, 1>(a, s);
-    if (wide <= 32 * W) return launch_attention<T, 32, 1, 1>(a, s);
-    if (a.nk <= 64 * W)  return attention_wave<T, 1>(a, s);
-    if (a.nk <= 128 * W) return attention_wave<T, 2>(a, s);
-    if (a.nk <= 256 * W) return attention_wave<T, 4>(a, s);
-    return attention_wave<T, 0>(a, s);
+    if (wide <= 8 * W)  return launch_attention<T, 8, 1, 1, MH>(a, s);
+    if (wide <= 16 * W) return launch_attention<T, 16, 1, 1, MH>(a, s);
+    if (wide <= 32 * W) return launch_attention<T, 32, 1, 1, MH>(a, s);
+    if (a.nk <= 64 * W)  return attention_wave<T, 1, MH>(a, s);
+    if (a.nk <= 128 * W) return attention_wave<T, 2, MH>(a, s);
+    if (a.nk <= 256 * W) return attention_wave<T, 4, MH>(a, s);
+    return attention_wave<T, 0, MH>(a, s);
 }
 
-hipError_t attention_rm_f64(const AttnArgs<double> &a, hipStream_t s) { return attention_rm<double>(a, s); }
-hipError_t attention_rm_f32(const AttnArgs<float> &a, hipStream_t s) { return attention_rm<float>(a, s); }
+hipError_t attention_rm_f64(const AttnArgs<double> &a, hipStream_t s) { return attention_rm<double, false>(a, s); }
+hipError_t attention_rm_f32(const AttnArgs<float> &a, hipStream_t s) { return attention_rm<float, false>(a, s); }
+hipError_t attention_mh_rm_f64(const AttnArgs<double> &a, hipStream_t s) { return attention_rm<double, true>(a, s); }
+hipError_t attention_mh_rm_f32(const AttnArgs<float> &a, hipStream_t s) { return attention_rm<float, true>(a, s); }
 
 }  // namespace crp

@@ -417,39 +417,60 @@ static int sddmm_check(const crp_csr_dev *A, int n, const void *X, long long ldX
     return 0;
 }
 
-static hipError_t attention_launch(const crp::AttnArgs<double> &a, hipStream_t s) { return crp::attention_rm_f64(a, s); }
-static hipError_t attention_launch(const crp::AttnArgs<float> &a, hipStream_t s) { return crp::attention_rm_f32(a, s); }
+// mh: the (row, head) instances (the crp_attention_*_mh_* entry points, whatever their heads); else the single-head ones
+static hipError_t attention_launch(const crp::AttnArgs<double> &a, bool mh, hipStream_t s)
+{
+    return mh ? crp::attention_mh_rm_f64(a, s) : crp::attention_rm_f64(a, s);
+}
+static hipError_t attention_launch(const crp::AttnArgs<float> &a, bool mh, hipStream_t s)
+{
+    return mh ? crp::attention_mh_rm_f32(a, s) : crp::attention_rm_f32(a, s);
+}
 // O = softmax_row(scale (Q K^T)|pattern(A) (+ A's values)) V (attention_kernels.hip), one dtype; val: the values in T, or nullptr
 template <class T>
 static int attention_csr(crp_csr_dev *A, int nk, int nv, double scale, const T *val, const T *Q, long long ldQ, const T *K0,
                          long long ldK0, const T *K1, long long ldK1, const T *V0, long long ldV0, const T *V1, long long ldV1, T *O,
-                         long long ldO, T *lse, T *p_out, const int *out_pos, hipStream_t s)
+                         long long ldO, T *lse, T *p_out, const int *out_pos, hipStream_t s, bool mh = false, int heads = 1)
 {
     crp::AttnArgs<T> a;
+    a.heads = heads;
     a.nrow = A->nrow; a.nk = nk; a.nv = nv; a.rowptr = A->rowptr; a.colidx = A->colidx; a.val = val; a.scale = (T) scale;
     a.Q = Q; a.ldQ = ldQ; a.K0 = K0; a.ldK0 = ldK0; a.K1 = K1; a.ldK1 = ldK1; a.V0 = V0; a.ldV0 = ldV0; a.V1 = V1; a.ldV1 = ldV1;
     a.O = O; a.ldO = ldO; a.lse = lse; a.p_out = p_out; a.rowmap = A->rowmap; a.out_pos = out_pos;
-    return (int) attention_launch(a, s);
+    return (int) attention_launch(a, mh, s);
 }
 // every argument is checked before anything is launched or allocated: a negative return has written nothing
 static int attention_check(const crp_csr_dev *A, int nk, int nv, double scale, int bias, const void *Q, long long ldQ, const void *K0,
                            long long ldK0, const void *K1, long long ldK1, const void *V0, long long ldV0, const void *V1, long long ldV1,
-                           const void *O, long long ldO)
+                           const void *O, long long ldO, int heads = 1)
 {
     if (A == NULL || Q == NULL || O == NULL) return -1;
-    if (nk < 1 || nv < 1 || (bias != 0 && bias != 1) || !std::isfinite(scale)) return -1;
+    if (nk < 1 || nv < 1 || heads < 1 || (bias != 0 && bias != 1) || !std::isfinite(scale)) return -1;
     if ((K0 == NULL || V0 == NULL) && A->b0_rows > 0) return -1;        // a column code names the first source
     if ((K1 == NULL || V1 == NULL) && A->b1_rows > 0) return -1;        // a column code names the second source
-    if (ldQ < nk || ldO < nv) return -4;
-    if ((K0 != NULL && ldK0 < nk) || (K1 != NULL && ldK1 < nk) || (V0 != NULL && ldV0 < nv) || (V1 != NULL && ldV1 < nv)) return -4;
+    const long long wk = (long long) heads * nk, wv = (long long) heads * nv;      // (nk, nv: the widths of one head)
+    if (ldQ < wk || ldO < wv) return -4;
+    if ((K0 != NULL && ldK0 < wk) || (K1 != NULL && ldK1 < wk) || (V0 != NULL && ldV0 < wv) || (V1 != NULL && ldV1 < wv)) return -4;
     return 0;
 }
 
 
-static hipError_t attention_bwd_launch(const crp::AttnBwdQArgs<double> &a, hipStream_t s) { return crp::attention_bwd_q_f64(a, s); }
-static hipError_t attention_bwd_launch(const crp::AttnBwdQArgs<float> &a, hipStream_t s) { return crp::attention_bwd_q_f32(a, s); }
-static hipError_t attention_bwd_launch(const crp::AttnBwdKVArgs<double> &a, hipStream_t s) { return crp::attention_bwd_kv_f64(a, s); }
-static hipError_t attention_bwd_launch(const crp::AttnBwdKVArgs<float> &a, hipStream_t s) { return crp::attention_bwd_kv_f32(a, s); }
+static hipError_t attention_bwd_launch(const crp::AttnBwdQArgs<double> &a, bool mh, hipStream_t s)
+{
+    return mh ? crp::attention_bwd_q_mh_f64(a, s) : crp::attention_bwd_q_f64(a, s);
+}
+static hipError_t attention_bwd_launch(const crp::AttnBwdQArgs<float> &a, bool mh, hipStream_t s)
+{
+    return mh ? crp::attention_bwd_q_mh_f32(a, s) : crp::attention_bwd_q_f32(a, s);
+}
+static hipError_t attention_bwd_launch(const crp::AttnBwdKVArgs<double> &a, bool mh, hipStream_t s)
+{
+    return mh ? crp::attention_bwd_kv_mh_f64(a, s) : crp::attention_bwd_kv_f64(a, s);
+}
+static hipError_t attention_bwd_launch(const crp::AttnBwdKVArgs<float> &a, bool mh, hipStream_t s)
+{
+    return mh ? crp::attention_bwd_kv_mh_f32(a, s) : crp::attention_bwd_kv_f32(a, s);
+}
 // the fp32 copy of the values, as crp_sddmm_csr_f32 mode 1 derives it; the values in T for the bias, or nullptr
 template <class T> static int attention_bias_values(crp_csr_dev *A, int bias, hipStream_t s, const T **val);
 template <> int attention_bias_values<double>(crp_csr_dev *A, int bias, hipStream_t, const double **val)
@@ -467,49 +488,53 @@ template <> int attention_bias_values<float>(crp_csr_dev *A, int bias, hipStream
     return 0;
 }
 // the fused backward (attention_bwd_kernels.hip), one dtype.  Every argument is checked before anything is launched or
-// allocated: a negative return has written nothing.
+// allocated: a negative return has written nothing.  nk, nv: the widths of one head (the cap is theirs); mh: the (row, head)
+// instances.
 template <class T>
 static int attention_bwd_q_csr(crp_csr_dev *A, int nk, int nv, double scale, int bias, const T *Q, long long ldQ, const T *K0, long long ldK0,
                                const T *K1, long long ldK1, const T *V0, long long ldV0, const T *V1, long long ldV1, const T *O,
                                long long ldO, const T *dO, long long lddO, const T *lse, T *dQ, long long lddQ, T *delta, T *ds_out,
-                               const int *out_pos, hipStream_t s)
+                               const int *out_pos, hipStream_t s, bool mh = false, int heads = 1)
 {
-    int rc = attention_check(A, nk, nv, scale, bias, Q, ldQ, K0, ldK0, K1, ldK1, V0, ldV0, V1, ldV1, O, ldO);
+    int rc = attention_check(A, nk, nv, scale, bias, Q, ldQ, K0, ldK0, K1, ldK1, V0, ldV0, V1, ldV1, O, ldO, heads);
     if (rc == 0 && (dO == NULL || lse == NULL || dQ == NULL || delta == NULL)) rc = -1;
-    if (rc == 0 && (lddO < nv || lddQ < nk)) rc = -4;
+    if (rc == 0 && (lddO < (long long) heads * nv || lddQ < (long long) heads * nk)) rc = -4;
     constexpr int cap = crp::ATTN_BWD_MAX_PIECES * 64 * (16 / (int) sizeof(T));
     if (rc == 0 && (nk > cap || nv > cap)) rc = CRP_ATTN_BWD_EWIDTH;
     if (rc != 0 || A->nrow == 0) return rc;
     crp::AttnBwdQArgs<T> a;
+    a.heads = heads;
     rc = attention_bias_values<T>(A, bias, s, &a.val);
     if (rc != 0) return rc;
     a.nrow = A->nrow; a.nk = nk; a.nv = nv; a.rowptr = A->rowptr; a.colidx = A->colidx; a.scale = (T) scale;
     a.Q = Q; a.ldQ = ldQ; a.K0 = K0; a.ldK0 = ldK0; a.K1 = K1; a.ldK1 = ldK1; a.V0 = V0; a.ldV0 = ldV0; a.V1 = V1; a.ldV1 = ldV1;
     a.O = O; a.ldO = ldO; a.dO = dO; a.lddO = lddO; a.lse = lse; a.dQ = dQ; a.lddQ = lddQ; a.delta = delta; a.ds_out = ds_out;
     a.rowmap = A->rowmap; a.out_pos = out_pos;
-    return (int) attention_bwd_launch(a, s);
+    return (int) attention_bwd_launch(a, mh, s);
 }
 template <class T>
 static int attention_bwd_kv_csr(crp_csr_dev *At, int nk, int nv, double scale, int bias, const T *K, long long ldK, const T *V, long long ldV,
                                 const T *Q, long long ldQ, const T *dO, long long lddO, const T *lse, const T *delta, T *dK,
-                                long long lddK, T *dV, long long lddV, hipStream_t s)
+                                long long lddK, T *dV, long long lddV, hipStream_t s, bool mh = false, int heads = 1)
 {
     if (At == NULL || K == NULL || V == NULL || dK == NULL || dV == NULL) return -1;
-    if (nk < 1 || nv < 1 || (bias != 0 && bias != 1) || !std::isfinite(scale)) return -1;
+    if (nk < 1 || nv < 1 || heads < 1 || (bias != 0 && bias != 1) || !std::isfinite(scale)) return -1;
     if (At->b1_rows > 0) return -1;                      // a code names a second source: this call takes one
     if ((Q == NULL || dO == NULL || lse == NULL || delta == NULL) && At->nnz > 0) return -1;
-    if (ldK < nk || lddK < nk || ldV < nv || lddV < nv) return -4;
-    if (At->nnz > 0 && (ldQ < nk || lddO < nv)) return -4;
+    const long long wk = (long long) heads * nk, wv = (long long) heads * nv;
+    if (ldK < wk || lddK < wk || ldV < wv || lddV < wv) return -4;
+    if (At->nnz > 0 && (ldQ < wk || lddO < wv)) return -4;
     constexpr int cap = crp::ATTN_BWD_MAX_PIECES * 64 * (16 / (int) sizeof(T));
     if (nk > cap || nv > cap) return CRP_ATTN_BWD_EWIDTH;
     if (At->nrow == 0) return 0;
     crp::AttnBwdKVArgs<T> a;
+    a.heads = heads;
     const int rc = attention_bias_values<T>(At, bias, s, &a.val);
     if (rc != 0) return rc;
     a.nrow = At->nrow; a.nk = nk; a.nv = nv; a.rowptr = At->rowptr; a.colidx = At->colidx; a.scale = (T) scale;
     a.K = K; a.ldK = ldK; a.V = V; a.ldV = ldV; a.Q = Q; a.ldQ = ldQ; a.dO = dO; a.lddO = lddO; a.lse = lse; a.delta = delta;
     a.dK = dK; a.lddK = lddK; a.dV = dV; a.lddV = lddV; a.rowmap = At->rowmap;
-    return (int) attention_bwd_launch(a, s);
+    return (int) attention_bwd_launch(a, mh, s);
 }
 
 extern "C" {
@@ -1167,6 +1192,69 @@ int crp_attention_bwd_kv_csr_f32(crp_csr_dev_p At, int nk, int nv, double scale,
 {
     return attention_bwd_kv_csr<float>(At, nk, nv, scale, bias, K, ldK, V, ldV, Q, ldQ, dO, lddO, lse, delta, dK, lddK, dV, lddV,
                                      (hipStream_t) stream);
+}
+
+// ---- ... with heads heads of dk / dv columns side by side in every operand (include/crpspmm_hip.h, "Multi-head"): head h's
+// bits are the single-head call's on the column views of head h
+
+int crp_attention_mh_csr_f64(crp_csr_dev_p A, int heads, int dk, int dv, double scale, int bias, const double *Q, long long ldQ, const double *K0,
+                             long long ldK0, const double *K1, long long ldK1, const double *V0, long long ldV0, const double *V1, long long ldV1,
+                             double *O, long long ldO, double *lse, double *p_out, const int *out_pos, void *stream)
+{
+    const int rc = attention_check(A, dk, dv, scale, bias, Q, ldQ, K0, ldK0, K1, ldK1, V0, ldV0, V1, ldV1, O, ldO, heads);
+    if (rc != 0 || A->nrow == 0) return rc;
+    return attention_csr<double>(A, dk, dv, scale, bias ? (const double *) A->val : nullptr, Q, ldQ, K0, ldK0, K1, ldK1, V0, ldV0, V1, ldV1,
+                                 O, ldO, lse, p_out, out_pos, (hipStream_t) stream, true, heads);
+}
+
+int crp_attention_mh_csr_f32(crp_csr_dev_p A, int heads, int dk, int dv, double scale, int bias, const float *Q, long long ldQ, const float *K0,
+                             long long ldK0, const float *K1, long long ldK1, const float *V0, long long ldV0, const float *V1, long long ldV1,
+                             float *O, long long ldO, float *lse, float *p_out, const int *out_pos, void *stream)
+{
+    const int rc = attention_check(A, dk, dv, scale, bias, Q, ldQ, K0, ldK0, K1, ldK1, V0, ldV0, V1, ldV1, O, ldO, heads);
+    if (rc != 0 || A->nrow == 0) return rc;
+    const hipStream_t s = (hipStream_t) stream;
+    if (bias == 1 && A->nnz > 0)                            // the fp32 copy of the values, as crp_sddmm_csr_f32 mode 1 derives it
+    {
+        const int rc1 = ensure_val32(A, s);
+        if (rc1 != 0) return rc1;
+    }
+    return attention_csr<float>(A, dk, dv, scale, (bias && A->nnz > 0) ? (const float *) A->val32 : nullptr, Q, ldQ, K0, ldK0, K1, ldK1, V0,
+                                ldV0, V1, ldV1, O, ldO, lse, p_out, out_pos, s, true, heads);
+}
+
+int crp_attention_bwd_q_mh_csr_f64(crp_csr_dev_p A, int heads, int dk, int dv, double scale, int bias, const double *Q, long long ldQ,
+                                   const double *K0, long long ldK0, const double *K1, long long ldK1, const double *V0, long long ldV0,
+                                   const double *V1, long long ldV1, const double *O, long long ldO, const double *dO, long long lddO,
+                                   const double *lse, double *dQ, long long lddQ, double *delta, double *ds_out, const int *out_pos, void *stream)
+{
+    return attention_bwd_q_csr<double>(A, dk, dv, scale, bias, Q, ldQ, K0, ldK0, K1, ldK1, V0, ldV0, V1, ldV1, O, ldO, dO, lddO, lse, dQ, lddQ,
+                                    delta, ds_out, out_pos, (hipStream_t) stream, true, heads);
+}
+
+int crp_attention_bwd_kv_mh_csr_f64(crp_csr_dev_p At, int heads, int dk, int dv, double scale, int bias, const double *K, long long ldK,
+                                    const double *V, long long ldV, const double *Q, long long ldQ, const double *dO, long long lddO,
+                                    const double *lse, const double *delta, double *dK, long long lddK, double *dV, long long lddV, void *stream)
+{
+    return attention_bwd_kv_csr<double>(At, dk, dv, scale, bias, K, ldK, V, ldV, Q, ldQ, dO, lddO, lse, delta, dK, lddK, dV, lddV,
+                                     (hipStream_t) stream, true, heads);
+}
+
+int crp_attention_bwd_q_mh_csr_f32(crp_csr_dev_p A, int heads, int dk, int dv, double scale, int bias, const float *Q, long long ldQ, const float *K0,
+                                   long long ldK0, const float *K1, long long ldK1, const float *V0, long long ldV0, const float *V1, long long ldV1,
+                                   const float *O, long long ldO, const float *dO, long long lddO, const float *lse, float *dQ, long long lddQ,
+                                   float *delta, float *ds_out, const int *out_pos, void *stream)
+{
+    return attention_bwd_q_csr<float>(A, dk, dv, scale, bias, Q, ldQ, K0, ldK0, K1, ldK1, V0, ldV0, V1, ldV1, O, ldO, dO, lddO, lse, dQ, lddQ,
+                                    delta, ds_out, out_pos, (hipStream_t) stream, true, heads);
+}
+
+int crp_attention_bwd_kv_mh_csr_f32(crp_csr_dev_p At, int heads, int dk, int dv, double scale, int bias, const float *K, long long ldK,
+                                    const float *V, long long ldV, const float *Q, long long ldQ, const float *dO, long long lddO, const float *lse,
+                                    const float *delta, float *dK, long long lddK, float *dV, long long lddV, void *stream)
+{
+    return attention_bwd_kv_csr<float>(At, dk, dv, scale, bias, K, ldK, V, ldV, Q, ldQ, dO, lddO, lse, delta, dK, lddK, dV, lddV,
+                                     (hipStream_t) stream, true, heads);
 }
 
 // ---- row softmax over a CSR pattern (softmax_kernels.hip).  Every argument is checked before anything is launched.

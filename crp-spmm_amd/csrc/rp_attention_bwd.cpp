@@ -1,5 +1,6 @@
 // rp_attention_bwd.cpp -- the row engine's fused attention backward (crp_rp_spmm_attention_bwd_ex / _f32_ex, include/crp_engine.h):
-// the one translation unit of the engines that names the device entry points of attention_bwd_kernels.hip.
+// the one translation unit of the engines that names the single-head device entry points of attention_bwd_kernels.hip (the
+// multi-head calls, rp_attention_mh.cpp, run attention_bwd_impl below with their own device calls).
 //
 // Data flow, every piece of which the engine has: the forward exchange of K then V, as the forward attention does it
 // (pack_exchange_run2: K's rows land in the forward receive buffer, V's in the attention's second one); bwd_q on the parts, through
@@ -41,20 +42,35 @@ static inline int attention_bwd_kv(crp_csr_dev_p At, int n, double scale, int bi
 }
 }  // namespace crp
 
-static double *delta_of(crp_rp_spmm *e, const double *) { return e->bw_delta_dev != nullptr ? e->bw_delta_dev.get() : e->bw_delta_dev.alloc((size_t) e->A_nrow + 1); }
-static float *delta_of(crp_rp_spmm *e, const float *) { return e->bw_delta32_dev != nullptr ? e->bw_delta32_dev.get() : e->bw_delta32_dev.alloc((size_t) e->A_nrow + 1); }
+// delta, one entry per row and head: allocated by the first call of a dtype for one head, grown through its owner by a call that
+// needs more (the free waits for the device, so no earlier call still reads the old array)
+template <class T> static T *delta_grow(crp::DevArray<T> &a, size_t *cap, size_t need)
+{
+    if (a != nullptr && *cap >= need) return a.get();
+    *cap = need;
+    return a.alloc(need);
+}
+static double *delta_of(crp_rp_spmm *e, const double *, size_t nh) { return delta_grow(e->bw_delta_dev, &e->bw_delta_cap, (size_t) e->A_nrow * nh + 1); }
+static float *delta_of(crp_rp_spmm *e, const float *, size_t nh) { return delta_grow(e->bw_delta32_dev, &e->bw_delta32_cap, (size_t) e->A_nrow * nh + 1); }
 
 template <class T>
 static void attention_bwd_impl(crp_rp_spmm *e, double scale, int bias, const T *Q, long long ldQ, const T *K, long long ldK, const T *V,
                                long long ldV, const T *O, long long ldO, const T *dO, long long lddO, const T *lse, T *dQ, long long lddQ,
-                               T *dK, long long lddK, T *dV, long long lddV, T *ds_out, void *stream_)
+                               T *dK, long long lddK, T *dV, long long lddV, T *ds_out, void *stream_, int heads = 0,
+                               crp::attn_bwd_q_mh_fn<T> q_mh = nullptr, crp::attn_bwd_kv_mh_fn<T> kv_mh = nullptr)
 {
+    // q_mh == nullptr: the single-head calls.  Else (the _mh_ calls, rp_attention_mh.cpp) the multi-head device calls and their
+    // heads of glb_n / heads columns each, to which the cap applies; only the part kernels and delta's size know
     if (e == NULL) return;
+    const bool mh = q_mh != nullptr;
+    ASSERT_PRINTF(!mh || (heads >= 1 && e->glb_n % heads == 0), "rp_spmm_attention_bwd_mh: heads (%d) must be positive and divide the %d columns\n",
+                  heads, e->glb_n);
     ASSERT_PRINTF(!e->plan_only, "rp_spmm_attention_bwd on a plan-only engine (no device state)\n");
     ASSERT_PRINTF(bias == 0 || bias == 1, "bias must be 0 or 1\n");
     ASSERT_PRINTF(scale - scale == 0.0, "scale must be finite\n");
     const int n = e->glb_n, kb = e->loc_B_nrow, m = e->A_nrow;
-    ASSERT_PRINTF(n <= 64 * 64 / (int) sizeof(T), "rp_spmm_attention_bwd: %d columns pass the fused backward's cap (%d)\n", n,
+    const int d = mh ? n / heads : n;                   // one head's width
+    ASSERT_PRINTF(d <= 64 * 64 / (int) sizeof(T), "rp_spmm_attention_bwd: %d columns pass the fused backward's cap (%d)\n", d,
                   64 * 64 / (int) sizeof(T));
     // device-resident row-major operands only
     const struct { const void *p; long long ld; int rows; const char *name; } ops[] = {
@@ -76,7 +92,7 @@ static void attention_bwd_impl(crp_rp_spmm *e, double scale, int bias, const T *
 
     const Xchg x = exchange_of(e, K);
     T *recv2 = attention_recv(e, x, K);
-    T *delta = delta_of(e, K);
+    T *delta = delta_of(e, K, mh ? (size_t) heads : 1);
     e->bw_built = true;
     if (n == 0)
     {
@@ -88,14 +104,19 @@ static void attention_bwd_impl(crp_rp_spmm *e, double scale, int bias, const T *
     pack_exchange_run2(e, x, recv2, K, ldK, V, ldV, s, t0, [&](crp_csr_dev_p A, int part) {
         if (crp_csr_dev_nrow(A) == 0) return;
         const int *pos = part == 1 ? e->sd_int_pos.get() : (part == 2 ? e->sd_bnd_pos.get() : nullptr);
-        HIP_OK(crp::attention_bwd_q(A, n, scale, bias, Q, ldQ, K, ldK, (const T *) x.recv, x.ld, V, ldV, (const T *) recv2, x.ld, O, ldO, dO, lddO,
-                                    lse, dQ, lddQ, delta, ds_out, pos, s));
+        if (mh)
+            HIP_OK(q_mh(A, heads, d, d, scale, bias, Q, ldQ, K, ldK, (const T *) x.recv, x.ld, V, ldV, (const T *) recv2, x.ld, O, ldO, dO, lddO,
+                        lse, dQ, lddQ, delta, ds_out, pos, s));
+        else
+            HIP_OK(crp::attention_bwd_q(A, n, scale, bias, Q, ldQ, K, ldK, (const T *) x.recv, x.ld, V, ldV, (const T *) recv2, x.ld, O, ldO, dO,
+                                        lddO, lse, dQ, lddQ, delta, ds_out, pos, s));
     });
     lap(e, s, t0, &e->t_spmm);
 
     // ---- the column side: the rows owed to peers in place over the received K and V rows, this rank's own directly
     auto kv = [&](crp_csr_dev_p At, const T *Kr, long long ldKr, const T *Vr, long long ldVr, T *dKr, long long lddKr, T *dVr, long long lddVr) {
-        HIP_OK(crp::attention_bwd_kv(At, n, scale, bias, Kr, ldKr, Vr, ldVr, Q, ldQ, dO, lddO, lse, delta, dKr, lddKr, dVr, lddVr, s));
+        if (mh) HIP_OK(kv_mh(At, heads, d, d, scale, bias, Kr, ldKr, Vr, ldVr, Q, ldQ, dO, lddO, lse, delta, dKr, lddKr, dVr, lddVr, s));
+        else HIP_OK(crp::attention_bwd_kv(At, n, scale, bias, Kr, ldKr, Vr, ldVr, Q, ldQ, dO, lddO, lse, delta, dKr, lddKr, dVr, lddVr, s));
     };
     auto reverse_exchange = [&](const void *from, void *xs) {
         const double tx0 = get_wtime_sec();
@@ -138,6 +159,23 @@ static void attention_bwd_impl(crp_rp_spmm *e, double scale, int bias, const T *
     complete(e, s, false, timing);
     e->t_exec += get_wtime_sec() - t_begin;
     e->n_exec++;
+}
+
+void rp_attention_bwd_mh(crp_rp_spmm *e, int heads, double scale, int bias, const double *Q, long long ldQ, const double *K, long long ldK,
+                         const double *V, long long ldV, const double *O, long long ldO, const double *dO, long long lddO, const double *lse,
+                         double *dQ, long long lddQ, double *dK, long long lddK, double *dV, long long lddV, double *ds_out, void *stream,
+                         crp::attn_bwd_q_mh_fn<double> q_call, crp::attn_bwd_kv_mh_fn<double> kv_call)
+{
+    attention_bwd_impl<double>(e, scale, bias, Q, ldQ, K, ldK, V, ldV, O, ldO, dO, lddO, lse, dQ, lddQ, dK, lddK, dV, lddV, ds_out, stream, heads,
+                               q_call, kv_call);
+}
+void rp_attention_bwd_mh(crp_rp_spmm *e, int heads, double scale, int bias, const float *Q, long long ldQ, const float *K, long long ldK,
+                         const float *V, long long ldV, const float *O, long long ldO, const float *dO, long long lddO, const float *lse,
+                         float *dQ, long long lddQ, float *dK, long long lddK, float *dV, long long lddV, float *ds_out, void *stream,
+                         crp::attn_bwd_q_mh_fn<float> q_call, crp::attn_bwd_kv_mh_fn<float> kv_call)
+{
+    attention_bwd_impl<float>(e, scale, bias, Q, ldQ, K, ldK, V, ldV, O, ldO, dO, lddO, lse, dQ, lddQ, dK, lddK, dV, lddV, ds_out, stream, heads,
+                              q_call, kv_call);
 }
 
 extern "C" {

@@ -1,6 +1,7 @@
 // rp_engine_impl.h -- the row engine's state (struct crp_rp_spmm) and the helpers that its translation units share: rp_engine.cpp
-// (init, exec, exec_t, sddmm, attention, value updates) and rp_attention_bwd.cpp (the fused attention backward, which alone names
-// the device entry points of attention_bwd_kernels.hip).  Internal: nothing outside csrc/ includes it.
+// (init, exec, exec_t, sddmm, attention, value updates), rp_attention_bwd.cpp (the fused attention backward, which alone names
+// the single-head device entry points of attention_bwd_kernels.hip) and rp_attention_mh.cpp (the multi-head attention calls, which
+// alone names the multi-head device entry points).  Internal: nothing outside csrc/ includes it.
 #ifndef CRP_RP_ENGINE_IMPL_H
 #define CRP_RP_ENGINE_IMPL_H
 
@@ -69,6 +70,7 @@ struct crp_rp_spmm
     bool bw_built = false;
     crp::DevArray<float>  bw_delta32_dev;
     crp::DevArray<double> bw_delta_dev;
+    size_t bw_delta32_cap = 0, bw_delta_cap = 0;        // entries; a multi-head call that needs A_nrow * heads grows its array
     // row softmax (crp_rp_spmm_row_softmax_ex), uploaded by its first call: A_rowptr as a device array
     crp::DevArray<int> sm_rowptr;
     // device value updates (crp_rp_spmm_update_values_dev), allocated by its first call: the new values as fp64 in the order the
@@ -252,6 +254,38 @@ static inline void refresh_host_values(crp_rp_spmm *e)
     }
     e->host_vals_stale = false;
 }
+
+// ---- the multi-head attention calls (crp_rp_spmm_attention_mh_ex and its kin, rp_attention_mh.cpp) ---------------------------------
+// rp_attention_mh.cpp is the one translation unit of the engines that names the multi-head device entry points; it hands them to
+// the implementations in rp_engine.cpp and rp_attention_bwd.cpp, which are the single-head calls' with `heads` passed to the part
+// kernels (a build of those two files over stand-ins for the device ABI needs no multi-head stand-in).
+namespace crp
+{
+template <class T>
+using attn_mh_fn = int (*)(crp_csr_dev_p, int, int, int, double, int, const T *, long long, const T *, long long, const T *, long long,
+                           const T *, long long, const T *, long long, T *, long long, T *, T *, const int *, void *);
+template <class T>
+using attn_bwd_q_mh_fn = int (*)(crp_csr_dev_p, int, int, int, double, int, const T *, long long, const T *, long long, const T *, long long,
+                                 const T *, long long, const T *, long long, const T *, long long, const T *, long long, const T *, T *,
+                                 long long, T *, T *, const int *, void *);
+template <class T>
+using attn_bwd_kv_mh_fn = int (*)(crp_csr_dev_p, int, int, int, double, int, const T *, long long, const T *, long long, const T *, long long,
+                                  const T *, long long, const T *, const T *, T *, long long, T *, long long, void *);
+}  // namespace crp
+void rp_attention_mh(crp_rp_spmm *e, int layout, int heads, double scale, int bias, const double *Q, long long ldQ, const double *K,
+                     long long ldK, const double *V, long long ldV, double *O, long long ldO, double *lse, double *p_out, void *stream,
+                     crp::attn_mh_fn<double> call);
+void rp_attention_mh(crp_rp_spmm *e, int layout, int heads, double scale, int bias, const float *Q, long long ldQ, const float *K,
+                     long long ldK, const float *V, long long ldV, float *O, long long ldO, float *lse, float *p_out, void *stream,
+                     crp::attn_mh_fn<float> call);
+void rp_attention_bwd_mh(crp_rp_spmm *e, int heads, double scale, int bias, const double *Q, long long ldQ, const double *K, long long ldK,
+                         const double *V, long long ldV, const double *O, long long ldO, const double *dO, long long lddO, const double *lse,
+                         double *dQ, long long lddQ, double *dK, long long lddK, double *dV, long long lddV, double *ds_out, void *stream,
+                         crp::attn_bwd_q_mh_fn<double> q_call, crp::attn_bwd_kv_mh_fn<double> kv_call);
+void rp_attention_bwd_mh(crp_rp_spmm *e, int heads, double scale, int bias, const float *Q, long long ldQ, const float *K, long long ldK,
+                         const float *V, long long ldV, const float *O, long long ldO, const float *dO, long long lddO, const float *lse,
+                         float *dQ, long long lddQ, float *dK, long long lddK, float *dV, long long lddV, float *ds_out, void *stream,
+                         crp::attn_bwd_q_mh_fn<float> q_call, crp::attn_bwd_kv_mh_fn<float> kv_call);
 
 // ---- what the fused attention and its backward share: the second receive buffer and the two-operand exchange ----------------------
 // first attention call of a dtype: the second receive buffer (rows of x.ld elements, zeroed once: the fp32 rows' pad columns are

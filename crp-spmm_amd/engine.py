@@ -119,6 +119,30 @@ def _vec_ptr(name, x, f32, count):
     return x.ctypes.data or None, x
 
 
+def _engine_heads(heads, glb_n):
+    """``heads`` of the engine's attention calls as an int >= 1 that divides glb_n, checked before any library call"""
+    if isinstance(heads, bool) or not isinstance(heads, (int, np.integer)):
+        raise TypeError("heads must be an int, got %r" % (heads,))
+    if heads < 1:
+        raise ValueError("heads must be at least 1, got %d" % heads)
+    if glb_n % heads:
+        raise ValueError("%d heads do not divide the engine's %d columns" % (heads, glb_n))
+    return int(heads)
+
+
+def _mh_vec(name, x, heads):
+    """A per-row or per-nonzero result of a multi-head call -- C-contiguous, (rows, heads) -- as the flat view the single-head
+    checks take; ``heads`` = 1 and None pass through."""
+    if heads == 1 or x is None:
+        return x
+    ndim = x.dim() if hasattr(x, "dim") else getattr(x, "ndim", None)
+    if ndim != 2 or x.shape[1] != heads:
+        raise ValueError("%s must be 2-D with %d columns (one per head)" % (name, heads))
+    if not (x.is_contiguous() if hasattr(x, "is_contiguous") else x.flags.c_contiguous):
+        raise ValueError("%s must be contiguous" % name)
+    return x.view(-1) if hasattr(x, "is_contiguous") else x.reshape(-1)
+
+
 def _f32_operands(B, C_out):
     """TypeError unless B and C are both float32 (``exec_t_f32``), before any C call."""
     if _operands_dtype(B, C_out) != "f32":
@@ -250,13 +274,16 @@ class RpSpmm:
         """True once a ``sddmm`` has uploaded the positions its row parts write through (crp_rp_spmm_sddmm_built)."""
         return bool(self._lib.crp_rp_spmm_sddmm_built(self.handle))
 
-    def attention(self, layout, Q, K, V, out, scale=1.0, bias=False, lse=None, p_out=None, stream=None):
+    def attention(self, layout, Q, K, V, out, scale=1.0, bias=False, lse=None, p_out=None, stream=None, heads=1):
         """Fused sparse attention over this rank's rows of A (crp_rp_spmm_attention_ex / _f32_ex, by the operands' dtype):
         out[i] = sum_p softmax_p(scale * <Q[i], K[c_p]> (+ the engine's current value of p with ``bias``)) * V[c_p] over the
         nonzeros p = (i, c_p) of row i.  Q and ``out`` are this rank's A_nrow x glb_n blocks, K and V its loc_B_nrow x glb_n
         blocks (layouts and operands as ``exec``); ``lse`` (A_nrow entries) and ``p_out`` (nnz entries in the order of the A_val
         given to init) are optional 1-D arrays or tensors of the same dtype, on the host or the device.  The engine's values
-        are not changed.  Mixed dtypes, wrong shapes and wrong lengths raise before the library is called."""
+        are not changed.  Mixed dtypes, wrong shapes and wrong lengths raise before the library is called.
+        ``heads`` > 1 (crp_rp_spmm_attention_mh_ex / _f32_ex): glb_n / heads columns per head, side by side; ``lse`` is then a
+        contiguous (A_nrow, heads) array and ``p_out`` a contiguous (nnz, heads) one.  ``heads`` must divide glb_n."""
+        heads = _engine_heads(heads, self.glb_n)
         dt = _operands_dtype(Q, K)
         if _operands_dtype(V, out) != dt:
             raise TypeError("Q, K, V and out must have the same dtype")
@@ -272,12 +299,16 @@ class RpSpmm:
         op, ldo, _ko = _ptr_ld(out, layout, f32)
         kb = getattr(self, "loc_B_nrow", None)
         _check_blocks(layout, self.glb_n, (("Q", Q, self.A_nrow), ("K", K, kb), ("V", V, kb), ("out", out, self.A_nrow)))
-        lp, _kl = _vec_ptr("lse", lse, f32, self.A_nrow)
-        pp, _kp = _vec_ptr("p_out", p_out, f32, self.nnz())
+        lp, _kl = _vec_ptr("lse", _mh_vec("lse", lse, heads), f32, self.A_nrow * heads)
+        pp, _kp = _vec_ptr("p_out", _mh_vec("p_out", p_out, heads), f32, self.nnz() * heads)
         if stream is None:
             stream = _current_stream(out)
         if stream is None:
             stream = _current_stream(Q)
+        if heads > 1:
+            fn = self._lib.crp_rp_spmm_attention_mh_f32_ex if f32 else self._lib.crp_rp_spmm_attention_mh_ex
+            fn(self.handle, layout, heads, scale, int(bool(bias)), qp, ldq, kp, ldk, vp, ldv, op, ldo, lp, pp, stream)
+            return
         fn = self._lib.crp_rp_spmm_attention_f32_ex if f32 else self._lib.crp_rp_spmm_attention_ex
         fn(self.handle, layout, scale, int(bool(bias)), qp, ldq, kp, ldk, vp, ldv, op, ldo, lp, pp, stream)
 
@@ -285,17 +316,25 @@ class RpSpmm:
         """True once an ``attention`` has allocated V's receive buffer (crp_rp_spmm_attention_built)."""
         return bool(self._lib.crp_rp_spmm_attention_built(self.handle))
 
-    def attention_bwd(self, Q, K, V, O, dO, lse, dQ, dK, dV, scale=1.0, bias=False, ds_out=None, stream=None):
+    def attention_bwd(self, Q, K, V, O, dO, lse, dQ, dK, dV, scale=1.0, bias=False, ds_out=None, stream=None, heads=1):
         """The fused backward of ``attention`` over this rank's rows of A (crp_rp_spmm_attention_bwd_ex / _f32_ex, by the operands'
         dtype): with ``O`` and ``lse`` as the forward wrote them and the upstream gradient ``dO``, writes dQ (A_nrow x glb_n), dK
         and dV (loc_B_nrow x glb_n) and optionally ``ds_out`` (nnz entries in A_val's order: the gradient of the bias).  Every
         operand is a row-major torch tensor on the device; host arrays and layout 1 are not offered.  glb_n is at most 512
-        (float64) / 1024 (float32).  Wrong types, dtypes, shapes and devices raise before the library is called."""
+        (float64) / 1024 (float32).  Wrong types, dtypes, shapes and devices raise before the library is called.
+        ``heads`` > 1 (crp_rp_spmm_attention_bwd_mh_ex / _f32_ex): glb_n / heads columns per head, to which the cap applies;
+        ``lse`` is a contiguous (A_nrow, heads) tensor and ``ds_out`` a contiguous (nnz, heads) one.  ``heads`` must divide
+        glb_n."""
         import torch
+        heads = _engine_heads(heads, self.glb_n)
+        if isinstance(lse, torch.Tensor):
+            lse = _mh_vec("lse", lse, heads)
+        if isinstance(ds_out, torch.Tensor):
+            ds_out = _mh_vec("ds_out", ds_out, heads)
         two_d = (("Q", Q, self.A_nrow), ("O", O, self.A_nrow), ("dO", dO, self.A_nrow), ("dQ", dQ, self.A_nrow),
                  ("K", K, getattr(self, "loc_B_nrow", None)), ("V", V, getattr(self, "loc_B_nrow", None)),
                  ("dK", dK, getattr(self, "loc_B_nrow", None)), ("dV", dV, getattr(self, "loc_B_nrow", None)))
-        vecs = (("lse", lse, self.A_nrow),) + ((("ds_out", ds_out, self.nnz()),) if ds_out is not None else ())
+        vecs = (("lse", lse, self.A_nrow * heads),) + ((("ds_out", ds_out, self.nnz() * heads),) if ds_out is not None else ())
         for name, t, _ in two_d + vecs:
             if not isinstance(t, torch.Tensor):
                 raise TypeError("%s must be a torch tensor on the device" % name)
@@ -317,14 +356,20 @@ class RpSpmm:
         if not np.isfinite(scale):
             raise ValueError("scale must be finite, got %r" % (scale,))
         cap = 512 if Q.dtype == torch.float64 else 1024
-        if self.glb_n > cap:
-            raise ValueError("the fused backward takes at most %d columns in %s, this engine has %d" % (cap, Q.dtype, self.glb_n))
+        if self.glb_n // heads > cap:
+            raise ValueError("the fused backward takes at most %d columns%s in %s, this engine has %d"
+                             % (cap, "" if heads == 1 else " per head", Q.dtype, self.glb_n // heads))
         for name, t, _ in two_d + vecs:
             if not t.is_cuda or t.device != Q.device:
                 raise TypeError("%s must be on the device, with Q" % name)
         if stream is None:
             stream = _current_stream(dQ)
         ptr = lambda t: (t.data_ptr() or None) if t is not None else None
+        if heads > 1:
+            fn = self._lib.crp_rp_spmm_attention_bwd_mh_f32_ex if Q.dtype == torch.float32 else self._lib.crp_rp_spmm_attention_bwd_mh_ex
+            fn(self.handle, heads, scale, int(bool(bias)), ptr(Q), Q.stride(0), ptr(K), K.stride(0), ptr(V), V.stride(0), ptr(O), O.stride(0),
+               ptr(dO), dO.stride(0), ptr(lse), ptr(dQ), dQ.stride(0), ptr(dK), dK.stride(0), ptr(dV), dV.stride(0), ptr(ds_out), stream)
+            return
         fn = self._lib.crp_rp_spmm_attention_bwd_f32_ex if Q.dtype == torch.float32 else self._lib.crp_rp_spmm_attention_bwd_ex
         fn(self.handle, scale, int(bool(bias)), ptr(Q), Q.stride(0), ptr(K), K.stride(0), ptr(V), V.stride(0), ptr(O), O.stride(0), ptr(dO),
            dO.stride(0), ptr(lse), ptr(dQ), dQ.stride(0), ptr(dK), dK.stride(0), ptr(dV), dV.stride(0), ptr(ds_out), stream)

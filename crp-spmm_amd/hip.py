@@ -158,7 +158,7 @@ class CsrDev:
         return out
 
     def attention(self, Q, K0, V0, K1=None, V1=None, scale=1.0, bias=False, out=None, lse=None, p_out=None, out_pos=None,
-                  stream=None):
+                  stream=None, heads=1):
         """Fused sparse attention over this matrix's pattern (crp_attention_csr_f64 / _f32, by the operands' dtype):
         out[i] = sum_p softmax_p(scale * <Q[i], K[c_p]> (+ the matrix's value of p with ``bias``)) * V[c_p] over the nonzeros
         p = (i, c_p) of row i; c >= 0 reads row c of K0 / V0, c < 0 row ~c of K1 / V1.  Q, K0, K1 are 2-D row-major float64 or
@@ -166,8 +166,13 @@ class CsrDev:
         row per row of Q (allocated when None).  Optional outputs: ``lse`` a 1-D contiguous tensor with an entry per row of
         ``out``, ``p_out`` a 1-D contiguous tensor of nnz entries for the probabilities -- nonzero p writes p_out[out_pos[p]]
         when ``out_pos`` (int32, nnz entries) is given.  The matrix's values are not changed.  Returns ``out``.  Mixed
-        dtypes, wrong shapes and tensors that are not on the device raise before the library is called."""
+        dtypes, wrong shapes and tensors that are not on the device raise before the library is called.
+        ``heads`` > 1 (crp_attention_mh_csr_*): the operands hold ``heads`` heads side by side, nk / heads and nv / heads
+        columns each (both must divide); head h of ``out`` is bit for bit this call on the column views of head h.  ``lse`` is
+        then a contiguous (rows, heads) tensor and ``p_out`` a contiguous (nnz, heads) one -- nonzero p writes row out_pos[p];
+        the matrix's value of p (``bias``) is shared by the heads.  ``heads`` = 1 is the call above, unchanged."""
         import torch
+        heads = _heads(heads)
         if (K1 is None) != (V1 is None):
             raise ValueError("K1 and V1 come together")
         kops = [("Q", Q), ("K0", K0)] + ([("K1", K1)] if K1 is not None else [])
@@ -188,6 +193,7 @@ class CsrDev:
                 raise TypeError("%s must be a torch tensor on the device" % name)
             if t.dtype != Q.dtype:
                 raise TypeError("%s must have the operands' dtype (%s is %s, Q is %s)" % (name, name, t.dtype, Q.dtype))
+        lse, p_out = _mh_flat("lse", lse, heads), _mh_flat("p_out", p_out, heads)
         if bias not in (False, True, 0, 1):
             raise ValueError("bias must be a bool, got %r" % (bias,))
         scale = float(scale)
@@ -196,6 +202,7 @@ class CsrDev:
         nk, nv = int(Q.shape[1]), int(V0.shape[1])
         if nk < 1 or nv < 1:
             raise ValueError("the operands need at least one column")
+        _mh_widths(nk, nv, heads)
         for name, t in kops[1:]:
             if t.shape[1] != nk:
                 raise ValueError("%s has %d columns, Q has %d" % (name, t.shape[1], nk))
@@ -213,8 +220,9 @@ class CsrDev:
         if out is not None and out.shape[0] < x_nrow:
             raise ValueError("out has %d rows, the matrix needs %d" % (out.shape[0], x_nrow))
         nnz = self.nnz
-        if lse is not None and (lse.dim() != 1 or not lse.is_contiguous() or lse.numel() < x_nrow):
-            raise ValueError("lse must be 1-D and contiguous with %d entries" % x_nrow)
+        if lse is not None and (lse.dim() != 1 or not lse.is_contiguous() or lse.numel() < x_nrow * heads):
+            raise ValueError("lse must be 1-D and contiguous with %d entries" % x_nrow if heads == 1 else
+                             "lse must hold %d rows of %d heads" % (x_nrow, heads))
         if out_pos is not None:
             if not (isinstance(out_pos, torch.Tensor) and out_pos.dtype == torch.int32 and out_pos.dim() == 1
                     and out_pos.is_contiguous()):
@@ -226,8 +234,8 @@ class CsrDev:
         if p_out is not None:
             if p_out.dim() != 1 or not p_out.is_contiguous():
                 raise ValueError("p_out must be 1-D and contiguous")
-            if out_pos is None and p_out.numel() < nnz:
-                raise ValueError("p_out has %d entries, the matrix %d nonzeros" % (p_out.numel(), nnz))
+            if out_pos is None and p_out.numel() < nnz * heads:
+                raise ValueError("p_out has %d entries, the matrix %d nonzeros" % (p_out.numel() // heads, nnz))
         named = kops + vops + [(n_, t) for n_, t in (("lse", lse), ("p_out", p_out), ("out_pos", out_pos)) if t is not None]
         for name, t in named:
             if not t.is_cuda or t.device != Q.device:
@@ -236,16 +244,20 @@ class CsrDev:
             out = torch.empty((x_nrow, nv), dtype=Q.dtype, device=Q.device)
         if self.nrow == 0:
             return out
-        fn = self._lib.crp_attention_csr_f64 if Q.dtype == torch.float64 else self._lib.crp_attention_csr_f32
+        if heads == 1:
+            fn, widths = (self._lib.crp_attention_csr_f64 if Q.dtype == torch.float64 else self._lib.crp_attention_csr_f32), (nk, nv)
+        else:
+            fn = self._lib.crp_attention_mh_csr_f64 if Q.dtype == torch.float64 else self._lib.crp_attention_mh_csr_f32
+            widths = (heads, nk // heads, nv // heads)
         k1p, ldk1, v1p, ldv1 = (K1.data_ptr(), K1.stride(0), V1.data_ptr(), V1.stride(0)) if K1 is not None else (None, 0, None, 0)
         ptr = lambda t: (t.data_ptr() or None) if t is not None else None
-        L.check(fn(self.handle, nk, nv, scale, int(bool(bias)), Q.data_ptr(), Q.stride(0), ptr(K0), K0.stride(0), k1p, ldk1,
+        L.check(fn(self.handle, *widths, scale, int(bool(bias)), Q.data_ptr(), Q.stride(0), ptr(K0), K0.stride(0), k1p, ldk1,
                    ptr(V0), V0.stride(0), v1p, ldv1, out.data_ptr(), out.stride(0), ptr(lse), ptr(p_out), ptr(out_pos),
                    _stream(out) if stream is None else stream), fn.__name__)
         return out
 
     def attention_bwd_q(self, Q, K0, V0, O, dO, lse, K1=None, V1=None, scale=1.0, bias=False, dQ=None, delta=None, ds_out=None,
-                        out_pos=None, stream=None):
+                        out_pos=None, stream=None, heads=1):
         """The row side of the fused backward of ``attention`` (crp_attention_bwd_q_csr_f64 / _f32, by the operands' dtype), on
         the handle the forward ran on: with ``O`` and ``lse`` as the forward wrote them and the upstream gradient ``dO``,
         dQ[i] = scale * sum_p dS_p K[c_p] and delta[i] = <dO[i], O[i]> for every row, dS_p = p_p (<dO[i], V[c_p]> - delta[i]),
@@ -254,14 +266,20 @@ class CsrDev:
         ``out_pos`` is given -- the gradient of the bias, in the order ``update_values`` takes.  ``dQ`` and ``delta`` are
         allocated when None.  No output may alias an input.  Widths over 512 (float64) / 1024 (float32) raise ValueError: the
         chain of ``row_softmax_bwd`` and the products serves those.  Returns (dQ, delta).  Every error is raised before the
-        library is called."""
+        library is called.
+        ``heads`` > 1 (crp_attention_bwd_q_mh_csr_*): ``heads`` heads side by side as in ``attention``; ``lse`` and ``delta``
+        are contiguous (rows, heads) tensors, ``ds_out`` a contiguous (nnz, heads) one whose sum over the heads is the
+        gradient of the matrix's values, and the width cap applies to one head.  ``heads`` = 1 is the call above, unchanged."""
         import torch
+        heads = _heads(heads)
+        delta_given = delta
+        lse, delta, ds_out = _mh_flat("lse", lse, heads), _mh_flat("delta", delta, heads), _mh_flat("ds_out", ds_out, heads)
         if (K1 is None) != (V1 is None):
             raise ValueError("K1 and V1 come together")
         kops = [("Q", Q), ("K0", K0)] + ([("K1", K1)] if K1 is not None else []) + ([("dQ", dQ)] if dQ is not None else [])
         vops = [("V0", V0)] + ([("V1", V1)] if V1 is not None else []) + [("O", O), ("dO", dO)]
         vecs = [("lse", lse)] + [(n_, t) for n_, t in (("delta", delta), ("ds_out", ds_out)) if t is not None]
-        nk, nv, scale, bias = _bwd_operands(kops, vops, vecs, scale, bias)
+        nk, nv, scale, bias = _bwd_operands(kops, vops, vecs, scale, bias, heads)
         x_nrow = getattr(self, "_x_nrow", self.nrow)
         for name, t in (("Q", Q), ("O", O), ("dO", dO), ("dQ", dQ)):
             if t is not None and t.shape[0] < x_nrow:
@@ -272,8 +290,9 @@ class CsrDev:
         if K1 is not None and V1.shape[0] != K1.shape[0]:
             raise ValueError("K1 has %d rows, V1 %d" % (K1.shape[0], V1.shape[0]))
         for name, t in (("lse", lse), ("delta", delta)):
-            if t is not None and t.numel() < x_nrow:
-                raise ValueError("%s must hold %d entries" % (name, x_nrow))
+            if t is not None and t.numel() < x_nrow * heads:
+                raise ValueError("%s must hold %d entries" % (name, x_nrow) if heads == 1 else
+                                 "%s must hold %d rows of %d heads" % (name, x_nrow, heads))
         nnz = self.nnz
         if out_pos is not None:
             if not (isinstance(out_pos, torch.Tensor) and out_pos.dtype == torch.int32 and out_pos.dim() == 1
@@ -283,34 +302,43 @@ class CsrDev:
                 raise ValueError("out_pos has %d entries, the matrix %d nonzeros" % (out_pos.numel(), nnz))
             if ds_out is None:
                 raise ValueError("out_pos needs a ds_out to write into")
-        elif ds_out is not None and ds_out.numel() < nnz:
-            raise ValueError("ds_out has %d entries, the matrix %d nonzeros" % (ds_out.numel(), nnz))
+        elif ds_out is not None and ds_out.numel() < nnz * heads:
+            raise ValueError("ds_out has %d entries, the matrix %d nonzeros" % (ds_out.numel() // heads, nnz))
         _bwd_on_device(kops + vops + vecs + ([("out_pos", out_pos)] if out_pos is not None else []))
         if dQ is None:
             dQ = torch.empty((x_nrow, nk), dtype=Q.dtype, device=Q.device)
         if delta is None:
-            delta = torch.empty((x_nrow,), dtype=Q.dtype, device=Q.device)
+            delta = delta_given = torch.empty((x_nrow,) if heads == 1 else (x_nrow, heads), dtype=Q.dtype, device=Q.device)
         if self.nrow == 0:
-            return dQ, delta
-        fn = self._lib.crp_attention_bwd_q_csr_f64 if Q.dtype == torch.float64 else self._lib.crp_attention_bwd_q_csr_f32
+            return dQ, delta_given
+        if heads == 1:
+            fn = self._lib.crp_attention_bwd_q_csr_f64 if Q.dtype == torch.float64 else self._lib.crp_attention_bwd_q_csr_f32
+            widths = (nk, nv)
+        else:
+            fn = self._lib.crp_attention_bwd_q_mh_csr_f64 if Q.dtype == torch.float64 else self._lib.crp_attention_bwd_q_mh_csr_f32
+            widths = (heads, nk // heads, nv // heads)
         k1p, ldk1, v1p, ldv1 = (K1.data_ptr(), K1.stride(0), V1.data_ptr(), V1.stride(0)) if K1 is not None else (None, 0, None, 0)
         ptr = lambda t: (t.data_ptr() or None) if t is not None else None
-        L.check(fn(self.handle, nk, nv, scale, bias, Q.data_ptr(), Q.stride(0), ptr(K0), K0.stride(0), k1p, ldk1, ptr(V0), V0.stride(0),
+        L.check(fn(self.handle, *widths, scale, bias, Q.data_ptr(), Q.stride(0), ptr(K0), K0.stride(0), k1p, ldk1, ptr(V0), V0.stride(0),
                    v1p, ldv1, O.data_ptr(), O.stride(0), dO.data_ptr(), dO.stride(0), lse.data_ptr(), dQ.data_ptr(), dQ.stride(0),
                    delta.data_ptr(), ptr(ds_out), ptr(out_pos), _stream(dQ) if stream is None else stream), fn.__name__)
-        return dQ, delta
+        return dQ, delta_given
 
-    def attention_bwd_kv(self, K, V, Q, dO, lse, delta, scale=1.0, bias=False, dK=None, dV=None, stream=None):
+    def attention_bwd_kv(self, K, V, Q, dO, lse, delta, scale=1.0, bias=False, dK=None, dV=None, stream=None, heads=1):
         """The column side of the fused backward of ``attention`` (crp_attention_bwd_kv_csr_f64 / _f32), on a handle of A^T
         (``from_transpose``): dK[c] = scale * sum_p dS_p Q[i_p] and dV[c] = sum_p p_p dO[i_p] over the entries of column c of A,
         with ``lse`` from the forward and ``delta`` from ``attention_bwd_q``.  K, Q, dK have nk columns, V, dO, dV nv; K, V, dK,
         dV a row per row of this handle, Q, dO, lse, delta one per column.  With ``bias`` the value added to a score is this
         handle's own.  ``dK is K`` and ``dV is V`` are allowed (same tensor); both are allocated when None.  Widths over 512
-        (float64) / 1024 (float32) raise ValueError.  Returns (dK, dV).  Every error is raised before the library is called."""
+        (float64) / 1024 (float32) raise ValueError.  Returns (dK, dV).  Every error is raised before the library is called.
+        ``heads`` > 1 (crp_attention_bwd_kv_mh_csr_*): ``heads`` heads side by side; ``lse`` and ``delta`` are the contiguous
+        (rows of A, heads) tensors of the row side, and the width cap applies to one head."""
         import torch
+        heads = _heads(heads)
+        lse, delta = _mh_flat("lse", lse, heads), _mh_flat("delta", delta, heads)
         kops = [("K", K), ("Q", Q)] + ([("dK", dK)] if dK is not None else [])
         vops = [("V", V), ("dO", dO)] + ([("dV", dV)] if dV is not None else [])
-        nk, nv, scale, bias = _bwd_operands(kops, vops, [("lse", lse), ("delta", delta)], scale, bias)
+        nk, nv, scale, bias = _bwd_operands(kops, vops, [("lse", lse), ("delta", delta)], scale, bias, heads)
         x_nrow = getattr(self, "_x_nrow", self.nrow)
         for name, t in (("K", K), ("V", V), ("dK", dK), ("dV", dV)):
             if t is not None and t.shape[0] < x_nrow:
@@ -319,8 +347,9 @@ class CsrDev:
             if t.shape[0] < self.ncol:
                 raise ValueError("%s has %d rows, the matrix has %d columns" % (name, t.shape[0], self.ncol))
         for name, t in (("lse", lse), ("delta", delta)):
-            if t.numel() < self.ncol:
-                raise ValueError("%s must hold %d entries" % (name, self.ncol))
+            if t.numel() < self.ncol * heads:
+                raise ValueError("%s must hold %d entries" % (name, self.ncol) if heads == 1 else
+                                 "%s must hold %d rows of %d heads" % (name, self.ncol, heads))
         _bwd_on_device(kops + vops + [("lse", lse), ("delta", delta)])
         if dK is None:
             dK = torch.empty((x_nrow, nk), dtype=K.dtype, device=K.device)
@@ -328,8 +357,13 @@ class CsrDev:
             dV = torch.empty((x_nrow, nv), dtype=K.dtype, device=K.device)
         if self.nrow == 0:
             return dK, dV
-        fn = self._lib.crp_attention_bwd_kv_csr_f64 if K.dtype == torch.float64 else self._lib.crp_attention_bwd_kv_csr_f32
-        L.check(fn(self.handle, nk, nv, scale, bias, K.data_ptr(), K.stride(0), V.data_ptr(), V.stride(0), Q.data_ptr() or None,
+        if heads == 1:
+            fn = self._lib.crp_attention_bwd_kv_csr_f64 if K.dtype == torch.float64 else self._lib.crp_attention_bwd_kv_csr_f32
+            widths = (nk, nv)
+        else:
+            fn = self._lib.crp_attention_bwd_kv_mh_csr_f64 if K.dtype == torch.float64 else self._lib.crp_attention_bwd_kv_mh_csr_f32
+            widths = (heads, nk // heads, nv // heads)
+        L.check(fn(self.handle, *widths, scale, bias, K.data_ptr(), K.stride(0), V.data_ptr(), V.stride(0), Q.data_ptr() or None,
                    Q.stride(0), dO.data_ptr() or None, dO.stride(0), lse.data_ptr() or None, delta.data_ptr() or None, dK.data_ptr(),
                    dK.stride(0), dV.data_ptr(), dV.stride(0), _stream(dK) if stream is None else stream), fn.__name__)
         return dK, dV
@@ -428,10 +462,36 @@ def _check_dev_vectors(named, nnz):
 BWD_WIDTH_CAP = {8: 512, 4: 1024}       # widest nk / nv of the fused attention backward, by the element size
 
 
-def _bwd_operands(kops, vops, vecs, scale, bias):
+def _heads(heads):
+    """``heads`` of the attention calls as an int >= 1, checked before any library call"""
+    if isinstance(heads, bool) or not isinstance(heads, (int, np.integer)):
+        raise TypeError("heads must be an int, got %r" % (heads,))
+    if heads < 1:
+        raise ValueError("heads must be at least 1, got %d" % heads)
+    return int(heads)
+
+
+def _mh_widths(nk, nv, heads):
+    if nk % heads or nv % heads:
+        raise ValueError("%d heads do not divide the widths (nk = %d, nv = %d)" % (heads, nk, nv))
+
+
+def _mh_flat(name, t, heads):
+    """A per-row or per-nonzero tensor of a multi-head call -- contiguous, (rows, heads) -- as the flat view the single-head
+    checks take; ``heads`` = 1, None and anything that is not a tensor pass through to those checks."""
+    import torch
+    if heads == 1 or not isinstance(t, torch.Tensor):
+        return t
+    if t.dim() != 2 or t.shape[1] != heads or not t.is_contiguous():
+        raise ValueError("%s must be a contiguous 2-D tensor with %d columns (one per head)" % (name, heads))
+    return t.view(-1)
+
+
+def _bwd_operands(kops, vops, vecs, scale, bias, heads=1):
     """The operands of the fused attention backward, checked before any library call: kops 2-D of one width nk, vops 2-D of one
     width nv, vecs 1-D and contiguous, all float64 or float32 of the first's dtype.  Returns (nk, nv, scale,
-    bias) as the C call takes them; the device is checked by _bwd_on_device."""
+    bias) as the C call takes them; the device is checked by _bwd_on_device.  ``heads`` must divide both widths, and the cap
+    applies to one head's."""
     import torch
     head, first = kops[0]
     for name, t in kops + vops + vecs:
@@ -461,9 +521,11 @@ def _bwd_operands(kops, vops, vecs, scale, bias):
         for name, t in ops[1:]:
             if t.shape[1] != n:
                 raise ValueError("%s has %d columns, %s has %d" % (name, t.shape[1], ops[0][0], n))
+    _mh_widths(nk, nv, heads)
     cap = BWD_WIDTH_CAP[first.element_size()]
-    if nk > cap or nv > cap:
-        raise ValueError("the fused backward takes at most %d columns in %s (nk = %d, nv = %d)" % (cap, first.dtype, nk, nv))
+    if nk // heads > cap or nv // heads > cap:
+        raise ValueError("the fused backward takes at most %d columns%s in %s (nk = %d, nv = %d)"
+                         % (cap, "" if heads == 1 else " per head", first.dtype, nk // heads, nv // heads))
     return nk, nv, scale, int(bool(bias))
 
 
@@ -526,17 +588,21 @@ def row_softmax_bwd(rowptr, y, dy, out=None, stream=None):
     return out
 
 
-def sparse_attention(A, At, Q, K, V, scale=1.0, bias=False):
+def sparse_attention(A, At, Q, K, V, scale=1.0, bias=False, heads=1):
     """softmax_row(scale * (Q K^T)|pattern(A) (+ A's values with ``bias``)) V as a differentiable function of Q, K and V: ``A`` is
     the ``CsrDev`` of the pattern, ``At`` the ``CsrDev.from_transpose`` of the same CSR (with ``bias`` both hold the same
     values).  The forward is ``A.attention``, which keeps O and lse; the backward is ``A.attention_bwd_q`` and
     ``At.attention_bwd_kv``.  Nothing nnz-sized is stored between the two.  2-D row-major cuda tensors of one dtype.  The
     matrix's values are constants here: with ``bias`` they enter the scores and get no gradient (``attention_bwd_q`` with
-    ``ds_out`` forms it).  ``At`` must be the transpose of ``A``: its shape and nonzero count are checked, its pattern is not."""
+    ``ds_out`` forms it).  ``At`` must be the transpose of ``A``: its shape and nonzero count are checked, its pattern is not.
+    ``heads`` > 1: Q, K, V hold ``heads`` heads side by side (the widths must divide); the result and the gradients are, bit for
+    bit, the per-head single-head results side by side."""
+    heads = _heads(heads)
+    _mh_widths(int(Q.shape[-1]), int(V.shape[-1]), heads)
     if At.nrow != A.ncol or At.ncol != A.nrow or At.nnz != A.nnz:
         raise ValueError("At is %d x %d with %d nonzeros: not the transpose of A (%d x %d, %d)"
                          % (At.nrow, At.ncol, At.nnz, A.nrow, A.ncol, A.nnz))
-    return _sparse_attention_fn().apply(Q, K, V, A, At, float(scale), bool(bias))
+    return _sparse_attention_fn().apply(Q, K, V, A, At, float(scale), bool(bias), heads)
 
 
 _SPARSE_ATTENTION_FN = None
@@ -551,22 +617,22 @@ def _sparse_attention_fn():
 
     class SparseAttention(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, Q, K, V, A, At, scale, bias):
+        def forward(ctx, Q, K, V, A, At, scale, bias, heads=1):
             Q, K, V = (t if t.stride(-1) == 1 else t.contiguous() for t in (Q.detach(), K.detach(), V.detach()))
-            lse = torch.empty((Q.shape[0],), dtype=Q.dtype, device=Q.device)
-            O = A.attention(Q, K, V, scale=scale, bias=bias, lse=lse)
+            lse = torch.empty((Q.shape[0],) if heads == 1 else (Q.shape[0], heads), dtype=Q.dtype, device=Q.device)
+            O = A.attention(Q, K, V, scale=scale, bias=bias, lse=lse, heads=heads)
             ctx.save_for_backward(Q, K, V, O, lse)
-            ctx.handles = (A, At, scale, bias)
+            ctx.handles = (A, At, scale, bias, heads)
             return O
 
         @staticmethod
         def backward(ctx, dO):
             Q, K, V, O, lse = ctx.saved_tensors
-            A, At, scale, bias = ctx.handles
+            A, At, scale, bias, heads = ctx.handles
             dO = dO if dO.stride(-1) == 1 else dO.contiguous()
-            dQ, delta = A.attention_bwd_q(Q, K, V, O, dO, lse, scale=scale, bias=bias)
-            dK, dV = At.attention_bwd_kv(K, V, Q, dO, lse, delta, scale=scale, bias=bias)
-            return dQ, dK, dV, None, None, None, None
+            dQ, delta = A.attention_bwd_q(Q, K, V, O, dO, lse, scale=scale, bias=bias, heads=heads)
+            dK, dV = At.attention_bwd_kv(K, V, Q, dO, lse, delta, scale=scale, bias=bias, heads=heads)
+            return dQ, dK, dV, None, None, None, None, None
 
     _SPARSE_ATTENTION_FN = SparseAttention
     return SparseAttention

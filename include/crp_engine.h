@@ -193,6 +193,33 @@ void crp_rp_spmm_attention_bwd_f32_ex(crp_rp_spmm_p rp_spmm, double scale, int b
                                       float *dQ, long long lddQ, float *dK, long long lddK, float *dV, long long lddV,
                                       float *ds_out, void *stream);
 int crp_rp_spmm_attention_bwd_built(crp_rp_spmm_p rp_spmm);
+/* Multi-head forms of the four calls above (crpspmm_hip.h, "Multi-head"): `heads` >= 1 must divide glb_n, and every head has
+ * dk = dv = glb_n / heads columns; any other value aborts, as the other argument errors of these calls do.  Head h of every
+ * output equals the single-head computation on columns [h d, (h + 1) d) bit for bit.  lse has A_nrow x heads entries (row-major)
+ * and p_out / ds_out have heads values per local nonzero: entry (p, h) at p * heads + h with p in A_val's order; the gradient of
+ * A's value of p is the caller's sum over h.  The K / V exchange, the reverse exchanges, the buffers, the staging, the
+ * statistics and the completion rule are those of the single-head calls, unchanged: whole rows of K and V travel, and only the
+ * part kernels receive `heads`.  The engine-owned delta grows to A_nrow x heads through its owner when a call needs more (that
+ * call blocks while the old array is freed).  crp_rp_spmm_attention_built and _bwd_built keep their meaning.  The backward's
+ * width cap (512 fp64, 1024 fp32) applies to glb_n / heads, so an engine wider than the cap has a fused backward once it has
+ * enough heads.  O, lse, p_out, dQ and ds_out equal crp_attention_mh_csr_* / crp_attention_bwd_q_mh_csr_* on the whole matrix
+ * bit for bit, across rank counts, timing modes and repeated calls; dK and dV as stated for the single-head backward. */
+void crp_rp_spmm_attention_mh_ex(crp_rp_spmm_p rp_spmm, int layout, int heads, double scale, int bias, const double *Q,
+                                 long long ldQ, const double *K, long long ldK, const double *V, long long ldV, double *O,
+                                 long long ldO, double *lse, double *p_out, void *stream);
+void crp_rp_spmm_attention_mh_f32_ex(crp_rp_spmm_p rp_spmm, int layout, int heads, double scale, int bias, const float *Q,
+                                     long long ldQ, const float *K, long long ldK, const float *V, long long ldV, float *O,
+                                     long long ldO, float *lse, float *p_out, void *stream);
+void crp_rp_spmm_attention_bwd_mh_ex(crp_rp_spmm_p rp_spmm, int heads, double scale, int bias, const double *Q, long long ldQ,
+                                     const double *K, long long ldK, const double *V, long long ldV, const double *O,
+                                     long long ldO, const double *dO, long long lddO, const double *lse,
+                                     double *dQ, long long lddQ, double *dK, long long lddK, double *dV, long long lddV,
+                                     double *ds_out, void *stream);
+void crp_rp_spmm_attention_bwd_mh_f32_ex(crp_rp_spmm_p rp_spmm, int heads, double scale, int bias, const float *Q, long long ldQ,
+                                         const float *K, long long ldK, const float *V, long long ldV, const float *O,
+                                         long long ldO, const float *dO, long long lddO, const float *lse,
+                                         float *dQ, long long lddQ, float *dK, long long lddK, float *dV, long long lddV,
+                                         float *ds_out, void *stream);
 void crp_rp_spmm_print_stat(crp_rp_spmm_p rp_spmm);
 void crp_rp_spmm_clear_stat(crp_rp_spmm_p rp_spmm);
 /* rp_spmm_init for a caller that ALSO holds the values in device memory, in the order of A_val (A_val_dev: the panel a

@@ -41,6 +41,10 @@
  * Two calls on one handle that run on different streams are the caller's to order whenever one of them writes
  * the handle's values (crp_csr_dev_update_values) or a row map; calls that only read the handle -- the products,
  * the SDDMM, the attention calls, the row softmax -- need no ordering among themselves.
+ * The multi-head attention calls (crp_attention_mh_csr_*, crp_attention_bwd_q_mh_csr_*, crp_attention_bwd_kv_mh_csr_*) are
+ * attention calls in every sentence above: asynchronous on `stream`, taken literally; in steady state they enqueue all of their
+ * device work there and nowhere else, allocate nothing, wait for nothing and touch no other stream, so they may be captured;
+ * the only state they may build is the handle's fp32 copy of the values (fp32, bias = 1), by the first call that needs it.
  */
 #ifndef CRPSPMM_HIP_H
 #define CRPSPMM_HIP_H
@@ -432,6 +436,59 @@ int crp_attention_bwd_kv_csr_f32(crp_csr_dev_p At, int nk, int nv, double scale,
                                  const float *Q, long long ldQ, const float *dO, long long lddO,
                                  const float *lse, const float *delta,
                                  float *dK, long long lddK, float *dV, long long lddV, void *stream);
+
+/* ---- Multi-head: the fused attention and its backward over `heads` heads side by side ----------------------------
+ * heads = H >= 1 heads of dk columns of Q / K / dQ / dK and dv columns of V / O / dO / dV: the operands have H dk and H dv
+ * columns, and head h owns columns [h dk, (h + 1) dk) and [h dv, (h + 1) dv).  For every row i, head h and entry p = (i, c_p):
+ *   s_{p,h} = scale * < Q[i]_h, K[c_p]_h >   (bias = 1: + A's value of p, one value per nonzero, shared by the heads)
+ *   O[i]_h  = sum_p softmax_p(s_{.,h}) * V[c_p]_h
+ * and the backward of the section above per head.  Per-row scalars are (rows, H) row-major -- lse[i H + h], delta[i H + h], with
+ * i the row of O (through the row map) -- and per-nonzero outputs (nnz, H): p_out[pos H + h], ds_out[pos H + h] with pos =
+ * out_pos[p], or p when out_pos is NULL (out_pos keeps nnz entries).  The gradient of A's value of p is the caller's sum of
+ * ds_out[pos H + h] over h.
+ * Bit contract: head h of every output equals, bit for bit, the single-head call above with nk = dk and nv = dv on the column
+ * views of head h (pointers advanced by h dk / h dv, the same leading dimensions): the instance, the order of the dots, the
+ * batches of 8, the rescales and the special cases (an empty row: +0 and lse = -inf for every head; masked edges; all-masked
+ * rows, per head) are those of (dtype, dk, dv), so the error bounds of DESIGN.md 5j and 5l hold with nk -> dk, nv -> dv.
+ * A group of L(dk, dv) lanes owns the unit (row, head); consecutive groups hold consecutive heads of a row.  The 16-byte path
+ * needs the single-head call's conditions and dk, dv multiples of W (they are the unit's nk, nv), so that every head's slice
+ * is aligned; else elements, in the same assignment.  bwd_kv keeps dK == K and dV == V legal: a group reads its own slice of
+ * the row whole before it writes it, and no other group reads that slice.
+ * Errors, all before anything is written: those of the single-head calls, with -1 also for heads < 1, -4 for a leading
+ * dimension below heads * dk or heads * dv, and CRP_ATTN_BWD_EWIDTH for a PER-HEAD width dk or dv over the cap (the total
+ * width is not capped).  rows * heads units that do not fit one launch (about 2^31 blocks) return a HIP error (> 0). */
+int crp_attention_mh_csr_f64(crp_csr_dev_p A, int heads, int dk, int dv, double scale, int bias,
+                             const double *Q, long long ldQ,
+                             const double *K0, long long ldK0, const double *K1, long long ldK1,
+                             const double *V0, long long ldV0, const double *V1, long long ldV1,
+                             double *O, long long ldO, double *lse, double *p_out, const int *out_pos, void *stream);
+int crp_attention_mh_csr_f32(crp_csr_dev_p A, int heads, int dk, int dv, double scale, int bias,
+                             const float *Q, long long ldQ,
+                             const float *K0, long long ldK0, const float *K1, long long ldK1,
+                             const float *V0, long long ldV0, const float *V1, long long ldV1,
+                             float *O, long long ldO, float *lse, float *p_out, const int *out_pos, void *stream);
+int crp_attention_bwd_q_mh_csr_f64(crp_csr_dev_p A, int heads, int dk, int dv, double scale, int bias,
+                                   const double *Q, long long ldQ,
+                                   const double *K0, long long ldK0, const double *K1, long long ldK1,
+                                   const double *V0, long long ldV0, const double *V1, long long ldV1,
+                                   const double *O, long long ldO, const double *dO, long long lddO, const double *lse,
+                                   double *dQ, long long lddQ, double *delta, double *ds_out, const int *out_pos, void *stream);
+int crp_attention_bwd_q_mh_csr_f32(crp_csr_dev_p A, int heads, int dk, int dv, double scale, int bias,
+                                   const float *Q, long long ldQ,
+                                   const float *K0, long long ldK0, const float *K1, long long ldK1,
+                                   const float *V0, long long ldV0, const float *V1, long long ldV1,
+                                   const float *O, long long ldO, const float *dO, long long lddO, const float *lse,
+                                   float *dQ, long long lddQ, float *delta, float *ds_out, const int *out_pos, void *stream);
+int crp_attention_bwd_kv_mh_csr_f64(crp_csr_dev_p At, int heads, int dk, int dv, double scale, int bias,
+                                    const double *K, long long ldK, const double *V, long long ldV,
+                                    const double *Q, long long ldQ, const double *dO, long long lddO,
+                                    const double *lse, const double *delta,
+                                    double *dK, long long lddK, double *dV, long long lddV, void *stream);
+int crp_attention_bwd_kv_mh_csr_f32(crp_csr_dev_p At, int heads, int dk, int dv, double scale, int bias,
+                                    const float *K, long long ldK, const float *V, long long ldV,
+                                    const float *Q, long long ldQ, const float *dO, long long lddO,
+                                    const float *lse, const float *delta,
+                                    float *dK, long long lddK, float *dV, long long lddV, void *stream);
 
 /* ---- row softmax over A's pattern (edge softmax) and its Jacobian product ------
  * For every row r with entries p in [rowptr[r], rowptr[r + 1]):
