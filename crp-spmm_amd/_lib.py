@@ -95,6 +95,16 @@ _V = C.c_void_p
 _I = C.c_int
 _LL = C.c_longlong
 
+# The device prototypes of the fused attention (crpspmm_hip.h): one argument list per kernel, shared by f64 and f32; a multi-head
+# entry point takes `heads` after the handle, so that (heads, dk, dv) stand in place of (nk, nv)
+_ATTENTION_ARGS = {
+    "attention": [_V, _I, _I, C.c_double, _I, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _V, _V, _V],
+    "attention_bwd_q": [_V, _I, _I, C.c_double, _I, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _V, _LL, _V, _V, _V, _V],
+    "attention_bwd_kv": [_V, _I, _I, C.c_double, _I, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _V, _V, _LL, _V, _LL, _V],
+}
+_ATTENTION_SIGNATURES = {"crp_%s%s_csr_%s" % (stem, mh, dt): (_I, args[:1] + [_I] * len(mh[:1]) + args[1:])
+                         for mh in ("", "_mh") for stem, args in _ATTENTION_ARGS.items() for dt in ("f64", "f32")}
+
 # name -> (restype, argtypes); every symbol declared in include/crpspmm_hip.h,
 # include/crp_comm.h, include/crp_engine.h, include/utils.h, include/spmat_part.h,
 # include/mmio_utils.h, include/crp_rccl.h, include/crp_part.h.  tests/test_host.py (the ABI test there) checks that the library
@@ -167,19 +177,7 @@ SIGNATURES = {
     "crp_spmm_csr_f64": (_I, [_V, _I, _I, _V, _LL, _V, _LL, _V, _LL, _I, _V]),
     "crp_sddmm_csr_f64": (_I, [_V, _I, _V, _LL, _V, _LL, _V, _LL, _V, _V, _I, _V]),
     "crp_sddmm_csr_f32": (_I, [_V, _I, _V, _LL, _V, _LL, _V, _LL, _V, _V, _I, _V]),
-    "crp_attention_csr_f64": (_I, [_V, _I, _I, C.c_double, _I, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _V, _V, _V]),
-    "crp_attention_csr_f32": (_I, [_V, _I, _I, C.c_double, _I, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _V, _V, _V]),
-    "crp_attention_bwd_q_csr_f64": (_I, [_V, _I, _I, C.c_double, _I, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _V, _LL, _V, _V, _V, _V]),
-    "crp_attention_bwd_q_csr_f32": (_I, [_V, _I, _I, C.c_double, _I, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _V, _LL, _V, _V, _V, _V]),
-    "crp_attention_bwd_kv_csr_f64": (_I, [_V, _I, _I, C.c_double, _I, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _V, _V, _LL, _V, _LL, _V]),
-    "crp_attention_bwd_kv_csr_f32": (_I, [_V, _I, _I, C.c_double, _I, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _V, _V, _LL, _V, _LL, _V]),
-    # ... multi-head: (heads, dk, dv) in place of (nk, nv)
-    "crp_attention_mh_csr_f64": (_I, [_V, _I, _I, _I, C.c_double, _I, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _V, _V, _V]),
-    "crp_attention_mh_csr_f32": (_I, [_V, _I, _I, _I, C.c_double, _I, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _V, _V, _V]),
-    "crp_attention_bwd_q_mh_csr_f64": (_I, [_V, _I, _I, _I, C.c_double, _I, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _V, _LL, _V, _V, _V, _V]),
-    "crp_attention_bwd_q_mh_csr_f32": (_I, [_V, _I, _I, _I, C.c_double, _I, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _V, _LL, _V, _V, _V, _V]),
-    "crp_attention_bwd_kv_mh_csr_f64": (_I, [_V, _I, _I, _I, C.c_double, _I, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _V, _V, _LL, _V, _LL, _V]),
-    "crp_attention_bwd_kv_mh_csr_f32": (_I, [_V, _I, _I, _I, C.c_double, _I, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _V, _V, _LL, _V, _LL, _V]),
+    **_ATTENTION_SIGNATURES,
     "crp_row_softmax_f64": (_I, [_I, _V, _V, _V, _V]),
     "crp_row_softmax_f32": (_I, [_I, _V, _V, _V, _V]),
     "crp_row_softmax_bwd_f64": (_I, [_I, _V, _V, _V, _V, _V]),
@@ -385,6 +383,25 @@ def load():
         fn.argtypes = args
     _lib = lib
     return lib
+
+
+def attention_entry(lib, stem, heads, f32, nk=None, nv=None):
+    """The entry point of an attention call in ``lib`` and the arguments that come before ``scale``, by (stem, heads, dtype).
+    With the widths, a device call ("attention", "attention_bwd_q", "attention_bwd_kv": crp_<stem>[_mh]_csr_f64 / _f32), which takes
+    (nk, nv), or (heads, nk / heads, nv / heads) for several heads; without, a call of the row engine ("rp_spmm_attention",
+    "rp_spmm_attention_bwd": crp_<stem>[_mh][_f32]_ex), which takes nothing, or (heads,).  One head is always the single-head
+    symbol."""
+    mh = heads > 1
+    fn = getattr(lib, _ATTENTION_ENTRY[stem, mh, bool(f32)])
+    if nk is None:
+        return fn, ((heads,) if mh else ())
+    return fn, ((heads, nk // heads, nv // heads) if mh else (nk, nv))
+
+
+_ATTENTION_ENTRY = {(stem, mh, f32): ("crp_%s%s_csr_%s" % (stem, "_mh" * mh, "f32" if f32 else "f64") if stem in _ATTENTION_ARGS else
+                                      "crp_%s%s%s_ex" % (stem, "_mh" * mh, "_f32" * f32))
+                    for stem in list(_ATTENTION_ARGS) + ["rp_spmm_attention", "rp_spmm_attention_bwd"]
+                    for mh in (False, True) for f32 in (False, True)}
 
 
 def check(rc, what):

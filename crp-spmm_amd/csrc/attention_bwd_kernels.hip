@@ -34,7 +34,7 @@
 // ALIASING.  bwd_kv: dK == K and dV == V (exactly) are legal: a group reads its K and V row whole before it writes them, and no
 // other group reads them.  bwd_q: no output may alias an input.
 //
-// MULTI-HEAD (the MH instances, attention_bwd_q_mh_* / attention_bwd_kv_mh_*).  a.heads = H heads of nk / nv columns each, side by
+// MULTI-HEAD (the MH instances: attention_bwd_q / attention_bwd_kv with mh).  a.heads = H heads of nk / nv columns each, side by
 // side in every operand, as in the forward: a group owns the unit (row, head) = (u / H, u % H) -- bwd_kv: (column c, head h) -- and
 // works on the column views of its head, so head h's bits are the single-head instance's.  lse and delta are (rows of A, H)
 // row-major, ds_out (nnz, H); val[p] is shared by the heads.  dK == K and dV == V stay legal: a group reads its own slice of the row
@@ -568,13 +568,16 @@ static hipError_t attention_bwd(const Args &a, hipStream_t s)
     return bwd_wave<T, 4, MH>(a, s);
 }
 
-hipError_t attention_bwd_q_f64(const AttnBwdQArgs<double> &a, hipStream_t s) { return attention_bwd<double, false>(a, s); }
-hipError_t attention_bwd_q_mh_f64(const AttnBwdQArgs<double> &a, hipStream_t s) { return attention_bwd<double, true>(a, s); }
-hipError_t attention_bwd_q_f32(const AttnBwdQArgs<float> &a, hipStream_t s) { return attention_bwd<float, false>(a, s); }
-hipError_t attention_bwd_q_mh_f32(const AttnBwdQArgs<float> &a, hipStream_t s) { return attention_bwd<float, true>(a, s); }
-hipError_t attention_bwd_kv_f64(const AttnBwdKVArgs<double> &a, hipStream_t s) { return attention_bwd<double, false>(a, s); }
-hipError_t attention_bwd_kv_mh_f64(const AttnBwdKVArgs<double> &a, hipStream_t s) { return attention_bwd<double, true>(a, s); }
-hipError_t attention_bwd_kv_f32(const AttnBwdKVArgs<float> &a, hipStream_t s) { return attention_bwd<float, false>(a, s); }
-hipError_t attention_bwd_kv_mh_f32(const AttnBwdKVArgs<float> &a, hipStream_t s) { return attention_bwd<float, true>(a, s); }
+// mh: the (row, head) / (column, head) instances, whatever a.heads; else the single-head ones
+template <typename T, class Args>
+static hipError_t attention_bwd_of(const Args &a, bool mh, hipStream_t s)
+{
+    if (!mh) return attention_bwd<T, false>(a, s);
+    return attention_bwd<T, true>(a, s);
+}
+hipError_t attention_bwd_q(const AttnBwdQArgs<double> &a, bool mh, hipStream_t s) { return attention_bwd_of<double>(a, mh, s); }
+hipError_t attention_bwd_q(const AttnBwdQArgs<float> &a, bool mh, hipStream_t s) { return attention_bwd_of<float>(a, mh, s); }
+hipError_t attention_bwd_kv(const AttnBwdKVArgs<double> &a, bool mh, hipStream_t s) { return attention_bwd_of<double>(a, mh, s); }
+hipError_t attention_bwd_kv(const AttnBwdKVArgs<float> &a, bool mh, hipStream_t s) { return attention_bwd_of<float>(a, mh, s); }
 
 }  // namespace crp

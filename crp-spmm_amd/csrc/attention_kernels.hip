@@ -36,7 +36,7 @@
 // taken to be finite: 0 * V must be 0).  An all-masked row keeps m == -inf and writes zeros, lse = -inf, p_out = 0.  A row with
 // NaN or +inf among its scores has unspecified outputs in that row only.
 //
-// MULTI-HEAD (the MH instances, attention_mh_rm_*).  a.heads = H heads of nk / nv columns each lie side by side in every operand:
+// MULTI-HEAD (the MH instances: attention_rm with mh).  a.heads = H heads of nk / nv columns each lie side by side in every operand:
 // head h owns columns [h nk, (h + 1) nk) of Q / K and [h nv, (h + 1) nv) of V / O.  A group owns the unit u = row * H + h
 // (row = u / H, h = u % H in 64 bits), so consecutive groups of a wave hold consecutive heads of one row, share its column
 // indices and gather adjacent slices of the same K / V row.  Everything above holds per unit with the operand bases advanced by
@@ -419,9 +419,20 @@ static hipError_t attention_rm(const AttnArgs<T> &a, hipStream_t s)
     return attention_wave<T, 0, MH>(a, s);
 }
 
-hipError_t attention_rm_f64(const AttnArgs<double> &a, hipStream_t s) { return attention_rm<double, false>(a, s); }
-hipError_t attention_rm_f32(const AttnArgs<float> &a, hipStream_t s) { return attention_rm<float, false>(a, s); }
-hipError_t attention_mh_rm_f64(const AttnArgs<double> &a, hipStream_t s) { return attention_rm<double, true>(a, s); }
-hipError_t attention_mh_rm_f32(const AttnArgs<float> &a, hipStream_t s) { return attention_rm<float, true>(a, s); }
+// (instantiated here, in this order, so that the kernels keep their places in the code object: both single-head families first)
+template hipError_t attention_rm<double, false>(const AttnArgs<double> &, hipStream_t);
+template hipError_t attention_rm<float, false>(const AttnArgs<float> &, hipStream_t);
+template hipError_t attention_rm<double, true>(const AttnArgs<double> &, hipStream_t);
+template hipError_t attention_rm<float, true>(const AttnArgs<float> &, hipStream_t);
+
+// mh: the (row, head) instances, whatever a.heads; else the single-head ones
+hipError_t attention_rm(const AttnArgs<double> &a, bool mh, hipStream_t s)
+{
+    return mh ? attention_rm<double, true>(a, s) : attention_rm<double, false>(a, s);
+}
+hipError_t attention_rm(const AttnArgs<float> &a, bool mh, hipStream_t s)
+{
+    return mh ? attention_rm<float, true>(a, s) : attention_rm<float, false>(a, s);
+}
 
 }  // namespace crp

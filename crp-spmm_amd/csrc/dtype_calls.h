@@ -47,17 +47,61 @@ static inline int sddmm(crp_csr_dev_p A, int n, const float *X, long long ldX, c
 {
     return crp_sddmm_csr_f32(A, n, X, ldX, Y0, ldY0, Y1, ldY1, out, out_pos, mode, s);
 }
-static inline int attention(crp_csr_dev_p A, int n, double scale, int bias, const double *Q, long long ldQ, const double *K0, long long ldK0,
-                            const double *K1, long long ldK1, const double *V0, long long ldV0, const double *V1, long long ldV1, double *O,
-                            long long ldO, double *lse, double *p_out, const int *out_pos, void *s)
+// the fused attention and its backward: heads == 0 is the single-head entry point (d: all the columns), heads >= 1 the multi-head
+// one with its heads of d columns each -- the one place that chooses between them
+static inline int attention(crp_csr_dev_p A, int heads, int d, double scale, int bias, const double *Q, long long ldQ, const double *K0,
+                            long long ldK0, const double *K1, long long ldK1, const double *V0, long long ldV0, const double *V1,
+                            long long ldV1, double *O, long long ldO, double *lse, double *p_out, const int *out_pos, void *s)
 {
-    return crp_attention_csr_f64(A, n, n, scale, bias, Q, ldQ, K0, ldK0, K1, ldK1, V0, ldV0, V1, ldV1, O, ldO, lse, p_out, out_pos, s);
+    if (heads >= 1)
+        return crp_attention_mh_csr_f64(A, heads, d, d, scale, bias, Q, ldQ, K0, ldK0, K1, ldK1, V0, ldV0, V1, ldV1, O, ldO, lse, p_out, out_pos, s);
+    return crp_attention_csr_f64(A, d, d, scale, bias, Q, ldQ, K0, ldK0, K1, ldK1, V0, ldV0, V1, ldV1, O, ldO, lse, p_out, out_pos, s);
 }
-static inline int attention(crp_csr_dev_p A, int n, double scale, int bias, const float *Q, long long ldQ, const float *K0, long long ldK0,
-                            const float *K1, long long ldK1, const float *V0, long long ldV0, const float *V1, long long ldV1, float *O,
-                            long long ldO, float *lse, float *p_out, const int *out_pos, void *s)
+static inline int attention(crp_csr_dev_p A, int heads, int d, double scale, int bias, const float *Q, long long ldQ, const float *K0,
+                            long long ldK0, const float *K1, long long ldK1, const float *V0, long long ldV0, const float *V1,
+                            long long ldV1, float *O, long long ldO, float *lse, float *p_out, const int *out_pos, void *s)
 {
-    return crp_attention_csr_f32(A, n, n, scale, bias, Q, ldQ, K0, ldK0, K1, ldK1, V0, ldV0, V1, ldV1, O, ldO, lse, p_out, out_pos, s);
+    if (heads >= 1)
+        return crp_attention_mh_csr_f32(A, heads, d, d, scale, bias, Q, ldQ, K0, ldK0, K1, ldK1, V0, ldV0, V1, ldV1, O, ldO, lse, p_out, out_pos, s);
+    return crp_attention_csr_f32(A, d, d, scale, bias, Q, ldQ, K0, ldK0, K1, ldK1, V0, ldV0, V1, ldV1, O, ldO, lse, p_out, out_pos, s);
+}
+static inline int attention_bwd_q(crp_csr_dev_p A, int heads, int d, double scale, int bias, const double *Q, long long ldQ, const double *K0,
+                                  long long ldK0, const double *K1, long long ldK1, const double *V0, long long ldV0, const double *V1,
+                                  long long ldV1, const double *O, long long ldO, const double *dO, long long lddO, const double *lse,
+                                  double *dQ, long long lddQ, double *delta, double *ds_out, const int *out_pos, void *s)
+{
+    if (heads >= 1)
+        return crp_attention_bwd_q_mh_csr_f64(A, heads, d, d, scale, bias, Q, ldQ, K0, ldK0, K1, ldK1, V0, ldV0, V1, ldV1, O, ldO, dO, lddO, lse,
+                                              dQ, lddQ, delta, ds_out, out_pos, s);
+    return crp_attention_bwd_q_csr_f64(A, d, d, scale, bias, Q, ldQ, K0, ldK0, K1, ldK1, V0, ldV0, V1, ldV1, O, ldO, dO, lddO, lse, dQ, lddQ,
+                                       delta, ds_out, out_pos, s);
+}
+static inline int attention_bwd_q(crp_csr_dev_p A, int heads, int d, double scale, int bias, const float *Q, long long ldQ, const float *K0,
+                                  long long ldK0, const float *K1, long long ldK1, const float *V0, long long ldV0, const float *V1,
+                                  long long ldV1, const float *O, long long ldO, const float *dO, long long lddO, const float *lse, float *dQ,
+                                  long long lddQ, float *delta, float *ds_out, const int *out_pos, void *s)
+{
+    if (heads >= 1)
+        return crp_attention_bwd_q_mh_csr_f32(A, heads, d, d, scale, bias, Q, ldQ, K0, ldK0, K1, ldK1, V0, ldV0, V1, ldV1, O, ldO, dO, lddO, lse,
+                                              dQ, lddQ, delta, ds_out, out_pos, s);
+    return crp_attention_bwd_q_csr_f32(A, d, d, scale, bias, Q, ldQ, K0, ldK0, K1, ldK1, V0, ldV0, V1, ldV1, O, ldO, dO, lddO, lse, dQ, lddQ,
+                                       delta, ds_out, out_pos, s);
+}
+static inline int attention_bwd_kv(crp_csr_dev_p At, int heads, int d, double scale, int bias, const double *K, long long ldK, const double *V,
+                                   long long ldV, const double *Q, long long ldQ, const double *dO, long long lddO, const double *lse,
+                                   const double *delta, double *dK, long long lddK, double *dV, long long lddV, void *s)
+{
+    if (heads >= 1)
+        return crp_attention_bwd_kv_mh_csr_f64(At, heads, d, d, scale, bias, K, ldK, V, ldV, Q, ldQ, dO, lddO, lse, delta, dK, lddK, dV, lddV, s);
+    return crp_attention_bwd_kv_csr_f64(At, d, d, scale, bias, K, ldK, V, ldV, Q, ldQ, dO, lddO, lse, delta, dK, lddK, dV, lddV, s);
+}
+static inline int attention_bwd_kv(crp_csr_dev_p At, int heads, int d, double scale, int bias, const float *K, long long ldK, const float *V,
+                                   long long ldV, const float *Q, long long ldQ, const float *dO, long long lddO, const float *lse,
+                                   const float *delta, float *dK, long long lddK, float *dV, long long lddV, void *s)
+{
+    if (heads >= 1)
+        return crp_attention_bwd_kv_mh_csr_f32(At, heads, d, d, scale, bias, K, ldK, V, ldV, Q, ldQ, dO, lddO, lse, delta, dK, lddK, dV, lddV, s);
+    return crp_attention_bwd_kv_csr_f32(At, d, d, scale, bias, K, ldK, V, ldV, Q, ldQ, dO, lddO, lse, delta, dK, lddK, dV, lddV, s);
 }
 static inline int sum_segments(int nseg, long long len, const double *src, long long stride, double *out, void *s)
 {

@@ -417,28 +417,6 @@ static int sddmm_check(const crp_csr_dev *A, int n, const void *X, long long ldX
     return 0;
 }
 
-// mh: the (row, head) instances (the crp_attention_*_mh_* entry points, whatever their heads); else the single-head ones
-static hipError_t attention_launch(const crp::AttnArgs<double> &a, bool mh, hipStream_t s)
-{
-    return mh ? crp::attention_mh_rm_f64(a, s) : crp::attention_rm_f64(a, s);
-}
-static hipError_t attention_launch(const crp::AttnArgs<float> &a, bool mh, hipStream_t s)
-{
-    return mh ? crp::attention_mh_rm_f32(a, s) : crp::attention_rm_f32(a, s);
-}
-// O = softmax_row(scale (Q K^T)|pattern(A) (+ A's values)) V (attention_kernels.hip), one dtype; val: the values in T, or nullptr
-template <class T>
-static int attention_csr(crp_csr_dev *A, int nk, int nv, double scale, const T *val, const T *Q, long long ldQ, const T *K0,
-                         long long ldK0, const T *K1, long long ldK1, const T *V0, long long ldV0, const T *V1, long long ldV1, T *O,
-                         long long ldO, T *lse, T *p_out, const int *out_pos, hipStream_t s, bool mh = false, int heads = 1)
-{
-    crp::AttnArgs<T> a;
-    a.heads = heads;
-    a.nrow = A->nrow; a.nk = nk; a.nv = nv; a.rowptr = A->rowptr; a.colidx = A->colidx; a.val = val; a.scale = (T) scale;
-    a.Q = Q; a.ldQ = ldQ; a.K0 = K0; a.ldK0 = ldK0; a.K1 = K1; a.ldK1 = ldK1; a.V0 = V0; a.ldV0 = ldV0; a.V1 = V1; a.ldV1 = ldV1;
-    a.O = O; a.ldO = ldO; a.lse = lse; a.p_out = p_out; a.rowmap = A->rowmap; a.out_pos = out_pos;
-    return (int) attention_launch(a, mh, s);
-}
 // every argument is checked before anything is launched or allocated: a negative return has written nothing
 static int attention_check(const crp_csr_dev *A, int nk, int nv, double scale, int bias, const void *Q, long long ldQ, const void *K0,
                            long long ldK0, const void *K1, long long ldK1, const void *V0, long long ldV0, const void *V1, long long ldV1,
@@ -454,23 +432,6 @@ static int attention_check(const crp_csr_dev *A, int nk, int nv, double scale, i
     return 0;
 }
 
-
-static hipError_t attention_bwd_launch(const crp::AttnBwdQArgs<double> &a, bool mh, hipStream_t s)
-{
-    return mh ? crp::attention_bwd_q_mh_f64(a, s) : crp::attention_bwd_q_f64(a, s);
-}
-static hipError_t attention_bwd_launch(const crp::AttnBwdQArgs<float> &a, bool mh, hipStream_t s)
-{
-    return mh ? crp::attention_bwd_q_mh_f32(a, s) : crp::attention_bwd_q_f32(a, s);
-}
-static hipError_t attention_bwd_launch(const crp::AttnBwdKVArgs<double> &a, bool mh, hipStream_t s)
-{
-    return mh ? crp::attention_bwd_kv_mh_f64(a, s) : crp::attention_bwd_kv_f64(a, s);
-}
-static hipError_t attention_bwd_launch(const crp::AttnBwdKVArgs<float> &a, bool mh, hipStream_t s)
-{
-    return mh ? crp::attention_bwd_kv_mh_f32(a, s) : crp::attention_bwd_kv_f32(a, s);
-}
 // the fp32 copy of the values, as crp_sddmm_csr_f32 mode 1 derives it; the values in T for the bias, or nullptr
 template <class T> static int attention_bias_values(crp_csr_dev *A, int bias, hipStream_t s, const T **val);
 template <> int attention_bias_values<double>(crp_csr_dev *A, int bias, hipStream_t, const double **val)
@@ -486,6 +447,24 @@ template <> int attention_bias_values<float>(crp_csr_dev *A, int bias, hipStream
     if (rc != 0) return rc;
     *val = (const float *) A->val32;
     return 0;
+}
+// O = softmax_row(scale (Q K^T)|pattern(A) (+ A's values)) V (attention_kernels.hip), one dtype.  nk, nv: the widths of one head;
+// mh: the (row, head) instances (the crp_attention_*_mh_* entry points, whatever their heads), else the single-head ones.
+template <class T>
+static int attention_fwd_csr(crp_csr_dev *A, int heads, bool mh, int nk, int nv, double scale, int bias, const T *Q, long long ldQ, const T *K0,
+                             long long ldK0, const T *K1, long long ldK1, const T *V0, long long ldV0, const T *V1, long long ldV1, T *O,
+                             long long ldO, T *lse, T *p_out, const int *out_pos, hipStream_t s)
+{
+    int rc = attention_check(A, nk, nv, scale, bias, Q, ldQ, K0, ldK0, K1, ldK1, V0, ldV0, V1, ldV1, O, ldO, heads);
+    if (rc != 0 || A->nrow == 0) return rc;
+    crp::AttnArgs<T> a;
+    a.heads = heads;
+    rc = attention_bias_values<T>(A, bias, s, &a.val);
+    if (rc != 0) return rc;
+    a.nrow = A->nrow; a.nk = nk; a.nv = nv; a.rowptr = A->rowptr; a.colidx = A->colidx; a.scale = (T) scale;
+    a.Q = Q; a.ldQ = ldQ; a.K0 = K0; a.ldK0 = ldK0; a.K1 = K1; a.ldK1 = ldK1; a.V0 = V0; a.ldV0 = ldV0; a.V1 = V1; a.ldV1 = ldV1;
+    a.O = O; a.ldO = ldO; a.lse = lse; a.p_out = p_out; a.rowmap = A->rowmap; a.out_pos = out_pos;
+    return (int) crp::attention_rm(a, mh, s);
 }
 // the fused backward (attention_bwd_kernels.hip), one dtype.  Every argument is checked before anything is launched or
 // allocated: a negative return has written nothing.  nk, nv: the widths of one head (the cap is theirs); mh: the (row, head)
@@ -510,7 +489,7 @@ static int attention_bwd_q_csr(crp_csr_dev *A, int nk, int nv, double scale, int
     a.Q = Q; a.ldQ = ldQ; a.K0 = K0; a.ldK0 = ldK0; a.K1 = K1; a.ldK1 = ldK1; a.V0 = V0; a.ldV0 = ldV0; a.V1 = V1; a.ldV1 = ldV1;
     a.O = O; a.ldO = ldO; a.dO = dO; a.lddO = lddO; a.lse = lse; a.dQ = dQ; a.lddQ = lddQ; a.delta = delta; a.ds_out = ds_out;
     a.rowmap = A->rowmap; a.out_pos = out_pos;
-    return (int) attention_bwd_launch(a, mh, s);
+    return (int) crp::attention_bwd_q(a, mh, s);
 }
 template <class T>
 static int attention_bwd_kv_csr(crp_csr_dev *At, int nk, int nv, double scale, int bias, const T *K, long long ldK, const T *V, long long ldV,
@@ -534,7 +513,7 @@ static int attention_bwd_kv_csr(crp_csr_dev *At, int nk, int nv, double scale, i
     a.nrow = At->nrow; a.nk = nk; a.nv = nv; a.rowptr = At->rowptr; a.colidx = At->colidx; a.scale = (T) scale;
     a.K = K; a.ldK = ldK; a.V = V; a.ldV = ldV; a.Q = Q; a.ldQ = ldQ; a.dO = dO; a.lddO = lddO; a.lse = lse; a.delta = delta;
     a.dK = dK; a.lddK = lddK; a.dV = dV; a.lddV = lddV; a.rowmap = At->rowmap;
-    return (int) attention_bwd_launch(a, mh, s);
+    return (int) crp::attention_bwd_kv(a, mh, s);
 }
 
 extern "C" {
@@ -1137,26 +1116,16 @@ int crp_attention_csr_f64(crp_csr_dev_p A, int nk, int nv, double scale, int bia
                           long long ldK0, const double *K1, long long ldK1, const double *V0, long long ldV0, const double *V1,
                           long long ldV1, double *O, long long ldO, double *lse, double *p_out, const int *out_pos, void *stream)
 {
-    const int rc = attention_check(A, nk, nv, scale, bias, Q, ldQ, K0, ldK0, K1, ldK1, V0, ldV0, V1, ldV1, O, ldO);
-    if (rc != 0 || A->nrow == 0) return rc;
-    return attention_csr<double>(A, nk, nv, scale, bias ? (const double *) A->val : nullptr, Q, ldQ, K0, ldK0, K1, ldK1, V0, ldV0, V1, ldV1,
-                                 O, ldO, lse, p_out, out_pos, (hipStream_t) stream);
+    return attention_fwd_csr<double>(A, 1, false, nk, nv, scale, bias, Q, ldQ, K0, ldK0, K1, ldK1, V0, ldV0, V1, ldV1, O, ldO, lse, p_out, out_pos,
+                                     (hipStream_t) stream);
 }
 
 int crp_attention_csr_f32(crp_csr_dev_p A, int nk, int nv, double scale, int bias, const float *Q, long long ldQ, const float *K0,
                           long long ldK0, const float *K1, long long ldK1, const float *V0, long long ldV0, const float *V1,
                           long long ldV1, float *O, long long ldO, float *lse, float *p_out, const int *out_pos, void *stream)
 {
-    const int rc = attention_check(A, nk, nv, scale, bias, Q, ldQ, K0, ldK0, K1, ldK1, V0, ldV0, V1, ldV1, O, ldO);
-    if (rc != 0 || A->nrow == 0) return rc;
-    const hipStream_t s = (hipStream_t) stream;
-    if (bias == 1 && A->nnz > 0)                            // the fp32 copy of the values, as crp_sddmm_csr_f32 mode 1 derives it
-    {
-        const int rc1 = ensure_val32(A, s);
-        if (rc1 != 0) return rc1;
-    }
-    return attention_csr<float>(A, nk, nv, scale, (bias && A->nnz > 0) ? (const float *) A->val32 : nullptr, Q, ldQ, K0, ldK0, K1, ldK1, V0,
-                                ldV0, V1, ldV1, O, ldO, lse, p_out, out_pos, s);
+    return attention_fwd_csr<float>(A, 1, false, nk, nv, scale, bias, Q, ldQ, K0, ldK0, K1, ldK1, V0, ldV0, V1, ldV1, O, ldO, lse, p_out, out_pos,
+                                    (hipStream_t) stream);
 }
 
 // ---- the fused backward of the sparse attention (attention_bwd_kernels.hip)
@@ -1201,26 +1170,16 @@ int crp_attention_mh_csr_f64(crp_csr_dev_p A, int heads, int dk, int dv, double 
                              long long ldK0, const double *K1, long long ldK1, const double *V0, long long ldV0, const double *V1, long long ldV1,
                              double *O, long long ldO, double *lse, double *p_out, const int *out_pos, void *stream)
 {
-    const int rc = attention_check(A, dk, dv, scale, bias, Q, ldQ, K0, ldK0, K1, ldK1, V0, ldV0, V1, ldV1, O, ldO, heads);
-    if (rc != 0 || A->nrow == 0) return rc;
-    return attention_csr<double>(A, dk, dv, scale, bias ? (const double *) A->val : nullptr, Q, ldQ, K0, ldK0, K1, ldK1, V0, ldV0, V1, ldV1,
-                                 O, ldO, lse, p_out, out_pos, (hipStream_t) stream, true, heads);
+    return attention_fwd_csr<double>(A, heads, true, dk, dv, scale, bias, Q, ldQ, K0, ldK0, K1, ldK1, V0, ldV0, V1, ldV1, O, ldO, lse, p_out, out_pos,
+                                     (hipStream_t) stream);
 }
 
 int crp_attention_mh_csr_f32(crp_csr_dev_p A, int heads, int dk, int dv, double scale, int bias, const float *Q, long long ldQ, const float *K0,
                              long long ldK0, const float *K1, long long ldK1, const float *V0, long long ldV0, const float *V1, long long ldV1,
                              float *O, long long ldO, float *lse, float *p_out, const int *out_pos, void *stream)
 {
-    const int rc = attention_check(A, dk, dv, scale, bias, Q, ldQ, K0, ldK0, K1, ldK1, V0, ldV0, V1, ldV1, O, ldO, heads);
-    if (rc != 0 || A->nrow == 0) return rc;
-    const hipStream_t s = (hipStream_t) stream;
-    if (bias == 1 && A->nnz > 0)                            // the fp32 copy of the values, as crp_sddmm_csr_f32 mode 1 derives it
-    {
-        const int rc1 = ensure_val32(A, s);
-        if (rc1 != 0) return rc1;
-    }
-    return attention_csr<float>(A, dk, dv, scale, (bias && A->nnz > 0) ? (const float *) A->val32 : nullptr, Q, ldQ, K0, ldK0, K1, ldK1, V0,
-                                ldV0, V1, ldV1, O, ldO, lse, p_out, out_pos, s, true, heads);
+    return attention_fwd_csr<float>(A, heads, true, dk, dv, scale, bias, Q, ldQ, K0, ldK0, K1, ldK1, V0, ldV0, V1, ldV1, O, ldO, lse, p_out, out_pos,
+                                    (hipStream_t) stream);
 }
 
 int crp_attention_bwd_q_mh_csr_f64(crp_csr_dev_p A, int heads, int dk, int dv, double scale, int bias, const double *Q, long long ldQ,

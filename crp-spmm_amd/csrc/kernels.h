@@ -131,7 +131,7 @@ template <typename T> struct AttnArgs      // attention_kernels.hip: O[i] = sum_
     T         *p_out;       // nullptr, or the probabilities per nonzero
     const int *rowmap;      // nullptr, or the Q / O row of every row (row-subset matrices)
     const int *out_pos;     // nullptr, or where nonzero p writes: p_out[out_pos[p]]
-    int heads = 1;          // read by the multi-head instances only (attention_mh_rm_*): nk and nv are then one head's widths
+    int heads = 1;          // read by the multi-head instances only (attention_rm, mh): nk and nv are then one head's widths
 };
 
 // attention_bwd_kernels.hip, row side: dQ[i] = scale sum_p dS_p K[c_p], delta[i] = <dO[i], O[i]>, ds_out[p] = dS_p over A's rows
@@ -165,7 +165,7 @@ template <typename T> struct AttnBwdQArgs
     T         *ds_out;      // nullptr, or dS per nonzero
     const int *rowmap;      // nullptr, or the Q / O / dO / dQ / lse / delta row of every row (row-subset matrices)
     const int *out_pos;     // nullptr, or where nonzero p writes: ds_out[out_pos[p]]
-    int heads = 1;          // read by the multi-head instances only (attention_bwd_q_mh_*)
+    int heads = 1;          // read by the multi-head instances only (attention_bwd_q, mh)
 };
 
 // attention_bwd_kernels.hip, column side, over a handle of A^T (row c = column c of A, entries = the rows i of A that hold c):
@@ -194,7 +194,7 @@ template <typename T> struct AttnBwdKVArgs
     T         *dV;          // may be V exactly
     int64_t    lddV;
     const int *rowmap;      // nullptr, or the K / V / dK / dV row of every row (row-subset matrices)
-    int heads = 1;          // read by the multi-head instances only (attention_bwd_kv_mh_*)
+    int heads = 1;          // read by the multi-head instances only (attention_bwd_kv, mh)
 };
 
 // The instance every SpMM launcher names at its hipLaunchKernelGGL, from its own template arguments ("rowgroup<16,2,1>",
@@ -235,25 +235,20 @@ hipError_t spmm_rm_f32_rowgroup(const SpmmArgsF32 &a, hipStream_t s);
 hipError_t sddmm_rm_f64(const SddmmArgs<double> &a, hipStream_t s);
 hipError_t sddmm_rm_f32(const SddmmArgs<float> &a, hipStream_t s);
 
-// attention_kernels.hip: fused scores, online row softmax and product with V; row-major operands, any widths and alignment
-hipError_t attention_rm_f64(const AttnArgs<double> &a, hipStream_t s);
-hipError_t attention_rm_f32(const AttnArgs<float> &a, hipStream_t s);
-// ... over (row, head) units: a.heads heads of a.nk / a.nv columns each, side by side in every operand; lse is (rows, heads) and
-// p_out (nnz, heads).  Head h's bits are attention_rm_*'s on the column views of head h.
-hipError_t attention_mh_rm_f64(const AttnArgs<double> &a, hipStream_t s);
-hipError_t attention_mh_rm_f32(const AttnArgs<float> &a, hipStream_t s);
+// attention_kernels.hip: fused scores, online row softmax and product with V; row-major operands, any widths and alignment.
+// mh: over (row, head) units -- a.heads heads of a.nk / a.nv columns each, side by side in every operand; lse is (rows, heads) and
+// p_out (nnz, heads).  Head h's bits are the single-head instances' on the column views of head h.  (mh is the entry point's, not
+// a.heads > 1: a multi-head call of one head runs the multi-head instances, a single-head call never does.)
+hipError_t attention_rm(const AttnArgs<double> &a, bool mh, hipStream_t s);
+hipError_t attention_rm(const AttnArgs<float> &a, bool mh, hipStream_t s);
 
-// attention_bwd_kernels.hip: the fused backward of attention_rm_*; nk and nv at most ATTN_BWD_MAX_PIECES * 64 * (16 / sizeof(T))
+// attention_bwd_kernels.hip: the fused backward of attention_rm; nk and nv at most ATTN_BWD_MAX_PIECES * 64 * (16 / sizeof(T)).
+// mh: over (row, head) and (column, head) units; the cap applies to one head's widths
 constexpr int ATTN_BWD_MAX_PIECES = 4;
-hipError_t attention_bwd_q_f64(const AttnBwdQArgs<double> &a, hipStream_t s);
-hipError_t attention_bwd_q_f32(const AttnBwdQArgs<float> &a, hipStream_t s);
-hipError_t attention_bwd_kv_f64(const AttnBwdKVArgs<double> &a, hipStream_t s);
-hipError_t attention_bwd_kv_f32(const AttnBwdKVArgs<float> &a, hipStream_t s);
-// ... over (row, head) and (column, head) units; the cap applies to one head's widths
-hipError_t attention_bwd_q_mh_f64(const AttnBwdQArgs<double> &a, hipStream_t s);
-hipError_t attention_bwd_q_mh_f32(const AttnBwdQArgs<float> &a, hipStream_t s);
-hipError_t attention_bwd_kv_mh_f64(const AttnBwdKVArgs<double> &a, hipStream_t s);
-hipError_t attention_bwd_kv_mh_f32(const AttnBwdKVArgs<float> &a, hipStream_t s);
+hipError_t attention_bwd_q(const AttnBwdQArgs<double> &a, bool mh, hipStream_t s);
+hipError_t attention_bwd_q(const AttnBwdQArgs<float> &a, bool mh, hipStream_t s);
+hipError_t attention_bwd_kv(const AttnBwdKVArgs<double> &a, bool mh, hipStream_t s);
+hipError_t attention_bwd_kv(const AttnBwdKVArgs<float> &a, bool mh, hipStream_t s);
 
 // softmax_kernels.hip: row softmax over a CSR pattern and its Jacobian product; rowptr entries index the value arrays directly
 hipError_t row_softmax_f64(int nrow, const int *rowptr, const double *s, double *y, hipStream_t st);

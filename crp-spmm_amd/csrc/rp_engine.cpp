@@ -380,77 +380,6 @@ static void sddmm_impl(crp_rp_spmm *e, int layout, const T *X, long long ldX, co
     e->n_exec++;
 }
 
-// ---- O = softmax_row(scale (Q K^T)|pattern(A) (+ A's values)) V over this rank's rows of A (crp_rp_spmm_attention_ex / _f32_ex)
-// mh_call == nullptr: the single-head calls.  Else (the _mh_ calls, rp_attention_mh.cpp) the multi-head device call and its heads
-// of glb_n / heads columns each -- only the part kernels and the sizes of lse (rows x heads) and p_out (nnz x heads) know; the
-// exchange moves whole rows of K and V either way.
-template <class T>
-static void attention_impl(crp_rp_spmm *e, int layout, double scale, int bias, const T *Q, long long ldQ, const T *K, long long ldK,
-                           const T *V, long long ldV, T *O, long long ldO, T *lse, T *p_out, void *stream_, int heads = 0,
-                           crp::attn_mh_fn<T> mh_call = nullptr)
-{
-    if (e == NULL) return;
-    const bool mh = mh_call != nullptr;
-    ASSERT_PRINTF(!mh || (heads >= 1 && e->glb_n % heads == 0), "rp_spmm_attention_mh: heads (%d) must be positive and divide the %d columns\n",
-                  heads, e->glb_n);
-    const size_t nh = mh ? (size_t) heads : 1;
-    ASSERT_PRINTF(!e->plan_only, "rp_spmm_attention on a plan-only engine (no device state)\n");
-    ASSERT_PRINTF(layout == 0 || layout == 1, "layout must be 0 or 1\n");
-    ASSERT_PRINTF(bias == 0 || bias == 1, "bias must be 0 or 1\n");
-    ASSERT_PRINTF(scale - scale == 0.0, "scale must be finite\n");
-    const double t_begin = get_wtime_sec();
-    void *s = stream_;
-    const int n = e->glb_n, kb = e->loc_B_nrow, m = e->A_nrow;
-    const size_t nnz = e->A_val.size();
-    const bool timing = e->timing != 0;
-    double t0;
-
-    const bool Q_on_dev = on_device(Q), K_on_dev = on_device(K), V_on_dev = on_device(V), O_on_dev = on_device(O);
-    const bool lse_host = lse != NULL && m > 0 && !on_device(lse), p_host = p_out != NULL && nnz > 0 && !on_device(p_out);
-
-    // ---- operands as device-resident row-major views: K takes B's buffers and the forward exchange, O takes C's
-    const Xchg x = exchange_of(e, K);
-    T *recv2 = attention_recv(e, x, K);
-    const crp::InView<T> Kv = crp::operand_in(layout, K, ldK, kb, n, K_on_dev, e->B_stage, e->B_rm, s);
-    const crp::InView<T> Vv = crp::operand_in(layout, V, ldV, kb, n, V_on_dev, e->V_stage, e->V_rm, s);
-    const crp::InView<T> Qv = crp::operand_in(layout, Q, ldQ, m, n, Q_on_dev, e->Q_stage, e->Q_rm, s);
-    const crp::OutView<T> Ov = crp::operand_out(layout, O, ldO, m, n, O_on_dev, e->C_stage, e->C_rm);
-    T *lsed = lse_host ? e->at_lse.grow<T>((size_t) m * nh) : lse;
-    T *pd = p_host ? e->sd_out.grow<T>(nnz * nh) : p_out;
-
-    // ---- pack and exchange K, then V; the kernels: the parts of a split engine write O and lse through their row maps and p_out
-    // through their positions in A_val
-    pack_exchange_run2(e, x, recv2, Kv.p, Kv.ld, Vv.p, Vv.ld, s, t0, [&](crp_csr_dev_p A, int part) {
-        if (n == 0 || crp_csr_dev_nrow(A) == 0) return;
-        const int *pos = part == 1 ? e->sd_int_pos.get() : (part == 2 ? e->sd_bnd_pos.get() : nullptr);
-        if (mh)
-            HIP_OK(mh_call(A, heads, n / heads, n / heads, scale, bias, Qv.p, Qv.ld, Kv.p, Kv.ld, (const T *) x.recv, x.ld, Vv.p, Vv.ld,
-                           (const T *) recv2, x.ld, Ov.p, Ov.ld, lsed, pd, pos, s));
-        else
-            HIP_OK(crp::attention(A, n, scale, bias, Qv.p, Qv.ld, Kv.p, Kv.ld, (const T *) x.recv, x.ld, Vv.p, Vv.ld, (const T *) recv2, x.ld,
-                                  Ov.p, Ov.ld, lsed, pd, pos, s));
-    });
-    if (lse_host) HIP_OK(crp_dev_memcpy(lse, lsed, (size_t) m * nh * sizeof(T), 1, s));
-    if (p_host) HIP_OK(crp_dev_memcpy(p_out, pd, nnz * nh * sizeof(T), 1, s));
-    const bool synced = crp::finish(Ov, s, [&] { lap(e, s, t0, &e->t_spmm); });
-    complete(e, s, synced, lse_host || p_host || !Q_on_dev || !K_on_dev || !V_on_dev || timing);
-    e->t_exec += get_wtime_sec() - t_begin;
-    e->n_exec++;
-}
-
-void rp_attention_mh(crp_rp_spmm *e, int layout, int heads, double scale, int bias, const double *Q, long long ldQ, const double *K,
-                     long long ldK, const double *V, long long ldV, double *O, long long ldO, double *lse, double *p_out, void *stream,
-                     crp::attn_mh_fn<double> call)
-{
-    attention_impl<double>(e, layout, scale, bias, Q, ldQ, K, ldK, V, ldV, O, ldO, lse, p_out, stream, heads, call);
-}
-void rp_attention_mh(crp_rp_spmm *e, int layout, int heads, double scale, int bias, const float *Q, long long ldQ, const float *K,
-                     long long ldK, const float *V, long long ldV, float *O, long long ldO, float *lse, float *p_out, void *stream,
-                     crp::attn_mh_fn<float> call)
-{
-    attention_impl<float>(e, layout, scale, bias, Q, ldQ, K, ldK, V, ldV, O, ldO, lse, p_out, stream, heads, call);
-}
-
 // ---- C := A^T * B (crp_rp_spmm_exec_t_ex); build_transposed: rp_engine_impl.h
 // new values (A_val, already copied into e->A_val) for the transposed matrices
 static void update_transposed_values(crp_rp_spmm *e)
@@ -559,22 +488,6 @@ void crp_rp_spmm_sddmm_f32_ex(crp_rp_spmm_p e, int layout, const float *X, long 
 }
 
 int crp_rp_spmm_sddmm_built(crp_rp_spmm_p e) { return (e && e->sd_built) ? 1 : 0; }
-
-void crp_rp_spmm_attention_ex(crp_rp_spmm_p e, int layout, double scale, int bias, const double *Q, long long ldQ, const double *K,
-                              long long ldK, const double *V, long long ldV, double *O, long long ldO, double *lse, double *p_out,
-                              void *stream_)
-{
-    attention_impl<double>(e, layout, scale, bias, Q, ldQ, K, ldK, V, ldV, O, ldO, lse, p_out, stream_);
-}
-
-void crp_rp_spmm_attention_f32_ex(crp_rp_spmm_p e, int layout, double scale, int bias, const float *Q, long long ldQ, const float *K,
-                                  long long ldK, const float *V, long long ldV, float *O, long long ldO, float *lse, float *p_out,
-                                  void *stream_)
-{
-    attention_impl<float>(e, layout, scale, bias, Q, ldQ, K, ldK, V, ldV, O, ldO, lse, p_out, stream_);
-}
-
-int crp_rp_spmm_attention_built(crp_rp_spmm_p e) { return (e && e->at_built) ? 1 : 0; }
 
 void crp_rp_spmm_exec_ex(crp_rp_spmm_p e, int BC_layout, const double *B, long long ldB, double *C,
                          long long ldC, void *stream_)

@@ -1,7 +1,6 @@
 // rp_engine_impl.h -- the row engine's state (struct crp_rp_spmm) and the helpers that its translation units share: rp_engine.cpp
-// (init, exec, exec_t, sddmm, attention, value updates), rp_attention_bwd.cpp (the fused attention backward, which alone names
-// the single-head device entry points of attention_bwd_kernels.hip) and rp_attention_mh.cpp (the multi-head attention calls, which
-// alone names the multi-head device entry points).  Internal: nothing outside csrc/ includes it.
+// (init, exec, exec_t, sddmm, value updates) and rp_attention.cpp (the fused attention, forward and backward, single- and
+// multi-head).  Internal: nothing outside csrc/ includes it.
 #ifndef CRP_RP_ENGINE_IMPL_H
 #define CRP_RP_ENGINE_IMPL_H
 
@@ -65,7 +64,7 @@ struct crp_rp_spmm
     crp::DevScratch at_lse, V_rm, V_stage, Q_rm, Q_stage;
     crp::DevArray<float>  at_recv32_dev;
     crp::DevArray<double> at_recv_dev;
-    // fused attention backward (crp_rp_spmm_attention_bwd_ex, rp_attention_bwd.cpp), allocated by its first call of a dtype: delta, one
+    // fused attention backward (crp_rp_spmm_attention_bwd_ex, rp_attention.cpp), allocated by its first call of a dtype: delta, one
     // entry per row of A, written by the row side and read by the column side
     bool bw_built = false;
     crp::DevArray<float>  bw_delta32_dev;
@@ -177,7 +176,7 @@ static inline void complete(crp_rp_spmm *e, void *s, bool synced, bool must_sync
     e->exec_pending = true;
 }
 
-// ---- the pieces pack_exchange_run and pack_exchange_run2 share ---------------------------------------------------------------------
+// ---- the pieces pack_exchange_run (rp_engine.cpp) and pack_exchange_run2 (rp_attention.cpp) share ---------------------------------------------------------------------
 // pack the rows of the row-major device operand Bd that other ranks asked for into x.send, on st (reference :232-262)
 template <class T>
 static inline void pack_rows(crp_rp_spmm *e, const Xchg &x, const T *Bd, long long ldBd, void *st)
@@ -253,92 +252,6 @@ static inline void refresh_host_values(crp_rp_spmm *e)
         HIP_OK(crp_stream_sync(e->stream));
     }
     e->host_vals_stale = false;
-}
-
-// ---- the multi-head attention calls (crp_rp_spmm_attention_mh_ex and its kin, rp_attention_mh.cpp) ---------------------------------
-// rp_attention_mh.cpp is the one translation unit of the engines that names the multi-head device entry points; it hands them to
-// the implementations in rp_engine.cpp and rp_attention_bwd.cpp, which are the single-head calls' with `heads` passed to the part
-// kernels (a build of those two files over stand-ins for the device ABI needs no multi-head stand-in).
-namespace crp
-{
-template <class T>
-using attn_mh_fn = int (*)(crp_csr_dev_p, int, int, int, double, int, const T *, long long, const T *, long long, const T *, long long,
-                           const T *, long long, const T *, long long, T *, long long, T *, T *, const int *, void *);
-template <class T>
-using attn_bwd_q_mh_fn = int (*)(crp_csr_dev_p, int, int, int, double, int, const T *, long long, const T *, long long, const T *, long long,
-                                 const T *, long long, const T *, long long, const T *, long long, const T *, long long, const T *, T *,
-                                 long long, T *, T *, const int *, void *);
-template <class T>
-using attn_bwd_kv_mh_fn = int (*)(crp_csr_dev_p, int, int, int, double, int, const T *, long long, const T *, long long, const T *, long long,
-                                  const T *, long long, const T *, const T *, T *, long long, T *, long long, void *);
-}  // namespace crp
-void rp_attention_mh(crp_rp_spmm *e, int layout, int heads, double scale, int bias, const double *Q, long long ldQ, const double *K,
-                     long long ldK, const double *V, long long ldV, double *O, long long ldO, double *lse, double *p_out, void *stream,
-                     crp::attn_mh_fn<double> call);
-void rp_attention_mh(crp_rp_spmm *e, int layout, int heads, double scale, int bias, const float *Q, long long ldQ, const float *K,
-                     long long ldK, const float *V, long long ldV, float *O, long long ldO, float *lse, float *p_out, void *stream,
-                     crp::attn_mh_fn<float> call);
-void rp_attention_bwd_mh(crp_rp_spmm *e, int heads, double scale, int bias, const double *Q, long long ldQ, const double *K, long long ldK,
-                         const double *V, long long ldV, const double *O, long long ldO, const double *dO, long long lddO, const double *lse,
-                         double *dQ, long long lddQ, double *dK, long long lddK, double *dV, long long lddV, double *ds_out, void *stream,
-                         crp::attn_bwd_q_mh_fn<double> q_call, crp::attn_bwd_kv_mh_fn<double> kv_call);
-void rp_attention_bwd_mh(crp_rp_spmm *e, int heads, double scale, int bias, const float *Q, long long ldQ, const float *K, long long ldK,
-                         const float *V, long long ldV, const float *O, long long ldO, const float *dO, long long lddO, const float *lse,
-                         float *dQ, long long lddQ, float *dK, long long lddK, float *dV, long long lddV, float *ds_out, void *stream,
-                         crp::attn_bwd_q_mh_fn<float> q_call, crp::attn_bwd_kv_mh_fn<float> kv_call);
-
-// ---- what the fused attention and its backward share: the second receive buffer and the two-operand exchange ----------------------
-// first attention call of a dtype: the second receive buffer (rows of x.ld elements, zeroed once: the fp32 rows' pad columns are
-// never written again), and the parts' positions in A_val; blocks
-template <class T>
-static inline T *attention_recv(crp_rp_spmm *e, const Xchg &x, crp::DevArray<T> &buf, bool *ready)
-{
-    if (!*ready)
-    {
-        upload_part_positions(e);
-        if (e->n_recv_rows > 0 && x.ld > 0) buf.zeroed((size_t) e->n_recv_rows * (size_t) x.ld);
-        *ready = true;
-        e->at_built = true;
-    }
-    return buf;
-}
-static inline double *attention_recv(crp_rp_spmm *e, const Xchg &x, const double *) { return attention_recv(e, x, e->at_recv_dev, &e->at_ready64); }
-static inline float *attention_recv(crp_rp_spmm *e, const Xchg &x, const float *) { return attention_recv(e, x, e->at_recv32_dev, &e->at_ready32); }
-
-// pack_exchange_run for two operands partitioned like B: the rows of Kd travel into x.recv, then those of Vd into recv2, both
-// through x.send, which is reused in stream order.  With timing off and a split engine the interior part is enqueued on s first and
-// both packs and both exchanges run beside it on the engine's second stream, from the point of s where the operands are ready; the
-// boundary part follows on s after the second exchange has landed.  Otherwise everything runs on s in sequence and, with timing
-// on, bills to t_pack and t_a2a (t0 is left at the start of the kernels).
-template <class T, class F>
-static inline void pack_exchange_run2(crp_rp_spmm *e, const Xchg &x, void *recv2, const T *Kd, long long ldKd, const T *Vd, long long ldVd, void *s,
-                               double &t0, F &&product)
-{
-    const bool timing = e->timing != 0;
-    if (timing) { HIP_OK(crp_stream_sync(s)); }
-    t0 = get_wtime_sec();
-    if (e->A_int != nullptr && !timing)
-    {
-        HIP_OK(crp_event_record(e->ev_packed, s));          // (here: the operands are ready)
-        product(e->A_int, 1);
-        HIP_OK(crp_stream_wait_event(e->xstream, e->ev_packed));
-        pack_rows(e, x, Kd, ldKd, e->xstream);
-        exchange_rows(e, x, x.recv, e->xstream);
-        pack_rows(e, x, Vd, ldVd, e->xstream);
-        exchange_rows(e, x, recv2, e->xstream);
-        HIP_OK(crp_event_record(e->ev_landed, e->xstream));
-        HIP_OK(crp_stream_wait_event(s, e->ev_landed));
-        product(e->A_bnd, 2);
-        return;
-    }
-    for (int op = 0; op < 2; op++)
-    {
-        pack_rows(e, x, op == 0 ? Kd : Vd, op == 0 ? ldKd : ldVd, s);
-        lap(e, s, t0, &e->t_pack);
-        if (e->nproc > 1) exchange_rows(e, x, op == 0 ? x.recv : recv2, s);
-        lap(e, s, t0, &e->t_a2a);
-    }
-    run_parts(e, product);
 }
 
 // ---- the transposed matrices (crp_rp_spmm_exec_t_ex, crp_rp_spmm_attention_bwd_ex) -----------------------------------------------

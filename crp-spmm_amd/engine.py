@@ -305,12 +305,8 @@ class RpSpmm:
             stream = _current_stream(out)
         if stream is None:
             stream = _current_stream(Q)
-        if heads > 1:
-            fn = self._lib.crp_rp_spmm_attention_mh_f32_ex if f32 else self._lib.crp_rp_spmm_attention_mh_ex
-            fn(self.handle, layout, heads, scale, int(bool(bias)), qp, ldq, kp, ldk, vp, ldv, op, ldo, lp, pp, stream)
-            return
-        fn = self._lib.crp_rp_spmm_attention_f32_ex if f32 else self._lib.crp_rp_spmm_attention_ex
-        fn(self.handle, layout, scale, int(bool(bias)), qp, ldq, kp, ldk, vp, ldv, op, ldo, lp, pp, stream)
+        fn, mh = L.attention_entry(self._lib, "rp_spmm_attention", heads, f32)
+        fn(self.handle, layout, *mh, scale, int(bool(bias)), qp, ldq, kp, ldk, vp, ldv, op, ldo, lp, pp, stream)
 
     def attention_built(self):
         """True once an ``attention`` has allocated V's receive buffer (crp_rp_spmm_attention_built)."""
@@ -365,13 +361,8 @@ class RpSpmm:
         if stream is None:
             stream = _current_stream(dQ)
         ptr = lambda t: (t.data_ptr() or None) if t is not None else None
-        if heads > 1:
-            fn = self._lib.crp_rp_spmm_attention_bwd_mh_f32_ex if Q.dtype == torch.float32 else self._lib.crp_rp_spmm_attention_bwd_mh_ex
-            fn(self.handle, heads, scale, int(bool(bias)), ptr(Q), Q.stride(0), ptr(K), K.stride(0), ptr(V), V.stride(0), ptr(O), O.stride(0),
-               ptr(dO), dO.stride(0), ptr(lse), ptr(dQ), dQ.stride(0), ptr(dK), dK.stride(0), ptr(dV), dV.stride(0), ptr(ds_out), stream)
-            return
-        fn = self._lib.crp_rp_spmm_attention_bwd_f32_ex if Q.dtype == torch.float32 else self._lib.crp_rp_spmm_attention_bwd_ex
-        fn(self.handle, scale, int(bool(bias)), ptr(Q), Q.stride(0), ptr(K), K.stride(0), ptr(V), V.stride(0), ptr(O), O.stride(0), ptr(dO),
+        fn, mh = L.attention_entry(self._lib, "rp_spmm_attention_bwd", heads, Q.dtype == torch.float32)
+        fn(self.handle, *mh, scale, int(bool(bias)), ptr(Q), Q.stride(0), ptr(K), K.stride(0), ptr(V), V.stride(0), ptr(O), O.stride(0), ptr(dO),
            dO.stride(0), ptr(lse), ptr(dQ), dQ.stride(0), ptr(dK), dK.stride(0), ptr(dV), dV.stride(0), ptr(ds_out), stream)
 
     def attention_bwd_built(self):

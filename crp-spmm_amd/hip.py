@@ -177,48 +177,19 @@ class CsrDev:
             raise ValueError("K1 and V1 come together")
         kops = [("Q", Q), ("K0", K0)] + ([("K1", K1)] if K1 is not None else [])
         vops = [("V0", V0)] + ([("V1", V1)] if V1 is not None else []) + ([("out", out)] if out is not None else [])
-        for name, t in kops + vops:
-            if not (isinstance(t, torch.Tensor) and t.dim() == 2):
-                raise TypeError("%s must be a 2-D torch tensor on the device" % name)
-            if t.dtype not in (torch.float64, torch.float32):
-                raise TypeError("%s must be float64 or float32, got %s" % (name, t.dtype))
-            if t.dtype != Q.dtype:
-                raise TypeError("the operands must have one dtype (Q is %s, %s is %s)" % (Q.dtype, name, t.dtype))
-            if t.shape[1] > 1 and t.stride(1) != 1:
-                raise ValueError("%s must be contiguous along its rows" % name)
-        for name, t in (("lse", lse), ("p_out", p_out)):
-            if t is None:
-                continue
-            if not isinstance(t, torch.Tensor):
-                raise TypeError("%s must be a torch tensor on the device" % name)
-            if t.dtype != Q.dtype:
-                raise TypeError("%s must have the operands' dtype (%s is %s, Q is %s)" % (name, name, t.dtype, Q.dtype))
+        vecs = [(n_, t) for n_, t in (("lse", lse), ("p_out", p_out)) if t is not None]
+        nk, nv, scale, bias = _attention_operands(kops, vops, vecs, scale, bias, heads, cap=False, by_operand=True)
         lse, p_out = _mh_flat("lse", lse, heads), _mh_flat("p_out", p_out, heads)
-        if bias not in (False, True, 0, 1):
-            raise ValueError("bias must be a bool, got %r" % (bias,))
-        scale = float(scale)
-        if not np.isfinite(scale):
-            raise ValueError("scale must be finite, got %r" % (scale,))
-        nk, nv = int(Q.shape[1]), int(V0.shape[1])
-        if nk < 1 or nv < 1:
-            raise ValueError("the operands need at least one column")
-        _mh_widths(nk, nv, heads)
-        for name, t in kops[1:]:
-            if t.shape[1] != nk:
-                raise ValueError("%s has %d columns, Q has %d" % (name, t.shape[1], nk))
-        for name, t in vops[1:]:
-            if t.shape[1] != nv:
-                raise ValueError("%s has %d columns, V0 has %d" % (name, t.shape[1], nv))
         x_nrow = getattr(self, "_x_nrow", self.nrow)
-        if Q.shape[0] < x_nrow:
-            raise ValueError("Q has %d rows, the matrix needs %d" % (Q.shape[0], x_nrow))
+        if Q.size(0) < x_nrow:
+            raise ValueError("Q has %d rows, the matrix needs %d" % (Q.size(0), x_nrow))
         for name, t in (("K0", K0), ("V0", V0)):
-            if t.shape[0] < self.ncol:
-                raise ValueError("%s has %d rows, the matrix has %d columns" % (name, t.shape[0], self.ncol))
-        if K1 is not None and V1.shape[0] != K1.shape[0]:
-            raise ValueError("K1 has %d rows, V1 %d" % (K1.shape[0], V1.shape[0]))
-        if out is not None and out.shape[0] < x_nrow:
-            raise ValueError("out has %d rows, the matrix needs %d" % (out.shape[0], x_nrow))
+            if t.size(0) < self.ncol:
+                raise ValueError("%s has %d rows, the matrix has %d columns" % (name, t.size(0), self.ncol))
+        if K1 is not None and V1.size(0) != K1.size(0):
+            raise ValueError("K1 has %d rows, V1 %d" % (K1.size(0), V1.size(0)))
+        if out is not None and out.size(0) < x_nrow:
+            raise ValueError("out has %d rows, the matrix needs %d" % (out.size(0), x_nrow))
         nnz = self.nnz
         if lse is not None and (lse.dim() != 1 or not lse.is_contiguous() or lse.numel() < x_nrow * heads):
             raise ValueError("lse must be 1-D and contiguous with %d entries" % x_nrow if heads == 1 else
@@ -236,22 +207,16 @@ class CsrDev:
                 raise ValueError("p_out must be 1-D and contiguous")
             if out_pos is None and p_out.numel() < nnz * heads:
                 raise ValueError("p_out has %d entries, the matrix %d nonzeros" % (p_out.numel() // heads, nnz))
-        named = kops + vops + [(n_, t) for n_, t in (("lse", lse), ("p_out", p_out), ("out_pos", out_pos)) if t is not None]
-        for name, t in named:
-            if not t.is_cuda or t.device != Q.device:
-                raise TypeError("%s must be on the device, with Q" % name)      # (all pointers are device pointers)
+        _attention_on_device(kops + vops + [(n_, t) for n_, t in (("lse", lse), ("p_out", p_out), ("out_pos", out_pos))
+                                            if t is not None])
         if out is None:
             out = torch.empty((x_nrow, nv), dtype=Q.dtype, device=Q.device)
         if self.nrow == 0:
             return out
-        if heads == 1:
-            fn, widths = (self._lib.crp_attention_csr_f64 if Q.dtype == torch.float64 else self._lib.crp_attention_csr_f32), (nk, nv)
-        else:
-            fn = self._lib.crp_attention_mh_csr_f64 if Q.dtype == torch.float64 else self._lib.crp_attention_mh_csr_f32
-            widths = (heads, nk // heads, nv // heads)
+        fn, widths = L.attention_entry(self._lib, "attention", heads, Q.dtype == torch.float32, nk, nv)
         k1p, ldk1, v1p, ldv1 = (K1.data_ptr(), K1.stride(0), V1.data_ptr(), V1.stride(0)) if K1 is not None else (None, 0, None, 0)
         ptr = lambda t: (t.data_ptr() or None) if t is not None else None
-        L.check(fn(self.handle, *widths, scale, int(bool(bias)), Q.data_ptr(), Q.stride(0), ptr(K0), K0.stride(0), k1p, ldk1,
+        L.check(fn(self.handle, *widths, scale, bias, Q.data_ptr(), Q.stride(0), ptr(K0), K0.stride(0), k1p, ldk1,
                    ptr(V0), V0.stride(0), v1p, ldv1, out.data_ptr(), out.stride(0), ptr(lse), ptr(p_out), ptr(out_pos),
                    _stream(out) if stream is None else stream), fn.__name__)
         return out
@@ -279,7 +244,7 @@ class CsrDev:
         kops = [("Q", Q), ("K0", K0)] + ([("K1", K1)] if K1 is not None else []) + ([("dQ", dQ)] if dQ is not None else [])
         vops = [("V0", V0)] + ([("V1", V1)] if V1 is not None else []) + [("O", O), ("dO", dO)]
         vecs = [("lse", lse)] + [(n_, t) for n_, t in (("delta", delta), ("ds_out", ds_out)) if t is not None]
-        nk, nv, scale, bias = _bwd_operands(kops, vops, vecs, scale, bias, heads)
+        nk, nv, scale, bias = _attention_operands(kops, vops, vecs, scale, bias, heads)
         x_nrow = getattr(self, "_x_nrow", self.nrow)
         for name, t in (("Q", Q), ("O", O), ("dO", dO), ("dQ", dQ)):
             if t is not None and t.shape[0] < x_nrow:
@@ -304,19 +269,14 @@ class CsrDev:
                 raise ValueError("out_pos needs a ds_out to write into")
         elif ds_out is not None and ds_out.numel() < nnz * heads:
             raise ValueError("ds_out has %d entries, the matrix %d nonzeros" % (ds_out.numel() // heads, nnz))
-        _bwd_on_device(kops + vops + vecs + ([("out_pos", out_pos)] if out_pos is not None else []))
+        _attention_on_device(kops + vops + vecs + ([("out_pos", out_pos)] if out_pos is not None else []))
         if dQ is None:
             dQ = torch.empty((x_nrow, nk), dtype=Q.dtype, device=Q.device)
         if delta is None:
             delta = delta_given = torch.empty((x_nrow,) if heads == 1 else (x_nrow, heads), dtype=Q.dtype, device=Q.device)
         if self.nrow == 0:
             return dQ, delta_given
-        if heads == 1:
-            fn = self._lib.crp_attention_bwd_q_csr_f64 if Q.dtype == torch.float64 else self._lib.crp_attention_bwd_q_csr_f32
-            widths = (nk, nv)
-        else:
-            fn = self._lib.crp_attention_bwd_q_mh_csr_f64 if Q.dtype == torch.float64 else self._lib.crp_attention_bwd_q_mh_csr_f32
-            widths = (heads, nk // heads, nv // heads)
+        fn, widths = L.attention_entry(self._lib, "attention_bwd_q", heads, Q.dtype == torch.float32, nk, nv)
         k1p, ldk1, v1p, ldv1 = (K1.data_ptr(), K1.stride(0), V1.data_ptr(), V1.stride(0)) if K1 is not None else (None, 0, None, 0)
         ptr = lambda t: (t.data_ptr() or None) if t is not None else None
         L.check(fn(self.handle, *widths, scale, bias, Q.data_ptr(), Q.stride(0), ptr(K0), K0.stride(0), k1p, ldk1, ptr(V0), V0.stride(0),
@@ -338,7 +298,7 @@ class CsrDev:
         lse, delta = _mh_flat("lse", lse, heads), _mh_flat("delta", delta, heads)
         kops = [("K", K), ("Q", Q)] + ([("dK", dK)] if dK is not None else [])
         vops = [("V", V), ("dO", dO)] + ([("dV", dV)] if dV is not None else [])
-        nk, nv, scale, bias = _bwd_operands(kops, vops, [("lse", lse), ("delta", delta)], scale, bias, heads)
+        nk, nv, scale, bias = _attention_operands(kops, vops, [("lse", lse), ("delta", delta)], scale, bias, heads)
         x_nrow = getattr(self, "_x_nrow", self.nrow)
         for name, t in (("K", K), ("V", V), ("dK", dK), ("dV", dV)):
             if t is not None and t.shape[0] < x_nrow:
@@ -350,19 +310,14 @@ class CsrDev:
             if t.numel() < self.ncol * heads:
                 raise ValueError("%s must hold %d entries" % (name, self.ncol) if heads == 1 else
                                  "%s must hold %d rows of %d heads" % (name, self.ncol, heads))
-        _bwd_on_device(kops + vops + [("lse", lse), ("delta", delta)])
+        _attention_on_device(kops + vops + [("lse", lse), ("delta", delta)])
         if dK is None:
             dK = torch.empty((x_nrow, nk), dtype=K.dtype, device=K.device)
         if dV is None:
             dV = torch.empty((x_nrow, nv), dtype=K.dtype, device=K.device)
         if self.nrow == 0:
             return dK, dV
-        if heads == 1:
-            fn = self._lib.crp_attention_bwd_kv_csr_f64 if K.dtype == torch.float64 else self._lib.crp_attention_bwd_kv_csr_f32
-            widths = (nk, nv)
-        else:
-            fn = self._lib.crp_attention_bwd_kv_mh_csr_f64 if K.dtype == torch.float64 else self._lib.crp_attention_bwd_kv_mh_csr_f32
-            widths = (heads, nk // heads, nv // heads)
+        fn, widths = L.attention_entry(self._lib, "attention_bwd_kv", heads, K.dtype == torch.float32, nk, nv)
         L.check(fn(self.handle, *widths, scale, bias, K.data_ptr(), K.stride(0), V.data_ptr(), V.stride(0), Q.data_ptr() or None,
                    Q.stride(0), dO.data_ptr() or None, dO.stride(0), lse.data_ptr() or None, delta.data_ptr() or None, dK.data_ptr(),
                    dK.stride(0), dV.data_ptr(), dV.stride(0), _stream(dK) if stream is None else stream), fn.__name__)
@@ -487,49 +442,61 @@ def _mh_flat(name, t, heads):
     return t.view(-1)
 
 
-def _bwd_operands(kops, vops, vecs, scale, bias, heads=1):
-    """The operands of the fused attention backward, checked before any library call: kops 2-D of one width nk, vops 2-D of one
-    width nv, vecs 1-D and contiguous, all float64 or float32 of the first's dtype.  Returns (nk, nv, scale,
-    bias) as the C call takes them; the device is checked by _bwd_on_device.  ``heads`` must divide both widths, and the cap
-    applies to one head's."""
+def _attention_operands(kops, vops, vecs, scale, bias, heads=1, cap=True, by_operand=False):
+    """The operands of the three attention wrappers, checked before any library call: kops 2-D of one width nk, vops 2-D of one
+    width nv, all float64 or float32 of the first's dtype, their rows contiguous; ``heads`` must divide both widths.  Returns
+    (nk, nv, scale, bias) as the C call takes them; the device is checked by _attention_on_device.  ``cap`` (the backward): one
+    head's widths are held to BWD_WIDTH_CAP.  The order decides which error an input with two faults gets, and each wrapper keeps
+    its own: by default (the backward) every type comes first and vecs are then held to 1-D and contiguous; ``by_operand`` (the
+    forward) judges an operand's rows before the next one's type and leaves the shapes of vecs to the caller."""
     import torch
     head, first = kops[0]
-    for name, t in kops + vops + vecs:
+    ops = kops + vops
+    rows_now = len(ops) if by_operand else 0
+    floats, dtype = (torch.float64, torch.float32), getattr(first, "dtype", None)
+    for i, (name, t) in enumerate(ops + vecs):
         if not isinstance(t, torch.Tensor):
             raise TypeError("%s must be a torch tensor on the device" % name)
-        if t.dtype not in (torch.float64, torch.float32):
+        if t.dtype not in floats:
             raise TypeError("%s must be float64 or float32, got %s" % (name, t.dtype))
-        if t.dtype != first.dtype:
-            raise TypeError("the operands must have one dtype (%s is %s, %s is %s)" % (head, first.dtype, name, t.dtype))
-    for name, t in kops + vops:
-        if t.dim() != 2:
-            raise TypeError("%s must be a 2-D torch tensor on the device" % name)
-        if t.shape[1] > 1 and t.stride(1) != 1:
-            raise ValueError("%s must be contiguous along its rows" % name)
-    for name, t in vecs:
-        if t.dim() != 1 or not t.is_contiguous():
-            raise ValueError("%s must be 1-D and contiguous" % name)
+        if t.dtype != dtype:
+            raise TypeError("the operands must have one dtype (%s is %s, %s is %s)" % (head, dtype, name, t.dtype))
+        if i < rows_now:
+            if t.dim() != 2:
+                raise TypeError("%s must be a 2-D torch tensor on the device" % name)
+            if t.size(1) > 1 and t.stride(1) != 1:
+                raise ValueError("%s must be contiguous along its rows" % name)
+    if not by_operand:
+        for name, t in ops:
+            if t.dim() != 2:
+                raise TypeError("%s must be a 2-D torch tensor on the device" % name)
+            if t.size(1) > 1 and t.stride(1) != 1:
+                raise ValueError("%s must be contiguous along its rows" % name)
+        for name, t in vecs:
+            if t.dim() != 1 or not t.is_contiguous():
+                raise ValueError("%s must be 1-D and contiguous" % name)
     if bias not in (False, True, 0, 1):
         raise ValueError("bias must be a bool, got %r" % (bias,))
     scale = float(scale)
     if not np.isfinite(scale):
         raise ValueError("scale must be finite, got %r" % (scale,))
-    nk, nv = int(first.shape[1]), int(vops[0][1].shape[1])
+    nk, nv = first.size(1), vops[0][1].size(1)
     if nk < 1 or nv < 1:
         raise ValueError("the operands need at least one column")
-    for (ops, n) in ((kops, nk), (vops, nv)):
-        for name, t in ops[1:]:
-            if t.shape[1] != n:
-                raise ValueError("%s has %d columns, %s has %d" % (name, t.shape[1], ops[0][0], n))
+    for (side, n) in ((kops, nk), (vops, nv)):
+        for name, t in side[1:]:
+            if t.size(1) != n:
+                raise ValueError("%s has %d columns, %s has %d" % (name, t.size(1), side[0][0], n))
     _mh_widths(nk, nv, heads)
-    cap = BWD_WIDTH_CAP[first.element_size()]
-    if nk // heads > cap or nv // heads > cap:
-        raise ValueError("the fused backward takes at most %d columns%s in %s (nk = %d, nv = %d)"
-                         % (cap, "" if heads == 1 else " per head", first.dtype, nk // heads, nv // heads))
+    if cap:
+        cap = BWD_WIDTH_CAP[first.element_size()]
+        if nk // heads > cap or nv // heads > cap:
+            raise ValueError("the fused backward takes at most %d columns%s in %s (nk = %d, nv = %d)"
+                             % (cap, "" if heads == 1 else " per head", first.dtype, nk // heads, nv // heads))
     return nk, nv, scale, int(bool(bias))
 
 
-def _bwd_on_device(named):
+def _attention_on_device(named):
     """... and, after every shape check, all of them on the first's device (all pointers are device pointers)"""
     head, first = named[0]
     for name, t in named:

@@ -271,19 +271,6 @@ int crp_sddmm_csr_f32(crp_csr_dev_p A, int, const float *X, long long, const flo
     live_csr(A);
     return kernel("sddmm_csr_f32", s, {R{A}, R{X}, R{A->b0 ? Y0 : NULL}, R{A->b1 ? Y1 : NULL}, R{pos}}, {W{out}});
 }
-int crp_attention_csr_f64(crp_csr_dev_p A, int, int, double, int, const double *Q, long long, const double *K0, long long, const double *K1,
-                          long long, const double *V0, long long, const double *V1, long long, double *O, long long, double *lse, double *p_out,
-                          const int *pos, void *s)
-{
-    live_csr(A);
-    return kernel("attention_csr_f64", s, {R{A}, R{Q}, R{A->b0 ? K0 : NULL}, R{A->b1 ? K1 : NULL}, R{A->b0 ? V0 : NULL}, R{A->b1 ? V1 : NULL}, R{pos}}, {W{O}, W{lse}, W{p_out}});
-}
-int crp_attention_csr_f32(crp_csr_dev_p A, int, int, double, int, const float *Q, long long, const float *K0, long long, const float *K1, long long,
-                          const float *V0, long long, const float *V1, long long, float *O, long long, float *lse, float *p_out, const int *pos, void *s)
-{
-    live_csr(A);
-    return kernel("attention_csr_f32", s, {R{A}, R{Q}, R{A->b0 ? K0 : NULL}, R{A->b1 ? K1 : NULL}, R{A->b0 ? V0 : NULL}, R{A->b1 ? V1 : NULL}, R{pos}}, {W{O}, W{lse}, W{p_out}});
-}
 int crp_row_softmax_f64(int, const int *rp, const double *x, double *y, void *s)
 {
     CHECK(in_device(rp, 4), "row pointer");
@@ -334,26 +321,41 @@ int crp_sum_segments_f64(int, long long, const double *src, long long, double *o
 int crp_sum_segments_f32(int, long long, const float *src, long long, float *out, void *s) { return kernel("sum_segments_f32", s, {R{src}}, {W{out}}); }
 int crp_transpose_f64(int, int, const double *src, long long, double *dst, long long, void *s) { return kernel("transpose_f64", s, {R{src}}, {W{dst}}); }
 int crp_transpose_f32(int, int, const float *src, long long, float *dst, long long, void *s) { return kernel("transpose_f32", s, {R{src}}, {W{dst}}); }
-// the fused attention backward (csrc/rp_attention_bwd.cpp; tests/host_engine_resources.cpp does not link it)
-#define BWD_Q_STANDIN(NAME, T)                                                                                                              \
-    int NAME(crp_csr_dev_p A, int, int, double, int, const T *Q, long long, const T *K0, long long, const T *K1, long long, const T *V0,    \
-             long long, const T *V1, long long, const T *O, long long, const T *dO, long long, const T *lse, T *dQ, long long, T *delta,     \
-             T *ds_out, const int *pos, void *s)                                                                                            \
+// the fused attention and its backward (csrc/rp_attention.cpp); the variadic part is the multi-head calls' `int heads,` after the handle
+#define FWD_STANDIN(NAME, T, ...)                                                                                                           \
+    int NAME(crp_csr_dev_p A, __VA_ARGS__ int, int, double, int, const T *Q, long long, const T *K0, long long, const T *K1, long long,     \
+             const T *V0, long long, const T *V1, long long, T *O, long long, T *lse, T *p_out, const int *pos, void *s)                    \
+    {                                                                                                                                       \
+        live_csr(A);                                                                                                                        \
+        return kernel(#NAME + 4, s, {R{A}, R{Q}, R{A->b0 ? K0 : NULL}, R{A->b1 ? K1 : NULL}, R{A->b0 ? V0 : NULL}, R{A->b1 ? V1 : NULL}, R{pos}}, {W{O}, W{lse}, W{p_out}});   \
+    }
+#define BWD_Q_STANDIN(NAME, T, ...)                                                                                                         \
+    int NAME(crp_csr_dev_p A, __VA_ARGS__ int, int, double, int, const T *Q, long long, const T *K0, long long, const T *K1, long long,     \
+             const T *V0, long long, const T *V1, long long, const T *O, long long, const T *dO, long long, const T *lse, T *dQ, long long, \
+             T *delta, T *ds_out, const int *pos, void *s)                                                                                  \
     {                                                                                                                                       \
         live_csr(A);                                                                                                                        \
         return kernel(#NAME + 4, s, {R{A}, R{Q}, R{A->b0 ? K0 : NULL}, R{A->b1 ? K1 : NULL}, R{A->b0 ? V0 : NULL}, R{A->b1 ? V1 : NULL}, R{O}, R{dO}, R{lse}, R{pos}}, {W{dQ}, W{delta}, W{ds_out}});   \
     }
-#define BWD_KV_STANDIN(NAME, T)                                                                                                             \
-    int NAME(crp_csr_dev_p At, int, int, double, int, const T *K, long long, const T *V, long long, const T *Q, long long, const T *dO,     \
-             long long, const T *lse, const T *delta, T *dK, long long, T *dV, long long, void *s)                                          \
+#define BWD_KV_STANDIN(NAME, T, ...)                                                                                                        \
+    int NAME(crp_csr_dev_p At, __VA_ARGS__ int, int, double, int, const T *K, long long, const T *V, long long, const T *Q, long long,      \
+             const T *dO, long long, const T *lse, const T *delta, T *dK, long long, T *dV, long long, void *s)                             \
     {                                                                                                                                       \
         live_csr(At);                                                                                                                       \
         return kernel(#NAME + 4, s, {R{At}, R{K}, R{V}, R{Q}, R{dO}, R{lse}, R{delta}}, {W{dK}, W{dV}});                                    \
     }
+FWD_STANDIN(crp_attention_csr_f64, double)
+FWD_STANDIN(crp_attention_csr_f32, float)
+FWD_STANDIN(crp_attention_mh_csr_f64, double, int,)
+FWD_STANDIN(crp_attention_mh_csr_f32, float, int,)
 BWD_Q_STANDIN(crp_attention_bwd_q_csr_f64, double)
 BWD_Q_STANDIN(crp_attention_bwd_q_csr_f32, float)
+BWD_Q_STANDIN(crp_attention_bwd_q_mh_csr_f64, double, int,)
+BWD_Q_STANDIN(crp_attention_bwd_q_mh_csr_f32, float, int,)
 BWD_KV_STANDIN(crp_attention_bwd_kv_csr_f64, double)
 BWD_KV_STANDIN(crp_attention_bwd_kv_csr_f32, float)
+BWD_KV_STANDIN(crp_attention_bwd_kv_mh_csr_f64, double, int,)
+BWD_KV_STANDIN(crp_attention_bwd_kv_mh_csr_f32, float, int,)
 }
 
 static void check_balanced(const char *what)

@@ -134,6 +134,16 @@ template <class T> static void dense_ops(crp_rp_spmm_p e, const Matrix &A, int l
     if (which == 2) attention(e, layout, 0.5, 1, Q.data(), ld, B.data(), ld, V.data(), ld, C.data(), ld, lse.data(), out.data(), NULL);
 }
 
+// the multi-head attention with host operands: N heads of one column each, lse and p_out with an entry per head
+template <class T> static void attention_mh(crp_rp_spmm_p e, const Matrix &A, int layout,
+                                            void (*call)(crp_rp_spmm_p, int, int, double, int, const T *, long long, const T *, long long, const T *,
+                                                         long long, T *, long long, T *, T *, void *))
+{
+    const int m = A.m, ld = layout == 0 ? N : m, heads = N;
+    std::vector<T> K((size_t) m * N, (T) 1), O((size_t) m * N), Q(K), V(K), lse((size_t) m * heads + 1), out(A.va.size() * heads + 1);
+    call(e, layout, heads, 0.5, 1, Q.data(), ld, K.data(), ld, V.data(), ld, O.data(), ld, lse.data(), out.data(), NULL);
+}
+
 // every operation once per dtype (the dense ones with host operands in both layouts); dev_update_first: the first device value
 // update comes before the first exec_t (its scratch for the transposed matrices is then built by the second one) or after it
 static void full_engine(const Matrix &A, bool dev_update_first)
@@ -176,6 +186,11 @@ static void full_engine(const Matrix &A, bool dev_update_first)
     {
         dense_ops<double>(e, A, layout, nullptr, nullptr, crp_rp_spmm_attention_ex, 2);
         dense_ops<float>(e, A, layout, nullptr, nullptr, crp_rp_spmm_attention_f32_ex, 2);
+    }
+    for (int layout = 0; layout < 2; layout++)
+    {
+        attention_mh<double>(e, A, layout, crp_rp_spmm_attention_mh_ex);
+        attention_mh<float>(e, A, layout, crp_rp_spmm_attention_mh_f32_ex);
     }
     // device operands with timing off: the exec returns asynchronously and leaves its event behind
     {

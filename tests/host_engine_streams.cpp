@@ -1,4 +1,4 @@
-// The ORDER of the row-parallel engine's device work across streams (csrc/rp_engine.cpp, csrc/rp_attention_bwd.cpp), checked on the
+// The ORDER of the row-parallel engine's device work across streams (csrc/rp_engine.cpp, csrc/rp_attention.cpp), checked on the
 // CPU under AddressSanitizer / UBSan; built and run by tests/test_host_sanitizers.py.  The device ABI is the set of host stand-ins of
 // tests/host_device_standins.h, which log every call as (call, stream, buffers read, buffers written) and every event record and wait.
 // A single-threaded fake communicator plays rank 0 of 2: it answers the plan's alltoall_i32 / alltoallv_i32 with fabricated but
@@ -139,7 +139,7 @@ int main()
     {
         Dev<double> B((size_t) m * N), C((size_t) m * N), X((size_t) m * N), Ct((size_t) m * N), out(nnz), Q((size_t) m * N), K((size_t) m * N),
             V((size_t) m * N), O((size_t) m * N), lse(m), p(nnz), dO((size_t) m * N), dQ((size_t) m * N), dK((size_t) m * N), dV((size_t) m * N),
-            ds(nnz), vals(nnz), vals2(nnz);
+            ds(nnz), vals(nnz), vals2(nnz), lse_mh((size_t) m * N), p_mh(nnz * N), ds_mh(nnz * N);      // (_mh: N heads of one column)
         Dev<float> Bf((size_t) m * N), Cf((size_t) m * N), Xf((size_t) m * N), outf(nnz), valsf(nnz);
         // what the caller wrote before: on the caller's stream (the engine must order its other streams after it)
         for (double *b : {B.p, X.p, Q.p, K.p, V.p, dO.p, vals.p}) crp_dev_memset(b, 0, 8, caller);
@@ -153,6 +153,8 @@ int main()
             crp_rp_spmm_sddmm_f32_ex(e, 0, Xf.p, N, Bf.p, N, outf.p, 1, s);
             crp_rp_spmm_attention_ex(e, 0, 0.5, 1, Q.p, N, K.p, N, V.p, N, O.p, N, lse.p, p.p, s);
             crp_rp_spmm_attention_bwd_ex(e, 0.5, 1, Q.p, N, K.p, N, V.p, N, O.p, N, dO.p, N, lse.p, dQ.p, N, dK.p, N, dV.p, N, ds.p, s);
+            crp_rp_spmm_attention_mh_ex(e, 0, N, 0.5, 1, Q.p, N, K.p, N, V.p, N, O.p, N, lse_mh.p, p_mh.p, s);
+            crp_rp_spmm_attention_bwd_mh_ex(e, N, 0.5, 1, Q.p, N, K.p, N, V.p, N, O.p, N, dO.p, N, lse_mh.p, dQ.p, N, dK.p, N, dV.p, N, ds_mh.p, s);
         };
         round_of_calls(caller);                                  // the first calls build what they need
         round_of_calls(caller);                                  // steady state

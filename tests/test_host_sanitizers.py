@@ -50,7 +50,7 @@ def test_engine_resources_under_asan_ubsan(tmp_path):
     if gxx is None:
         pytest.skip("no g++")
     src = os.path.join(ROOT, "crp-spmm_amd", "csrc")
-    files = [os.path.join(src, f) for f in ("rp_engine.cpp", "para2d_engine.cpp", "knobs.cpp", "host_support.cpp")]
+    files = [os.path.join(src, f) for f in ("rp_engine.cpp", "rp_attention.cpp", "para2d_engine.cpp", "knobs.cpp", "host_support.cpp")]
     exe = str(tmp_path / "host_engine_resources")
     cmd = [gxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
            "-fno-omit-frame-pointer", "-pthread", "-I" + os.path.join(ROOT, "include"), "-I" + src,
@@ -74,7 +74,7 @@ def test_engine_stream_order_under_asan_ubsan(tmp_path):
     if gxx is None:
         pytest.skip("no g++")
     src = os.path.join(ROOT, "crp-spmm_amd", "csrc")
-    files = [os.path.join(src, f) for f in ("rp_engine.cpp", "rp_attention_bwd.cpp", "knobs.cpp", "host_support.cpp")]
+    files = [os.path.join(src, f) for f in ("rp_engine.cpp", "rp_attention.cpp", "knobs.cpp", "host_support.cpp")]
     exe = str(tmp_path / "host_engine_streams")
     cmd = [gxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
            "-fno-omit-frame-pointer", "-pthread", "-I" + os.path.join(ROOT, "include"), "-I" + src,
