@@ -104,6 +104,14 @@ _ATTENTION_ARGS = {
 }
 _ATTENTION_SIGNATURES = {"crp_%s%s_csr_%s" % (stem, mh, dt): (_I, args[:1] + [_I] * len(mh[:1]) + args[1:])
                          for mh in ("", "_mh") for stem, args in _ATTENTION_ARGS.items() for dt in ("f64", "f32")}
+# ... and of the fused GAT attention: (handle, heads, dv, slope, bias, ...), shared by f64 and f32
+_GAT_ARGS = {
+    "gat_attention": [_V, _I, _I, C.c_double, _I, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _V, _V, _V],
+    "gat_attention_bwd_row": [_V, _I, _I, C.c_double, _I, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _V, _LL, _V, _V,
+                              _V, _V],
+    "gat_attention_bwd_col": [_V, _I, _I, C.c_double, _I, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _V, _V, _LL, _V, _LL, _V],
+}
+_GAT_SIGNATURES = {"crp_%s_csr_%s" % (stem, dt): (_I, args) for stem, args in _GAT_ARGS.items() for dt in ("f64", "f32")}
 
 # name -> (restype, argtypes); every symbol declared in include/crpspmm_hip.h,
 # include/crp_comm.h, include/crp_engine.h, include/utils.h, include/spmat_part.h,
@@ -178,6 +186,7 @@ SIGNATURES = {
     "crp_sddmm_csr_f64": (_I, [_V, _I, _V, _LL, _V, _LL, _V, _LL, _V, _V, _I, _V]),
     "crp_sddmm_csr_f32": (_I, [_V, _I, _V, _LL, _V, _LL, _V, _LL, _V, _V, _I, _V]),
     **_ATTENTION_SIGNATURES,
+    **_GAT_SIGNATURES,
     "crp_row_softmax_f64": (_I, [_I, _V, _V, _V, _V]),
     "crp_row_softmax_f32": (_I, [_I, _V, _V, _V, _V]),
     "crp_row_softmax_bwd_f64": (_I, [_I, _V, _V, _V, _V, _V]),
@@ -229,6 +238,9 @@ SIGNATURES = {
     "crp_rp_spmm_attention_mh_f32_ex": (None, [_V, _I, _I, C.c_double, _I, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _V, _V]),
     "crp_rp_spmm_attention_bwd_mh_ex": (None, [_V, _I, C.c_double, _I, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _V, _LL, _V, _LL, _V, _LL, _V, _V]),
     "crp_rp_spmm_attention_bwd_mh_f32_ex": (None, [_V, _I, C.c_double, _I, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _V, _LL, _V, _LL, _V, _LL, _V, _V]),
+    "crp_rp_spmm_gat_ex": (None, [_V, _I, _I, C.c_double, _I, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _V, _V]),
+    "crp_rp_spmm_gat_f32_ex": (None, [_V, _I, _I, C.c_double, _I, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _V, _V]),
+    "crp_rp_spmm_gat_built": (_I, [_V]),
     "crp_rp_spmm_print_stat": (None, [_V]),
     "crp_rp_spmm_clear_stat": (None, [_V]),
     "crp_rp_spmm_get_plan": (None, [_V, C.POINTER(RpPlanView)]),

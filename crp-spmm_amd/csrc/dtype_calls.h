@@ -103,6 +103,19 @@ static inline int attention_bwd_kv(crp_csr_dev_p At, int heads, int d, double sc
         return crp_attention_bwd_kv_mh_csr_f32(At, heads, d, d, scale, bias, K, ldK, V, ldV, Q, ldQ, dO, lddO, lse, delta, dK, lddK, dV, lddV, s);
     return crp_attention_bwd_kv_csr_f32(At, d, d, scale, bias, K, ldK, V, ldV, Q, ldQ, dO, lddO, lse, delta, dK, lddK, dV, lddV, s);
 }
+// the fused GAT attention (additive LeakyReLU scores), forward
+static inline int gat_attention(crp_csr_dev_p A, int heads, int dv, double slope, int bias, const double *el, long long ldel, const double *er0,
+                                long long lder0, const double *er1, long long lder1, const double *V0, long long ldV0, const double *V1,
+                                long long ldV1, double *O, long long ldO, double *lse, double *p_out, const int *out_pos, void *s)
+{
+    return crp_gat_attention_csr_f64(A, heads, dv, slope, bias, el, ldel, er0, lder0, er1, lder1, V0, ldV0, V1, ldV1, O, ldO, lse, p_out, out_pos, s);
+}
+static inline int gat_attention(crp_csr_dev_p A, int heads, int dv, double slope, int bias, const float *el, long long ldel, const float *er0,
+                                long long lder0, const float *er1, long long lder1, const float *V0, long long ldV0, const float *V1,
+                                long long ldV1, float *O, long long ldO, float *lse, float *p_out, const int *out_pos, void *s)
+{
+    return crp_gat_attention_csr_f32(A, heads, dv, slope, bias, el, ldel, er0, lder0, er1, lder1, V0, ldV0, V1, ldV1, O, ldO, lse, p_out, out_pos, s);
+}
 static inline int sum_segments(int nseg, long long len, const double *src, long long stride, double *out, void *s)
 {
     return crp_sum_segments_f64(nseg, len, src, stride, out, s);

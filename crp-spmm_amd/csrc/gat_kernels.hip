@@ -1,0 +1,736 @@
+// gat_kernels.hip -- fused GAT attention over A's pattern for gfx950 (MI355X, wave64), fp64 and fp32, forward and backward.
+// For every row i, head h and entry p = (i, c_p), p in the handle's CSR order:
+//     z_p = el[i][h] + er[c_p][h]          a_p = z_p > 0 ? z_p : slope * z_p          s_p = a_p (bias: + A's current value of p)
+//     O[i]_h = sum_p softmax_p(s) * V[c_p]_h
+// -- the additive LeakyReLU score of a graph attention layer in place of the scaled dot product of attention_kernels.hip: two
+// scalars per node and head and no K.  From the scores on everything is attention_kernels.hip's: the batches of 8, the online
+// softmax, lse / p_out, the (row, head) units and the column-to-lane assignment.  No atomics, no LDS, no partial result in memory.
+//
+// OPERANDS.  heads = H >= 1 heads of nv columns each lie side by side in V / O / dO / dV: head h owns columns [h nv, (h + 1) nv).
+// el is (rows of O, H) with leading dimension ldel, read through the row map like Q; er0 / er1 are the two sources of the column
+// code exactly as V0 / V1 (c >= 0 -> row c of er0 / V0, c < 0 -> row ~c of er1 / V1).  lse, delta are (rows, H) row-major;
+// p_out, ds_out are (nnz, H): entry (pos, h) at pos * H + h with pos = out_pos[p], or p.  val[p] (bias) is shared by the heads.
+//
+// INSTANCE.  W = elements per 16 bytes, G(n) = 8, 16, 32, 64 for n <= 8 W, 16 W, 32 W, else (the SDDMM's group for a width n):
+// LPR = G(nv) lanes own the unit u = row * H + h (consecutive groups hold consecutive heads of a row).  Column j of the head's
+// slice belongs to lane (j / W) % LPR, piece (j / W) / LPR of that lane.  Forward: PV = the smallest of 1, 2, 4, 8 pieces that
+// covers nv; a wider head is processed in column blocks of 8 LPR W columns with the scores formed again for every block (same
+// bits).  Backward: PV = 1, 2 or 4, wider heads are refused by the launchers.  Operands that cannot be accessed in 16-byte pieces
+// are accessed element by element in the SAME assignment.
+//
+// SCORES.  Every lane forms the score of entry (lir & 7) of the batch itself, from one scalar load of er and the unit's el, which
+// it keeps for the row: no K walk and no butterfly.  The gather of that scalar (and of the bias value) is issued ahead of the
+// batch's V loads, and those before the exponentials.  z, a and s are rounded one by one -- gt_score compiles with contraction
+// off, so slope * z + val never becomes an FMA -- and so is dZ = dS * g ahead of its sum (gt_dz).
+//
+// FIXED ORDER.  Forward: attention_kernels.hip's, verbatim, from s on; O, lse and p_out are bit for bit what that file's order
+// gives for these scores and (dtype, nv).  Backward: p = exp(s - lse), dP = < dO[i]_h, V[c]_h > and D = < dO[i]_h, O[i]_h > as the
+// SDDMM forms a dot for (dtype, nv) (per lane FMAs in ascending j from +0, then the balanced tree over the lane number),
+// dS = p * (dP - D) (p == 0: +0), dZ = dS * g with g = z > 0 ? 1 : slope.  Row side (a handle of A): delta = D, d_el = the sum of
+// the row's dZ, one IEEE addition per entry from +0 in ascending p, ds_out = dS.  Column side (a handle of A^T): d_er = the same
+// sum in that handle's CSR order, dV[c][j] = fma(p_u, dO[i_u][j], acc) from +0 in that order.  s, p, dP, dS and dZ have the same
+// bits on both sides.  Slots of a last partial batch count as s = -inf (forward) and p = dS = dZ = +0 (backward) with the row's
+// last entry's operand rows.
+//
+// SPECIAL CASES.  attention_kernels.hip's and attention_bwd_kernels.hip's: an empty row writes +0 and lse = -inf for every head; a
+// one-entry row gives O = V[c]; s = -inf (a bias value, or z = -inf with slope > 0) is a masked edge; an all-masked row gives
+// zeros; NaN or +inf among a row's scores (slope = 0 with an infinite z is this case) leaves that row's outputs unspecified.
+// Rows with lse = -inf give +0 everywhere in the backward; delta is still written.
+//
+// ALIASING.  Column side: dV == V (exactly) is legal, a group reads its slice of V[c] whole before it writes it.  Nothing else.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <initializer_list>
+#include <type_traits>
+#include "kernels.h"
+
+namespace crp {
+
+constexpr int GT_UNR = 8;
+
+template <typename T> struct GtPiece;
+template <> struct GtPiece<double> { typedef double type __attribute__((ext_vector_type(2))); static constexpr int VW = 2; };
+template <> struct GtPiece<float>  { typedef float type __attribute__((ext_vector_type(4))); static constexpr int VW = 4; };
+
+__device__ __forceinline__ double gt_exp(double x) { return exp(x); }
+__device__ __forceinline__ float  gt_exp(float x) { return expf(x); }
+__device__ __forceinline__ double gt_log(double x) { return log(x); }
+__device__ __forceinline__ float  gt_log(float x) { return logf(x); }
+template <typename T> __device__ __forceinline__ T gt_ninf() { return -__builtin_huge_val(); }
+template <> __device__ __forceinline__ float gt_ninf<float>() { return -__builtin_huge_valf(); }
+
+template <int LPR>
+__device__ __forceinline__ int gt_bcast_i(int v, int j)
+{
+    if constexpr (LPR == 64) return __builtin_amdgcn_readlane(v, j);
+    else return __shfl(v, j, LPR);
+}
+
+// s = lrelu(el + er) (+ val): three statements, three roundings.  hipcc contracts across statements by default; here it may not.
+// *g = the derivative of the LeakyReLU at z.
+template <typename T>
+__device__ __forceinline__ T gt_score(const T el, const T er, const T slope, const bool bias, const T val, T *g)
+{
+#pragma clang fp contract(off)
+    const T z = el + er;
+    const bool pos = z > (T) 0;
+    T s = slope * z;
+    s = pos ? z : s;
+    if (bias) s = s + val;
+    *g = pos ? (T) 1 : slope;
+    return s;
+}
+// dZ = dS * g, rounded before it is added to anything
+template <typename T>
+__device__ __forceinline__ T gt_dz(const T ds, const T g)
+{
+#pragma clang fp contract(off)
+    const T dz = ds * g;
+    return dz;
+}
+
+// where the er scalar of column code c and head h lies
+template <typename T>
+__device__ __forceinline__ const T *gt_er(const int c, const int64_t h, const T *er0, const int64_t lder0, const T *er1, const int64_t lder1)
+{
+    return ((c >= 0) ? (er0 + (int64_t) c * lder0) : (er1 + (int64_t) (~c) * lder1)) + h;
+}
+
+// ---- forward ------------------------------------------------------------------------------------------------------------------
+// LPR lanes per unit (row, head); PV pieces of the accumulator per lane and V block.  VEC: 16-byte accesses; else elements.
+template <typename T, int LPR, int PV, bool VEC>
+__global__ __launch_bounds__(256) void gat_fwd_kernel(const GatArgs<T> a)
+{
+    typedef typename GtPiece<T>::type PT;
+    constexpr int VW  = GtPiece<T>::VW;
+    constexpr int RPB = 256 / LPR;
+    constexpr int UNR = GT_UNR;
+    constexpr int VC  = PV < 4 ? PV : 4;                // pieces of V per load chunk (8 VC pieces in flight)
+    constexpr int VBW = LPR * VW * PV;                  // columns of a V block
+    const int lir = threadIdx.x % LPR;                  // lane in the unit's group
+    const int64_t u = (int64_t) blockIdx.x * RPB + threadIdx.x / LPR;
+    const int64_t nh = a.heads;
+    if (u >= (int64_t) a.nrow * nh) return;
+    const int row = (int) (u / nh);
+    const int64_t h = u % nh;
+    int pb = a.rowptr[row];
+    const int pe = a.rowptr[row + 1];
+    if constexpr (LPR == 64) pb = __builtin_amdgcn_readfirstlane(pb);
+    const int nv = a.nv;
+    const int64_t orow = a.rowmap ? a.rowmap[row] : row;        // rowmap: the el and O row of every row of a row-subset matrix
+    const T ninf = gt_ninf<T>();
+    const int64_t hv = h * nv;                          // the head's first column
+    const int64_t srow = orow * nh + h;                 // the unit's entry of lse
+    T *const orp = a.O + orow * a.ldO + hv;
+
+    // this lane's piece v of block vb of O[orow]
+    auto store_o = [&](const T (*acc)[VW], const int vb) {
+#pragma unroll
+        for (int v = 0; v < PV; v++)
+        {
+            const int c = vb + (v * LPR + lir) * VW;
+            if constexpr (VEC)
+            {
+                PT t;
+#pragma unroll
+                for (int w = 0; w < VW; w++) t[w] = acc[v][w];
+                if (c < nv) *reinterpret_cast<PT *>(orp + c) = t;
+            }
+            else
+            {
+#pragma unroll
+                for (int w = 0; w < VW; w++)
+                    if (c + w < nv) orp[c + w] = acc[v][w];
+            }
+        }
+    };
+
+    if (pb >= pe)                                       // an empty row: zeros; el is not read
+    {
+        T z[PV][VW];
+#pragma unroll
+        for (int v = 0; v < PV; v++)
+#pragma unroll
+            for (int w = 0; w < VW; w++) z[v][w] = (T) 0;
+        for (int vb = 0; vb < nv; vb += VBW) store_o(z, vb);
+        if (a.lse != nullptr && lir == 0) a.lse[srow] = ninf;
+        return;
+    }
+    const T elv = a.el[orow * a.ldel + h];              // kept for the row
+    const T slope = a.slope;
+    const bool bias = a.val != nullptr;
+
+    // this lane's pieces v0 .. v0 + VC - 1 of block vb of the 8 V rows (slots past nv: column 0, not used)
+    auto load_v = [&](T (&vv)[UNR][VC][VW], const int vb, const int v0, const T *(&vrow)[UNR]) {
+#pragma unroll
+        for (int q = 0; q < UNR; q++)
+#pragma unroll
+            for (int v = 0; v < VC; v++)
+            {
+                const int c = vb + ((v0 + v) * LPR + lir) * VW;
+                if constexpr (VEC)
+                {
+                    const PT t = *reinterpret_cast<const PT *>(vrow[q] + ((c < nv) ? c : 0));
+#pragma unroll
+                    for (int w = 0; w < VW; w++) vv[q][v][w] = t[w];
+                }
+                else
+                {
+#pragma unroll
+                    for (int w = 0; w < VW; w++) vv[q][v][w] = vrow[q][(c + w < nv) ? c + w : 0];
+                }
+            }
+    };
+
+    for (int vb = 0; vb < nv; vb += VBW)
+    {
+        const bool first = vb == 0;                     // the block that writes lse and p_out
+        T m = ninf, l = (T) 0;
+        T acc[PV][VW];
+#pragma unroll
+        for (int v = 0; v < PV; v++)
+#pragma unroll
+            for (int w = 0; w < VW; w++) acc[v][w] = (T) 0;
+
+        for (int p0 = pb; p0 < pe; p0 += LPR)
+        {
+            const int my = p0 + lir;
+            const int c = (my < pe) ? a.colidx[my] : 0;
+            const int cnt = min(LPR, pe - p0);
+            for (int j = 0; j < cnt; j += UNR)
+            {
+                // the scalar of this lane's entry (lir & 7) of the batch goes out first: a tiny gather under the V loads.
+                // Indices past the row end are clamped to the row's last entry: a valid row whose score counts as -inf
+                const int mine = j + (lir & 7);
+                const int mcl = min(mine, cnt - 1);
+                const int cm = __shfl(c, mcl, LPR);
+                const T erv = *gt_er<T>(cm, h, a.er0, a.lder0, a.er1, a.lder1);
+                const T bv = bias ? a.val[p0 + mcl] : (T) 0;
+                const T *vrow[UNR];
+#pragma unroll
+                for (int q = 0; q < UNR; q++)
+                {
+                    const int cj = gt_bcast_i<LPR>(c, min(j + q, cnt - 1));
+                    vrow[q] = ((cj >= 0) ? (a.V0 + (int64_t) cj * a.ldV0) : (a.V1 + (int64_t) (~cj) * a.ldV1)) + hv;
+                }
+                // the first V pieces of the batch go out before the exponentials
+                T vv[UNR][VC][VW];
+                load_v(vv, vb, 0, vrow);
+                __builtin_amdgcn_sched_barrier(0);
+
+                T s = ninf;
+                if (mine < cnt)
+                {
+                    T g;
+                    s = gt_score<T>(elv, erv, slope, bias, bv, &g);
+                    if (first && a.p_out != nullptr && lir < UNR)
+                    {
+                        const int p = p0 + mine;
+                        a.p_out[(int64_t) (a.out_pos ? a.out_pos[p] : p) * nh + h] = s;
+                    }
+                }
+                T bm = fmax(s, __shfl_xor(s, 1, LPR));
+                bm = fmax(bm, __shfl_xor(bm, 2, LPR));
+                bm = fmax(bm, __shfl_xor(bm, 4, LPR));
+                const T mn = fmax(m, bm);
+                T f = (T) 1, e = (T) 0;
+                if (mn != ninf)                         // (else every entry so far is masked: l and acc stay 0)
+                {
+                    f = gt_exp(m - mn);
+                    e = gt_exp(s - mn);
+                }
+                m = mn;
+                T eu[UNR];
+#pragma unroll
+                for (int q = 0; q < UNR; q++) eu[q] = __shfl(e, q, LPR);
+                l = l * f;
+#pragma unroll
+                for (int q = 0; q < UNR; q++) l = l + eu[q];
+#pragma unroll
+                for (int v = 0; v < PV; v++)
+#pragma unroll
+                    for (int w = 0; w < VW; w++) acc[v][w] = acc[v][w] * f;
+#pragma unroll
+                for (int v0 = 0; v0 < PV; v0 += VC)
+                {
+                    if (v0 > 0)
+                    {
+                        load_v(vv, vb, v0, vrow);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+#pragma unroll
+                    for (int q = 0; q < UNR; q++)
+#pragma unroll
+                        for (int v = 0; v < VC; v++)
+#pragma unroll
+                            for (int w = 0; w < VW; w++) acc[v0 + v][w] = fma(eu[q], vv[q][v][w], acc[v0 + v][w]);
+                }
+            }
+        }
+
+        const bool masked = m == ninf;                  // every entry masked: zeros, not 0 / 0
+#pragma unroll
+        for (int v = 0; v < PV; v++)
+#pragma unroll
+            for (int w = 0; w < VW; w++) acc[v][w] = masked ? (T) 0 : acc[v][w] / l;
+        store_o(acc, vb);
+        if (first)
+        {
+            if (a.lse != nullptr && lir == 0) a.lse[srow] = masked ? ninf : m + gt_log(l);
+            if (a.p_out != nullptr && lir < UNR)
+                for (int p = pb + lir; p < pe; p += UNR)        // this lane's own stores
+                {
+                    const int64_t pos = (int64_t) (a.out_pos ? a.out_pos[p] : p) * nh + h;
+                    const T sv = a.p_out[pos];
+                    a.p_out[pos] = masked ? (T) 0 : gt_exp(sv - m) / l;
+                }
+        }
+    }
+}
+
+// ---- backward: the pieces (attention_bwd_kernels.hip's, without the K side) ---------------------------------------------------
+// pieces per lane and row of one load step: two by 16-byte accesses, one by elements, so that no instance spills
+template <int P, bool VEC> constexpr int gt_ch = VEC ? (P < 2 ? P : 2) : 1;
+
+template <int K0, int END, int STEP, class F>
+__device__ __forceinline__ void gt_static_for(F &&f)
+{
+    if constexpr (K0 < END)
+    {
+        f(std::integral_constant<int, K0>{});
+        gt_static_for<K0 + STEP, END, STEP>(f);
+    }
+}
+
+// The zero of gt_load8's `again`: opaque as long as nothing lets the compiler prove nv >= 0, so that the second read of a batch's
+// rows stays a load of its own (a cache hit) instead of 8 rows held in registers across the batch.
+template <int VW> __device__ __forceinline__ int gt_again(const int nv) { return VW * (int) (nv < 0); }
+
+// this lane's NP pieces of a row of n columns: piece q starts at column (q * LPR + lir) * VW; slots past n hold 0
+template <typename T, int LPR, int NP, bool VEC>
+__device__ __forceinline__ void gt_load_row(T (&x)[NP][GtPiece<T>::VW], const T *row, const int n, const int lir)
+{
+    typedef typename GtPiece<T>::type PT;
+    constexpr int VW = GtPiece<T>::VW;
+#pragma unroll
+    for (int v = 0; v < NP; v++)
+    {
+        const int c = (v * LPR + lir) * VW;
+        if constexpr (VEC)
+        {
+            PT t = {};
+            if (c < n) t = *reinterpret_cast<const PT *>(row + c);
+#pragma unroll
+            for (int w = 0; w < VW; w++) x[v][w] = t[w];
+        }
+        else
+        {
+#pragma unroll
+            for (int w = 0; w < VW; w++) x[v][w] = (c + w < n) ? row[c + w] : (T) 0;
+        }
+    }
+}
+
+// ... and the store of them (slots past n are not written)
+template <typename T, int LPR, int NP, bool VEC>
+__device__ __forceinline__ void gt_store_row(const T (&x)[NP][GtPiece<T>::VW], T *row, const int n, const int lir)
+{
+    typedef typename GtPiece<T>::type PT;
+    constexpr int VW = GtPiece<T>::VW;
+#pragma unroll
+    for (int v = 0; v < NP; v++)
+    {
+        const int c = (v * LPR + lir) * VW;
+        if constexpr (VEC)
+        {
+            PT t;
+#pragma unroll
+            for (int w = 0; w < VW; w++) t[w] = x[v][w];
+            if (c < n) *reinterpret_cast<PT *>(row + c) = t;
+        }
+        else
+        {
+#pragma unroll
+            for (int w = 0; w < VW; w++)
+                if (c + w < n) row[c + w] = x[v][w];
+        }
+    }
+}
+
+// this lane's pieces piece0 .. piece0 + CH - 1 of the 8 rows y[q] (slots past n: column 0, a valid address, not used)
+template <typename T, int LPR, int CH, bool VEC>
+__device__ __forceinline__ void gt_load8(T (&yv)[GT_UNR][CH][GtPiece<T>::VW], const T *const (&y)[GT_UNR], const int piece0, const int n,
+                                         const int lir, const int again = 0)
+{
+    typedef typename GtPiece<T>::type PT;
+    constexpr int VW = GtPiece<T>::VW;
+#pragma unroll
+    for (int q = 0; q < GT_UNR; q++)
+#pragma unroll
+        for (int v = 0; v < CH; v++)
+        {
+            const int c = ((piece0 + v) * LPR + lir) * VW;
+            if constexpr (VEC)
+            {
+                const PT t = *reinterpret_cast<const PT *>(y[q] + again + (unsigned) ((c < n) ? c : 0));
+#pragma unroll
+                for (int w = 0; w < VW; w++) yv[q][v][w] = t[w];
+            }
+            else
+            {
+#pragma unroll
+                for (int w = 0; w < VW; w++) yv[q][v][w] = (y[q] + again)[(unsigned) ((c + w < n) ? c + w : 0)];
+            }
+        }
+}
+
+// part[q] = the lane's part of < x, row y[q] > (width n, NP pieces): per step the gathers go out before the step's FMAs, which
+// run in column order (the SDDMM's chunk)
+template <typename T, int LPR, int NP, bool VEC>
+__device__ __forceinline__ void gt_dots(T (&part)[GT_UNR], const T (&x)[NP][GtPiece<T>::VW], const T *const (&y)[GT_UNR], const int n,
+                                        const int lir)
+{
+    constexpr int VW = GtPiece<T>::VW;
+    constexpr int CH = gt_ch<NP, VEC>;
+#pragma unroll
+    for (int q = 0; q < GT_UNR; q++) part[q] = (T) 0;
+    gt_static_for<0, NP, (VEC ? 2 : 1)>([&](auto kc) {
+        constexpr int K = decltype(kc)::value;
+        T yv[GT_UNR][CH][VW];
+        gt_load8<T, LPR, CH, VEC>(yv, y, K, n, lir);
+        __builtin_amdgcn_sched_barrier(0);              // every load of the step is in flight before the first FMA waits for one
+#pragma unroll
+        for (int q = 0; q < GT_UNR; q++)
+#pragma unroll
+            for (int v = 0; v < CH; v++)
+#pragma unroll
+                for (int w = 0; w < VW; w++)
+                {
+                    const int c = ((K + v) * LPR + lir) * VW + w;
+                    if (c < n) part[q] = fma(x[K + v][w], yv[q][v][w], part[q]);
+                }
+        if constexpr (!VEC) __builtin_amdgcn_sched_barrier(0);      // (by elements: the next step's loads wait, for the registers)
+    });
+}
+
+// reduce-scatter butterfly of the SDDMM: after it lane l holds entry (l & 7) of the batch summed over the group
+template <typename T, int LPR>
+__device__ __forceinline__ T gt_reduce8(const T (&part)[GT_UNR], const int lir)
+{
+    const bool b0 = (lir & 1) != 0, b1 = (lir & 2) != 0, b2 = (lir & 4) != 0;
+    T q4[4], q2[2];
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+    {
+        const T keep = b0 ? part[2 * i + 1] : part[2 * i], send = b0 ? part[2 * i] : part[2 * i + 1];
+        q4[i] = keep + __shfl_xor(send, 1, LPR);
+    }
+#pragma unroll
+    for (int i = 0; i < 2; i++)
+    {
+        const T keep = b1 ? q4[2 * i + 1] : q4[2 * i], send = b1 ? q4[2 * i] : q4[2 * i + 1];
+        q2[i] = keep + __shfl_xor(send, 2, LPR);
+    }
+    T r = (b2 ? q2[1] : q2[0]) + __shfl_xor(b2 ? q2[0] : q2[1], 4, LPR);
+#pragma unroll
+    for (int mask = 8; mask < LPR; mask <<= 1) r = r + __shfl_xor(r, mask, LPR);
+    return r;
+}
+
+// p, dS and dZ of one entry from its score, the LeakyReLU's derivative and dP (see FIXED ORDER); dead: lse == -inf
+template <typename T>
+__device__ __forceinline__ void gt_entry(const T s, const T g, const T dp, const T lse, const T delta, const bool dead, T *pp, T *ds, T *dz)
+{
+    const T e = dead ? (T) 0 : gt_exp(s - lse);
+    *pp = e;
+    *ds = (e == (T) 0) ? (T) 0 : e * (dp - delta);
+    *dz = (e == (T) 0) ? (T) 0 : gt_dz<T>(*ds, g);
+}
+
+// ---- backward, row side: delta, d_el and ds_out over a handle of A ----------------------------------------------------------------
+template <typename T, int LPR, int PV, bool VEC>
+__global__ __launch_bounds__(256) void gat_bwd_row_kernel(const GatBwdRowArgs<T> a)
+{
+    constexpr int VW  = GtPiece<T>::VW;
+    constexpr int RPB = 256 / LPR;
+    constexpr int UNR = GT_UNR;
+    const int lir = threadIdx.x % LPR;
+    const int64_t u = (int64_t) blockIdx.x * RPB + threadIdx.x / LPR;
+    const int64_t nh = a.heads;
+    if (u >= (int64_t) a.nrow * nh) return;
+    const int row = (int) (u / nh);
+    const int64_t h = u % nh;
+    int pb = a.rowptr[row];
+    const int pe = a.rowptr[row + 1];
+    if constexpr (LPR == 64) pb = __builtin_amdgcn_readfirstlane(pb);
+    const int nv = a.nv;
+    const int64_t orow = a.rowmap ? a.rowmap[row] : row;
+    const int64_t hv = h * nv;
+    const int64_t srow = orow * nh + h;                 // the unit's entry of lse and delta
+    const T ninf = gt_ninf<T>();
+
+    // D = < dO[i]_h, O[i]_h >, the SDDMM's dot for (dtype, nv); every lane of the group ends with the same bits
+    T xd[PV][VW];
+    gt_load_row<T, LPR, PV, VEC>(xd, a.dO + orow * a.lddO + hv, nv, lir);
+    T delta = (T) 0;
+    {
+        T xo[PV][VW];
+        gt_load_row<T, LPR, PV, VEC>(xo, a.O + orow * a.ldO + hv, nv, lir);
+#pragma unroll
+        for (int v = 0; v < PV; v++)
+#pragma unroll
+            for (int w = 0; w < VW; w++)
+                if ((v * LPR + lir) * VW + w < nv) delta = fma(xd[v][w], xo[v][w], delta);
+#pragma unroll
+        for (int mask = 1; mask < LPR; mask <<= 1) delta = delta + __shfl_xor(delta, mask, LPR);
+    }
+    if (lir == 0) a.delta[srow] = delta;
+
+    T *const delp = a.d_el + orow * a.ldd_el + h;
+    const T lse = a.lse[srow];
+    if (pb >= pe || lse == ninf)                        // an empty or all-masked row: +0 everywhere; el is not read
+    {
+        if (lir == 0) *delp = (T) 0;
+        if (a.ds_out != nullptr)
+            for (int p = pb + lir; p < pe; p += LPR) a.ds_out[(int64_t) (a.out_pos ? a.out_pos[p] : p) * nh + h] = (T) 0;
+        return;
+    }
+    const T elv = a.el[orow * a.ldel + h];
+    const T slope = a.slope;
+    const bool bias = a.val != nullptr;
+    T sum = (T) 0;                                      // d_el: the same bits in every lane
+
+    for (int p0 = pb; p0 < pe; p0 += LPR)
+    {
+        const int my = p0 + lir;
+        const int c = (my < pe) ? a.colidx[my] : 0;
+        const int cnt = min(LPR, pe - p0);
+        for (int j = 0; j < cnt; j += UNR)
+        {
+            // indices past the row end are clamped to the row's last entry: a valid row whose dS counts as +0
+            const int mine = j + (lir & 7);
+            const int mcl = min(mine, cnt - 1);
+            const int cm = __shfl(c, mcl, LPR);
+            const T erv = *gt_er<T>(cm, h, a.er0, a.lder0, a.er1, a.lder1);
+            const T bv = bias ? a.val[p0 + mcl] : (T) 0;
+            const T *vrow[UNR];
+#pragma unroll
+            for (int q = 0; q < UNR; q++)
+            {
+                const int cj = gt_bcast_i<LPR>(c, min(j + q, cnt - 1));
+                vrow[q] = ((cj >= 0) ? (a.V0 + (int64_t) cj * a.ldV0) : (a.V1 + (int64_t) (~cj) * a.ldV1)) + hv;
+            }
+            T pp[UNR];
+            gt_dots<T, LPR, PV, VEC>(pp, xd, vrow, nv, lir);
+            const T rp = gt_reduce8<T, LPR>(pp, lir);
+            // every lane holds the score and dP of entry (lir & 7) of the batch
+            T prob = (T) 0, ds = (T) 0, dz = (T) 0;
+            if (mine < cnt)
+            {
+                T g;
+                const T s = gt_score<T>(elv, erv, slope, bias, bv, &g);
+                gt_entry<T>(s, g, rp, lse, delta, false, &prob, &ds, &dz);
+                if (a.ds_out != nullptr && lir < UNR)
+                {
+                    const int p = p0 + mine;
+                    a.ds_out[(int64_t) (a.out_pos ? a.out_pos[p] : p) * nh + h] = ds;
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < UNR; q++) sum = sum + __shfl(dz, q, LPR);
+        }
+    }
+    if (lir == 0) *delp = sum;
+}
+
+// ---- backward, column side: d_er and dV over a handle of A^T (the unit is (column c, head h)) ----------------------------------
+template <typename T, int LPR, int PV, bool VEC>
+__global__ __launch_bounds__(256) void gat_bwd_col_kernel(const GatBwdColArgs<T> a)
+{
+    constexpr int VW  = GtPiece<T>::VW;
+    constexpr int RPB = 256 / LPR;
+    constexpr int UNR = GT_UNR;
+    constexpr int CV  = gt_ch<PV, VEC>;
+    const int lir = threadIdx.x % LPR;
+    const int64_t u = (int64_t) blockIdx.x * RPB + threadIdx.x / LPR;
+    const int64_t nh = a.heads;
+    if (u >= (int64_t) a.nrow * nh) return;
+    const int row = (int) (u / nh);
+    const int64_t h = u % nh;
+    int pb = a.rowptr[row];
+    const int pe = a.rowptr[row + 1];
+    if constexpr (LPR == 64) pb = __builtin_amdgcn_readfirstlane(pb);
+    const int nv = a.nv;
+    const int64_t crow = a.rowmap ? a.rowmap[row] : row;
+    const T ninf = gt_ninf<T>();
+    const int64_t hv = h * nv;
+    T *const dvrow = a.dV + crow * a.lddV + hv;
+    T *const derp = a.d_er + crow * a.ldd_er + h;
+
+    T accV[PV][VW];
+#pragma unroll
+    for (int v = 0; v < PV; v++)
+#pragma unroll
+        for (int w = 0; w < VW; w++) accV[v][w] = (T) 0;
+    if (pb >= pe)                                       // a column no row names: +0; its er and V row are not read
+    {
+        gt_store_row<T, LPR, PV, VEC>(accV, dvrow, nv, lir);
+        if (lir == 0) *derp = (T) 0;
+        return;
+    }
+    // er[c][h] and V[c]_h whole, before anything of this unit is written (dV == V)
+    T xv[PV][VW];
+    gt_load_row<T, LPR, PV, VEC>(xv, a.V + crow * a.ldV + hv, nv, lir);
+    const T erv = a.er[crow * a.lder + h];
+    const T slope = a.slope;
+    const bool bias = a.val != nullptr;
+    const int again = gt_again<VW>(a.nv);
+    T sum = (T) 0;                                      // d_er: the same bits in every lane
+
+    for (int p0 = pb; p0 < pe; p0 += LPR)
+    {
+        const int my = p0 + lir;
+        const int c = (my < pe) ? a.colidx[my] : 0;
+        const int cnt = min(LPR, pe - p0);
+        for (int j = 0; j < cnt; j += UNR)
+        {
+            const int mine = j + (lir & 7);
+            const int mcl = min(mine, cnt - 1);
+            const int64_t im = __shfl(c, mcl, LPR);     // the row of A of this lane's entry
+            const T elv = a.el[im * a.ldel + h];
+            const T lse = a.lse[im * nh + h];
+            const T dl = a.delta[im * nh + h];
+            const T bv = bias ? a.val[p0 + mcl] : (T) 0;
+            const T *drow[UNR];
+#pragma unroll
+            for (int q = 0; q < UNR; q++)
+            {
+                const int ij = gt_bcast_i<LPR>(c, min(j + q, cnt - 1));
+                drow[q] = a.dO + (int64_t) ij * a.lddO + hv;
+            }
+            T pp[UNR];
+            gt_dots<T, LPR, PV, VEC>(pp, xv, drow, nv, lir);
+            const T rp = gt_reduce8<T, LPR>(pp, lir);
+            T prob = (T) 0, ds = (T) 0, dz = (T) 0;
+            if (mine < cnt)
+            {
+                T g;
+                const T s = gt_score<T>(elv, erv, slope, bias, bv, &g);
+                gt_entry<T>(s, g, rp, lse, dl, lse == ninf, &prob, &ds, &dz);
+            }
+            T cp[UNR];
+#pragma unroll
+            for (int q = 0; q < UNR; q++)
+            {
+                sum = sum + __shfl(dz, q, LPR);
+                cp[q] = __shfl(prob, q, LPR);
+            }
+            gt_static_for<0, PV, (VEC ? 2 : 1)>([&](auto kc) {
+                constexpr int K = decltype(kc)::value;
+                T dv[UNR][CV][VW];
+                gt_load8<T, LPR, CV, VEC>(dv, drow, K, nv, lir, again);        // (cache hits: the dots read these rows)
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int q = 0; q < UNR; q++)
+#pragma unroll
+                    for (int v = 0; v < CV; v++)
+#pragma unroll
+                        for (int w = 0; w < VW; w++) accV[K + v][w] = fma(cp[q], dv[q][v][w], accV[K + v][w]);
+                if constexpr (!VEC) __builtin_amdgcn_sched_barrier(0);
+            });
+        }
+    }
+    gt_store_row<T, LPR, PV, VEC>(accV, dvrow, nv, lir);
+    if (lir == 0) *derp = sum;
+}
+
+// ---- launchers ----------------------------------------------------------------------------------------------------------------
+static inline bool gt_aligned(std::initializer_list<const void *> ptrs, std::initializer_list<int64_t> lds, int vw)
+{
+    uintptr_t bits = 0;
+    for (const void *p : ptrs) bits |= (uintptr_t) p;
+    bool ok = bits % 16 == 0;
+    for (int64_t ld : lds) ok = ok && ld % vw == 0;
+    return ok;
+}
+
+// the grid of nrow * heads units, RPB per block; false when it does not fit one launch (before anything is written)
+static inline bool gt_grid(int nrow, int heads, int rpb, dim3 *grid)
+{
+    const int64_t blocks = ((int64_t) nrow * heads + rpb - 1) / rpb;
+    if (blocks > INT32_MAX) return false;
+    *grid = dim3((unsigned) blocks);
+    return true;
+}
+
+// (nv % VW == 0 keeps every head's slice on a 16-byte boundary; the leading dimension of a source that is NULL is not read)
+template <typename T, int LPR, int PV>
+static hipError_t launch_gat(const GatArgs<T> &a, hipStream_t s)
+{
+    constexpr int VW = GtPiece<T>::VW;
+    const bool vec = gt_aligned({a.V0, a.V1, a.O}, {a.nv, a.ldO, a.V0 ? a.ldV0 : 0, a.V1 ? a.ldV1 : 0}, VW);
+    dim3 grid;
+    if (!gt_grid(a.nrow, a.heads, 256 / LPR, &grid)) return hipErrorInvalidValue;
+    if (vec) hipLaunchKernelGGL((gat_fwd_kernel<T, LPR, PV, true>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((gat_fwd_kernel<T, LPR, PV, false>), grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+template <typename T, int LPR, int PV>
+static hipError_t launch_gat(const GatBwdRowArgs<T> &a, hipStream_t s)
+{
+    constexpr int VW = GtPiece<T>::VW;
+    const bool vec = gt_aligned({a.V0, a.V1, a.O, a.dO}, {a.nv, a.ldO, a.lddO, a.V0 ? a.ldV0 : 0, a.V1 ? a.ldV1 : 0}, VW);
+    dim3 grid;
+    if (!gt_grid(a.nrow, a.heads, 256 / LPR, &grid)) return hipErrorInvalidValue;
+    if (vec) hipLaunchKernelGGL((gat_bwd_row_kernel<T, LPR, PV, true>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((gat_bwd_row_kernel<T, LPR, PV, false>), grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+template <typename T, int LPR, int PV>
+static hipError_t launch_gat(const GatBwdColArgs<T> &a, hipStream_t s)
+{
+    constexpr int VW = GtPiece<T>::VW;
+    const bool vec = gt_aligned({a.V, a.dO, a.dV}, {a.nv, a.ldV, a.lddO, a.lddV}, VW);
+    dim3 grid;
+    if (!gt_grid(a.nrow, a.heads, 256 / LPR, &grid)) return hipErrorInvalidValue;
+    if (vec) hipLaunchKernelGGL((gat_bwd_col_kernel<T, LPR, PV, true>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((gat_bwd_col_kernel<T, LPR, PV, false>), grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+// The instance, from (dtype, nv) alone (the rule is stated at the top of this file)
+template <typename T>
+static hipError_t gat_fwd(const GatArgs<T> &a, hipStream_t s)
+{
+    constexpr int W = 16 / (int) sizeof(T);
+    if (a.nrow <= 0) return hipSuccess;
+    if (a.nv <= 8 * W)   return launch_gat<T, 8, 1>(a, s);
+    if (a.nv <= 16 * W)  return launch_gat<T, 16, 1>(a, s);
+    if (a.nv <= 32 * W)  return launch_gat<T, 32, 1>(a, s);
+    if (a.nv <= 64 * W)  return launch_gat<T, 64, 1>(a, s);
+    if (a.nv <= 128 * W) return launch_gat<T, 64, 2>(a, s);
+    if (a.nv <= 256 * W) return launch_gat<T, 64, 4>(a, s);
+    return launch_gat<T, 64, 8>(a, s);
+}
+template <typename T, class Args>
+static hipError_t gat_bwd(const Args &a, hipStream_t s)
+{
+    constexpr int W = 16 / (int) sizeof(T), CAP = ATTN_BWD_MAX_PIECES * 64 * W;
+    if (a.nv > CAP) return hipErrorInvalidValue;         // (the entry points refuse these before they come here)
+    if (a.nrow <= 0) return hipSuccess;
+    if (a.nv <= 8 * W)   return launch_gat<T, 8, 1>(a, s);
+    if (a.nv <= 16 * W)  return launch_gat<T, 16, 1>(a, s);
+    if (a.nv <= 32 * W)  return launch_gat<T, 32, 1>(a, s);
+    if (a.nv <= 64 * W)  return launch_gat<T, 64, 1>(a, s);
+    if (a.nv <= 128 * W) return launch_gat<T, 64, 2>(a, s);
+    return launch_gat<T, 64, 4>(a, s);
+}
+
+hipError_t gat_attention_rm(const GatArgs<double> &a, hipStream_t s) { return gat_fwd<double>(a, s); }
+hipError_t gat_attention_rm(const GatArgs<float> &a, hipStream_t s) { return gat_fwd<float>(a, s); }
+hipError_t gat_attention_bwd_row(const GatBwdRowArgs<double> &a, hipStream_t s) { return gat_bwd<double>(a, s); }
+hipError_t gat_attention_bwd_row(const GatBwdRowArgs<float> &a, hipStream_t s) { return gat_bwd<float>(a, s); }
+hipError_t gat_attention_bwd_col(const GatBwdColArgs<double> &a, hipStream_t s) { return gat_bwd<double>(a, s); }
+hipError_t gat_attention_bwd_col(const GatBwdColArgs<float> &a, hipStream_t s) { return gat_bwd<float>(a, s); }
+
+}  // namespace crp

@@ -516,6 +516,83 @@ static int attention_bwd_kv_csr(crp_csr_dev *At, int nk, int nv, double scale, i
     return (int) crp::attention_bwd_kv(a, mh, s);
 }
 
+// ---- the fused GAT attention (gat_kernels.hip), one dtype.  Every argument is checked before anything is launched or allocated: a
+// negative return has written nothing.  dv: the width of one head.
+static int gat_check(const crp_csr_dev *A, int heads, int dv, double slope, int bias, const void *el, long long ldel, const void *er0,
+                     long long lder0, const void *er1, long long lder1, const void *V0, long long ldV0, const void *V1, long long ldV1,
+                     const void *O, long long ldO)
+{
+    if (A == NULL || el == NULL || O == NULL) return -1;
+    if (heads < 1 || dv < 1 || (bias != 0 && bias != 1) || !std::isfinite(slope)) return -1;
+    if ((er0 == NULL || V0 == NULL) && A->b0_rows > 0) return -1;       // a column code names the first source
+    if ((er1 == NULL || V1 == NULL) && A->b1_rows > 0) return -1;       // a column code names the second source
+    const long long wv = (long long) heads * dv;
+    if (ldel < heads || ldO < wv) return -4;
+    if ((er0 != NULL && lder0 < heads) || (er1 != NULL && lder1 < heads) || (V0 != NULL && ldV0 < wv) || (V1 != NULL && ldV1 < wv)) return -4;
+    return 0;
+}
+template <class T>
+static int gat_fwd_csr(crp_csr_dev *A, int heads, int dv, double slope, int bias, const T *el, long long ldel, const T *er0, long long lder0,
+                       const T *er1, long long lder1, const T *V0, long long ldV0, const T *V1, long long ldV1, T *O, long long ldO, T *lse,
+                       T *p_out, const int *out_pos, hipStream_t s)
+{
+    int rc = gat_check(A, heads, dv, slope, bias, el, ldel, er0, lder0, er1, lder1, V0, ldV0, V1, ldV1, O, ldO);
+    if (rc != 0 || A->nrow == 0) return rc;
+    crp::GatArgs<T> a;
+    rc = attention_bias_values<T>(A, bias, s, &a.val);
+    if (rc != 0) return rc;
+    a.nrow = A->nrow; a.nv = dv; a.heads = heads; a.rowptr = A->rowptr; a.colidx = A->colidx; a.slope = (T) slope;
+    a.el = el; a.ldel = ldel; a.er0 = er0; a.lder0 = lder0; a.er1 = er1; a.lder1 = lder1;
+    a.V0 = V0; a.ldV0 = ldV0; a.V1 = V1; a.ldV1 = ldV1;
+    a.O = O; a.ldO = ldO; a.lse = lse; a.p_out = p_out; a.rowmap = A->rowmap; a.out_pos = out_pos;
+    return (int) crp::gat_attention_rm(a, s);
+}
+template <class T>
+static int gat_bwd_row_csr(crp_csr_dev *A, int heads, int dv, double slope, int bias, const T *el, long long ldel, const T *er0, long long lder0,
+                           const T *er1, long long lder1, const T *V0, long long ldV0, const T *V1, long long ldV1, const T *O, long long ldO,
+                           const T *dO, long long lddO, const T *lse, T *d_el, long long ldd_el, T *delta, T *ds_out, const int *out_pos,
+                           hipStream_t s)
+{
+    int rc = gat_check(A, heads, dv, slope, bias, el, ldel, er0, lder0, er1, lder1, V0, ldV0, V1, ldV1, O, ldO);
+    if (rc == 0 && (dO == NULL || lse == NULL || d_el == NULL || delta == NULL)) rc = -1;
+    if (rc == 0 && (lddO < (long long) heads * dv || ldd_el < heads)) rc = -4;
+    constexpr int cap = crp::ATTN_BWD_MAX_PIECES * 64 * (16 / (int) sizeof(T));
+    if (rc == 0 && dv > cap) rc = CRP_ATTN_BWD_EWIDTH;
+    if (rc != 0 || A->nrow == 0) return rc;
+    crp::GatBwdRowArgs<T> a;
+    rc = attention_bias_values<T>(A, bias, s, &a.val);
+    if (rc != 0) return rc;
+    a.nrow = A->nrow; a.nv = dv; a.heads = heads; a.rowptr = A->rowptr; a.colidx = A->colidx; a.slope = (T) slope;
+    a.el = el; a.ldel = ldel; a.er0 = er0; a.lder0 = lder0; a.er1 = er1; a.lder1 = lder1;
+    a.V0 = V0; a.ldV0 = ldV0; a.V1 = V1; a.ldV1 = ldV1;
+    a.O = O; a.ldO = ldO; a.dO = dO; a.lddO = lddO; a.lse = lse; a.d_el = d_el; a.ldd_el = ldd_el; a.delta = delta; a.ds_out = ds_out;
+    a.rowmap = A->rowmap; a.out_pos = out_pos;
+    return (int) crp::gat_attention_bwd_row(a, s);
+}
+template <class T>
+static int gat_bwd_col_csr(crp_csr_dev *At, int heads, int dv, double slope, int bias, const T *er, long long lder, const T *V, long long ldV,
+                           const T *el, long long ldel, const T *dO, long long lddO, const T *lse, const T *delta, T *d_er, long long ldd_er,
+                           T *dV, long long lddV, hipStream_t s)
+{
+    if (At == NULL || er == NULL || V == NULL || d_er == NULL || dV == NULL) return -1;
+    if (heads < 1 || dv < 1 || (bias != 0 && bias != 1) || !std::isfinite(slope)) return -1;
+    if (At->b1_rows > 0) return -1;                      // a code names a second source: this call takes one
+    if ((el == NULL || dO == NULL || lse == NULL || delta == NULL) && At->nnz > 0) return -1;
+    const long long wv = (long long) heads * dv;
+    if (lder < heads || ldd_er < heads || ldV < wv || lddV < wv) return -4;
+    if (At->nnz > 0 && (ldel < heads || lddO < wv)) return -4;
+    constexpr int cap = crp::ATTN_BWD_MAX_PIECES * 64 * (16 / (int) sizeof(T));
+    if (dv > cap) return CRP_ATTN_BWD_EWIDTH;
+    if (At->nrow == 0) return 0;
+    crp::GatBwdColArgs<T> a;
+    const int rc = attention_bias_values<T>(At, bias, s, &a.val);
+    if (rc != 0) return rc;
+    a.nrow = At->nrow; a.nv = dv; a.heads = heads; a.rowptr = At->rowptr; a.colidx = At->colidx; a.slope = (T) slope;
+    a.er = er; a.lder = lder; a.V = V; a.ldV = ldV; a.el = el; a.ldel = ldel; a.dO = dO; a.lddO = lddO; a.lse = lse; a.delta = delta;
+    a.d_er = d_er; a.ldd_er = ldd_er; a.dV = dV; a.lddV = lddV; a.rowmap = At->rowmap;
+    return (int) crp::gat_attention_bwd_col(a, s);
+}
+
 extern "C" {
 
 const char *crp_hip_version(void) { return "crpspmm-hip 0.1 gfx950"; }
@@ -1215,6 +1292,34 @@ int crp_attention_bwd_kv_mh_csr_f32(crp_csr_dev_p At, int heads, int dk, int dv,
     return attention_bwd_kv_csr<float>(At, dk, dv, scale, bias, K, ldK, V, ldV, Q, ldQ, dO, lddO, lse, delta, dK, lddK, dV, lddV,
                                      (hipStream_t) stream, true, heads);
 }
+
+// ---- the fused GAT attention: additive LeakyReLU scores, forward and the two-handle backward (gat_kernels.hip)
+#define CRP_GAT_ENTRY_POINTS(SFX, T)                                                                                                              \
+    int crp_gat_attention_csr_##SFX(crp_csr_dev_p A, int heads, int dv, double slope, int bias, const T *el, long long ldel, const T *er0,        \
+                                    long long lder0, const T *er1, long long lder1, const T *V0, long long ldV0, const T *V1, long long ldV1,     \
+                                    T *O, long long ldO, T *lse, T *p_out, const int *out_pos, void *stream)                                      \
+    {                                                                                                                                             \
+        return gat_fwd_csr<T>(A, heads, dv, slope, bias, el, ldel, er0, lder0, er1, lder1, V0, ldV0, V1, ldV1, O, ldO, lse, p_out, out_pos,      \
+                              (hipStream_t) stream);                                                                                              \
+    }                                                                                                                                             \
+    int crp_gat_attention_bwd_row_csr_##SFX(crp_csr_dev_p A, int heads, int dv, double slope, int bias, const T *el, long long ldel,              \
+                                            const T *er0, long long lder0, const T *er1, long long lder1, const T *V0, long long ldV0,            \
+                                            const T *V1, long long ldV1, const T *O, long long ldO, const T *dO, long long lddO, const T *lse,    \
+                                            T *d_el, long long ldd_el, T *delta, T *ds_out, const int *out_pos, void *stream)                     \
+    {                                                                                                                                             \
+        return gat_bwd_row_csr<T>(A, heads, dv, slope, bias, el, ldel, er0, lder0, er1, lder1, V0, ldV0, V1, ldV1, O, ldO, dO, lddO, lse, d_el,  \
+                                  ldd_el, delta, ds_out, out_pos, (hipStream_t) stream);                                                          \
+    }                                                                                                                                             \
+    int crp_gat_attention_bwd_col_csr_##SFX(crp_csr_dev_p At, int heads, int dv, double slope, int bias, const T *er, long long lder, const T *V, \
+                                            long long ldV, const T *el, long long ldel, const T *dO, long long lddO, const T *lse,                \
+                                            const T *delta, T *d_er, long long ldd_er, T *dV, long long lddV, void *stream)                       \
+    {                                                                                                                                             \
+        return gat_bwd_col_csr<T>(At, heads, dv, slope, bias, er, lder, V, ldV, el, ldel, dO, lddO, lse, delta, d_er, ldd_er, dV, lddV,           \
+                                  (hipStream_t) stream);                                                                                          \
+    }
+CRP_GAT_ENTRY_POINTS(f64, double)
+CRP_GAT_ENTRY_POINTS(f32, float)
+#undef CRP_GAT_ENTRY_POINTS
 
 // ---- row softmax over a CSR pattern (softmax_kernels.hip).  Every argument is checked before anything is launched.
 int crp_row_softmax_f64(int nrow, const int *rowptr, const double *s, double *y, void *stream)

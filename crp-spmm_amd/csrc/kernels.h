@@ -197,6 +197,94 @@ template <typename T> struct AttnBwdKVArgs
     int heads = 1;          // read by the multi-head instances only (attention_bwd_kv, mh)
 };
 
+// gat_kernels.hip: O[i]_h = sum_p softmax_p(lrelu(el[i][h] + er[c_p][h]) (+ val[p])) V[c_p]_h over (row, head) units
+template <typename T> struct GatArgs
+{
+    int nrow;
+    int nv;                 // columns of one head of V and O
+    int heads;
+    const int *rowptr;
+    const int *colidx;
+    const T   *val;         // the values in T (bias), or nullptr
+    T          slope;
+    const T   *el;          // (rows of O, heads)
+    int64_t    ldel;
+    const T   *er0;         // the two sources of the column code, (rows of V0 / V1, heads)
+    int64_t    lder0;
+    const T   *er1;
+    int64_t    lder1;
+    const T   *V0;
+    int64_t    ldV0;
+    const T   *V1;
+    int64_t    ldV1;
+    T         *O;
+    int64_t    ldO;
+    T         *lse;         // nullptr, or (rows, heads), indexed like the rows of O
+    T         *p_out;       // nullptr, or the probabilities, (nnz, heads)
+    const int *rowmap;      // nullptr, or the el / O row of every row (row-subset matrices)
+    const int *out_pos;     // nullptr, or where nonzero p writes: row out_pos[p] of p_out
+};
+
+// gat_kernels.hip, row side of the backward over a handle of A: delta = <dO[i]_h, O[i]_h>, d_el = sum_p dZ_p, ds_out = dS_p
+template <typename T> struct GatBwdRowArgs
+{
+    int nrow;
+    int nv;
+    int heads;
+    const int *rowptr;
+    const int *colidx;
+    const T   *val;
+    T          slope;
+    const T   *el;
+    int64_t    ldel;
+    const T   *er0;
+    int64_t    lder0;
+    const T   *er1;
+    int64_t    lder1;
+    const T   *V0;
+    int64_t    ldV0;
+    const T   *V1;
+    int64_t    ldV1;
+    const T   *O;
+    int64_t    ldO;
+    const T   *dO;
+    int64_t    lddO;
+    const T   *lse;         // (rows, heads), as the forward wrote it
+    T         *d_el;        // (rows, heads), indexed like el
+    int64_t    ldd_el;
+    T         *delta;       // (rows, heads), indexed like lse
+    T         *ds_out;      // nullptr, or dS, (nnz, heads)
+    const int *rowmap;      // nullptr, or the el / O / dO / d_el / lse / delta row of every row
+    const int *out_pos;     // nullptr, or where nonzero p writes: row out_pos[p] of ds_out
+};
+
+// gat_kernels.hip, column side over a handle of A^T (row c = column c of A): d_er[c][h] = sum_p dZ_p, dV[c]_h = sum_p p_p dO[i_p]_h
+template <typename T> struct GatBwdColArgs
+{
+    int nrow;               // rows of the transposed handle
+    int nv;
+    int heads;
+    const int *rowptr;
+    const int *colidx;      // rows of el / dO / lse / delta (one source: no negative code)
+    const T   *val;         // the transposed handle's values in T (bias), or nullptr
+    T          slope;
+    const T   *er;
+    int64_t    lder;
+    const T   *V;
+    int64_t    ldV;
+    const T   *el;
+    int64_t    ldel;
+    const T   *dO;
+    int64_t    lddO;
+    const T   *lse;
+    const T   *delta;
+    T         *d_er;
+    int64_t    ldd_er;
+    T         *dV;          // may be V exactly (a group reads its slice whole before it writes it)
+    int64_t    lddV;
+    const int *rowmap;      // nullptr, or the er / V / d_er / dV row of every row (row-subset matrices)
+};
+
 // The instance every SpMM launcher names at its hipLaunchKernelGGL, from its own template arguments ("rowgroup<16,2,1>",
 // "panel<8,2,2,a32,b1>", "team2<f64,NV1,b0,compact>", ...): a string with static storage, per host thread.  hip_api.hip copies
 // it into the handle after the product (crp_csr_dev_last_kernel); nothing else reads it.
@@ -249,6 +337,15 @@ hipError_t attention_bwd_q(const AttnBwdQArgs<double> &a, bool mh, hipStream_t s
 hipError_t attention_bwd_q(const AttnBwdQArgs<float> &a, bool mh, hipStream_t s);
 hipError_t attention_bwd_kv(const AttnBwdKVArgs<double> &a, bool mh, hipStream_t s);
 hipError_t attention_bwd_kv(const AttnBwdKVArgs<float> &a, bool mh, hipStream_t s);
+
+// gat_kernels.hip: the fused GAT attention (additive LeakyReLU scores) over (row, head) units and its two-handle backward; the
+// backward's per-head width is capped as attention_bwd's
+hipError_t gat_attention_rm(const GatArgs<double> &a, hipStream_t s);
+hipError_t gat_attention_rm(const GatArgs<float> &a, hipStream_t s);
+hipError_t gat_attention_bwd_row(const GatBwdRowArgs<double> &a, hipStream_t s);
+hipError_t gat_attention_bwd_row(const GatBwdRowArgs<float> &a, hipStream_t s);
+hipError_t gat_attention_bwd_col(const GatBwdColArgs<double> &a, hipStream_t s);
+hipError_t gat_attention_bwd_col(const GatBwdColArgs<float> &a, hipStream_t s);
 
 // softmax_kernels.hip: row softmax over a CSR pattern and its Jacobian product; rowptr entries index the value arrays directly
 hipError_t row_softmax_f64(int nrow, const int *rowptr, const double *s, double *y, hipStream_t st);

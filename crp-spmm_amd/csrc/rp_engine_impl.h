@@ -1,6 +1,6 @@
 // rp_engine_impl.h -- the row engine's state (struct crp_rp_spmm) and the helpers that its translation units share: rp_engine.cpp
-// (init, exec, exec_t, sddmm, value updates) and rp_attention.cpp (the fused attention, forward and backward, single- and
-// multi-head).  Internal: nothing outside csrc/ includes it.
+// (init, exec, exec_t, sddmm, value updates), rp_attention.cpp (the fused attention, forward and backward, single- and
+// multi-head) and rp_gat.cpp (the fused GAT attention, forward).  Internal: nothing outside csrc/ includes it.
 #ifndef CRP_RP_ENGINE_IMPL_H
 #define CRP_RP_ENGINE_IMPL_H
 
@@ -15,6 +15,16 @@
 #include "operand_view.h"
 #include "par.h"
 #include <algorithm>
+
+// The narrow exchange of the GAT attention's er (rp_gat.cpp): rows of ld elements -- `heads` of them, fp32 rows padded to whole
+// 8-byte words -- through buffers of their own, with the forward plan's per-peer counts and displacements taken by rows
+template <class T> struct GatXchg
+{
+    int heads = 0;                               // 0: not set up
+    long long ld = 0;
+    std::vector<long long> sc, sd, rc, rd;       // in 8-byte words, as alltoallv_dev_f64 takes them
+    crp::DevArray<T> recv, send;
+};
 
 struct crp_rp_spmm
 {
@@ -70,6 +80,11 @@ struct crp_rp_spmm
     crp::DevArray<float>  bw_delta32_dev;
     crp::DevArray<double> bw_delta_dev;
     size_t bw_delta32_cap = 0, bw_delta_cap = 0;        // entries; a multi-head call that needs A_nrow * heads grows its array
+    // fused GAT attention (crp_rp_spmm_gat_ex, rp_gat.cpp): the narrow exchange of er, one per dtype, set up by the first call of
+    // that dtype and again by a call with another number of heads
+    bool gt_built = false;
+    GatXchg<float>  gt_x32;
+    GatXchg<double> gt_x64;
     // row softmax (crp_rp_spmm_row_softmax_ex), uploaded by its first call: A_rowptr as a device array
     crp::DevArray<int> sm_rowptr;
     // device value updates (crp_rp_spmm_update_values_dev), allocated by its first call: the new values as fp64 in the order the

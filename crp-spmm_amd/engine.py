@@ -312,6 +312,56 @@ class RpSpmm:
         """True once an ``attention`` has allocated V's receive buffer (crp_rp_spmm_attention_built)."""
         return bool(self._lib.crp_rp_spmm_attention_built(self.handle))
 
+    def gat_attention(self, layout, el, er, V, out, slope=0.2, bias=False, lse=None, p_out=None, stream=None, heads=1):
+        """Fused GAT attention over this rank's rows of A (crp_rp_spmm_gat_ex / _f32_ex, by the operands' dtype): for every head h,
+        out[i]_h = sum_p softmax_p(leaky_relu(el[i, h] + er[c_p, h], slope) (+ the engine's current value of p with ``bias``))
+        * V[c_p]_h over the nonzeros p = (i, c_p) of row i.  V and ``out`` are this rank's loc_B_nrow x glb_n and A_nrow x glb_n
+        blocks (layouts and operands as ``exec``) with glb_n / heads columns per head; ``el`` (A_nrow, heads) and ``er``
+        (loc_B_nrow, heads) are row-major torch tensors on the device; ``lse`` (A_nrow, heads) and ``p_out`` (nnz, heads), in the
+        order of the A_val given to init, are optional contiguous arrays or tensors on the host or the device (1-D with one
+        head).  The engine's values are not changed.  Every error is raised before the library is called."""
+        import torch
+        heads = _engine_heads(heads, self.glb_n)
+        dt = _operands_dtype(V, out)
+        f32 = dt == "f32"
+        want = torch.float32 if f32 else torch.float64
+        kb = getattr(self, "loc_B_nrow", None)
+        for name, t, rows in (("el", el, self.A_nrow), ("er", er, kb)):
+            if not isinstance(t, torch.Tensor):
+                raise TypeError("%s must be a torch tensor on the device" % name)
+            if t.dtype != want:
+                raise TypeError("%s must have the dtype of V and out (%s is %s)" % (name, name, t.dtype))
+            if t.dim() != 2:
+                raise TypeError("%s must be 2-D" % name)
+            if t.shape[1] != heads or (rows is not None and t.shape[0] < rows):
+                raise ValueError("%s is %s, this rank needs (%s, %d)" % (name, tuple(t.shape), rows, heads))
+            if t.shape[1] > 1 and t.stride(1) != 1:
+                raise ValueError("%s must be contiguous along its rows" % name)
+        if bias not in (False, True, 0, 1):
+            raise ValueError("bias must be a bool, got %r" % (bias,))
+        slope = float(slope)
+        if not np.isfinite(slope):
+            raise ValueError("slope must be finite, got %r" % (slope,))
+        vp, ldv, _kv = _ptr_ld(V, layout, f32)
+        op, ldo, _ko = _ptr_ld(out, layout, f32)
+        _check_blocks(layout, self.glb_n, (("V", V, kb), ("out", out, self.A_nrow)))
+        lp, _kl = _vec_ptr("lse", _mh_vec("lse", lse, heads), f32, self.A_nrow * heads)
+        pp, _kp = _vec_ptr("p_out", _mh_vec("p_out", p_out, heads), f32, self.nnz() * heads)
+        for name, t in (("el", el), ("er", er)):
+            if not t.is_cuda:
+                raise TypeError("%s must be on the device" % name)
+        if stream is None:
+            stream = _current_stream(out)
+        if stream is None:
+            stream = _current_stream(el)
+        fn = self._lib.crp_rp_spmm_gat_f32_ex if f32 else self._lib.crp_rp_spmm_gat_ex
+        fn(self.handle, layout, heads, slope, int(bool(bias)), el.data_ptr() or None, max(el.stride(0), heads), er.data_ptr() or None,
+           max(er.stride(0), heads), vp, ldv, op, ldo, lp, pp, stream)
+
+    def gat_built(self):
+        """True once a ``gat_attention`` has set up the narrow exchange of er (crp_rp_spmm_gat_built)."""
+        return bool(self._lib.crp_rp_spmm_gat_built(self.handle))
+
     def attention_bwd(self, Q, K, V, O, dO, lse, dQ, dK, dV, scale=1.0, bias=False, ds_out=None, stream=None, heads=1):
         """The fused backward of ``attention`` over this rank's rows of A (crp_rp_spmm_attention_bwd_ex / _f32_ex, by the operands'
         dtype): with ``O`` and ``lse`` as the forward wrote them and the upstream gradient ``dO``, writes dQ (A_nrow x glb_n), dK

@@ -323,6 +323,138 @@ class CsrDev:
                    dK.stride(0), dV.data_ptr(), dV.stride(0), _stream(dK) if stream is None else stream), fn.__name__)
         return dK, dV
 
+    def gat_attention(self, el, er0, V0, er1=None, V1=None, slope=0.2, bias=False, out=None, lse=None, p_out=None, out_pos=None,
+                      stream=None, heads=1):
+        """Fused GAT attention over this matrix's pattern (crp_gat_attention_csr_f64 / _f32, by the operands' dtype): for every
+        head h, out[i]_h = sum_p softmax_p(leaky_relu(el[i, h] + er[c_p, h], slope) (+ the matrix's value of p with ``bias``))
+        * V[c_p]_h over the nonzeros p = (i, c_p) of row i; c >= 0 reads row c of er0 / V0, c < 0 row ~c of er1 / V1.  ``el`` is
+        a 2-D (rows, heads) tensor, ``er0`` / ``er1`` (rows of V0 / V1, heads), ``V0`` / ``V1`` have heads * dv columns, all
+        row-major float64 or float32 cuda tensors of one dtype; ``out`` has V's width and a row per row of ``el`` (allocated
+        when None).  Optional outputs: ``lse`` contiguous (rows, heads), ``p_out`` contiguous (nnz, heads) -- nonzero p writes
+        row out_pos[p] when ``out_pos`` (int32, nnz entries) is given; with one head both may be 1-D.  The matrix's values are
+        not changed.  Returns ``out``.  Every error is raised before the library is called."""
+        import torch
+        heads = _heads(heads)
+        if (er1 is None) != (V1 is None):
+            raise ValueError("er1 and V1 come together")
+        sops = [("el", el), ("er0", er0)] + ([("er1", er1)] if er1 is not None else [])
+        vops = [("V0", V0)] + ([("V1", V1)] if V1 is not None else []) + ([("out", out)] if out is not None else [])
+        vecs = [(n_, t) for n_, t in (("lse", lse), ("p_out", p_out)) if t is not None]
+        nv, slope, bias = _gat_operands(sops, vops, vecs, slope, bias, heads, cap=False)
+        lse, p_out = _gat_flat("lse", lse, heads), _gat_flat("p_out", p_out, heads)
+        x_nrow = getattr(self, "_x_nrow", self.nrow)
+        for name, t in (("el", el), ("out", out)):
+            if t is not None and t.size(0) < x_nrow:
+                raise ValueError("%s has %d rows, the matrix needs %d" % (name, t.size(0), x_nrow))
+        for name, t in (("er0", er0), ("V0", V0)):
+            if t.size(0) < self.ncol:
+                raise ValueError("%s has %d rows, the matrix has %d columns" % (name, t.size(0), self.ncol))
+        if er1 is not None and V1.size(0) != er1.size(0):
+            raise ValueError("er1 has %d rows, V1 %d" % (er1.size(0), V1.size(0)))
+        nnz = self.nnz
+        if lse is not None and lse.numel() < x_nrow * heads:
+            raise ValueError("lse must hold %d rows of %d heads" % (x_nrow, heads))
+        _gat_out_pos(out_pos, p_out, "p_out", nnz, heads)
+        _attention_on_device(sops + vops + [(n_, t) for n_, t in (("lse", lse), ("p_out", p_out), ("out_pos", out_pos))
+                                            if t is not None])
+        if out is None:
+            out = torch.empty((x_nrow, nv), dtype=el.dtype, device=el.device)
+        if self.nrow == 0:
+            return out
+        fn = self._lib.crp_gat_attention_csr_f32 if el.dtype == torch.float32 else self._lib.crp_gat_attention_csr_f64
+        e1p, lde1, v1p, ldv1 = (er1.data_ptr(), er1.stride(0), V1.data_ptr(), V1.stride(0)) if er1 is not None else (None, 0, None, 0)
+        ptr = lambda t: (t.data_ptr() or None) if t is not None else None
+        L.check(fn(self.handle, heads, nv // heads, slope, bias, el.data_ptr(), el.stride(0), ptr(er0), er0.stride(0), e1p, lde1,
+                   ptr(V0), V0.stride(0), v1p, ldv1, out.data_ptr(), out.stride(0), ptr(lse), ptr(p_out), ptr(out_pos),
+                   _stream(out) if stream is None else stream), fn.__name__)
+        return out
+
+    def gat_attention_bwd_row(self, el, er0, V0, O, dO, lse, er1=None, V1=None, slope=0.2, bias=False, d_el=None, delta=None,
+                              ds_out=None, out_pos=None, stream=None, heads=1):
+        """The row side of the fused backward of ``gat_attention`` (crp_gat_attention_bwd_row_csr_f64 / _f32), on the handle the
+        forward ran on: with ``O`` and ``lse`` as the forward wrote them and the upstream gradient ``dO``, delta[i, h] =
+        <dO[i]_h, O[i]_h> and d_el[i, h] = the sum over the row of dZ_p = dS_p * (z_p > 0 ? 1 : slope), dS_p = p_p (<dO[i]_h,
+        V[c_p]_h> - delta[i, h]), p_p = exp(s_p - lse[i, h]).  ``d_el`` (rows, heads) and ``delta`` contiguous (rows, heads) are
+        allocated when None; ``ds_out`` (optional, contiguous (nnz, heads)) receives dS_p -- at row out_pos[p] when ``out_pos``
+        is given -- whose sum over the heads is the gradient of the matrix's values.  No output may alias an input.  A head
+        wider than 512 (float64) / 1024 (float32) columns raises ValueError.  Returns (d_el, delta)."""
+        import torch
+        heads = _heads(heads)
+        if (er1 is None) != (V1 is None):
+            raise ValueError("er1 and V1 come together")
+        sops = [("el", el), ("er0", er0)] + ([("er1", er1)] if er1 is not None else []) + ([("d_el", d_el)] if d_el is not None else [])
+        vops = [("V0", V0)] + ([("V1", V1)] if V1 is not None else []) + [("O", O), ("dO", dO)]
+        vecs = [("lse", lse)] + [(n_, t) for n_, t in (("delta", delta), ("ds_out", ds_out)) if t is not None]
+        nv, slope, bias = _gat_operands(sops, vops, vecs, slope, bias, heads)
+        delta_given = delta
+        lse, delta, ds_out = _gat_flat("lse", lse, heads), _gat_flat("delta", delta, heads), _gat_flat("ds_out", ds_out, heads)
+        x_nrow = getattr(self, "_x_nrow", self.nrow)
+        for name, t in (("el", el), ("O", O), ("dO", dO), ("d_el", d_el)):
+            if t is not None and t.size(0) < x_nrow:
+                raise ValueError("%s has %d rows, the matrix needs %d" % (name, t.size(0), x_nrow))
+        for name, t in (("er0", er0), ("V0", V0)):
+            if t.size(0) < self.ncol:
+                raise ValueError("%s has %d rows, the matrix has %d columns" % (name, t.size(0), self.ncol))
+        if er1 is not None and V1.size(0) != er1.size(0):
+            raise ValueError("er1 has %d rows, V1 %d" % (er1.size(0), V1.size(0)))
+        for name, t in (("lse", lse), ("delta", delta)):
+            if t is not None and t.numel() < x_nrow * heads:
+                raise ValueError("%s must hold %d rows of %d heads" % (name, x_nrow, heads))
+        _gat_out_pos(out_pos, ds_out, "ds_out", self.nnz, heads)
+        _attention_on_device(sops + vops + vecs + ([("out_pos", out_pos)] if out_pos is not None else []))
+        if d_el is None:
+            d_el = torch.empty((x_nrow, heads), dtype=el.dtype, device=el.device)
+        if delta is None:
+            delta_given = torch.empty((x_nrow, heads), dtype=el.dtype, device=el.device)
+            delta = delta_given.view(-1)
+        if self.nrow == 0:
+            return d_el, delta_given
+        fn = self._lib.crp_gat_attention_bwd_row_csr_f32 if el.dtype == torch.float32 else self._lib.crp_gat_attention_bwd_row_csr_f64
+        e1p, lde1, v1p, ldv1 = (er1.data_ptr(), er1.stride(0), V1.data_ptr(), V1.stride(0)) if er1 is not None else (None, 0, None, 0)
+        ptr = lambda t: (t.data_ptr() or None) if t is not None else None
+        L.check(fn(self.handle, heads, nv // heads, slope, bias, el.data_ptr(), el.stride(0), ptr(er0), er0.stride(0), e1p, lde1,
+                   ptr(V0), V0.stride(0), v1p, ldv1, O.data_ptr(), O.stride(0), dO.data_ptr(), dO.stride(0), lse.data_ptr(),
+                   d_el.data_ptr(), d_el.stride(0), delta.data_ptr(), ptr(ds_out), ptr(out_pos),
+                   _stream(d_el) if stream is None else stream), fn.__name__)
+        return d_el, delta_given
+
+    def gat_attention_bwd_col(self, er, V, el, dO, lse, delta, slope=0.2, bias=False, d_er=None, dV=None, stream=None, heads=1):
+        """The column side of the fused backward of ``gat_attention`` (crp_gat_attention_bwd_col_csr_f64 / _f32), on a handle of
+        A^T (``from_transpose``): d_er[c, h] = the sum over column c of A of dZ_p and dV[c]_h = sum_p p_p dO[i_p]_h, with ``lse``
+        from the forward and ``delta`` from ``gat_attention_bwd_row``.  ``er``, ``d_er`` (rows of this handle, heads) and ``V``,
+        ``dV`` have a row per row of this handle; ``el``, ``dO``, ``lse``, ``delta`` one per column.  With ``bias`` the value added
+        to a score is this handle's own.  ``dV is V`` is allowed (same tensor); both outputs are allocated when None.  A head wider
+        than 512 (float64) / 1024 (float32) columns raises ValueError.  Returns (d_er, dV)."""
+        import torch
+        heads = _heads(heads)
+        sops = [("er", er), ("el", el)] + ([("d_er", d_er)] if d_er is not None else [])
+        vops = [("V", V), ("dO", dO)] + ([("dV", dV)] if dV is not None else [])
+        nv, slope, bias = _gat_operands(sops, vops, [("lse", lse), ("delta", delta)], slope, bias, heads)
+        lse, delta = _gat_flat("lse", lse, heads), _gat_flat("delta", delta, heads)
+        x_nrow = getattr(self, "_x_nrow", self.nrow)
+        for name, t in (("er", er), ("V", V), ("d_er", d_er), ("dV", dV)):
+            if t is not None and t.size(0) < x_nrow:
+                raise ValueError("%s has %d rows, the matrix needs %d" % (name, t.size(0), x_nrow))
+        for name, t in (("el", el), ("dO", dO)):
+            if t.size(0) < self.ncol:
+                raise ValueError("%s has %d rows, the matrix has %d columns" % (name, t.size(0), self.ncol))
+        for name, t in (("lse", lse), ("delta", delta)):
+            if t.numel() < self.ncol * heads:
+                raise ValueError("%s must hold %d rows of %d heads" % (name, self.ncol, heads))
+        _attention_on_device(sops + vops + [("lse", lse), ("delta", delta)])
+        if d_er is None:
+            d_er = torch.empty((x_nrow, heads), dtype=er.dtype, device=er.device)
+        if dV is None:
+            dV = torch.empty((x_nrow, nv), dtype=er.dtype, device=er.device)
+        if self.nrow == 0:
+            return d_er, dV
+        fn = self._lib.crp_gat_attention_bwd_col_csr_f32 if er.dtype == torch.float32 else self._lib.crp_gat_attention_bwd_col_csr_f64
+        L.check(fn(self.handle, heads, nv // heads, slope, bias, er.data_ptr(), er.stride(0), V.data_ptr(), V.stride(0),
+                   el.data_ptr() or None, el.stride(0), dO.data_ptr() or None, dO.stride(0), lse.data_ptr() or None,
+                   delta.data_ptr() or None, d_er.data_ptr(), d_er.stride(0), dV.data_ptr(), dV.stride(0),
+                   _stream(dV) if stream is None else stream), fn.__name__)
+        return d_er, dV
+
     def row_softmax(self, s, out=None, stream=None):
         """Row softmax over this matrix's pattern (crp_csr_dev_row_softmax_f64 / _f32, by the dtype of ``s``): for every row,
         out[p] = exp(s[p] - max) / sum over the row's nonzeros p, which count in the handle's CSR order -- what ``sddmm``
@@ -496,6 +628,74 @@ def _attention_operands(kops, vops, vecs, scale, bias, heads=1, cap=True, by_ope
     return nk, nv, scale, int(bool(bias))
 
 
+def _gat_operands(sops, vops, vecs, slope, bias, heads, cap=True):
+    """The operands of the three GAT wrappers, checked before any library call: sops 2-D with ``heads`` columns (el, er, their
+    gradients), vops 2-D of one width that ``heads`` divides, vecs per-row or per-nonzero tensors, all float64 or float32 of the
+    first's dtype, rows contiguous.  Returns (nv, slope, bias) as the C call takes them -- nv the whole width of V; the device is
+    checked by _attention_on_device.  ``cap`` (the backward): one head's width is held to BWD_WIDTH_CAP."""
+    import torch
+    head, first = sops[0]
+    floats, dtype = (torch.float64, torch.float32), getattr(first, "dtype", None)
+    for name, t in sops + vops + vecs:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s must be a torch tensor on the device" % name)
+        if t.dtype not in floats:
+            raise TypeError("%s must be float64 or float32, got %s" % (name, t.dtype))
+        if t.dtype != dtype:
+            raise TypeError("the operands must have one dtype (%s is %s, %s is %s)" % (head, dtype, name, t.dtype))
+    for name, t in sops + vops:
+        if t.dim() != 2:
+            raise TypeError("%s must be a 2-D torch tensor on the device" % name)
+        if t.size(1) > 1 and t.stride(1) != 1:
+            raise ValueError("%s must be contiguous along its rows" % name)
+    if bias not in (False, True, 0, 1):
+        raise ValueError("bias must be a bool, got %r" % (bias,))
+    slope = float(slope)
+    if not np.isfinite(slope):
+        raise ValueError("slope must be finite, got %r" % (slope,))
+    for name, t in sops:
+        if t.size(1) != heads:
+            raise ValueError("%s has %d columns, the call %d heads" % (name, t.size(1), heads))
+    nv = vops[0][1].size(1)
+    if nv < 1:
+        raise ValueError("the operands need at least one column")
+    for name, t in vops[1:]:
+        if t.size(1) != nv:
+            raise ValueError("%s has %d columns, %s has %d" % (name, t.size(1), vops[0][0], nv))
+    if nv % heads:
+        raise ValueError("%d heads do not divide the width (nv = %d)" % (heads, nv))
+    if cap:
+        cap = BWD_WIDTH_CAP[first.element_size()]
+        if nv // heads > cap:
+            raise ValueError("the fused backward takes at most %d columns per head in %s (dv = %d)" % (cap, first.dtype, nv // heads))
+    return nv, slope, int(bool(bias))
+
+
+def _gat_flat(name, t, heads):
+    """A per-row or per-nonzero tensor of a GAT call -- contiguous (rows, heads), or 1-D with one head -- as a flat view"""
+    if t is None:
+        return t
+    if t.dim() == 1 and heads == 1 and t.is_contiguous():
+        return t
+    if t.dim() != 2 or t.shape[1] != heads or not t.is_contiguous():
+        raise ValueError("%s must be a contiguous 2-D tensor with %d columns (one per head)" % (name, heads))
+    return t.view(-1)
+
+
+def _gat_out_pos(out_pos, out, name, nnz, heads):
+    """``out_pos`` and the per-nonzero output (flat) it indexes, as the attention wrappers check them"""
+    import torch
+    if out_pos is not None:
+        if not (isinstance(out_pos, torch.Tensor) and out_pos.dtype == torch.int32 and out_pos.dim() == 1 and out_pos.is_contiguous()):
+            raise TypeError("out_pos must be a contiguous 1-D int32 torch tensor on the device")
+        if out_pos.numel() != nnz:
+            raise ValueError("out_pos has %d entries, the matrix %d nonzeros" % (out_pos.numel(), nnz))
+        if out is None:
+            raise ValueError("out_pos needs a %s to write into" % name)
+    elif out is not None and out.numel() < nnz * heads:
+        raise ValueError("%s has %d rows, the matrix %d nonzeros" % (name, out.numel() // heads, nnz))
+
+
 def _attention_on_device(named):
     """... and, after every shape check, all of them on the first's device (all pointers are device pointers)"""
     head, first = named[0]
@@ -603,6 +803,54 @@ def _sparse_attention_fn():
 
     _SPARSE_ATTENTION_FN = SparseAttention
     return SparseAttention
+
+
+def gat_attention(A, At, el, er, V, slope=0.2, bias=False, heads=1):
+    """The GAT layer's attention, out[i]_h = sum_p softmax_p(leaky_relu(el[i, h] + er[c_p, h], slope) (+ A's values with ``bias``))
+    V[c_p]_h, as a differentiable function of el, er and V: ``A`` is the ``CsrDev`` of the pattern, ``At`` the
+    ``CsrDev.from_transpose`` of the same CSR (with ``bias`` both hold the same values).  The forward is ``A.gat_attention``,
+    which keeps O and lse; the backward is ``A.gat_attention_bwd_row`` and ``At.gat_attention_bwd_col``.  Nothing nnz-sized is
+    stored between the two.  ``el`` (rows, heads), ``er`` (columns, heads) and ``V`` (columns, heads * dv) are 2-D row-major cuda
+    tensors of one dtype.  The matrix's values are constants here.  ``At`` must be the transpose of ``A``: its shape and nonzero
+    count are checked, its pattern is not."""
+    heads = _heads(heads)
+    if At.nrow != A.ncol or At.ncol != A.nrow or At.nnz != A.nnz:
+        raise ValueError("At is %d x %d with %d nonzeros: not the transpose of A (%d x %d, %d)"
+                         % (At.nrow, At.ncol, At.nnz, A.nrow, A.ncol, A.nnz))
+    return _gat_attention_fn().apply(el, er, V, A, At, float(slope), bool(bias), heads)
+
+
+_GAT_ATTENTION_FN = None
+
+
+def _gat_attention_fn():
+    """the autograd.Function behind ``gat_attention``, made on first use"""
+    global _GAT_ATTENTION_FN
+    if _GAT_ATTENTION_FN is not None:
+        return _GAT_ATTENTION_FN
+    import torch
+
+    class GatAttention(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, el, er, V, A, At, slope, bias, heads):
+            el, er, V = (t if t.dim() != 2 or t.stride(-1) == 1 else t.contiguous() for t in (el.detach(), er.detach(), V.detach()))
+            lse = torch.empty((el.shape[0], heads), dtype=el.dtype, device=el.device)
+            O = A.gat_attention(el, er, V, slope=slope, bias=bias, lse=lse, heads=heads)
+            ctx.save_for_backward(el, er, V, O, lse)
+            ctx.handles = (A, At, slope, bias, heads)
+            return O
+
+        @staticmethod
+        def backward(ctx, dO):
+            el, er, V, O, lse = ctx.saved_tensors
+            A, At, slope, bias, heads = ctx.handles
+            dO = dO if dO.stride(-1) == 1 else dO.contiguous()
+            d_el, delta = A.gat_attention_bwd_row(el, er, V, O, dO, lse, slope=slope, bias=bias, heads=heads)
+            d_er, dV = At.gat_attention_bwd_col(er, V, el, dO, lse, delta, slope=slope, bias=bias, heads=heads)
+            return d_el, d_er, dV, None, None, None, None, None
+
+    _GAT_ATTENTION_FN = GatAttention
+    return GatAttention
 
 
 def spmm_csr(A, B0, C_out, n=None, layout=0, B1=None, variant=0, stream=None):

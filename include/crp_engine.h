@@ -220,6 +220,32 @@ void crp_rp_spmm_attention_bwd_mh_f32_ex(crp_rp_spmm_p rp_spmm, int heads, doubl
                                          long long ldO, const float *dO, long long lddO, const float *lse,
                                          float *dQ, long long lddQ, float *dK, long long lddK, float *dV, long long lddV,
                                          float *ds_out, void *stream);
+/* Fused GAT attention over this rank's rows of A, forward (crpspmm_hip.h, crp_gat_attention_csr_*): for every local row i, head h
+ * and nonzero p = (i, c_p) of the GLOBAL matrix, s = leaky_relu(el[i][h] + er[c_p][h], slope) (+ the engine's current value of p
+ * when bias = 1) and O[i]_h = sum_p softmax_p(s) * V[c_p]_h.  `heads` >= 1 must divide glb_n (anything else aborts), and every
+ * head has dv = glb_n / heads columns.  V and O are this rank's loc_B_nrow x glb_n and A_nrow x glb_n blocks, in either layout,
+ * on the host or the device, handled as crp_rp_spmm_attention_mh_ex handles them; el (A_nrow x heads, ldel >= heads) and er
+ * (loc_B_nrow x heads, lder >= heads) are row-major DEVICE pointers (anything else aborts); lse (A_nrow x heads) and p_out
+ * (heads values per local nonzero: entry (p, h) at p * heads + h, p in A_val's order) are optional, host or device.
+ * Data flow: V travels as B does, into the forward exchange's receive buffer; er travels in a narrow exchange of its own --
+ * rows of `heads` elements (fp32: padded to whole 8-byte words), gathered with the forward plan's row indices into a send
+ * buffer of its own and received into a per-dtype buffer, with the per-peer counts and displacements of the forward plan
+ * taken by rows.  The first call of a dtype allocates both and nothing before it does (crp_rp_spmm_gat_built: 0, then 1; that
+ * call blocks, as does a call with another number of heads, which sets them up again).  With timing off and a split engine
+ * the interior rows' kernel is enqueued first on the caller's stream, both packs and exchanges run on the engine's second
+ * stream, and the boundary rows' kernel follows after they have landed; with timing on the phases run in sequence.  The parts
+ * write O and lse through their row maps and p_out through the positions crp_rp_spmm_sddmm_ex uses.  The engine's values are
+ * not changed.  O, lse and p_out equal crp_gat_attention_csr_* on the whole matrix bit for bit, whatever the rank count, the
+ * timing mode and the number of calls.  Statistics and the completion rule as crp_rp_spmm_attention_ex.  glb_n = 0 computes
+ * nothing.  A plan-only engine aborts, as do a layout or a bias other than 0 or 1 and a non-finite slope; a NULL engine is a
+ * no-op.  The engine backward is not offered yet: the handle calls crp_gat_attention_bwd_*_csr_* serve one device. */
+void crp_rp_spmm_gat_ex(crp_rp_spmm_p rp_spmm, int layout, int heads, double slope, int bias, const double *el, long long ldel,
+                        const double *er, long long lder, const double *V, long long ldV, double *O, long long ldO,
+                        double *lse, double *p_out, void *stream);
+void crp_rp_spmm_gat_f32_ex(crp_rp_spmm_p rp_spmm, int layout, int heads, double slope, int bias, const float *el, long long ldel,
+                            const float *er, long long lder, const float *V, long long ldV, float *O, long long ldO,
+                            float *lse, float *p_out, void *stream);
+int crp_rp_spmm_gat_built(crp_rp_spmm_p rp_spmm);
 void crp_rp_spmm_print_stat(crp_rp_spmm_p rp_spmm);
 void crp_rp_spmm_clear_stat(crp_rp_spmm_p rp_spmm);
 /* rp_spmm_init for a caller that ALSO holds the values in device memory, in the order of A_val (A_val_dev: the panel a

@@ -45,6 +45,8 @@
  * attention calls in every sentence above: asynchronous on `stream`, taken literally; in steady state they enqueue all of their
  * device work there and nowhere else, allocate nothing, wait for nothing and touch no other stream, so they may be captured;
  * the only state they may build is the handle's fp32 copy of the values (fp32, bias = 1), by the first call that needs it.
+ * The same holds, word for word, for the GAT attention calls (crp_gat_attention_csr_*, crp_gat_attention_bwd_row_csr_*,
+ * crp_gat_attention_bwd_col_csr_*).
  */
 #ifndef CRPSPMM_HIP_H
 #define CRPSPMM_HIP_H
@@ -489,6 +491,80 @@ int crp_attention_bwd_kv_mh_csr_f32(crp_csr_dev_p At, int heads, int dk, int dv,
                                     const float *Q, long long ldQ, const float *dO, long long lddO,
                                     const float *lse, const float *delta,
                                     float *dK, long long lddK, float *dV, long long lddV, void *stream);
+
+/* ---- fused GAT attention: additive LeakyReLU scores over A's pattern, forward and backward --------------------------
+ * The score of a graph attention layer in place of the scaled dot product: two scalars per node and head, and no K.  For every
+ * row i of the handle, head h < heads and entry p = (i, c_p), p in the handle's CSR order:
+ *   z = el[i][h] + er[c_p][h]                    (one rounding)
+ *   a = z > 0 ? z : slope * z                    (one rounding: torch.nn.functional.leaky_relu)
+ *   s = a        (bias = 1: s = a + A's current value of p, one more rounding; the value is shared by the heads, and the fp32
+ *                 form adds the fp32 copy that crp_sddmm_csr_f32 mode 1 uses)
+ *   O[i]_h = sum_p softmax_p(s) * V[c_p]_h
+ * Every step is rounded on its own: slope * z + value is never contracted into an FMA.  slope is any finite double; the fp32
+ * form rounds it to float once; slope = 1 is the plain additive score.
+ * Operands (row-major device pointers): V / O / dO / dV have heads * dv columns, head h owns columns [h dv, (h + 1) dv).  el is
+ * (rows of O, heads) with ldel >= heads, read through the handle's row map like Q of crp_attention_csr_*; er0 / er1 are the two
+ * sources of the column code exactly as V0 / V1 (lder >= heads; a source no code names may be NULL).  Per-row scalars lse,
+ * delta, d_el are (rows, heads) -- lse and delta contiguous, entry i heads + h with i the row of O -- and the per-nonzero
+ * outputs p_out, ds_out are (nnz, heads): entry pos heads + h with pos = out_pos[p], or p when out_pos is NULL.
+ * Forward: from the scores on this is crp_attention_mh_csr_* verbatim -- batches of 8 entries in ascending p, m' = max(m,
+ * batch), f = exp(m - m'), e_u = exp(s_u - m'), l = l f then l + e_u in ascending u, acc = acc f then fma(e_u, V[c_u][j], acc) in
+ * ascending u, O = acc / l, lse = m + log l, p_out = exp(s - m) / l, the maximum never deferred -- so O, lse and p_out are bit
+ * for bit what that order gives for these scores and (dtype, dv).  A group of G(dv) lanes owns the unit (row, head); each lane
+ * forms the score of entry (lane & 7) of a batch from one scalar load of er.  Special cases as there: an empty row writes +0
+ * and lse = -inf for every head; a one-entry row gives O = V[c] bit for bit; s = -inf (a bias value of -inf, or z = -inf with
+ * slope > 0) is a masked edge; an all-masked row gives zeros; NaN or +inf among a row's scores (slope = 0 with an infinite z is
+ * this case) leaves that row's outputs unspecified.
+ * Backward, from el, er, V, O, lse and dO, with s re-formed exactly as above:  p = exp(s - lse[i][h]),  dP = < dO[i]_h, V[c]_h >,
+ * D = < dO[i]_h, O[i]_h > (both as crp_sddmm_csr_* forms a dot for (dtype, dv)),  dS = p (dP - D) (p == 0: +0),  dZ = dS g with
+ * g = z > 0 ? 1 : slope (one rounding).
+ *   crp_gat_attention_bwd_row_csr_*, over a handle of A (two sources, row map and out_pos as in crp_attention_bwd_q_mh_csr_*):
+ *   writes delta[i][h] = D and d_el[i][h] = the sum of the row's dZ -- one IEEE addition per entry from +0 in ascending p -- both
+ *   required, and, when ds_out is not NULL, ds_out[(pos, h)] = dS: the gradient of A's values per head.
+ *   crp_gat_attention_bwd_col_csr_*, over a handle of A^T (crp_csr_dev_create_t; one source: negative codes return -1; the row
+ *   map selects the er / V / d_er / dV row): takes delta as the row side wrote it and writes d_er[c][h] = the sum of the column's
+ *   dZ, from +0 in the handle's CSR order, and dV[c]_h with acc = fma(p_u, dO[i_u][j], acc) from +0 in that order.  With bias = 1
+ *   the value added is this handle's own value of the entry.  dV == V with the same pointer and leading dimension is legal; no
+ *   other aliasing is.
+ * s, p, dP, dS and dZ have the same bits on both sides.  Rows with lse = -inf give +0 everywhere; delta is still written.  The
+ * per-head width cap is the attention backward's: dv <= 4 * 64 * W, else CRP_ATTN_BWD_EWIDTH with nothing written.
+ * Error bounds: DESIGN.md 5o.  Asynchronous on `stream`.  Returns 0 (also for a handle without rows: nothing is launched), a
+ * HIP error (> 0; rows * heads units that do not fit one launch among them), or a negative argument error before which nothing
+ * is written: -1 for a NULL handle or required pointer (forward: el, O and an er or V source that a code names; row side also
+ * dO, lse, d_el, delta; column side: er, V, d_er, dV, and el, dO, lse, delta when the handle has a nonzero), heads < 1, dv < 1, a
+ * bias other than 0 or 1, a non-finite slope; -4 for a leading dimension below its width (heads, or heads * dv). */
+int crp_gat_attention_csr_f64(crp_csr_dev_p A, int heads, int dv, double slope, int bias,
+                              const double *el, long long ldel,
+                              const double *er0, long long lder0, const double *er1, long long lder1,
+                              const double *V0, long long ldV0, const double *V1, long long ldV1,
+                              double *O, long long ldO, double *lse, double *p_out, const int *out_pos, void *stream);
+int crp_gat_attention_bwd_row_csr_f64(crp_csr_dev_p A, int heads, int dv, double slope, int bias,
+                                      const double *el, long long ldel,
+                                      const double *er0, long long lder0, const double *er1, long long lder1,
+                                      const double *V0, long long ldV0, const double *V1, long long ldV1,
+                                      const double *O, long long ldO, const double *dO, long long lddO, const double *lse,
+                                      double *d_el, long long ldd_el, double *delta, double *ds_out, const int *out_pos, void *stream);
+int crp_gat_attention_bwd_col_csr_f64(crp_csr_dev_p At, int heads, int dv, double slope, int bias,
+                                      const double *er, long long lder, const double *V, long long ldV,
+                                      const double *el, long long ldel, const double *dO, long long lddO,
+                                      const double *lse, const double *delta,
+                                      double *d_er, long long ldd_er, double *dV, long long lddV, void *stream);
+int crp_gat_attention_csr_f32(crp_csr_dev_p A, int heads, int dv, double slope, int bias,
+                              const float *el, long long ldel,
+                              const float *er0, long long lder0, const float *er1, long long lder1,
+                              const float *V0, long long ldV0, const float *V1, long long ldV1,
+                              float *O, long long ldO, float *lse, float *p_out, const int *out_pos, void *stream);
+int crp_gat_attention_bwd_row_csr_f32(crp_csr_dev_p A, int heads, int dv, double slope, int bias,
+                                      const float *el, long long ldel,
+                                      const float *er0, long long lder0, const float *er1, long long lder1,
+                                      const float *V0, long long ldV0, const float *V1, long long ldV1,
+                                      const float *O, long long ldO, const float *dO, long long lddO, const float *lse,
+                                      float *d_el, long long ldd_el, float *delta, float *ds_out, const int *out_pos, void *stream);
+int crp_gat_attention_bwd_col_csr_f32(crp_csr_dev_p At, int heads, int dv, double slope, int bias,
+                                      const float *er, long long lder, const float *V, long long ldV,
+                                      const float *el, long long ldel, const float *dO, long long lddO,
+                                      const float *lse, const float *delta,
+                                      float *d_er, long long ldd_er, float *dV, long long lddV, void *stream);
 
 /* ---- row softmax over A's pattern (edge softmax) and its Jacobian product ------
  * For every row r with entries p in [rowptr[r], rowptr[r + 1]):
