@@ -112,6 +112,14 @@ _GAT_ARGS = {
     "gat_attention_bwd_col": [_V, _I, _I, C.c_double, _I, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _V, _V, _LL, _V, _LL, _V],
 }
 _GAT_SIGNATURES = {"crp_%s_csr_%s" % (stem, dt): (_I, args) for stem, args in _GAT_ARGS.items() for dt in ("f64", "f32")}
+# ... and of the fused GATv2 attention: (handle, heads, dv, slope, bias, ...), shared by f64 and f32
+_GATV2_ARGS = {
+    "gatv2_attention": [_V, _I, _I, C.c_double, _I, _V, _LL, _V, _LL, _V, _LL, _V, _V, _LL, _V, _V, _V, _V],
+    "gatv2_attention_bwd_row": [_V, _I, _I, C.c_double, _I, _V, _LL, _V, _LL, _V, _LL, _V, _V, _LL, _V, _LL, _V, _V, _LL, _V, _LL, _V, _V,
+                                _V, _V],
+    "gatv2_attention_bwd_col": [_V, _I, _I, C.c_double, _I, _V, _LL, _V, _LL, _V, _V, _LL, _V, _V, _V, _LL, _V],
+}
+_GATV2_SIGNATURES = {"crp_%s_csr_%s" % (stem, dt): (_I, args) for stem, args in _GATV2_ARGS.items() for dt in ("f64", "f32")}
 
 # name -> (restype, argtypes); every symbol declared in include/crpspmm_hip.h,
 # include/crp_comm.h, include/crp_engine.h, include/utils.h, include/spmat_part.h,
@@ -187,6 +195,7 @@ SIGNATURES = {
     "crp_sddmm_csr_f32": (_I, [_V, _I, _V, _LL, _V, _LL, _V, _LL, _V, _V, _I, _V]),
     **_ATTENTION_SIGNATURES,
     **_GAT_SIGNATURES,
+    **_GATV2_SIGNATURES,
     "crp_row_softmax_f64": (_I, [_I, _V, _V, _V, _V]),
     "crp_row_softmax_f32": (_I, [_I, _V, _V, _V, _V]),
     "crp_row_softmax_bwd_f64": (_I, [_I, _V, _V, _V, _V, _V]),
@@ -205,6 +214,8 @@ SIGNATURES = {
     "crp_gather_vals_f32_f64": (_I, [_LL, _V, _V, _V, _V]),
     "crp_sum_segments_f64": (_I, [_I, _LL, _V, _LL, _V, _V]),
     "crp_sum_segments_f32": (_I, [_I, _LL, _V, _LL, _V, _V]),
+    "crp_col_sum_f64": (_I, [_I, _I, _V, _LL, _V, _V, _V]),
+    "crp_col_sum_f32": (_I, [_I, _I, _V, _LL, _V, _V, _V]),
     "crp_transpose_f64": (_I, [_I, _I, _V, _LL, _V, _LL, _V]),
     "crp_gather_rows_f32": (_I, [_I, _I, _I, _V, _V, _LL, _V, _LL, _V]),
     "crp_scatter_rows_f32": (_I, [_I, _I, _I, _V, _V, _LL, _V, _LL, _V]),
@@ -241,6 +252,9 @@ SIGNATURES = {
     "crp_rp_spmm_gat_ex": (None, [_V, _I, _I, C.c_double, _I, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _V, _V]),
     "crp_rp_spmm_gat_f32_ex": (None, [_V, _I, _I, C.c_double, _I, _V, _LL, _V, _LL, _V, _LL, _V, _LL, _V, _V, _V]),
     "crp_rp_spmm_gat_built": (_I, [_V]),
+    "crp_rp_spmm_gatv2_ex": (None, [_V, _I, _I, C.c_double, _I, _V, _LL, _V, _V, _LL, _V, _LL, _V, _V, _V]),
+    "crp_rp_spmm_gatv2_f32_ex": (None, [_V, _I, _I, C.c_double, _I, _V, _LL, _V, _V, _LL, _V, _LL, _V, _V, _V]),
+    "crp_rp_spmm_gatv2_built": (_I, [_V]),
     "crp_rp_spmm_print_stat": (None, [_V]),
     "crp_rp_spmm_clear_stat": (None, [_V]),
     "crp_rp_spmm_get_plan": (None, [_V, C.POINTER(RpPlanView)]),

@@ -116,6 +116,19 @@ static inline int gat_attention(crp_csr_dev_p A, int heads, int dv, double slope
 {
     return crp_gat_attention_csr_f32(A, heads, dv, slope, bias, el, ldel, er0, lder0, er1, lder1, V0, ldV0, V1, ldV1, O, ldO, lse, p_out, out_pos, s);
 }
+// the fused GATv2 attention (a LeakyReLU inside the dot with a), forward
+static inline int gatv2_attention(crp_csr_dev_p A, int heads, int dv, double slope, int bias, const double *XT, long long ldXT, const double *XS0,
+                                  long long ldXS0, const double *XS1, long long ldXS1, const double *a, double *O, long long ldO, double *lse,
+                                  double *p_out, const int *out_pos, void *s)
+{
+    return crp_gatv2_attention_csr_f64(A, heads, dv, slope, bias, XT, ldXT, XS0, ldXS0, XS1, ldXS1, a, O, ldO, lse, p_out, out_pos, s);
+}
+static inline int gatv2_attention(crp_csr_dev_p A, int heads, int dv, double slope, int bias, const float *XT, long long ldXT, const float *XS0,
+                                  long long ldXS0, const float *XS1, long long ldXS1, const float *a, float *O, long long ldO, float *lse,
+                                  float *p_out, const int *out_pos, void *s)
+{
+    return crp_gatv2_attention_csr_f32(A, heads, dv, slope, bias, XT, ldXT, XS0, ldXS0, XS1, ldXS1, a, O, ldO, lse, p_out, out_pos, s);
+}
 static inline int sum_segments(int nseg, long long len, const double *src, long long stride, double *out, void *s)
 {
     return crp_sum_segments_f64(nseg, len, src, stride, out, s);

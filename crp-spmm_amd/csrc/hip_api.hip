@@ -593,6 +593,84 @@ static int gat_bwd_col_csr(crp_csr_dev *At, int heads, int dv, double slope, int
     return (int) crp::gat_attention_bwd_col(a, s);
 }
 
+// ---- the fused GATv2 attention (gatv2_kernels.hip), one dtype.  Every argument is checked before anything is launched or allocated:
+// a negative return has written nothing.  dv: the width of one head, capped in both directions.
+template <class T>
+static int gatv2_check(const crp_csr_dev *A, int heads, int dv, double slope, int bias, const void *XT, long long ldXT, const void *XS0,
+                       long long ldXS0, const void *XS1, long long ldXS1, const void *av, const void *O, long long ldO)
+{
+    if (A == NULL || XT == NULL || av == NULL || O == NULL) return -1;
+    if (heads < 1 || dv < 1 || (bias != 0 && bias != 1) || !std::isfinite(slope)) return -1;
+    if (XS0 == NULL && A->b0_rows > 0) return -1;        // a column code names the first source
+    if (XS1 == NULL && A->b1_rows > 0) return -1;        // a column code names the second source
+    const long long wv = (long long) heads * dv;
+    if (ldXT < wv || ldO < wv || (XS0 != NULL && ldXS0 < wv) || (XS1 != NULL && ldXS1 < wv)) return -4;
+    constexpr int cap = crp::ATTN_BWD_MAX_PIECES * 64 * (16 / (int) sizeof(T));
+    if (dv > cap) return CRP_GATV2_EWIDTH;
+    return 0;
+}
+template <class T>
+static int gatv2_fwd_csr(crp_csr_dev *A, int heads, int dv, double slope, int bias, const T *XT, long long ldXT, const T *XS0, long long ldXS0,
+                         const T *XS1, long long ldXS1, const T *av, T *O, long long ldO, T *lse, T *p_out, const int *out_pos, hipStream_t s)
+{
+    int rc = gatv2_check<T>(A, heads, dv, slope, bias, XT, ldXT, XS0, ldXS0, XS1, ldXS1, av, O, ldO);
+    if (rc != 0 || A->nrow == 0) return rc;
+    crp::Gatv2Args<T> a;
+    rc = attention_bias_values<T>(A, bias, s, &a.val);
+    if (rc != 0) return rc;
+    a.nrow = A->nrow; a.nv = dv; a.heads = heads; a.rowptr = A->rowptr; a.colidx = A->colidx; a.slope = (T) slope;
+    a.XT = XT; a.ldXT = ldXT; a.XS0 = XS0; a.ldXS0 = ldXS0; a.XS1 = XS1; a.ldXS1 = ldXS1; a.av = av;
+    a.O = O; a.ldO = ldO; a.lse = lse; a.p_out = p_out; a.rowmap = A->rowmap; a.out_pos = out_pos;
+    return (int) crp::gatv2_attention_rm(a, s);
+}
+template <class T>
+static int gatv2_bwd_row_csr(crp_csr_dev *A, int heads, int dv, double slope, int bias, const T *XT, long long ldXT, const T *XS0,
+                             long long ldXS0, const T *XS1, long long ldXS1, const T *av, const T *O, long long ldO, const T *dO, long long lddO,
+                             const T *lse, T *dXT, long long lddXT, T *da_part, long long ldda, T *delta, T *ds_out, const int *out_pos,
+                             hipStream_t s)
+{
+    int rc = 0;
+    if (A == NULL || dO == NULL || lse == NULL || dXT == NULL || da_part == NULL || delta == NULL) rc = -1;
+    if (rc == 0) rc = gatv2_check<T>(A, heads, dv, slope, bias, XT, ldXT, XS0, ldXS0, XS1, ldXS1, av, O, ldO);
+    if (rc == 0 || rc == CRP_GATV2_EWIDTH)
+    {
+        const long long wv = (long long) heads * dv;
+        if (lddO < wv || lddXT < wv || ldda < wv) rc = -4;
+    }
+    if (rc != 0 || A->nrow == 0) return rc;
+    crp::Gatv2BwdRowArgs<T> a;
+    rc = attention_bias_values<T>(A, bias, s, &a.val);
+    if (rc != 0) return rc;
+    a.nrow = A->nrow; a.nv = dv; a.heads = heads; a.rowptr = A->rowptr; a.colidx = A->colidx; a.slope = (T) slope;
+    a.XT = XT; a.ldXT = ldXT; a.XS0 = XS0; a.ldXS0 = ldXS0; a.XS1 = XS1; a.ldXS1 = ldXS1; a.av = av;
+    a.O = O; a.ldO = ldO; a.dO = dO; a.lddO = lddO; a.lse = lse; a.dXT = dXT; a.lddXT = lddXT; a.da_part = da_part; a.ldda = ldda;
+    a.delta = delta; a.ds_out = ds_out; a.rowmap = A->rowmap; a.out_pos = out_pos;
+    return (int) crp::gatv2_attention_bwd_row(a, s);
+}
+template <class T>
+static int gatv2_bwd_col_csr(crp_csr_dev *At, int heads, int dv, double slope, int bias, const T *XS, long long ldXS, const T *XT,
+                             long long ldXT, const T *av, const T *dO, long long lddO, const T *lse, const T *delta, T *dXS, long long lddXS,
+                             hipStream_t s)
+{
+    if (At == NULL || XS == NULL || av == NULL || dXS == NULL) return -1;
+    if (heads < 1 || dv < 1 || (bias != 0 && bias != 1) || !std::isfinite(slope)) return -1;
+    if (At->b1_rows > 0) return -1;                      // a code names a second source: this call takes one
+    if ((XT == NULL || dO == NULL || lse == NULL || delta == NULL) && At->nnz > 0) return -1;
+    const long long wv = (long long) heads * dv;
+    if (ldXS < wv || lddXS < wv) return -4;
+    if (At->nnz > 0 && (ldXT < wv || lddO < wv)) return -4;
+    constexpr int cap = crp::ATTN_BWD_MAX_PIECES * 64 * (16 / (int) sizeof(T));
+    if (dv > cap) return CRP_GATV2_EWIDTH;
+    if (At->nrow == 0) return 0;
+    crp::Gatv2BwdColArgs<T> a;
+    const int rc = attention_bias_values<T>(At, bias, s, &a.val);
+    if (rc != 0) return rc;
+    a.nrow = At->nrow; a.nv = dv; a.heads = heads; a.rowptr = At->rowptr; a.colidx = At->colidx; a.slope = (T) slope;
+    a.XS = XS; a.ldXS = ldXS; a.XT = XT; a.ldXT = ldXT; a.av = av; a.dO = dO; a.lddO = lddO; a.lse = lse; a.delta = delta;
+    a.dXS = dXS; a.lddXS = lddXS; a.rowmap = At->rowmap;
+    return (int) crp::gatv2_attention_bwd_col(a, s);
+}
+
 extern "C" {
 
 const char *crp_hip_version(void) { return "crpspmm-hip 0.1 gfx950"; }
@@ -1321,6 +1399,33 @@ CRP_GAT_ENTRY_POINTS(f64, double)
 CRP_GAT_ENTRY_POINTS(f32, float)
 #undef CRP_GAT_ENTRY_POINTS
 
+// ---- the fused GATv2 attention: a LeakyReLU inside the dot with a, forward and the two-handle backward (gatv2_kernels.hip)
+#define CRP_GATV2_ENTRY_POINTS(SFX, T)                                                                                                            \
+    int crp_gatv2_attention_csr_##SFX(crp_csr_dev_p A, int heads, int dv, double slope, int bias, const T *XT, long long ldXT, const T *XS0,      \
+                                      long long ldXS0, const T *XS1, long long ldXS1, const T *a, T *O, long long ldO, T *lse, T *p_out,          \
+                                      const int *out_pos, void *stream)                                                                           \
+    {                                                                                                                                             \
+        return gatv2_fwd_csr<T>(A, heads, dv, slope, bias, XT, ldXT, XS0, ldXS0, XS1, ldXS1, a, O, ldO, lse, p_out, out_pos,                      \
+                                (hipStream_t) stream);                                                                                            \
+    }                                                                                                                                             \
+    int crp_gatv2_attention_bwd_row_csr_##SFX(crp_csr_dev_p A, int heads, int dv, double slope, int bias, const T *XT, long long ldXT,            \
+                                              const T *XS0, long long ldXS0, const T *XS1, long long ldXS1, const T *a, const T *O,               \
+                                              long long ldO, const T *dO, long long lddO, const T *lse, T *dXT, long long lddXT, T *da_part,      \
+                                              long long ldda, T *delta, T *ds_out, const int *out_pos, void *stream)                              \
+    {                                                                                                                                             \
+        return gatv2_bwd_row_csr<T>(A, heads, dv, slope, bias, XT, ldXT, XS0, ldXS0, XS1, ldXS1, a, O, ldO, dO, lddO, lse, dXT, lddXT, da_part,  \
+                                    ldda, delta, ds_out, out_pos, (hipStream_t) stream);                                                          \
+    }                                                                                                                                             \
+    int crp_gatv2_attention_bwd_col_csr_##SFX(crp_csr_dev_p At, int heads, int dv, double slope, int bias, const T *XS, long long ldXS,           \
+                                              const T *XT, long long ldXT, const T *a, const T *dO, long long lddO, const T *lse,                 \
+                                              const T *delta, T *dXS, long long lddXS, void *stream)                                              \
+    {                                                                                                                                             \
+        return gatv2_bwd_col_csr<T>(At, heads, dv, slope, bias, XS, ldXS, XT, ldXT, a, dO, lddO, lse, delta, dXS, lddXS, (hipStream_t) stream);  \
+    }
+CRP_GATV2_ENTRY_POINTS(f64, double)
+CRP_GATV2_ENTRY_POINTS(f32, float)
+#undef CRP_GATV2_ENTRY_POINTS
+
 // ---- row softmax over a CSR pattern (softmax_kernels.hip).  Every argument is checked before anything is launched.
 int crp_row_softmax_f64(int nrow, const int *rowptr, const double *s, double *y, void *stream)
 {
@@ -1598,6 +1703,20 @@ int crp_sum_segments_f32(int nseg, long long len, const float *src, long long se
     if (nseg > 1 && seg_stride < len) return -4;
     if (len == 0) return 0;
     return (int) crp::sum_segments_f32(nseg, len, src, seg_stride, out, (hipStream_t) stream);
+}
+
+int crp_col_sum_f64(int nrow, int n, const double *src, long long lds, double *work, double *out, void *stream)
+{
+    if (nrow < 0 || n < 0 || out == NULL || (nrow > 0 && n > 0 && (src == NULL || work == NULL))) return -1;
+    if (nrow > 0 && lds < n) return -4;
+    return (int) crp::col_sum_f64(nrow, n, src, lds, work, out, (hipStream_t) stream);
+}
+
+int crp_col_sum_f32(int nrow, int n, const float *src, long long lds, float *work, float *out, void *stream)
+{
+    if (nrow < 0 || n < 0 || out == NULL || (nrow > 0 && n > 0 && (src == NULL || work == NULL))) return -1;
+    if (nrow > 0 && lds < n) return -4;
+    return (int) crp::col_sum_f32(nrow, n, src, lds, work, out, (hipStream_t) stream);
 }
 
 int crp_transpose_f64(int nrow, int ncol, const double *src, long long lds, double *dst, long long ldd,

@@ -285,6 +285,87 @@ template <typename T> struct GatBwdColArgs
     const int *rowmap;      // nullptr, or the er / V / d_er / dV row of every row (row-subset matrices)
 };
 
+// gatv2_kernels.hip: O[i]_h = sum_p softmax_p(sum_j a[h][j] lrelu(XT[i]_h[j] + XS[c_p]_h[j]) (+ val[p])) XS[c_p]_h over (row, head) units
+template <typename T> struct Gatv2Args
+{
+    int nrow;
+    int nv;                 // columns of one head of XT, XS, a and O
+    int heads;
+    const int *rowptr;
+    const int *colidx;
+    const T   *val;         // the values in T (bias), or nullptr
+    T          slope;
+    const T   *XT;          // (rows of O, heads * nv)
+    int64_t    ldXT;
+    const T   *XS0;         // the two sources of the column code
+    int64_t    ldXS0;
+    const T   *XS1;
+    int64_t    ldXS1;
+    const T   *av;          // heads * nv contiguous elements
+    T         *O;
+    int64_t    ldO;
+    T         *lse;         // nullptr, or (rows, heads), indexed like the rows of O
+    T         *p_out;       // nullptr, or the probabilities, (nnz, heads)
+    const int *rowmap;      // nullptr, or the XT / O row of every row (row-subset matrices)
+    const int *out_pos;     // nullptr, or where nonzero p writes: row out_pos[p] of p_out
+};
+
+// gatv2_kernels.hip, row side of the backward over a handle of A: delta, dXT, da_part (the row's share of d/da), ds_out
+template <typename T> struct Gatv2BwdRowArgs
+{
+    int nrow;
+    int nv;
+    int heads;
+    const int *rowptr;
+    const int *colidx;
+    const T   *val;
+    T          slope;
+    const T   *XT;
+    int64_t    ldXT;
+    const T   *XS0;
+    int64_t    ldXS0;
+    const T   *XS1;
+    int64_t    ldXS1;
+    const T   *av;
+    const T   *O;
+    int64_t    ldO;
+    const T   *dO;
+    int64_t    lddO;
+    const T   *lse;         // (rows, heads), as the forward wrote it
+    T         *dXT;         // (rows, heads * nv), indexed like XT
+    int64_t    lddXT;
+    T         *da_part;     // (rows, heads * nv), indexed like XT
+    int64_t    ldda;
+    T         *delta;       // (rows, heads), indexed like lse
+    T         *ds_out;      // nullptr, or dS, (nnz, heads)
+    const int *rowmap;      // nullptr, or the XT / O / dO / dXT / da_part / lse / delta row of every row
+    const int *out_pos;     // nullptr, or where nonzero p writes: row out_pos[p] of ds_out
+};
+
+// gatv2_kernels.hip, column side over a handle of A^T (row c = column c of A): dXS[c]_h = sum_p dS_p ag_p + sum_p p_p dO[i_p]_h
+template <typename T> struct Gatv2BwdColArgs
+{
+    int nrow;               // rows of the transposed handle
+    int nv;
+    int heads;
+    const int *rowptr;
+    const int *colidx;      // rows of XT / dO / lse / delta (one source: no negative code)
+    const T   *val;         // the transposed handle's values in T (bias), or nullptr
+    T          slope;
+    const T   *XS;
+    int64_t    ldXS;
+    const T   *XT;
+    int64_t    ldXT;
+    const T   *av;
+    const T   *dO;
+    int64_t    lddO;
+    const T   *lse;
+    const T   *delta;
+    T         *dXS;         // may be XS exactly (a group reads its slice whole before it writes it)
+    int64_t    lddXS;
+    const int *rowmap;      // nullptr, or the XS / dXS row of every row (row-subset matrices)
+};
+
 // The instance every SpMM launcher names at its hipLaunchKernelGGL, from its own template arguments ("rowgroup<16,2,1>",
 // "panel<8,2,2,a32,b1>", "team2<f64,NV1,b0,compact>", ...): a string with static storage, per host thread.  hip_api.hip copies
 // it into the handle after the product (crp_csr_dev_last_kernel); nothing else reads it.
@@ -347,6 +428,15 @@ hipError_t gat_attention_bwd_row(const GatBwdRowArgs<float> &a, hipStream_t s);
 hipError_t gat_attention_bwd_col(const GatBwdColArgs<double> &a, hipStream_t s);
 hipError_t gat_attention_bwd_col(const GatBwdColArgs<float> &a, hipStream_t s);
 
+// gatv2_kernels.hip: the fused GATv2 attention (a LeakyReLU inside the dot with a) over (row, head) units and its two-handle
+// backward; the per-head width is capped as attention_bwd's, in both directions
+hipError_t gatv2_attention_rm(const Gatv2Args<double> &a, hipStream_t s);
+hipError_t gatv2_attention_rm(const Gatv2Args<float> &a, hipStream_t s);
+hipError_t gatv2_attention_bwd_row(const Gatv2BwdRowArgs<double> &a, hipStream_t s);
+hipError_t gatv2_attention_bwd_row(const Gatv2BwdRowArgs<float> &a, hipStream_t s);
+hipError_t gatv2_attention_bwd_col(const Gatv2BwdColArgs<double> &a, hipStream_t s);
+hipError_t gatv2_attention_bwd_col(const Gatv2BwdColArgs<float> &a, hipStream_t s);
+
 // softmax_kernels.hip: row softmax over a CSR pattern and its Jacobian product; rowptr entries index the value arrays directly
 hipError_t row_softmax_f64(int nrow, const int *rowptr, const double *s, double *y, hipStream_t st);
 hipError_t row_softmax_f32(int nrow, const int *rowptr, const float *s, float *y, hipStream_t st);
@@ -369,6 +459,9 @@ hipError_t scatter_add_rows_f32(int nseg, int n, const int *seg_row, const int *
 // out[p] = the sum over j < nseg of src[j * seg_stride + p], added left to right (p < len)
 hipError_t sum_segments_f64(int nseg, int64_t len, const double *src, int64_t seg_stride, double *out, hipStream_t s);
 hipError_t sum_segments_f32(int nseg, int64_t len, const float *src, int64_t seg_stride, float *out, hipStream_t s);
+// out[j] = the sum of column j of src (nrow x n): blocks of 256 rows from +0 in ascending row into work, then sum_segments over the blocks
+hipError_t col_sum_f64(int nrow, int n, const double *src, int64_t lds, double *work, double *out, hipStream_t s);
+hipError_t col_sum_f32(int nrow, int n, const float *src, int64_t lds, float *work, float *out, hipStream_t s);
 hipError_t convert_f64_f32(int64_t n, const double *src, float *dst, hipStream_t s);
 hipError_t transpose_f64(int nrow, int ncol, const double *src, int64_t lds, double *dst, int64_t ldd,
                          hipStream_t s);

@@ -434,6 +434,47 @@ hipError_t sum_segments_f32(int nseg, int64_t len, const float *src, int64_t seg
     return sum_segments<float>(nseg, len, src, seg_stride, out, s);
 }
 
+// Column sums of a row-major nrow x n array (the reduction of the GATv2 backward's da_part over the rows): block b of 256
+// consecutive rows is summed per column from +0 in ascending row by one thread -- work[b * n + j], coalesced across the columns --
+// and sum_segments adds the blocks left to right in ascending b.  Plain IEEE additions of single elements: the bits are a function
+// of (dtype, nrow, n, data) only.  No atomics, no LDS.  sum_segments alone would be one serial chain of nrow additions on n threads.
+constexpr int COL_SUM_ROWS = 256;
+template <class T>
+__global__ __launch_bounds__(256) void col_block_sum_kernel(const int nrow, const int n, const int ncb, const T *__restrict__ src,
+                                                            const int64_t lds, T *__restrict__ work)
+{
+    const int blk = (int) (blockIdx.x / (unsigned) ncb);
+    const int col = (int) (blockIdx.x % (unsigned) ncb) * 256 + (int) threadIdx.x;
+    if (col >= n) return;
+    const int r0 = blk * COL_SUM_ROWS, r1 = min(nrow, r0 + COL_SUM_ROWS);
+    T acc = (T) 0;
+    for (int r = r0; r < r1; r++) acc = acc + src[(int64_t) r * lds + col];
+    work[(int64_t) blk * n + col] = acc;
+}
+
+template <class T>
+static hipError_t col_sum(int nrow, int n, const T *src, int64_t lds, T *work, T *out, hipStream_t s)
+{
+    if (n <= 0) return hipSuccess;
+    if (nrow <= 0) return hipMemsetAsync(out, 0, (size_t) n * sizeof(T), s);        // an empty sum: +0
+    const int64_t nblk = ((int64_t) nrow + COL_SUM_ROWS - 1) / COL_SUM_ROWS, ncb = ((int64_t) n + 255) / 256;
+    if (nblk * ncb > INT32_MAX) return hipErrorInvalidValue;            // before anything is written
+    hipLaunchKernelGGL((col_block_sum_kernel<T>), dim3((unsigned) (nblk * ncb)), dim3(256), 0, s, nrow, n, (int) ncb, src, lds, work);
+    const hipError_t rc = hipGetLastError();
+    if (rc != hipSuccess) return rc;
+    return sum_segments<T>((int) nblk, n, work, n, out, s);
+}
+
+hipError_t col_sum_f64(int nrow, int n, const double *src, int64_t lds, double *work, double *out, hipStream_t s)
+{
+    return col_sum<double>(nrow, n, src, lds, work, out, s);
+}
+
+hipError_t col_sum_f32(int nrow, int n, const float *src, int64_t lds, float *work, float *out, hipStream_t s)
+{
+    return col_sum<float>(nrow, n, src, lds, work, out, s);
+}
+
 // fp32 copy of fp64 values (the fp32 path keeps A's values in fp64 as the caller gave them and derives its own copy)
 __global__ void convert_f64_f32_kernel(const int64_t n, const double *__restrict__ src, float *__restrict__ dst)
 {

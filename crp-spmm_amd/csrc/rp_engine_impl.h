@@ -1,6 +1,6 @@
 // rp_engine_impl.h -- the row engine's state (struct crp_rp_spmm) and the helpers that its translation units share: rp_engine.cpp
 // (init, exec, exec_t, sddmm, value updates), rp_attention.cpp (the fused attention, forward and backward, single- and
-// multi-head) and rp_gat.cpp (the fused GAT attention, forward).  Internal: nothing outside csrc/ includes it.
+// multi-head) and rp_gat.cpp (the fused GAT and GATv2 attention, forward).  Internal: nothing outside csrc/ includes it.
 #ifndef CRP_RP_ENGINE_IMPL_H
 #define CRP_RP_ENGINE_IMPL_H
 
@@ -85,6 +85,8 @@ struct crp_rp_spmm
     bool gt_built = false;
     GatXchg<float>  gt_x32;
     GatXchg<double> gt_x64;
+    // fused GATv2 attention (crp_rp_spmm_gatv2_ex, rp_gat.cpp): XS travels as B does, so the first call uploads the parts' positions only
+    bool gv2_built = false;
     // row softmax (crp_rp_spmm_row_softmax_ex), uploaded by its first call: A_rowptr as a device array
     crp::DevArray<int> sm_rowptr;
     // device value updates (crp_rp_spmm_update_values_dev), allocated by its first call: the new values as fp64 in the order the

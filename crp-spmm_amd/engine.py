@@ -362,6 +362,62 @@ class RpSpmm:
         """True once a ``gat_attention`` has set up the narrow exchange of er (crp_rp_spmm_gat_built)."""
         return bool(self._lib.crp_rp_spmm_gat_built(self.handle))
 
+    def gatv2_attention(self, layout, XT, a, XS, out, slope=0.2, bias=False, lse=None, p_out=None, stream=None, heads=1):
+        """Fused GATv2 attention over this rank's rows of A (crp_rp_spmm_gatv2_ex / _f32_ex, by the operands' dtype): for every head
+        h, out[i]_h = sum_p softmax_p(sum_j a[h, j] leaky_relu(XT[i]_h[j] + XS[c_p]_h[j], slope) (+ the engine's current value of p
+        with ``bias``)) * XS[c_p]_h over the nonzeros p = (i, c_p) of row i.  XS and ``out`` are this rank's loc_B_nrow x glb_n and
+        A_nrow x glb_n blocks (layouts and operands as ``exec``) with glb_n / heads columns per head; XS travels as B does.  ``XT``
+        (A_nrow, glb_n), row-major, and ``a`` (glb_n contiguous elements, 1-D or (heads, dv)) are torch tensors on the device;
+        ``lse`` (A_nrow, heads) and ``p_out`` (nnz, heads), in the order of the A_val given to init, are optional contiguous
+        arrays or tensors on the host or the device (1-D with one head).  The engine's values are not changed.  Every error is
+        raised before the library is called."""
+        import torch
+        heads = _engine_heads(heads, self.glb_n)
+        dt = _operands_dtype(XS, out)
+        f32 = dt == "f32"
+        want = torch.float32 if f32 else torch.float64
+        for name, t in (("XT", XT), ("a", a)):
+            if not isinstance(t, torch.Tensor):
+                raise TypeError("%s must be a torch tensor on the device" % name)
+            if t.dtype != want:
+                raise TypeError("%s must have the dtype of XS and out (%s is %s)" % (name, name, t.dtype))
+        if XT.dim() != 2:
+            raise TypeError("XT must be 2-D")
+        if XT.shape[1] != self.glb_n or XT.shape[0] < self.A_nrow:
+            raise ValueError("XT is %s, this rank needs (%d, %d)" % (tuple(XT.shape), self.A_nrow, self.glb_n))
+        if XT.shape[1] > 1 and XT.stride(1) != 1:
+            raise ValueError("XT must be contiguous along its rows")
+        if a.dim() not in (1, 2) or a.numel() != self.glb_n or not a.is_contiguous() or (a.dim() == 2 and a.shape[0] != heads):
+            raise ValueError("a must hold glb_n = %d contiguous elements, 1-D or (heads, dv); it is %s" % (self.glb_n, tuple(a.shape)))
+        cap = 4 * 64 * (4 if f32 else 2)
+        if self.glb_n // heads > cap:
+            raise ValueError("the fused GATv2 attention takes at most %d columns per head (dv = %d)" % (cap, self.glb_n // heads))
+        if bias not in (False, True, 0, 1):
+            raise ValueError("bias must be a bool, got %r" % (bias,))
+        slope = float(slope)
+        if not np.isfinite(slope):
+            raise ValueError("slope must be finite, got %r" % (slope,))
+        kb = getattr(self, "loc_B_nrow", None)
+        xp, ldx, _kx = _ptr_ld(XS, layout, f32)
+        op, ldo, _ko = _ptr_ld(out, layout, f32)
+        _check_blocks(layout, self.glb_n, (("XS", XS, kb), ("out", out, self.A_nrow)))
+        lp, _kl = _vec_ptr("lse", _mh_vec("lse", lse, heads), f32, self.A_nrow * heads)
+        pp, _kp = _vec_ptr("p_out", _mh_vec("p_out", p_out, heads), f32, self.nnz() * heads)
+        for name, t in (("XT", XT), ("a", a)):
+            if not t.is_cuda:
+                raise TypeError("%s must be on the device" % name)
+        if stream is None:
+            stream = _current_stream(out)
+        if stream is None:
+            stream = _current_stream(XT)
+        fn = self._lib.crp_rp_spmm_gatv2_f32_ex if f32 else self._lib.crp_rp_spmm_gatv2_ex
+        fn(self.handle, layout, heads, slope, int(bool(bias)), XT.data_ptr() or None, max(XT.stride(0), self.glb_n), a.data_ptr() or None,
+           xp, ldx, op, ldo, lp, pp, stream)
+
+    def gatv2_built(self):
+        """True once a ``gatv2_attention`` has uploaded the parts' positions (crp_rp_spmm_gatv2_built)."""
+        return bool(self._lib.crp_rp_spmm_gatv2_built(self.handle))
+
     def attention_bwd(self, Q, K, V, O, dO, lse, dQ, dK, dV, scale=1.0, bias=False, ds_out=None, stream=None, heads=1):
         """The fused backward of ``attention`` over this rank's rows of A (crp_rp_spmm_attention_bwd_ex / _f32_ex, by the operands'
         dtype): with ``O`` and ``lse`` as the forward wrote them and the upstream gradient ``dO``, writes dQ (A_nrow x glb_n), dK

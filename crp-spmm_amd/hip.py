@@ -455,6 +455,125 @@ class CsrDev:
                    _stream(dV) if stream is None else stream), fn.__name__)
         return d_er, dV
 
+    def gatv2_attention(self, XT, XS0, a, XS1=None, slope=0.2, bias=False, out=None, lse=None, p_out=None, out_pos=None, stream=None,
+                        heads=1):
+        """Fused GATv2 attention over this matrix's pattern (crp_gatv2_attention_csr_f64 / _f32, by the operands' dtype): for every
+        head h, s_p = sum_j a[h, j] * leaky_relu(XT[i]_h[j] + XS[c_p]_h[j], slope) (+ the matrix's value of p with ``bias``) and
+        out[i]_h = sum_p softmax_p(s) * XS[c_p]_h over the nonzeros p = (i, c_p) of row i; c >= 0 reads row c of XS0, c < 0 row ~c
+        of XS1.  ``XT`` (rows, heads * dv) and ``XS0`` / ``XS1`` are 2-D row-major float64 or float32 cuda tensors of one dtype and
+        width; ``a`` holds heads * dv contiguous elements (1-D, or (heads, dv)); ``out`` has that width and a row per row of
+        ``XT`` (allocated when None).  Optional outputs: ``lse`` contiguous (rows, heads), ``p_out`` contiguous (nnz, heads) --
+        nonzero p writes row out_pos[p] when ``out_pos`` (int32, nnz entries) is given; with one head both may be 1-D.  A head
+        wider than 512 (float64) / 1024 (float32) columns raises ValueError.  The matrix's values are not changed.  Returns
+        ``out``.  Every error is raised before the library is called."""
+        import torch
+        heads = _heads(heads)
+        vops = [("XT", XT), ("XS0", XS0)] + ([("XS1", XS1)] if XS1 is not None else []) + ([("out", out)] if out is not None else [])
+        vecs = [(n_, t) for n_, t in (("lse", lse), ("p_out", p_out)) if t is not None]
+        nv, slope, bias = _gatv2_operands(vops, vecs, a, slope, bias, heads)
+        lse, p_out = _gat_flat("lse", lse, heads), _gat_flat("p_out", p_out, heads)
+        x_nrow = getattr(self, "_x_nrow", self.nrow)
+        for name, t in (("XT", XT), ("out", out)):
+            if t is not None and t.size(0) < x_nrow:
+                raise ValueError("%s has %d rows, the matrix needs %d" % (name, t.size(0), x_nrow))
+        if XS0.size(0) < self.ncol:
+            raise ValueError("XS0 has %d rows, the matrix has %d columns" % (XS0.size(0), self.ncol))
+        if lse is not None and lse.numel() < x_nrow * heads:
+            raise ValueError("lse must hold %d rows of %d heads" % (x_nrow, heads))
+        _gat_out_pos(out_pos, p_out, "p_out", self.nnz, heads)
+        _attention_on_device(vops + [("a", a)] + [(n_, t) for n_, t in (("lse", lse), ("p_out", p_out), ("out_pos", out_pos))
+                                                  if t is not None])
+        if out is None:
+            out = torch.empty((x_nrow, nv), dtype=XT.dtype, device=XT.device)
+        if self.nrow == 0:
+            return out
+        fn = self._lib.crp_gatv2_attention_csr_f32 if XT.dtype == torch.float32 else self._lib.crp_gatv2_attention_csr_f64
+        x1p, ldx1 = (XS1.data_ptr(), XS1.stride(0)) if XS1 is not None else (None, 0)
+        ptr = lambda t: (t.data_ptr() or None) if t is not None else None
+        L.check(fn(self.handle, heads, nv // heads, slope, bias, XT.data_ptr(), XT.stride(0), ptr(XS0), XS0.stride(0), x1p, ldx1,
+                   a.data_ptr(), out.data_ptr(), out.stride(0), ptr(lse), ptr(p_out), ptr(out_pos),
+                   _stream(out) if stream is None else stream), fn.__name__)
+        return out
+
+    def gatv2_attention_bwd_row(self, XT, XS0, a, O, dO, lse, XS1=None, slope=0.2, bias=False, dXT=None, da_part=None, delta=None,
+                                ds_out=None, out_pos=None, stream=None, heads=1):
+        """The row side of the fused backward of ``gatv2_attention`` (crp_gatv2_attention_bwd_row_csr_f64 / _f32), on the handle the
+        forward ran on: with ``O`` and ``lse`` as the forward wrote them and the upstream gradient ``dO``, delta[i, h] =
+        <dO[i]_h, O[i]_h>, dXT[i]_h[j] = sum_p dS_p * (z_pj > 0 ? a[h, j] : a[h, j] * slope) and da_part[i]_h[j] = sum_p dS_p *
+        leaky_relu(z_pj) -- the row's share of the gradient of ``a``, which ``col_sum`` adds over the rows -- with dS_p = p_p
+        (<dO[i]_h, XS[c_p]_h> - delta[i, h]) and p_p = exp(s_p - lse[i, h]).  ``dXT``, ``da_part`` (rows, heads * dv) and ``delta``
+        contiguous (rows, heads) are allocated when None; ``ds_out`` (optional, contiguous (nnz, heads)) receives dS_p -- at row
+        out_pos[p] when ``out_pos`` is given.  No output may alias an input.  Returns (dXT, da_part, delta)."""
+        import torch
+        heads = _heads(heads)
+        vops = ([("XT", XT), ("XS0", XS0)] + ([("XS1", XS1)] if XS1 is not None else []) + [("O", O), ("dO", dO)]
+                + [(n_, t) for n_, t in (("dXT", dXT), ("da_part", da_part)) if t is not None])
+        vecs = [("lse", lse)] + [(n_, t) for n_, t in (("delta", delta), ("ds_out", ds_out)) if t is not None]
+        nv, slope, bias = _gatv2_operands(vops, vecs, a, slope, bias, heads)
+        delta_given = delta
+        lse, delta, ds_out = _gat_flat("lse", lse, heads), _gat_flat("delta", delta, heads), _gat_flat("ds_out", ds_out, heads)
+        x_nrow = getattr(self, "_x_nrow", self.nrow)
+        for name, t in (("XT", XT), ("O", O), ("dO", dO), ("dXT", dXT), ("da_part", da_part)):
+            if t is not None and t.size(0) < x_nrow:
+                raise ValueError("%s has %d rows, the matrix needs %d" % (name, t.size(0), x_nrow))
+        if XS0.size(0) < self.ncol:
+            raise ValueError("XS0 has %d rows, the matrix has %d columns" % (XS0.size(0), self.ncol))
+        for name, t in (("lse", lse), ("delta", delta)):
+            if t is not None and t.numel() < x_nrow * heads:
+                raise ValueError("%s must hold %d rows of %d heads" % (name, x_nrow, heads))
+        _gat_out_pos(out_pos, ds_out, "ds_out", self.nnz, heads)
+        _attention_on_device(vops + [("a", a)] + vecs + ([("out_pos", out_pos)] if out_pos is not None else []))
+        if dXT is None:
+            dXT = torch.empty((x_nrow, nv), dtype=XT.dtype, device=XT.device)
+        if da_part is None:
+            da_part = torch.empty((x_nrow, nv), dtype=XT.dtype, device=XT.device)
+        if delta is None:
+            delta_given = torch.empty((x_nrow, heads), dtype=XT.dtype, device=XT.device)
+            delta = delta_given.view(-1)
+        if self.nrow == 0:
+            return dXT, da_part, delta_given
+        fn = self._lib.crp_gatv2_attention_bwd_row_csr_f32 if XT.dtype == torch.float32 else self._lib.crp_gatv2_attention_bwd_row_csr_f64
+        x1p, ldx1 = (XS1.data_ptr(), XS1.stride(0)) if XS1 is not None else (None, 0)
+        ptr = lambda t: (t.data_ptr() or None) if t is not None else None
+        L.check(fn(self.handle, heads, nv // heads, slope, bias, XT.data_ptr(), XT.stride(0), ptr(XS0), XS0.stride(0), x1p, ldx1,
+                   a.data_ptr(), O.data_ptr(), O.stride(0), dO.data_ptr(), dO.stride(0), lse.data_ptr(), dXT.data_ptr(), dXT.stride(0),
+                   da_part.data_ptr(), da_part.stride(0), delta.data_ptr(), ptr(ds_out), ptr(out_pos),
+                   _stream(dXT) if stream is None else stream), fn.__name__)
+        return dXT, da_part, delta_given
+
+    def gatv2_attention_bwd_col(self, XS, XT, a, dO, lse, delta, slope=0.2, bias=False, dXS=None, stream=None, heads=1):
+        """The column side of the fused backward of ``gatv2_attention`` (crp_gatv2_attention_bwd_col_csr_f64 / _f32), on a handle of
+        A^T (``from_transpose``): dXS[c]_h = sum_p dS_p * (z_p > 0 ? a_h : a_h * slope) + sum_p p_p dO[i_p]_h over column c of A --
+        two sums in this handle's order and one addition -- with ``lse`` from the forward and ``delta`` from
+        ``gatv2_attention_bwd_row``.  ``XS`` and ``dXS`` have a row per row of this handle; ``XT``, ``dO``, ``lse``, ``delta`` one per
+        column.  With ``bias`` the value added to a score is this handle's own.  ``dXS is XS`` is allowed (same tensor); it is
+        allocated when None.  Returns dXS."""
+        import torch
+        heads = _heads(heads)
+        vops = [("XS", XS), ("XT", XT), ("dO", dO)] + ([("dXS", dXS)] if dXS is not None else [])
+        nv, slope, bias = _gatv2_operands(vops, [("lse", lse), ("delta", delta)], a, slope, bias, heads)
+        lse, delta = _gat_flat("lse", lse, heads), _gat_flat("delta", delta, heads)
+        x_nrow = getattr(self, "_x_nrow", self.nrow)
+        for name, t in (("XS", XS), ("dXS", dXS)):
+            if t is not None and t.size(0) < x_nrow:
+                raise ValueError("%s has %d rows, the matrix needs %d" % (name, t.size(0), x_nrow))
+        for name, t in (("XT", XT), ("dO", dO)):
+            if t.size(0) < self.ncol:
+                raise ValueError("%s has %d rows, the matrix has %d columns" % (name, t.size(0), self.ncol))
+        for name, t in (("lse", lse), ("delta", delta)):
+            if t.numel() < self.ncol * heads:
+                raise ValueError("%s must hold %d rows of %d heads" % (name, self.ncol, heads))
+        _attention_on_device(vops + [("a", a), ("lse", lse), ("delta", delta)])
+        if dXS is None:
+            dXS = torch.empty((x_nrow, nv), dtype=XS.dtype, device=XS.device)
+        if self.nrow == 0:
+            return dXS
+        fn = self._lib.crp_gatv2_attention_bwd_col_csr_f32 if XS.dtype == torch.float32 else self._lib.crp_gatv2_attention_bwd_col_csr_f64
+        L.check(fn(self.handle, heads, nv // heads, slope, bias, XS.data_ptr(), XS.stride(0), XT.data_ptr() or None, XT.stride(0),
+                   a.data_ptr(), dO.data_ptr() or None, dO.stride(0), lse.data_ptr() or None, delta.data_ptr() or None,
+                   dXS.data_ptr(), dXS.stride(0), _stream(dXS) if stream is None else stream), fn.__name__)
+        return dXS
+
     def row_softmax(self, s, out=None, stream=None):
         """Row softmax over this matrix's pattern (crp_csr_dev_row_softmax_f64 / _f32, by the dtype of ``s``): for every row,
         out[p] = exp(s[p] - max) / sum over the row's nonzeros p, which count in the handle's CSR order -- what ``sddmm``
@@ -696,6 +815,47 @@ def _gat_out_pos(out_pos, out, name, nnz, heads):
         raise ValueError("%s has %d rows, the matrix %d nonzeros" % (name, out.numel() // heads, nnz))
 
 
+def _gatv2_operands(vops, vecs, a, slope, bias, heads):
+    """The operands of the three GATv2 wrappers, checked before any library call: vops 2-D of one width that ``heads`` divides,
+    vecs per-row or per-nonzero tensors, ``a`` that many contiguous elements, all float64 or float32 of the first's dtype, rows
+    contiguous; one head's width is held to BWD_WIDTH_CAP in both directions.  Returns (nv, slope, bias) as the C call takes them
+    -- nv the whole width; the device is checked by _attention_on_device."""
+    import torch
+    head, first = vops[0]
+    floats, dtype = (torch.float64, torch.float32), getattr(first, "dtype", None)
+    for name, t in vops + [("a", a)] + vecs:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s must be a torch tensor on the device" % name)
+        if t.dtype not in floats:
+            raise TypeError("%s must be float64 or float32, got %s" % (name, t.dtype))
+        if t.dtype != dtype:
+            raise TypeError("the operands must have one dtype (%s is %s, %s is %s)" % (head, dtype, name, t.dtype))
+    for name, t in vops:
+        if t.dim() != 2:
+            raise TypeError("%s must be a 2-D torch tensor on the device" % name)
+        if t.size(1) > 1 and t.stride(1) != 1:
+            raise ValueError("%s must be contiguous along its rows" % name)
+    if bias not in (False, True, 0, 1):
+        raise ValueError("bias must be a bool, got %r" % (bias,))
+    slope = float(slope)
+    if not np.isfinite(slope):
+        raise ValueError("slope must be finite, got %r" % (slope,))
+    nv = first.size(1)
+    if nv < 1:
+        raise ValueError("the operands need at least one column")
+    for name, t in vops[1:]:
+        if t.size(1) != nv:
+            raise ValueError("%s has %d columns, %s has %d" % (name, t.size(1), head, nv))
+    if nv % heads:
+        raise ValueError("%d heads do not divide the width (nv = %d)" % (heads, nv))
+    if a.dim() not in (1, 2) or a.numel() != nv or not a.is_contiguous() or (a.dim() == 2 and a.size(0) != heads):
+        raise ValueError("a must hold heads * dv = %d contiguous elements, 1-D or (heads, dv); it is %s" % (nv, tuple(a.shape)))
+    cap = BWD_WIDTH_CAP[first.element_size()]
+    if nv // heads > cap:
+        raise ValueError("the fused GATv2 attention takes at most %d columns per head in %s (dv = %d)" % (cap, first.dtype, nv // heads))
+    return nv, slope, int(bool(bias))
+
+
 def _attention_on_device(named):
     """... and, after every shape check, all of them on the first's device (all pointers are device pointers)"""
     head, first = named[0]
@@ -851,6 +1011,92 @@ def _gat_attention_fn():
 
     _GAT_ATTENTION_FN = GatAttention
     return GatAttention
+
+
+def col_sum(src, out=None, stream=None):
+    """Column sums of a 2-D row-major float64 or float32 cuda tensor (crp_col_sum_f64 / _f32): blocks of 256 consecutive rows
+    are summed per column from +0 in ascending row, and the block sums are added left to right -- a fixed order, no atomics,
+    so the bits depend on the dtype, the shape and the data only.  ``out`` (contiguous, one element per column) is allocated
+    when None.  Returns ``out``.  Every error is raised before the library is called."""
+    import torch
+    if not isinstance(src, torch.Tensor) or src.dim() != 2:
+        raise TypeError("src must be a 2-D torch tensor on the device")
+    if src.dtype not in (torch.float64, torch.float32):
+        raise TypeError("src must be float64 or float32, got %s" % (src.dtype,))
+    if src.size(0) > 0 and src.size(1) > 1 and src.stride(1) != 1:
+        raise ValueError("src must be contiguous along its rows")
+    nrow, n = src.shape
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or out.dtype != src.dtype:
+            raise TypeError("out must be a torch tensor of src's dtype")
+        if out.numel() != n or not out.is_contiguous():
+            raise ValueError("out must hold %d contiguous elements" % n)
+    _attention_on_device([("src", src)] + ([("out", out)] if out is not None else []))
+    if out is None:
+        out = torch.empty((n,), dtype=src.dtype, device=src.device)
+    if n == 0:
+        return out
+    work = torch.empty((max(1, (nrow + 255) // 256) * n,), dtype=src.dtype, device=src.device)
+    lib = L.load()
+    fn = lib.crp_col_sum_f32 if src.dtype == torch.float32 else lib.crp_col_sum_f64
+    L.check(fn(nrow, n, src.data_ptr() or None, max(src.stride(0), n), work.data_ptr(), out.data_ptr(),
+               _stream(out) if stream is None else stream), fn.__name__)
+    return out
+
+
+def gatv2_attention(A, At, XT, XS, a, slope=0.2, bias=False, heads=1):
+    """The GATv2 layer's attention, out[i]_h = sum_p softmax_p(sum_j a[h, j] leaky_relu(XT[i]_h[j] + XS[c_p]_h[j], slope) (+ A's
+    values with ``bias``)) XS[c_p]_h, as a differentiable function of XT, XS and a: ``A`` is the ``CsrDev`` of the pattern, ``At``
+    the ``CsrDev.from_transpose`` of the same CSR (with ``bias`` both hold the same values).  The forward is
+    ``A.gatv2_attention``, which keeps O and lse; the backward is ``A.gatv2_attention_bwd_row``, ``At.gatv2_attention_bwd_col`` and
+    ``col_sum`` of the rows' shares of the gradient of ``a``.  Nothing nnz-sized is stored.  ``XT`` (rows, heads * dv) and ``XS``
+    (columns, heads * dv) are 2-D row-major cuda tensors of one dtype, ``a`` holds heads * dv elements (1-D or (heads, dv)).  One
+    tensor may be passed as XT and XS (shared weights): its gradient is the sum of both.  The matrix's values are constants here.
+    ``At`` must be the transpose of ``A``: its shape and nonzero count are checked, its pattern is not."""
+    heads = _heads(heads)
+    if At.nrow != A.ncol or At.ncol != A.nrow or At.nnz != A.nnz:
+        raise ValueError("At is %d x %d with %d nonzeros: not the transpose of A (%d x %d, %d)"
+                         % (At.nrow, At.ncol, At.nnz, A.nrow, A.ncol, A.nnz))
+    return _gatv2_attention_fn().apply(XT, XS, a, A, At, float(slope), bool(bias), heads)
+
+
+_GATV2_ATTENTION_FN = None
+
+
+def _gatv2_attention_fn():
+    """the autograd.Function behind ``gatv2_attention``, made on first use"""
+    global _GATV2_ATTENTION_FN
+    if _GATV2_ATTENTION_FN is not None:
+        return _GATV2_ATTENTION_FN
+    import torch
+
+    class Gatv2Attention(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, XT, XS, a, A, At, slope, bias, heads):
+            XT, XS = (t if t.dim() != 2 or t.stride(-1) == 1 else t.contiguous() for t in (XT.detach(), XS.detach()))
+            a = a.detach().contiguous()
+            lse = torch.empty((XT.shape[0], heads), dtype=XT.dtype, device=XT.device)
+            O = A.gatv2_attention(XT, XS, a, slope=slope, bias=bias, lse=lse, heads=heads)
+            ctx.save_for_backward(XT, XS, a, O, lse)
+            ctx.handles = (A, At, slope, bias, heads)
+            return O
+
+        @staticmethod
+        def backward(ctx, dO):
+            XT, XS, a, O, lse = ctx.saved_tensors
+            A, At, slope, bias, heads = ctx.handles
+            dO = dO if dO.stride(-1) == 1 else dO.contiguous()
+            dXT = da_part = None
+            if getattr(A, "_x_nrow", A.nrow) != A.nrow:         # a row subset writes the rows it names: the others are zero
+                dXT, da_part = torch.zeros_like(XT), torch.zeros_like(XT)
+            dXT, da_part, delta = A.gatv2_attention_bwd_row(XT, XS, a, O, dO, lse, slope=slope, bias=bias, dXT=dXT, da_part=da_part,
+                                                            heads=heads)
+            dXS = At.gatv2_attention_bwd_col(XS, XT, a, dO, lse, delta, slope=slope, bias=bias, heads=heads)
+            da = col_sum(da_part).view(a.shape)
+            return dXT, dXS, da, None, None, None, None, None
+
+    _GATV2_ATTENTION_FN = Gatv2Attention
+    return Gatv2Attention
 
 
 def spmm_csr(A, B0, C_out, n=None, layout=0, B1=None, variant=0, stream=None):

@@ -246,6 +246,28 @@ void crp_rp_spmm_gat_f32_ex(crp_rp_spmm_p rp_spmm, int layout, int heads, double
                             const float *er, long long lder, const float *V, long long ldV, float *O, long long ldO,
                             float *lse, float *p_out, void *stream);
 int crp_rp_spmm_gat_built(crp_rp_spmm_p rp_spmm);
+/* Fused GATv2 attention over this rank's rows of A, forward (crpspmm_hip.h, crp_gatv2_attention_csr_*): for every local row i, head
+ * h and nonzero p = (i, c_p) of the GLOBAL matrix, s = sum_j a_h[j] leaky_relu(XT[i]_h[j] + XS[c_p]_h[j], slope) (+ the engine's
+ * current value of p when bias = 1) and O[i]_h = sum_p softmax_p(s) * XS[c_p]_h.  `heads` >= 1 must divide glb_n and every head has
+ * dv = glb_n / heads columns, at most the width cap of the handle call (anything else aborts).  XS and O are this rank's
+ * loc_B_nrow x glb_n and A_nrow x glb_n blocks, in either layout, on the host or the device, handled as crp_rp_spmm_gat_ex
+ * handles V and O: XS travels as B does, through the forward exchange only -- the same layouts, host operands and split-engine
+ * overlap -- and there is no second exchange.  XT (A_nrow x glb_n, row-major, ldXT >= glb_n) and a (glb_n elements) are DEVICE
+ * pointers local to the rank (anything else aborts); lse (A_nrow x heads) and p_out (heads values per local nonzero: entry
+ * (p, h) at p * heads + h, p in A_val's order) are optional, host or device.  The parts write O and lse through their row maps
+ * and p_out through the positions crp_rp_spmm_sddmm_ex uses; the first call uploads those and nothing before it does
+ * (crp_rp_spmm_gatv2_built: 0, then 1; that call blocks).  The engine's values are not changed.  O, lse and p_out equal
+ * crp_gatv2_attention_csr_* on the whole matrix bit for bit, whatever the rank count, the timing mode and the number of calls.
+ * Statistics and the completion rule as crp_rp_spmm_attention_ex.  glb_n = 0 computes nothing.  A plan-only engine aborts, as
+ * do a layout or a bias other than 0 or 1 and a non-finite slope; a NULL engine is a no-op.  The engine backward is not offered
+ * yet: the handle calls crp_gatv2_attention_bwd_*_csr_* serve one device. */
+void crp_rp_spmm_gatv2_ex(crp_rp_spmm_p rp_spmm, int layout, int heads, double slope, int bias, const double *XT, long long ldXT,
+                          const double *a, const double *XS, long long ldXS, double *O, long long ldO,
+                          double *lse, double *p_out, void *stream);
+void crp_rp_spmm_gatv2_f32_ex(crp_rp_spmm_p rp_spmm, int layout, int heads, double slope, int bias, const float *XT, long long ldXT,
+                              const float *a, const float *XS, long long ldXS, float *O, long long ldO,
+                              float *lse, float *p_out, void *stream);
+int crp_rp_spmm_gatv2_built(crp_rp_spmm_p rp_spmm);
 void crp_rp_spmm_print_stat(crp_rp_spmm_p rp_spmm);
 void crp_rp_spmm_clear_stat(crp_rp_spmm_p rp_spmm);
 /* rp_spmm_init for a caller that ALSO holds the values in device memory, in the order of A_val (A_val_dev: the panel a

@@ -566,6 +566,79 @@ int crp_gat_attention_bwd_col_csr_f32(crp_csr_dev_p At, int heads, int dv, doubl
                                       const float *lse, const float *delta,
                                       float *d_er, long long ldd_er, float *dV, long long lddV, void *stream);
 
+/* ---- fused GATv2 attention: a LeakyReLU inside the dot with a, over A's pattern, forward and backward ----------------
+ * The score of a GATv2 layer.  For every row i of the handle, head h < heads and entry p = (i, c_p), p in the handle's CSR order:
+ *   z_j = XT[i]_h[j] + XS[c_p]_h[j]              (one rounding)
+ *   r_j = z_j > 0 ? z_j : slope * z_j            (one rounding, never contracted with anything)
+ *   s   = sum_j a_h[j] r_j                       (as crp_sddmm_csr_* forms a dot for (dtype, dv): per lane fma(a_j, r_j, acc) in
+ *                                                 ascending j from +0 in the SDDMM's column-to-lane assignment for G(dv) lanes,
+ *                                                 then the balanced binary tree over the lane number)
+ *   bias = 1: s = s + A's current value of p, one more rounding (shared by the heads; fp32: the fp32 copy of crp_sddmm_csr_f32)
+ *   O[i]_h = sum_p softmax_p(s) * XS[c_p]_h
+ * The gathered row XS[c] is the score operand and the value operand.  slope is any finite double; the fp32 form rounds it to
+ * float once.
+ * Operands (row-major device pointers): XT / O / dO / dXT / da_part / dXS have heads * dv columns, head h owns columns
+ * [h dv, (h + 1) dv).  XT is (rows of O, heads * dv), read through the handle's row map like Q of crp_attention_csr_*; XS0 / XS1
+ * are the two sources of the column code exactly as V0 / V1 of crp_gat_attention_csr_* (a source no code names may be NULL); a is
+ * heads * dv contiguous elements.  lse and delta are (rows, heads), contiguous; p_out and ds_out are (nnz, heads): entry
+ * pos heads + h with pos = out_pos[p], or p when out_pos is NULL.
+ * Forward: from s on this is crp_attention_mh_csr_* verbatim (batches of 8 in ascending p, the maximum taken at every batch,
+ * O = acc / l, lse = m + log l, p_out = exp(s - m) / l, acc = fma(e_u, XS[c_u][j], acc)): O, lse and p_out are bit for bit what
+ * that order gives for these scores and (dtype, dv).  Special cases as there and as crp_gat_attention_csr_*: an empty row writes
+ * +0 and lse = -inf for every head; a one-entry row gives O = XS[c] bit for bit; s = -inf is a masked edge; an all-masked row
+ * writes zeros; NaN or +inf among a row's scores leaves that row's outputs unspecified.  XS is taken to be finite.
+ * Backward, with s re-formed exactly as above:  p = exp(s - lse[i][h]),  dP = < dO[i]_h, XS[c]_h >,  D = < dO[i]_h, O[i]_h > (both
+ * the SDDMM's dot for (dtype, dv)),  dS = p (dP - D) (p == 0: +0),  ag_j = z_j > 0 ? a_j : as_j with as_j = fl(a_j slope).
+ *   crp_gatv2_attention_bwd_row_csr_*, over a handle of A (two sources, row map, out_pos): writes delta[i][h] = D,
+ *   dXT[i]_h[j] with acc = fma(dS_p, ag_pj, acc) and da_part[i]_h[j] with acc = fma(dS_p, r_pj, acc), both from +0 in ascending p
+ *   -- da_part (rows, heads * dv) is the row's share of the gradient of a: crp_col_sum_* of it over the rows is da, nothing
+ *   nnz-sized is stored; all three required -- and, when ds_out is not NULL, ds_out[(pos, h)] = dS.  A row-subset handle writes
+ *   the rows its map names and no others.
+ *   crp_gatv2_attention_bwd_col_csr_*, over a handle of A^T (crp_csr_dev_create_t; one source: negative codes return -1; the
+ *   row map selects the XS / dXS row): takes delta as the row side wrote it, keeps accZ = fma(dS, ag, accZ) and
+ *   accV = fma(p, dO[i][j], accV) from +0 in that handle's CSR order and writes dXS[c]_h = accZ + accV, one addition.  With
+ *   XT = 0 and slope = 1 the two are the bits of crp_attention_bwd_kv_mh_csr_*'s dK and dV for Q = a in every row, K = V = XS.
+ *   With bias = 1 the value added is this handle's own value of the entry.  dXS == XS with the same pointer and leading
+ *   dimension is legal; no other aliasing is.
+ * s, p, dP and dS have the same bits on both sides.  Rows with lse = -inf give +0 everywhere; delta is still written.
+ * Width cap, both directions: a lane keeps its pieces of XT (or XS[c]), a and as for the unit, so dv <= 4 * 64 * W per head (512
+ * in fp64, 1024 in fp32); wider heads return CRP_GATV2_EWIDTH with nothing written.
+ * Error bounds: DESIGN.md 5p.  Asynchronous on `stream`; the stream contract of the attention calls holds word for word.
+ * Returns 0 (also for a handle without rows: nothing is launched), a HIP error (> 0), or a negative argument error before which
+ * nothing is written: -1 for a NULL handle or required pointer (forward: XT, a, O and a source that a code names; row side also
+ * dO, lse, dXT, da_part, delta; column side: XS, a, dXS, and XT, dO, lse, delta when the handle has a nonzero), heads < 1,
+ * dv < 1, a bias other than 0 or 1, a non-finite slope, negative column codes on the column side; -4 for a leading dimension
+ * below heads * dv; CRP_GATV2_EWIDTH. */
+#define CRP_GATV2_EWIDTH (-6)      /* dv above 4 * 64 * (elements per 16 bytes): the value of CRP_ATTN_BWD_EWIDTH */
+int crp_gatv2_attention_csr_f64(crp_csr_dev_p A, int heads, int dv, double slope, int bias,
+                                const double *XT, long long ldXT,
+                                const double *XS0, long long ldXS0, const double *XS1, long long ldXS1, const double *a,
+                                double *O, long long ldO, double *lse, double *p_out, const int *out_pos, void *stream);
+int crp_gatv2_attention_bwd_row_csr_f64(crp_csr_dev_p A, int heads, int dv, double slope, int bias,
+                                        const double *XT, long long ldXT,
+                                        const double *XS0, long long ldXS0, const double *XS1, long long ldXS1, const double *a,
+                                        const double *O, long long ldO, const double *dO, long long lddO, const double *lse,
+                                        double *dXT, long long lddXT, double *da_part, long long ldda,
+                                        double *delta, double *ds_out, const int *out_pos, void *stream);
+int crp_gatv2_attention_bwd_col_csr_f64(crp_csr_dev_p At, int heads, int dv, double slope, int bias,
+                                        const double *XS, long long ldXS, const double *XT, long long ldXT, const double *a,
+                                        const double *dO, long long lddO, const double *lse, const double *delta,
+                                        double *dXS, long long lddXS, void *stream);
+int crp_gatv2_attention_csr_f32(crp_csr_dev_p A, int heads, int dv, double slope, int bias,
+                                const float *XT, long long ldXT,
+                                const float *XS0, long long ldXS0, const float *XS1, long long ldXS1, const float *a,
+                                float *O, long long ldO, float *lse, float *p_out, const int *out_pos, void *stream);
+int crp_gatv2_attention_bwd_row_csr_f32(crp_csr_dev_p A, int heads, int dv, double slope, int bias,
+                                        const float *XT, long long ldXT,
+                                        const float *XS0, long long ldXS0, const float *XS1, long long ldXS1, const float *a,
+                                        const float *O, long long ldO, const float *dO, long long lddO, const float *lse,
+                                        float *dXT, long long lddXT, float *da_part, long long ldda,
+                                        float *delta, float *ds_out, const int *out_pos, void *stream);
+int crp_gatv2_attention_bwd_col_csr_f32(crp_csr_dev_p At, int heads, int dv, double slope, int bias,
+                                        const float *XS, long long ldXS, const float *XT, long long ldXT, const float *a,
+                                        const float *dO, long long lddO, const float *lse, const float *delta,
+                                        float *dXS, long long lddXS, void *stream);
+
 /* ---- row softmax over A's pattern (edge softmax) and its Jacobian product ------
  * For every row r with entries p in [rowptr[r], rowptr[r + 1]):
  *   forward :  m = max_p s[p],  e_p = exp(s[p] - m),  y[p] = e_p / sum_q e_q
@@ -644,6 +717,15 @@ int crp_gather_vals_f32_f64(long long n, const int *map, const float *src, doubl
  * nseg > 1, or a positive HIP error; nothing is written before the arguments have passed. */
 int crp_sum_segments_f64(int nseg, long long len, const double *src, long long seg_stride, double *out, void *stream);
 int crp_sum_segments_f32(int nseg, long long len, const float *src, long long seg_stride, float *out, void *stream);
+/* column sums: out[j] = the sum over r < nrow of src[r * lds + j] for j < n (da of the GATv2 backward from da_part).  Rows are
+ * taken in blocks of 256 consecutive rows; a block's sum per column runs from +0 in ascending row into work[b * n + j], and the
+ * block sums are then added left to right in ascending block, which is crp_sum_segments_*'s order.  work holds
+ * ceil(nrow / 256) * n elements.  Plain IEEE additions, no atomics and no LDS: the bits are a function of (dtype, nrow, n, data)
+ * only, not of lds or alignment, and repeated calls are bit-identical.  nrow == 0 writes +0.  Asynchronous on `stream`; device
+ * pointers.  Returns 0, -1 for a negative count, a NULL out or, with work to do, a NULL src or work, -4 for lds < n, or a
+ * positive HIP error; nothing is written before the arguments have passed. */
+int crp_col_sum_f64(int nrow, int n, const double *src, long long lds, double *work, double *out, void *stream);
+int crp_col_sum_f32(int nrow, int n, const float *src, long long lds, float *work, float *out, void *stream);
 /* out-of-place transpose: dst[c][r] = src[r][c] for an nrow x ncol row-major
  * src (equivalently col-major <-> row-major conversion). */
 int crp_transpose_f64(int nrow, int ncol, const double *src, long long lds,
