@@ -120,6 +120,12 @@ _GATV2_ARGS = {
     "gatv2_attention_bwd_col": [_V, _I, _I, C.c_double, _I, _V, _LL, _V, _LL, _V, _V, _LL, _V, _V, _V, _LL, _V],
 }
 _GATV2_SIGNATURES = {"crp_%s_csr_%s" % (stem, dt): (_I, args) for stem, args in _GATV2_ARGS.items() for dt in ("f64", "f32")}
+# ... and of both with attention dropout: crp_gat_attention_drop[_bwd_row|_bwd_col]_csr_*, (drop, seed) before the stream
+_ULL = C.c_ulonglong
+_DROP_SIGNATURES = {"crp_%s_csr_%s" % (stem.replace("_attention", "_attention_drop"), dt): (_I, args[:-1] + [C.c_double, _ULL, _V])
+                    for table in (_GAT_ARGS, _GATV2_ARGS) for stem, args in table.items() for dt in ("f64", "f32")}
+_DROP_SIGNATURES["crp_dropout_keep_host"] = (_I, [_ULL, C.c_uint, C.c_uint, C.c_uint, C.c_double])
+_DROP_SIGNATURES["crp_dropout_mask_csr"] = (_I, [_V, _I, C.c_double, _ULL, _V, _V, _V])
 
 # name -> (restype, argtypes); every symbol declared in include/crpspmm_hip.h,
 # include/crp_comm.h, include/crp_engine.h, include/utils.h, include/spmat_part.h,
@@ -196,6 +202,7 @@ SIGNATURES = {
     **_ATTENTION_SIGNATURES,
     **_GAT_SIGNATURES,
     **_GATV2_SIGNATURES,
+    **_DROP_SIGNATURES,
     "crp_row_softmax_f64": (_I, [_I, _V, _V, _V, _V]),
     "crp_row_softmax_f32": (_I, [_I, _V, _V, _V, _V]),
     "crp_row_softmax_bwd_f64": (_I, [_I, _V, _V, _V, _V, _V]),

@@ -38,6 +38,14 @@
 // Rows with lse = -inf give +0 everywhere in the backward; delta is still written.
 //
 // ALIASING.  Column side: dV == V (exactly) is legal, a group reads its slice of V[c] whole before it writes it.  Nothing else.
+//
+// DROPOUT (the DROP instances; a.drop, dropout.h).  k_p = the keep bit of (row of O, column code, head).  Forward:
+// scores, batches, m, f, e_u and l are the plain call's -- the softmax runs over all edges -- and only the accumulator changes:
+// acc = fma(k_u ? e_u : +0, V[c_u][j], acc), O = fl(fl(acc / l) rs); lse and p_out keep the plain call's bits.  Backward: p, s, g
+// and D = < dO, O > (O is the dropped O) as above, dP' = k ? fl(dP rs) : +0, dS = p (dP' - D), and the value-side weight of dV is
+// w = k ? fl(p rs) : +0.  The two products with rs are roundings of their own (gt_mul).  The lane that loads the column code of
+// its own entry of a chunk draws that entry's bit -- one draw per entry and (unit, V block) -- and one ballot hands the chunk's
+// bits to the group; a batch takes its 8 bits from that word.  DROP = false compiles to the code without any of this.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <initializer_list>
@@ -88,6 +96,27 @@ __device__ __forceinline__ T gt_dz(const T ds, const T g)
     const T dz = ds * g;
     return dz;
 }
+// the products with rs of the DROP instances: roundings of their own, so that dP rs - D never becomes one FMA
+template <typename T>
+__device__ __forceinline__ T gt_mul(const T x, const T y)
+{
+#pragma clang fp contract(off)
+    const T r = x * y;
+    return r;
+}
+
+// The keep bits of a chunk of LPR entries: the lane that holds entry `lir` of the chunk (live: it has one) draws the bit of
+// (r, c, h); bit e of the result is entry e's, the same word in every lane of the group.  Every lane of a group is active here
+// together (the chunk loop's bounds are the group's); lanes of other groups that are not contribute 0 to bits this group drops.
+template <typename T, int LPR>
+__device__ __forceinline__ unsigned long long gt_keep_bits(const DropArgs<T> &d, const bool live, const uint32_t r, const uint32_t c,
+                                                           const uint32_t h, const int lir)
+{
+    const bool k = live && dropout_keep(d.seed_lo, d.seed_hi, r, c, h, d.thr);
+    const unsigned long long all = __ballot(k);
+    if constexpr (LPR == 64) return all;
+    else return all >> ((threadIdx.x & 63u) - (unsigned) lir);
+}
 
 // where the er scalar of column code c and head h lies
 template <typename T>
@@ -98,7 +127,7 @@ __device__ __forceinline__ const T *gt_er(const int c, const int64_t h, const T 
 
 // ---- forward ------------------------------------------------------------------------------------------------------------------
 // LPR lanes per unit (row, head); PV pieces of the accumulator per lane and V block.  VEC: 16-byte accesses; else elements.
-template <typename T, int LPR, int PV, bool VEC>
+template <typename T, int LPR, int PV, bool VEC, bool DROP>
 __global__ __launch_bounds__(256) void gat_fwd_kernel(const GatArgs<T> a)
 {
     typedef typename GtPiece<T>::type PT;
@@ -197,6 +226,8 @@ __global__ __launch_bounds__(256) void gat_fwd_kernel(const GatArgs<T> a)
             const int my = p0 + lir;
             const int c = (my < pe) ? a.colidx[my] : 0;
             const int cnt = min(LPR, pe - p0);
+            unsigned long long km = 0;                  // (DROP: the chunk's keep bits)
+            if constexpr (DROP) km = gt_keep_bits<T, LPR>(a.drop, my < pe, (uint32_t) orow, (uint32_t) c, (uint32_t) h, lir);
             for (int j = 0; j < cnt; j += UNR)
             {
                 // the scalar of this lane's entry (lir & 7) of the batch goes out first: a tiny gather under the V loads.
@@ -246,6 +277,12 @@ __global__ __launch_bounds__(256) void gat_fwd_kernel(const GatArgs<T> a)
                 l = l * f;
 #pragma unroll
                 for (int q = 0; q < UNR; q++) l = l + eu[q];
+                if constexpr (DROP)                     // l has every edge; the accumulator takes the kept ones
+                {
+                    const unsigned kb = (unsigned) (km >> j);
+#pragma unroll
+                    for (int q = 0; q < UNR; q++) eu[q] = ((kb >> q) & 1u) ? eu[q] : (T) 0;
+                }
 #pragma unroll
                 for (int v = 0; v < PV; v++)
 #pragma unroll
@@ -272,7 +309,11 @@ __global__ __launch_bounds__(256) void gat_fwd_kernel(const GatArgs<T> a)
 #pragma unroll
         for (int v = 0; v < PV; v++)
 #pragma unroll
-            for (int w = 0; w < VW; w++) acc[v][w] = masked ? (T) 0 : acc[v][w] / l;
+            for (int w = 0; w < VW; w++)
+            {
+                acc[v][w] = masked ? (T) 0 : acc[v][w] / l;
+                if constexpr (DROP) acc[v][w] = gt_mul<T>(acc[v][w], a.drop.rs);
+            }
         store_o(acc, vb);
         if (first)
         {
@@ -437,18 +478,25 @@ __device__ __forceinline__ T gt_reduce8(const T (&part)[GT_UNR], const int lir)
     return r;
 }
 
-// p, dS and dZ of one entry from its score, the LeakyReLU's derivative and dP (see FIXED ORDER); dead: lse == -inf
-template <typename T>
-__device__ __forceinline__ void gt_entry(const T s, const T g, const T dp, const T lse, const T delta, const bool dead, T *pp, T *ds, T *dz)
+// p, dS and dZ of one entry from its score, the LeakyReLU's derivative and dP (see FIXED ORDER); dead: lse == -inf.  DROP: dP
+// counts as dP' = keep ? fl(dP rs) : +0, and *pp is the value-side weight w = keep ? fl(p rs) : +0 (see DROPOUT)
+template <typename T, bool DROP>
+__device__ __forceinline__ void gt_entry(const T s, const T g, T dp, const T lse, const T delta, const bool dead, const bool keep, const T rs,
+                                         T *pp, T *ds, T *dz)
 {
     const T e = dead ? (T) 0 : gt_exp(s - lse);
-    *pp = e;
+    if constexpr (DROP)
+    {
+        dp = keep ? gt_mul<T>(dp, rs) : (T) 0;
+        *pp = keep ? gt_mul<T>(e, rs) : (T) 0;
+    }
+    else *pp = e;
     *ds = (e == (T) 0) ? (T) 0 : e * (dp - delta);
     *dz = (e == (T) 0) ? (T) 0 : gt_dz<T>(*ds, g);
 }
 
 // ---- backward, row side: delta, d_el and ds_out over a handle of A ----------------------------------------------------------------
-template <typename T, int LPR, int PV, bool VEC>
+template <typename T, int LPR, int PV, bool VEC, bool DROP>
 __global__ __launch_bounds__(256) void gat_bwd_row_kernel(const GatBwdRowArgs<T> a)
 {
     constexpr int VW  = GtPiece<T>::VW;
@@ -505,6 +553,8 @@ __global__ __launch_bounds__(256) void gat_bwd_row_kernel(const GatBwdRowArgs<T>
         const int my = p0 + lir;
         const int c = (my < pe) ? a.colidx[my] : 0;
         const int cnt = min(LPR, pe - p0);
+        unsigned long long km = 0;                      // (DROP: the chunk's keep bits)
+        if constexpr (DROP) km = gt_keep_bits<T, LPR>(a.drop, my < pe, (uint32_t) orow, (uint32_t) c, (uint32_t) h, lir);
         for (int j = 0; j < cnt; j += UNR)
         {
             // indices past the row end are clamped to the row's last entry: a valid row whose dS counts as +0
@@ -529,7 +579,7 @@ __global__ __launch_bounds__(256) void gat_bwd_row_kernel(const GatBwdRowArgs<T>
             {
                 T g;
                 const T s = gt_score<T>(elv, erv, slope, bias, bv, &g);
-                gt_entry<T>(s, g, rp, lse, delta, false, &prob, &ds, &dz);
+                gt_entry<T, DROP>(s, g, rp, lse, delta, false, ((km >> mine) & 1u) != 0, a.drop.rs, &prob, &ds, &dz);
                 if (a.ds_out != nullptr && lir < UNR)
                 {
                     const int p = p0 + mine;
@@ -544,7 +594,7 @@ __global__ __launch_bounds__(256) void gat_bwd_row_kernel(const GatBwdRowArgs<T>
 }
 
 // ---- backward, column side: d_er and dV over a handle of A^T (the unit is (column c, head h)) ----------------------------------
-template <typename T, int LPR, int PV, bool VEC>
+template <typename T, int LPR, int PV, bool VEC, bool DROP>
 __global__ __launch_bounds__(256) void gat_bwd_col_kernel(const GatBwdColArgs<T> a)
 {
     constexpr int VW  = GtPiece<T>::VW;
@@ -592,6 +642,8 @@ __global__ __launch_bounds__(256) void gat_bwd_col_kernel(const GatBwdColArgs<T>
         const int my = p0 + lir;
         const int c = (my < pe) ? a.colidx[my] : 0;
         const int cnt = min(LPR, pe - p0);
+        unsigned long long km = 0;                      // (DROP: the chunk's keep bits; the entry's row of A is r, this unit's row c)
+        if constexpr (DROP) km = gt_keep_bits<T, LPR>(a.drop, my < pe, (uint32_t) c, (uint32_t) crow, (uint32_t) h, lir);
         for (int j = 0; j < cnt; j += UNR)
         {
             const int mine = j + (lir & 7);
@@ -616,7 +668,7 @@ __global__ __launch_bounds__(256) void gat_bwd_col_kernel(const GatBwdColArgs<T>
             {
                 T g;
                 const T s = gt_score<T>(elv, erv, slope, bias, bv, &g);
-                gt_entry<T>(s, g, rp, lse, dl, lse == ninf, &prob, &ds, &dz);
+                gt_entry<T, DROP>(s, g, rp, lse, dl, lse == ninf, ((km >> mine) & 1u) != 0, a.drop.rs, &prob, &ds, &dz);
             }
             T cp[UNR];
 #pragma unroll
@@ -671,8 +723,13 @@ static hipError_t launch_gat(const GatArgs<T> &a, hipStream_t s)
     const bool vec = gt_aligned({a.V0, a.V1, a.O}, {a.nv, a.ldO, a.V0 ? a.ldV0 : 0, a.V1 ? a.ldV1 : 0}, VW);
     dim3 grid;
     if (!gt_grid(a.nrow, a.heads, 256 / LPR, &grid)) return hipErrorInvalidValue;
-    if (vec) hipLaunchKernelGGL((gat_fwd_kernel<T, LPR, PV, true>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((gat_fwd_kernel<T, LPR, PV, false>), grid, dim3(256), 0, s, a);
+    if (a.drop.on)
+    {
+        if (vec) hipLaunchKernelGGL((gat_fwd_kernel<T, LPR, PV, true, true>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((gat_fwd_kernel<T, LPR, PV, false, true>), grid, dim3(256), 0, s, a);
+    }
+    else if (vec) hipLaunchKernelGGL((gat_fwd_kernel<T, LPR, PV, true, false>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((gat_fwd_kernel<T, LPR, PV, false, false>), grid, dim3(256), 0, s, a);
     return hipGetLastError();
 }
 template <typename T, int LPR, int PV>
@@ -682,8 +739,13 @@ static hipError_t launch_gat(const GatBwdRowArgs<T> &a, hipStream_t s)
     const bool vec = gt_aligned({a.V0, a.V1, a.O, a.dO}, {a.nv, a.ldO, a.lddO, a.V0 ? a.ldV0 : 0, a.V1 ? a.ldV1 : 0}, VW);
     dim3 grid;
     if (!gt_grid(a.nrow, a.heads, 256 / LPR, &grid)) return hipErrorInvalidValue;
-    if (vec) hipLaunchKernelGGL((gat_bwd_row_kernel<T, LPR, PV, true>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((gat_bwd_row_kernel<T, LPR, PV, false>), grid, dim3(256), 0, s, a);
+    if (a.drop.on)
+    {
+        if (vec) hipLaunchKernelGGL((gat_bwd_row_kernel<T, LPR, PV, true, true>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((gat_bwd_row_kernel<T, LPR, PV, false, true>), grid, dim3(256), 0, s, a);
+    }
+    else if (vec) hipLaunchKernelGGL((gat_bwd_row_kernel<T, LPR, PV, true, false>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((gat_bwd_row_kernel<T, LPR, PV, false, false>), grid, dim3(256), 0, s, a);
     return hipGetLastError();
 }
 template <typename T, int LPR, int PV>
@@ -693,8 +755,13 @@ static hipError_t launch_gat(const GatBwdColArgs<T> &a, hipStream_t s)
     const bool vec = gt_aligned({a.V, a.dO, a.dV}, {a.nv, a.ldV, a.lddO, a.lddV}, VW);
     dim3 grid;
     if (!gt_grid(a.nrow, a.heads, 256 / LPR, &grid)) return hipErrorInvalidValue;
-    if (vec) hipLaunchKernelGGL((gat_bwd_col_kernel<T, LPR, PV, true>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((gat_bwd_col_kernel<T, LPR, PV, false>), grid, dim3(256), 0, s, a);
+    if (a.drop.on)
+    {
+        if (vec) hipLaunchKernelGGL((gat_bwd_col_kernel<T, LPR, PV, true, true>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((gat_bwd_col_kernel<T, LPR, PV, false, true>), grid, dim3(256), 0, s, a);
+    }
+    else if (vec) hipLaunchKernelGGL((gat_bwd_col_kernel<T, LPR, PV, true, false>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((gat_bwd_col_kernel<T, LPR, PV, false, false>), grid, dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

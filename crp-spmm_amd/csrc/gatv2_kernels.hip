@@ -47,6 +47,14 @@
 //
 // ALIASING.  Column side: dXS == XS (exactly) is legal, a group reads its slice of XS[c] whole before it writes it and no other
 // unit reads it.  Nothing else.
+//
+// DROPOUT (the DROP instances; a.drop, dropout.h).  k_p = the keep bit of (row of O, column code, head).  Forward:
+// scores, batches, m, f, e_u and l are the plain call's -- the softmax runs over all edges -- and only the accumulator changes:
+// acc = fma(k_u ? e_u : +0, XS[c_u][j], acc), O = fl(fl(acc / l) rs); lse and p_out keep the plain call's bits.  Backward: p, s
+// and D = < dO, O > (O is the dropped O) as above, dP' = k ? fl(dP rs) : +0, dS = p (dP' - D), and accV takes the weight
+// w = k ? fl(p rs) : +0 in the place of p.  The two products with rs are roundings of their own (g2_mul).  The lane that loads the
+// column code of its own entry of a chunk draws that entry's bit, one ballot hands the chunk's bits to the group, and a batch takes
+// its 8 bits from that word.  DROP = false compiles to the code without any of this.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <initializer_list>
@@ -86,7 +94,7 @@ __device__ __forceinline__ T g2_lrelu(const T xt, const T xs, const T slope, boo
     *pos = z > (T) 0;
     return *pos ? z : sz;
 }
-// as = a * slope, rounded before it is used in anything
+// as = a * slope, rounded before it is used in anything; the products with rs of the DROP instances likewise
 template <typename T>
 __device__ __forceinline__ T g2_mul(const T x, const T y)
 {
@@ -101,6 +109,19 @@ __device__ __forceinline__ T g2_add(const T x, const T y)
 #pragma clang fp contract(off)
     const T r = x + y;
     return r;
+}
+
+// The keep bits of a chunk of LPR entries: the lane that holds entry `lir` of the chunk (live: it has one) draws the bit of
+// (r, c, h); bit e of the result is entry e's, the same word in every lane of the group.  Every lane of a group is active here
+// together (the chunk loop's bounds are the group's); lanes of other groups that are not contribute 0 to bits this group drops.
+template <typename T, int LPR>
+__device__ __forceinline__ unsigned long long g2_keep_bits(const DropArgs<T> &d, const bool live, const uint32_t r, const uint32_t c,
+                                                           const uint32_t h, const int lir)
+{
+    const bool k = live && dropout_keep(d.seed_lo, d.seed_hi, r, c, h, d.thr);
+    const unsigned long long all = __ballot(k);
+    if constexpr (LPR == 64) return all;
+    else return all >> ((threadIdx.x & 63u) - (unsigned) lir);
 }
 
 // pieces per lane and row of one load step: two by 16-byte accesses, one by elements, so that no instance spills
@@ -251,18 +272,25 @@ __device__ __forceinline__ const T *g2_xs(const int c, const int64_t hv, const T
     return ((c >= 0) ? (XS0 + (int64_t) c * ld0) : (XS1 + (int64_t) (~c) * ld1)) + hv;
 }
 
-// p and dS of one entry from its score and dP (see FIXED ORDER); dead: lse == -inf
-template <typename T>
-__device__ __forceinline__ void g2_entry(const T s, const T dp, const T lse, const T delta, const bool dead, T *pp, T *ds)
+// p and dS of one entry from its score and dP (see FIXED ORDER); dead: lse == -inf.  DROP: dP counts as dP' = keep ? fl(dP rs) : +0,
+// and *pp is the value-side weight w = keep ? fl(p rs) : +0 (see DROPOUT)
+template <typename T, bool DROP>
+__device__ __forceinline__ void g2_entry(const T s, T dp, const T lse, const T delta, const bool dead, const bool keep, const T rs, T *pp,
+                                         T *ds)
 {
     const T e = dead ? (T) 0 : g2_exp(s - lse);
-    *pp = e;
+    if constexpr (DROP)
+    {
+        dp = keep ? g2_mul<T>(dp, rs) : (T) 0;
+        *pp = keep ? g2_mul<T>(e, rs) : (T) 0;
+    }
+    else *pp = e;
     *ds = (e == (T) 0) ? (T) 0 : e * (dp - delta);
 }
 
 // ---- forward ------------------------------------------------------------------------------------------------------------------
 // LPR lanes per unit (row, head); P pieces of XT, a and the accumulator per lane.  VEC: 16-byte accesses; else elements.
-template <typename T, int LPR, int P, bool VEC>
+template <typename T, int LPR, int P, bool VEC, bool DROP>
 __global__ __launch_bounds__(256) void gatv2_fwd_kernel(const Gatv2Args<T> a)
 {
     constexpr int VW  = G2Piece<T>::VW;
@@ -309,6 +337,8 @@ __global__ __launch_bounds__(256) void gatv2_fwd_kernel(const Gatv2Args<T> a)
         const int my = p0 + lir;
         const int c = (my < pe) ? a.colidx[my] : 0;
         const int cnt = min(LPR, pe - p0);
+        unsigned long long km = 0;                      // (DROP: the chunk's keep bits)
+        if constexpr (DROP) km = g2_keep_bits<T, LPR>(a.drop, my < pe, (uint32_t) orow, (uint32_t) c, (uint32_t) h, lir);
         for (int j = 0; j < cnt; j += UNR)
         {
             // indices past the row end are clamped to the row's last entry: a valid row whose score counts as -inf
@@ -379,6 +409,12 @@ __global__ __launch_bounds__(256) void gatv2_fwd_kernel(const Gatv2Args<T> a)
             l = l * f;
 #pragma unroll
             for (int q = 0; q < UNR; q++) l = l + eu[q];
+            if constexpr (DROP)                         // l has every edge; the accumulator takes the kept ones
+            {
+                const unsigned kb = (unsigned) (km >> j);
+#pragma unroll
+                for (int q = 0; q < UNR; q++) eu[q] = ((kb >> q) & 1u) ? eu[q] : (T) 0;
+            }
 #pragma unroll
             for (int v = 0; v < P; v++)
 #pragma unroll
@@ -404,7 +440,11 @@ __global__ __launch_bounds__(256) void gatv2_fwd_kernel(const Gatv2Args<T> a)
 #pragma unroll
     for (int v = 0; v < P; v++)
 #pragma unroll
-        for (int w = 0; w < VW; w++) acc[v][w] = masked ? (T) 0 : acc[v][w] / l;
+        for (int w = 0; w < VW; w++)
+        {
+            acc[v][w] = masked ? (T) 0 : acc[v][w] / l;
+            if constexpr (DROP) acc[v][w] = g2_mul<T>(acc[v][w], a.drop.rs);
+        }
     g2_store_row<T, LPR, P, VEC>(acc, orp, nv, lir);
     if (a.lse != nullptr && lir == 0) a.lse[srow] = masked ? ninf : m + g2_log(l);
     if (a.p_out != nullptr && lir < UNR)
@@ -417,7 +457,7 @@ __global__ __launch_bounds__(256) void gatv2_fwd_kernel(const Gatv2Args<T> a)
 }
 
 // ---- backward, row side: delta, dXT, da_part and ds_out over a handle of A ----------------------------------------------------------
-template <typename T, int LPR, int P, bool VEC>
+template <typename T, int LPR, int P, bool VEC, bool DROP>
 __global__ __launch_bounds__(256) void gatv2_bwd_row_kernel(const Gatv2BwdRowArgs<T> a)
 {
     constexpr int VW  = G2Piece<T>::VW;
@@ -488,6 +528,8 @@ __global__ __launch_bounds__(256) void gatv2_bwd_row_kernel(const Gatv2BwdRowArg
         const int my = p0 + lir;
         const int c = (my < pe) ? a.colidx[my] : 0;
         const int cnt = min(LPR, pe - p0);
+        unsigned long long km = 0;                      // (DROP: the chunk's keep bits)
+        if constexpr (DROP) km = g2_keep_bits<T, LPR>(a.drop, my < pe, (uint32_t) orow, (uint32_t) c, (uint32_t) h, lir);
         for (int j = 0; j < cnt; j += UNR)
         {
             // indices past the row end are clamped to the row's last entry: a valid row whose dS counts as +0
@@ -544,7 +586,7 @@ __global__ __launch_bounds__(256) void gatv2_bwd_row_kernel(const Gatv2BwdRowArg
             if (mine < cnt)
             {
                 const T s = bias ? g2_add<T>(dot, bv) : dot;
-                g2_entry<T>(s, rp, lse, delta, false, &prob, &ds);
+                g2_entry<T, DROP>(s, rp, lse, delta, false, ((km >> mine) & 1u) != 0, a.drop.rs, &prob, &ds);
                 if (a.ds_out != nullptr && lir < UNR)
                 {
                     const int p = p0 + mine;
@@ -584,7 +626,7 @@ __global__ __launch_bounds__(256) void gatv2_bwd_row_kernel(const Gatv2BwdRowArg
 }
 
 // ---- backward, column side: dXS over a handle of A^T (the unit is (column c, head h)) ------------------------------------------
-template <typename T, int LPR, int P, bool VEC>
+template <typename T, int LPR, int P, bool VEC, bool DROP>
 __global__ __launch_bounds__(256) void gatv2_bwd_col_kernel(const Gatv2BwdColArgs<T> a)
 {
     constexpr int VW  = G2Piece<T>::VW;
@@ -633,6 +675,8 @@ __global__ __launch_bounds__(256) void gatv2_bwd_col_kernel(const Gatv2BwdColArg
         const int my = p0 + lir;
         const int c = (my < pe) ? a.colidx[my] : 0;
         const int cnt = min(LPR, pe - p0);
+        unsigned long long km = 0;                      // (DROP: the chunk's keep bits; the entry's row of A is r, this unit's row c)
+        if constexpr (DROP) km = g2_keep_bits<T, LPR>(a.drop, my < pe, (uint32_t) c, (uint32_t) crow, (uint32_t) h, lir);
         for (int j = 0; j < cnt; j += UNR)
         {
             const int mine = j + (lir & 7);
@@ -695,7 +739,7 @@ __global__ __launch_bounds__(256) void gatv2_bwd_col_kernel(const Gatv2BwdColArg
             if (mine < cnt)
             {
                 const T s = bias ? g2_add<T>(dot, bv) : dot;
-                g2_entry<T>(s, rp, lse, dl, lse == ninf, &prob, &ds);
+                g2_entry<T, DROP>(s, rp, lse, dl, lse == ninf, ((km >> mine) & 1u) != 0, a.drop.rs, &prob, &ds);
             }
             T dsu[UNR], pu[UNR];
 #pragma unroll
@@ -765,8 +809,13 @@ static hipError_t launch_gatv2(const Gatv2Args<T> &a, hipStream_t s)
     const bool vec = g2_aligned({a.XT, a.XS0, a.XS1, a.av, a.O}, {a.nv, a.ldXT, a.ldO, a.XS0 ? a.ldXS0 : 0, a.XS1 ? a.ldXS1 : 0}, VW);
     dim3 grid;
     if (!g2_grid(a.nrow, a.heads, 256 / LPR, &grid)) return hipErrorInvalidValue;
-    if (vec) hipLaunchKernelGGL((gatv2_fwd_kernel<T, LPR, P, true>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((gatv2_fwd_kernel<T, LPR, P, false>), grid, dim3(256), 0, s, a);
+    if (a.drop.on)
+    {
+        if (vec) hipLaunchKernelGGL((gatv2_fwd_kernel<T, LPR, P, true, true>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((gatv2_fwd_kernel<T, LPR, P, false, true>), grid, dim3(256), 0, s, a);
+    }
+    else if (vec) hipLaunchKernelGGL((gatv2_fwd_kernel<T, LPR, P, true, false>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((gatv2_fwd_kernel<T, LPR, P, false, false>), grid, dim3(256), 0, s, a);
     return hipGetLastError();
 }
 template <typename T, int LPR, int P>
@@ -777,8 +826,13 @@ static hipError_t launch_gatv2(const Gatv2BwdRowArgs<T> &a, hipStream_t s)
                                 {a.nv, a.ldXT, a.ldO, a.lddO, a.lddXT, a.ldda, a.XS0 ? a.ldXS0 : 0, a.XS1 ? a.ldXS1 : 0}, VW);
     dim3 grid;
     if (!g2_grid(a.nrow, a.heads, 256 / LPR, &grid)) return hipErrorInvalidValue;
-    if (vec) hipLaunchKernelGGL((gatv2_bwd_row_kernel<T, LPR, P, true>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((gatv2_bwd_row_kernel<T, LPR, P, false>), grid, dim3(256), 0, s, a);
+    if (a.drop.on)
+    {
+        if (vec) hipLaunchKernelGGL((gatv2_bwd_row_kernel<T, LPR, P, true, true>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((gatv2_bwd_row_kernel<T, LPR, P, false, true>), grid, dim3(256), 0, s, a);
+    }
+    else if (vec) hipLaunchKernelGGL((gatv2_bwd_row_kernel<T, LPR, P, true, false>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((gatv2_bwd_row_kernel<T, LPR, P, false, false>), grid, dim3(256), 0, s, a);
     return hipGetLastError();
 }
 template <typename T, int LPR, int P>
@@ -789,8 +843,13 @@ static hipError_t launch_gatv2(const Gatv2BwdColArgs<T> &a, hipStream_t s)
     const bool vec = g2_aligned({a.XS, a.XT, a.av, a.dO, a.dXS}, {a.nv, a.ldXS, a.XT ? a.ldXT : 0, a.dO ? a.lddO : 0, a.lddXS}, VW);
     dim3 grid;
     if (!g2_grid(a.nrow, a.heads, 256 / LPR, &grid)) return hipErrorInvalidValue;
-    if (vec) hipLaunchKernelGGL((gatv2_bwd_col_kernel<T, LPR, P, true>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((gatv2_bwd_col_kernel<T, LPR, P, false>), grid, dim3(256), 0, s, a);
+    if (a.drop.on)
+    {
+        if (vec) hipLaunchKernelGGL((gatv2_bwd_col_kernel<T, LPR, P, true, true>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((gatv2_bwd_col_kernel<T, LPR, P, false, true>), grid, dim3(256), 0, s, a);
+    }
+    else if (vec) hipLaunchKernelGGL((gatv2_bwd_col_kernel<T, LPR, P, true, false>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((gatv2_bwd_col_kernel<T, LPR, P, false, false>), grid, dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

@@ -517,13 +517,15 @@ static int attention_bwd_kv_csr(crp_csr_dev *At, int nk, int nv, double scale, i
 }
 
 // ---- the fused GAT attention (gat_kernels.hip), one dtype.  Every argument is checked before anything is launched or allocated: a
-// negative return has written nothing.  dv: the width of one head.
+// negative return has written nothing.  dv: the width of one head.  drop, seed: the attention dropout of the _drop_ entry points
+// (dropout.h); the plain entry points pass 0, which takes the instances without it.
+static bool drop_rate_ok(double drop) { return drop >= 0.0 && drop < 1.0; }         // (NaN fails both)
 static int gat_check(const crp_csr_dev *A, int heads, int dv, double slope, int bias, const void *el, long long ldel, const void *er0,
                      long long lder0, const void *er1, long long lder1, const void *V0, long long ldV0, const void *V1, long long ldV1,
-                     const void *O, long long ldO)
+                     const void *O, long long ldO, double drop)
 {
     if (A == NULL || el == NULL || O == NULL) return -1;
-    if (heads < 1 || dv < 1 || (bias != 0 && bias != 1) || !std::isfinite(slope)) return -1;
+    if (heads < 1 || dv < 1 || (bias != 0 && bias != 1) || !std::isfinite(slope) || !drop_rate_ok(drop)) return -1;
     if ((er0 == NULL || V0 == NULL) && A->b0_rows > 0) return -1;       // a column code names the first source
     if ((er1 == NULL || V1 == NULL) && A->b1_rows > 0) return -1;       // a column code names the second source
     const long long wv = (long long) heads * dv;
@@ -534,9 +536,9 @@ static int gat_check(const crp_csr_dev *A, int heads, int dv, double slope, int 
 template <class T>
 static int gat_fwd_csr(crp_csr_dev *A, int heads, int dv, double slope, int bias, const T *el, long long ldel, const T *er0, long long lder0,
                        const T *er1, long long lder1, const T *V0, long long ldV0, const T *V1, long long ldV1, T *O, long long ldO, T *lse,
-                       T *p_out, const int *out_pos, hipStream_t s)
+                       T *p_out, const int *out_pos, hipStream_t s, double drop = 0.0, unsigned long long seed = 0)
 {
-    int rc = gat_check(A, heads, dv, slope, bias, el, ldel, er0, lder0, er1, lder1, V0, ldV0, V1, ldV1, O, ldO);
+    int rc = gat_check(A, heads, dv, slope, bias, el, ldel, er0, lder0, er1, lder1, V0, ldV0, V1, ldV1, O, ldO, drop);
     if (rc != 0 || A->nrow == 0) return rc;
     crp::GatArgs<T> a;
     rc = attention_bias_values<T>(A, bias, s, &a.val);
@@ -545,15 +547,16 @@ static int gat_fwd_csr(crp_csr_dev *A, int heads, int dv, double slope, int bias
     a.el = el; a.ldel = ldel; a.er0 = er0; a.lder0 = lder0; a.er1 = er1; a.lder1 = lder1;
     a.V0 = V0; a.ldV0 = ldV0; a.V1 = V1; a.ldV1 = ldV1;
     a.O = O; a.ldO = ldO; a.lse = lse; a.p_out = p_out; a.rowmap = A->rowmap; a.out_pos = out_pos;
+    a.drop = crp::dropout_args<T>(drop, seed);
     return (int) crp::gat_attention_rm(a, s);
 }
 template <class T>
 static int gat_bwd_row_csr(crp_csr_dev *A, int heads, int dv, double slope, int bias, const T *el, long long ldel, const T *er0, long long lder0,
                            const T *er1, long long lder1, const T *V0, long long ldV0, const T *V1, long long ldV1, const T *O, long long ldO,
                            const T *dO, long long lddO, const T *lse, T *d_el, long long ldd_el, T *delta, T *ds_out, const int *out_pos,
-                           hipStream_t s)
+                           hipStream_t s, double drop = 0.0, unsigned long long seed = 0)
 {
-    int rc = gat_check(A, heads, dv, slope, bias, el, ldel, er0, lder0, er1, lder1, V0, ldV0, V1, ldV1, O, ldO);
+    int rc = gat_check(A, heads, dv, slope, bias, el, ldel, er0, lder0, er1, lder1, V0, ldV0, V1, ldV1, O, ldO, drop);
     if (rc == 0 && (dO == NULL || lse == NULL || d_el == NULL || delta == NULL)) rc = -1;
     if (rc == 0 && (lddO < (long long) heads * dv || ldd_el < heads)) rc = -4;
     constexpr int cap = crp::ATTN_BWD_MAX_PIECES * 64 * (16 / (int) sizeof(T));
@@ -567,15 +570,16 @@ static int gat_bwd_row_csr(crp_csr_dev *A, int heads, int dv, double slope, int 
     a.V0 = V0; a.ldV0 = ldV0; a.V1 = V1; a.ldV1 = ldV1;
     a.O = O; a.ldO = ldO; a.dO = dO; a.lddO = lddO; a.lse = lse; a.d_el = d_el; a.ldd_el = ldd_el; a.delta = delta; a.ds_out = ds_out;
     a.rowmap = A->rowmap; a.out_pos = out_pos;
+    a.drop = crp::dropout_args<T>(drop, seed);
     return (int) crp::gat_attention_bwd_row(a, s);
 }
 template <class T>
 static int gat_bwd_col_csr(crp_csr_dev *At, int heads, int dv, double slope, int bias, const T *er, long long lder, const T *V, long long ldV,
                            const T *el, long long ldel, const T *dO, long long lddO, const T *lse, const T *delta, T *d_er, long long ldd_er,
-                           T *dV, long long lddV, hipStream_t s)
+                           T *dV, long long lddV, hipStream_t s, double drop = 0.0, unsigned long long seed = 0)
 {
     if (At == NULL || er == NULL || V == NULL || d_er == NULL || dV == NULL) return -1;
-    if (heads < 1 || dv < 1 || (bias != 0 && bias != 1) || !std::isfinite(slope)) return -1;
+    if (heads < 1 || dv < 1 || (bias != 0 && bias != 1) || !std::isfinite(slope) || !drop_rate_ok(drop)) return -1;
     if (At->b1_rows > 0) return -1;                      // a code names a second source: this call takes one
     if ((el == NULL || dO == NULL || lse == NULL || delta == NULL) && At->nnz > 0) return -1;
     const long long wv = (long long) heads * dv;
@@ -590,6 +594,7 @@ static int gat_bwd_col_csr(crp_csr_dev *At, int heads, int dv, double slope, int
     a.nrow = At->nrow; a.nv = dv; a.heads = heads; a.rowptr = At->rowptr; a.colidx = At->colidx; a.slope = (T) slope;
     a.er = er; a.lder = lder; a.V = V; a.ldV = ldV; a.el = el; a.ldel = ldel; a.dO = dO; a.lddO = lddO; a.lse = lse; a.delta = delta;
     a.d_er = d_er; a.ldd_er = ldd_er; a.dV = dV; a.lddV = lddV; a.rowmap = At->rowmap;
+    a.drop = crp::dropout_args<T>(drop, seed);
     return (int) crp::gat_attention_bwd_col(a, s);
 }
 
@@ -597,10 +602,10 @@ static int gat_bwd_col_csr(crp_csr_dev *At, int heads, int dv, double slope, int
 // a negative return has written nothing.  dv: the width of one head, capped in both directions.
 template <class T>
 static int gatv2_check(const crp_csr_dev *A, int heads, int dv, double slope, int bias, const void *XT, long long ldXT, const void *XS0,
-                       long long ldXS0, const void *XS1, long long ldXS1, const void *av, const void *O, long long ldO)
+                       long long ldXS0, const void *XS1, long long ldXS1, const void *av, const void *O, long long ldO, double drop)
 {
     if (A == NULL || XT == NULL || av == NULL || O == NULL) return -1;
-    if (heads < 1 || dv < 1 || (bias != 0 && bias != 1) || !std::isfinite(slope)) return -1;
+    if (heads < 1 || dv < 1 || (bias != 0 && bias != 1) || !std::isfinite(slope) || !drop_rate_ok(drop)) return -1;
     if (XS0 == NULL && A->b0_rows > 0) return -1;        // a column code names the first source
     if (XS1 == NULL && A->b1_rows > 0) return -1;        // a column code names the second source
     const long long wv = (long long) heads * dv;
@@ -611,9 +616,10 @@ static int gatv2_check(const crp_csr_dev *A, int heads, int dv, double slope, in
 }
 template <class T>
 static int gatv2_fwd_csr(crp_csr_dev *A, int heads, int dv, double slope, int bias, const T *XT, long long ldXT, const T *XS0, long long ldXS0,
-                         const T *XS1, long long ldXS1, const T *av, T *O, long long ldO, T *lse, T *p_out, const int *out_pos, hipStream_t s)
+                         const T *XS1, long long ldXS1, const T *av, T *O, long long ldO, T *lse, T *p_out, const int *out_pos, hipStream_t s,
+                         double drop = 0.0, unsigned long long seed = 0)
 {
-    int rc = gatv2_check<T>(A, heads, dv, slope, bias, XT, ldXT, XS0, ldXS0, XS1, ldXS1, av, O, ldO);
+    int rc = gatv2_check<T>(A, heads, dv, slope, bias, XT, ldXT, XS0, ldXS0, XS1, ldXS1, av, O, ldO, drop);
     if (rc != 0 || A->nrow == 0) return rc;
     crp::Gatv2Args<T> a;
     rc = attention_bias_values<T>(A, bias, s, &a.val);
@@ -621,17 +627,18 @@ static int gatv2_fwd_csr(crp_csr_dev *A, int heads, int dv, double slope, int bi
     a.nrow = A->nrow; a.nv = dv; a.heads = heads; a.rowptr = A->rowptr; a.colidx = A->colidx; a.slope = (T) slope;
     a.XT = XT; a.ldXT = ldXT; a.XS0 = XS0; a.ldXS0 = ldXS0; a.XS1 = XS1; a.ldXS1 = ldXS1; a.av = av;
     a.O = O; a.ldO = ldO; a.lse = lse; a.p_out = p_out; a.rowmap = A->rowmap; a.out_pos = out_pos;
+    a.drop = crp::dropout_args<T>(drop, seed);
     return (int) crp::gatv2_attention_rm(a, s);
 }
 template <class T>
 static int gatv2_bwd_row_csr(crp_csr_dev *A, int heads, int dv, double slope, int bias, const T *XT, long long ldXT, const T *XS0,
                              long long ldXS0, const T *XS1, long long ldXS1, const T *av, const T *O, long long ldO, const T *dO, long long lddO,
                              const T *lse, T *dXT, long long lddXT, T *da_part, long long ldda, T *delta, T *ds_out, const int *out_pos,
-                             hipStream_t s)
+                             hipStream_t s, double drop = 0.0, unsigned long long seed = 0)
 {
     int rc = 0;
     if (A == NULL || dO == NULL || lse == NULL || dXT == NULL || da_part == NULL || delta == NULL) rc = -1;
-    if (rc == 0) rc = gatv2_check<T>(A, heads, dv, slope, bias, XT, ldXT, XS0, ldXS0, XS1, ldXS1, av, O, ldO);
+    if (rc == 0) rc = gatv2_check<T>(A, heads, dv, slope, bias, XT, ldXT, XS0, ldXS0, XS1, ldXS1, av, O, ldO, drop);
     if (rc == 0 || rc == CRP_GATV2_EWIDTH)
     {
         const long long wv = (long long) heads * dv;
@@ -645,15 +652,16 @@ static int gatv2_bwd_row_csr(crp_csr_dev *A, int heads, int dv, double slope, in
     a.XT = XT; a.ldXT = ldXT; a.XS0 = XS0; a.ldXS0 = ldXS0; a.XS1 = XS1; a.ldXS1 = ldXS1; a.av = av;
     a.O = O; a.ldO = ldO; a.dO = dO; a.lddO = lddO; a.lse = lse; a.dXT = dXT; a.lddXT = lddXT; a.da_part = da_part; a.ldda = ldda;
     a.delta = delta; a.ds_out = ds_out; a.rowmap = A->rowmap; a.out_pos = out_pos;
+    a.drop = crp::dropout_args<T>(drop, seed);
     return (int) crp::gatv2_attention_bwd_row(a, s);
 }
 template <class T>
 static int gatv2_bwd_col_csr(crp_csr_dev *At, int heads, int dv, double slope, int bias, const T *XS, long long ldXS, const T *XT,
                              long long ldXT, const T *av, const T *dO, long long lddO, const T *lse, const T *delta, T *dXS, long long lddXS,
-                             hipStream_t s)
+                             hipStream_t s, double drop = 0.0, unsigned long long seed = 0)
 {
     if (At == NULL || XS == NULL || av == NULL || dXS == NULL) return -1;
-    if (heads < 1 || dv < 1 || (bias != 0 && bias != 1) || !std::isfinite(slope)) return -1;
+    if (heads < 1 || dv < 1 || (bias != 0 && bias != 1) || !std::isfinite(slope) || !drop_rate_ok(drop)) return -1;
     if (At->b1_rows > 0) return -1;                      // a code names a second source: this call takes one
     if ((XT == NULL || dO == NULL || lse == NULL || delta == NULL) && At->nnz > 0) return -1;
     const long long wv = (long long) heads * dv;
@@ -668,6 +676,7 @@ static int gatv2_bwd_col_csr(crp_csr_dev *At, int heads, int dv, double slope, i
     a.nrow = At->nrow; a.nv = dv; a.heads = heads; a.rowptr = At->rowptr; a.colidx = At->colidx; a.slope = (T) slope;
     a.XS = XS; a.ldXS = ldXS; a.XT = XT; a.ldXT = ldXT; a.av = av; a.dO = dO; a.lddO = lddO; a.lse = lse; a.delta = delta;
     a.dXS = dXS; a.lddXS = lddXS; a.rowmap = At->rowmap;
+    a.drop = crp::dropout_args<T>(drop, seed);
     return (int) crp::gatv2_attention_bwd_col(a, s);
 }
 
@@ -1425,6 +1434,78 @@ CRP_GAT_ENTRY_POINTS(f32, float)
 CRP_GATV2_ENTRY_POINTS(f64, double)
 CRP_GATV2_ENTRY_POINTS(f32, float)
 #undef CRP_GATV2_ENTRY_POINTS
+
+// ---- ... and both with attention dropout (dropout.h): the same argument lists with (drop, seed) before the stream;
+// drop == 0 takes the instances of the calls above
+#define CRP_GAT_DROP_ENTRY_POINTS(SFX, T)                                                                                                                                 \
+    int crp_gat_attention_drop_csr_##SFX(crp_csr_dev_p A, int heads, int dv, double slope, int bias, const T *el, long long ldel, const T *er0,                           \
+                                    long long lder0, const T *er1, long long lder1, const T *V0, long long ldV0, const T *V1, long long ldV1,                             \
+                                    T *O, long long ldO, T *lse, T *p_out, const int *out_pos, double drop, unsigned long long seed, void *stream)                        \
+    {                                                                                                                                                                     \
+        return gat_fwd_csr<T>(A, heads, dv, slope, bias, el, ldel, er0, lder0, er1, lder1, V0, ldV0, V1, ldV1, O, ldO, lse, p_out, out_pos,                               \
+                              (hipStream_t) stream, drop, seed);                                                                                                          \
+    }                                                                                                                                                                     \
+    int crp_gat_attention_drop_bwd_row_csr_##SFX(crp_csr_dev_p A, int heads, int dv, double slope, int bias, const T *el, long long ldel,                                 \
+                                            const T *er0, long long lder0, const T *er1, long long lder1, const T *V0, long long ldV0,                                    \
+                                            const T *V1, long long ldV1, const T *O, long long ldO, const T *dO, long long lddO, const T *lse,                            \
+                                            T *d_el, long long ldd_el, T *delta, T *ds_out, const int *out_pos, double drop, unsigned long long seed, void *stream)       \
+    {                                                                                                                                                                     \
+        return gat_bwd_row_csr<T>(A, heads, dv, slope, bias, el, ldel, er0, lder0, er1, lder1, V0, ldV0, V1, ldV1, O, ldO, dO, lddO, lse, d_el,                           \
+                                  ldd_el, delta, ds_out, out_pos, (hipStream_t) stream, drop, seed);                                                                      \
+    }                                                                                                                                                                     \
+    int crp_gat_attention_drop_bwd_col_csr_##SFX(crp_csr_dev_p At, int heads, int dv, double slope, int bias, const T *er, long long lder, const T *V,                    \
+                                            long long ldV, const T *el, long long ldel, const T *dO, long long lddO, const T *lse,                                        \
+                                            const T *delta, T *d_er, long long ldd_er, T *dV, long long lddV, double drop, unsigned long long seed, void *stream)         \
+    {                                                                                                                                                                     \
+        return gat_bwd_col_csr<T>(At, heads, dv, slope, bias, er, lder, V, ldV, el, ldel, dO, lddO, lse, delta, d_er, ldd_er, dV, lddV,                                   \
+                                  (hipStream_t) stream, drop, seed);                                                                                                      \
+    }
+CRP_GAT_DROP_ENTRY_POINTS(f64, double)
+CRP_GAT_DROP_ENTRY_POINTS(f32, float)
+#undef CRP_GAT_DROP_ENTRY_POINTS
+
+#define CRP_GATV2_DROP_ENTRY_POINTS(SFX, T)                                                                                                                               \
+    int crp_gatv2_attention_drop_csr_##SFX(crp_csr_dev_p A, int heads, int dv, double slope, int bias, const T *XT, long long ldXT, const T *XS0,                         \
+                                      long long ldXS0, const T *XS1, long long ldXS1, const T *a, T *O, long long ldO, T *lse, T *p_out,                                  \
+                                      const int *out_pos, double drop, unsigned long long seed, void *stream)                                                             \
+    {                                                                                                                                                                     \
+        return gatv2_fwd_csr<T>(A, heads, dv, slope, bias, XT, ldXT, XS0, ldXS0, XS1, ldXS1, a, O, ldO, lse, p_out, out_pos,                                              \
+                                (hipStream_t) stream, drop, seed);                                                                                                        \
+    }                                                                                                                                                                     \
+    int crp_gatv2_attention_drop_bwd_row_csr_##SFX(crp_csr_dev_p A, int heads, int dv, double slope, int bias, const T *XT, long long ldXT,                               \
+                                              const T *XS0, long long ldXS0, const T *XS1, long long ldXS1, const T *a, const T *O,                                       \
+                                              long long ldO, const T *dO, long long lddO, const T *lse, T *dXT, long long lddXT, T *da_part,                              \
+                                              long long ldda, T *delta, T *ds_out, const int *out_pos, double drop, unsigned long long seed, void *stream)                \
+    {                                                                                                                                                                     \
+        return gatv2_bwd_row_csr<T>(A, heads, dv, slope, bias, XT, ldXT, XS0, ldXS0, XS1, ldXS1, a, O, ldO, dO, lddO, lse, dXT, lddXT, da_part,                           \
+                                    ldda, delta, ds_out, out_pos, (hipStream_t) stream, drop, seed);                                                                      \
+    }                                                                                                                                                                     \
+    int crp_gatv2_attention_drop_bwd_col_csr_##SFX(crp_csr_dev_p At, int heads, int dv, double slope, int bias, const T *XS, long long ldXS,                              \
+                                              const T *XT, long long ldXT, const T *a, const T *dO, long long lddO, const T *lse,                                         \
+                                              const T *delta, T *dXS, long long lddXS, double drop, unsigned long long seed, void *stream)                                \
+    {                                                                                                                                                                     \
+        return gatv2_bwd_col_csr<T>(At, heads, dv, slope, bias, XS, ldXS, XT, ldXT, a, dO, lddO, lse, delta, dXS, lddXS, (hipStream_t) stream, drop, seed);               \
+    }
+CRP_GATV2_DROP_ENTRY_POINTS(f64, double)
+CRP_GATV2_DROP_ENTRY_POINTS(f32, float)
+#undef CRP_GATV2_DROP_ENTRY_POINTS
+
+// ---- the dropout mask on its own (dropout.h): one draw on the host, and the (nnz, heads) keep flags of a handle
+int crp_dropout_keep_host(unsigned long long seed, unsigned r, unsigned c, unsigned h, double drop)
+{
+    if (!drop_rate_ok(drop)) return -1;
+    return crp::dropout_keep((uint32_t) seed, (uint32_t) (seed >> 32), r, c, h, crp::dropout_threshold(drop)) ? 1 : 0;
+}
+
+int crp_dropout_mask_csr(crp_csr_dev_p A, int heads, double drop, unsigned long long seed, unsigned char *mask, const int *out_pos,
+                         void *stream)
+{
+    if (A == NULL || heads < 1 || !drop_rate_ok(drop)) return -1;
+    if (A->nnz == 0 || A->nrow == 0) return 0;
+    if (mask == NULL) return -1;
+    return (int) crp::dropout_mask_csr(A->nrow, heads, A->rowptr, A->colidx, A->rowmap, (bool) A->tmap, drop, seed, mask, out_pos,
+                                       (hipStream_t) stream);
+}
 
 // ---- row softmax over a CSR pattern (softmax_kernels.hip).  Every argument is checked before anything is launched.
 int crp_row_softmax_f64(int nrow, const int *rowptr, const double *s, double *y, void *stream)

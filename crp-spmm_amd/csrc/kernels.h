@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include "dropout.h"
 
 namespace crp {
 
@@ -223,6 +224,7 @@ template <typename T> struct GatArgs
     T         *p_out;       // nullptr, or the probabilities, (nnz, heads)
     const int *rowmap;      // nullptr, or the el / O row of every row (row-subset matrices)
     const int *out_pos;     // nullptr, or where nonzero p writes: row out_pos[p] of p_out
+    DropArgs<T> drop;       // attention dropout (dropout.h); off by default
 };
 
 // gat_kernels.hip, row side of the backward over a handle of A: delta = <dO[i]_h, O[i]_h>, d_el = sum_p dZ_p, ds_out = dS_p
@@ -256,6 +258,7 @@ template <typename T> struct GatBwdRowArgs
     T         *ds_out;      // nullptr, or dS, (nnz, heads)
     const int *rowmap;      // nullptr, or the el / O / dO / d_el / lse / delta row of every row
     const int *out_pos;     // nullptr, or where nonzero p writes: row out_pos[p] of ds_out
+    DropArgs<T> drop;       // attention dropout (dropout.h); off by default
 };
 
 // gat_kernels.hip, column side over a handle of A^T (row c = column c of A): d_er[c][h] = sum_p dZ_p, dV[c]_h = sum_p p_p dO[i_p]_h
@@ -283,6 +286,7 @@ template <typename T> struct GatBwdColArgs
     T         *dV;          // may be V exactly (a group reads its slice whole before it writes it)
     int64_t    lddV;
     const int *rowmap;      // nullptr, or the er / V / d_er / dV row of every row (row-subset matrices)
+    DropArgs<T> drop;       // attention dropout (dropout.h); off by default
 };
 
 // gatv2_kernels.hip: O[i]_h = sum_p softmax_p(sum_j a[h][j] lrelu(XT[i]_h[j] + XS[c_p]_h[j]) (+ val[p])) XS[c_p]_h over (row, head) units
@@ -308,6 +312,7 @@ template <typename T> struct Gatv2Args
     T         *p_out;       // nullptr, or the probabilities, (nnz, heads)
     const int *rowmap;      // nullptr, or the XT / O row of every row (row-subset matrices)
     const int *out_pos;     // nullptr, or where nonzero p writes: row out_pos[p] of p_out
+    DropArgs<T> drop;       // attention dropout (dropout.h); off by default
 };
 
 // gatv2_kernels.hip, row side of the backward over a handle of A: delta, dXT, da_part (the row's share of d/da), ds_out
@@ -340,6 +345,7 @@ template <typename T> struct Gatv2BwdRowArgs
     T         *ds_out;      // nullptr, or dS, (nnz, heads)
     const int *rowmap;      // nullptr, or the XT / O / dO / dXT / da_part / lse / delta row of every row
     const int *out_pos;     // nullptr, or where nonzero p writes: row out_pos[p] of ds_out
+    DropArgs<T> drop;       // attention dropout (dropout.h); off by default
 };
 
 // gatv2_kernels.hip, column side over a handle of A^T (row c = column c of A): dXS[c]_h = sum_p dS_p ag_p + sum_p p_p dO[i_p]_h
@@ -364,6 +370,7 @@ template <typename T> struct Gatv2BwdColArgs
     T         *dXS;         // may be XS exactly (a group reads its slice whole before it writes it)
     int64_t    lddXS;
     const int *rowmap;      // nullptr, or the XS / dXS row of every row (row-subset matrices)
+    DropArgs<T> drop;       // attention dropout (dropout.h); off by default
 };
 
 // The instance every SpMM launcher names at its hipLaunchKernelGGL, from its own template arguments ("rowgroup<16,2,1>",
@@ -420,7 +427,7 @@ hipError_t attention_bwd_kv(const AttnBwdKVArgs<double> &a, bool mh, hipStream_t
 hipError_t attention_bwd_kv(const AttnBwdKVArgs<float> &a, bool mh, hipStream_t s);
 
 // gat_kernels.hip: the fused GAT attention (additive LeakyReLU scores) over (row, head) units and its two-handle backward; the
-// backward's per-head width is capped as attention_bwd's
+// backward's per-head width is capped as attention_bwd's.  a.drop.on takes the DROP instances (attention dropout, dropout.h)
 hipError_t gat_attention_rm(const GatArgs<double> &a, hipStream_t s);
 hipError_t gat_attention_rm(const GatArgs<float> &a, hipStream_t s);
 hipError_t gat_attention_bwd_row(const GatBwdRowArgs<double> &a, hipStream_t s);
@@ -429,13 +436,17 @@ hipError_t gat_attention_bwd_col(const GatBwdColArgs<double> &a, hipStream_t s);
 hipError_t gat_attention_bwd_col(const GatBwdColArgs<float> &a, hipStream_t s);
 
 // gatv2_kernels.hip: the fused GATv2 attention (a LeakyReLU inside the dot with a) over (row, head) units and its two-handle
-// backward; the per-head width is capped as attention_bwd's, in both directions
+// backward; the per-head width is capped as attention_bwd's, in both directions.  a.drop.on takes the DROP instances
 hipError_t gatv2_attention_rm(const Gatv2Args<double> &a, hipStream_t s);
 hipError_t gatv2_attention_rm(const Gatv2Args<float> &a, hipStream_t s);
 hipError_t gatv2_attention_bwd_row(const Gatv2BwdRowArgs<double> &a, hipStream_t s);
 hipError_t gatv2_attention_bwd_row(const Gatv2BwdRowArgs<float> &a, hipStream_t s);
 hipError_t gatv2_attention_bwd_col(const Gatv2BwdColArgs<double> &a, hipStream_t s);
 hipError_t gatv2_attention_bwd_col(const Gatv2BwdColArgs<float> &a, hipStream_t s);
+
+// dropout_kernels.hip: the keep flags of dropout.h over a CSR, (nnz, heads) bytes at (out_pos ? out_pos[p] : p) * heads + h
+hipError_t dropout_mask_csr(int nrow, int heads, const int *rowptr, const int *colidx, const int *rowmap, bool transposed, double drop,
+                            unsigned long long seed, uint8_t *mask, const int *out_pos, hipStream_t s);
 
 // softmax_kernels.hip: row softmax over a CSR pattern and its Jacobian product; rowptr entries index the value arrays directly
 hipError_t row_softmax_f64(int nrow, const int *rowptr, const double *s, double *y, hipStream_t st);

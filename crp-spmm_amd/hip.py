@@ -324,7 +324,7 @@ class CsrDev:
         return dK, dV
 
     def gat_attention(self, el, er0, V0, er1=None, V1=None, slope=0.2, bias=False, out=None, lse=None, p_out=None, out_pos=None,
-                      stream=None, heads=1):
+                      stream=None, heads=1, dropout=0.0, seed=0):
         """Fused GAT attention over this matrix's pattern (crp_gat_attention_csr_f64 / _f32, by the operands' dtype): for every
         head h, out[i]_h = sum_p softmax_p(leaky_relu(el[i, h] + er[c_p, h], slope) (+ the matrix's value of p with ``bias``))
         * V[c_p]_h over the nonzeros p = (i, c_p) of row i; c >= 0 reads row c of er0 / V0, c < 0 row ~c of er1 / V1.  ``el`` is
@@ -332,9 +332,13 @@ class CsrDev:
         row-major float64 or float32 cuda tensors of one dtype; ``out`` has V's width and a row per row of ``el`` (allocated
         when None).  Optional outputs: ``lse`` contiguous (rows, heads), ``p_out`` contiguous (nnz, heads) -- nonzero p writes
         row out_pos[p] when ``out_pos`` (int32, nnz entries) is given; with one head both may be 1-D.  The matrix's values are
-        not changed.  Returns ``out``.  Every error is raised before the library is called."""
+        not changed.  ``dropout`` > 0 drops the attention coefficients after the softmax at that rate, by the mask of
+        ``dropout_mask(heads, dropout, seed)``, and scales the kept ones by 1 / (1 - dropout) (crp_gat_attention_drop_csr_*);
+        ``lse`` and ``p_out`` are those of the call without it.  Returns ``out``.  Every error is raised before the library is
+        called."""
         import torch
         heads = _heads(heads)
+        dropout, seed = _dropout(dropout, seed)
         if (er1 is None) != (V1 is None):
             raise ValueError("er1 and V1 come together")
         sops = [("el", el), ("er0", er0)] + ([("er1", er1)] if er1 is not None else [])
@@ -361,25 +365,27 @@ class CsrDev:
             out = torch.empty((x_nrow, nv), dtype=el.dtype, device=el.device)
         if self.nrow == 0:
             return out
-        fn = self._lib.crp_gat_attention_csr_f32 if el.dtype == torch.float32 else self._lib.crp_gat_attention_csr_f64
+        fn, drop = _drop_entry(self._lib, "gat_attention", "", el.dtype == torch.float32, dropout, seed)
         e1p, lde1, v1p, ldv1 = (er1.data_ptr(), er1.stride(0), V1.data_ptr(), V1.stride(0)) if er1 is not None else (None, 0, None, 0)
         ptr = lambda t: (t.data_ptr() or None) if t is not None else None
         L.check(fn(self.handle, heads, nv // heads, slope, bias, el.data_ptr(), el.stride(0), ptr(er0), er0.stride(0), e1p, lde1,
-                   ptr(V0), V0.stride(0), v1p, ldv1, out.data_ptr(), out.stride(0), ptr(lse), ptr(p_out), ptr(out_pos),
+                   ptr(V0), V0.stride(0), v1p, ldv1, out.data_ptr(), out.stride(0), ptr(lse), ptr(p_out), ptr(out_pos), *drop,
                    _stream(out) if stream is None else stream), fn.__name__)
         return out
 
     def gat_attention_bwd_row(self, el, er0, V0, O, dO, lse, er1=None, V1=None, slope=0.2, bias=False, d_el=None, delta=None,
-                              ds_out=None, out_pos=None, stream=None, heads=1):
+                              ds_out=None, out_pos=None, stream=None, heads=1, dropout=0.0, seed=0):
         """The row side of the fused backward of ``gat_attention`` (crp_gat_attention_bwd_row_csr_f64 / _f32), on the handle the
         forward ran on: with ``O`` and ``lse`` as the forward wrote them and the upstream gradient ``dO``, delta[i, h] =
         <dO[i]_h, O[i]_h> and d_el[i, h] = the sum over the row of dZ_p = dS_p * (z_p > 0 ? 1 : slope), dS_p = p_p (<dO[i]_h,
         V[c_p]_h> - delta[i, h]), p_p = exp(s_p - lse[i, h]).  ``d_el`` (rows, heads) and ``delta`` contiguous (rows, heads) are
         allocated when None; ``ds_out`` (optional, contiguous (nnz, heads)) receives dS_p -- at row out_pos[p] when ``out_pos``
         is given -- whose sum over the heads is the gradient of the matrix's values.  No output may alias an input.  A head
-        wider than 512 (float64) / 1024 (float32) columns raises ValueError.  Returns (d_el, delta)."""
+        wider than 512 (float64) / 1024 (float32) columns raises ValueError.  ``dropout`` and ``seed``: the forward's (``O`` is the
+        dropped output; dP counts as 0 on a dropped edge and as dP / (1 - dropout) on a kept one).  Returns (d_el, delta)."""
         import torch
         heads = _heads(heads)
+        dropout, seed = _dropout(dropout, seed)
         if (er1 is None) != (V1 is None):
             raise ValueError("er1 and V1 come together")
         sops = [("el", el), ("er0", er0)] + ([("er1", er1)] if er1 is not None else []) + ([("d_el", d_el)] if d_el is not None else [])
@@ -409,24 +415,27 @@ class CsrDev:
             delta = delta_given.view(-1)
         if self.nrow == 0:
             return d_el, delta_given
-        fn = self._lib.crp_gat_attention_bwd_row_csr_f32 if el.dtype == torch.float32 else self._lib.crp_gat_attention_bwd_row_csr_f64
+        fn, drop = _drop_entry(self._lib, "gat_attention", "_bwd_row", el.dtype == torch.float32, dropout, seed)
         e1p, lde1, v1p, ldv1 = (er1.data_ptr(), er1.stride(0), V1.data_ptr(), V1.stride(0)) if er1 is not None else (None, 0, None, 0)
         ptr = lambda t: (t.data_ptr() or None) if t is not None else None
         L.check(fn(self.handle, heads, nv // heads, slope, bias, el.data_ptr(), el.stride(0), ptr(er0), er0.stride(0), e1p, lde1,
                    ptr(V0), V0.stride(0), v1p, ldv1, O.data_ptr(), O.stride(0), dO.data_ptr(), dO.stride(0), lse.data_ptr(),
-                   d_el.data_ptr(), d_el.stride(0), delta.data_ptr(), ptr(ds_out), ptr(out_pos),
+                   d_el.data_ptr(), d_el.stride(0), delta.data_ptr(), ptr(ds_out), ptr(out_pos), *drop,
                    _stream(d_el) if stream is None else stream), fn.__name__)
         return d_el, delta_given
 
-    def gat_attention_bwd_col(self, er, V, el, dO, lse, delta, slope=0.2, bias=False, d_er=None, dV=None, stream=None, heads=1):
+    def gat_attention_bwd_col(self, er, V, el, dO, lse, delta, slope=0.2, bias=False, d_er=None, dV=None, stream=None, heads=1,
+                              dropout=0.0, seed=0):
         """The column side of the fused backward of ``gat_attention`` (crp_gat_attention_bwd_col_csr_f64 / _f32), on a handle of
         A^T (``from_transpose``): d_er[c, h] = the sum over column c of A of dZ_p and dV[c]_h = sum_p p_p dO[i_p]_h, with ``lse``
         from the forward and ``delta`` from ``gat_attention_bwd_row``.  ``er``, ``d_er`` (rows of this handle, heads) and ``V``,
         ``dV`` have a row per row of this handle; ``el``, ``dO``, ``lse``, ``delta`` one per column.  With ``bias`` the value added
         to a score is this handle's own.  ``dV is V`` is allowed (same tensor); both outputs are allocated when None.  A head wider
-        than 512 (float64) / 1024 (float32) columns raises ValueError.  Returns (d_er, dV)."""
+        than 512 (float64) / 1024 (float32) columns raises ValueError.  ``dropout`` and ``seed``: the forward's; this handle draws
+        the bits the forward's handle drew.  Returns (d_er, dV)."""
         import torch
         heads = _heads(heads)
+        dropout, seed = _dropout(dropout, seed)
         sops = [("er", er), ("el", el)] + ([("d_er", d_er)] if d_er is not None else [])
         vops = [("V", V), ("dO", dO)] + ([("dV", dV)] if dV is not None else [])
         nv, slope, bias = _gat_operands(sops, vops, [("lse", lse), ("delta", delta)], slope, bias, heads)
@@ -448,15 +457,15 @@ class CsrDev:
             dV = torch.empty((x_nrow, nv), dtype=er.dtype, device=er.device)
         if self.nrow == 0:
             return d_er, dV
-        fn = self._lib.crp_gat_attention_bwd_col_csr_f32 if er.dtype == torch.float32 else self._lib.crp_gat_attention_bwd_col_csr_f64
+        fn, drop = _drop_entry(self._lib, "gat_attention", "_bwd_col", er.dtype == torch.float32, dropout, seed)
         L.check(fn(self.handle, heads, nv // heads, slope, bias, er.data_ptr(), er.stride(0), V.data_ptr(), V.stride(0),
                    el.data_ptr() or None, el.stride(0), dO.data_ptr() or None, dO.stride(0), lse.data_ptr() or None,
-                   delta.data_ptr() or None, d_er.data_ptr(), d_er.stride(0), dV.data_ptr(), dV.stride(0),
+                   delta.data_ptr() or None, d_er.data_ptr(), d_er.stride(0), dV.data_ptr(), dV.stride(0), *drop,
                    _stream(dV) if stream is None else stream), fn.__name__)
         return d_er, dV
 
     def gatv2_attention(self, XT, XS0, a, XS1=None, slope=0.2, bias=False, out=None, lse=None, p_out=None, out_pos=None, stream=None,
-                        heads=1):
+                        heads=1, dropout=0.0, seed=0):
         """Fused GATv2 attention over this matrix's pattern (crp_gatv2_attention_csr_f64 / _f32, by the operands' dtype): for every
         head h, s_p = sum_j a[h, j] * leaky_relu(XT[i]_h[j] + XS[c_p]_h[j], slope) (+ the matrix's value of p with ``bias``) and
         out[i]_h = sum_p softmax_p(s) * XS[c_p]_h over the nonzeros p = (i, c_p) of row i; c >= 0 reads row c of XS0, c < 0 row ~c
@@ -464,10 +473,13 @@ class CsrDev:
         width; ``a`` holds heads * dv contiguous elements (1-D, or (heads, dv)); ``out`` has that width and a row per row of
         ``XT`` (allocated when None).  Optional outputs: ``lse`` contiguous (rows, heads), ``p_out`` contiguous (nnz, heads) --
         nonzero p writes row out_pos[p] when ``out_pos`` (int32, nnz entries) is given; with one head both may be 1-D.  A head
-        wider than 512 (float64) / 1024 (float32) columns raises ValueError.  The matrix's values are not changed.  Returns
-        ``out``.  Every error is raised before the library is called."""
+        wider than 512 (float64) / 1024 (float32) columns raises ValueError.  The matrix's values are not changed.  ``dropout`` > 0
+        drops the attention coefficients after the softmax at that rate, by the mask of ``dropout_mask(heads, dropout, seed)``,
+        and scales the kept ones by 1 / (1 - dropout) (crp_gatv2_attention_drop_csr_*); ``lse`` and ``p_out`` are those of the
+        call without it.  Returns ``out``.  Every error is raised before the library is called."""
         import torch
         heads = _heads(heads)
+        dropout, seed = _dropout(dropout, seed)
         vops = [("XT", XT), ("XS0", XS0)] + ([("XS1", XS1)] if XS1 is not None else []) + ([("out", out)] if out is not None else [])
         vecs = [(n_, t) for n_, t in (("lse", lse), ("p_out", p_out)) if t is not None]
         nv, slope, bias = _gatv2_operands(vops, vecs, a, slope, bias, heads)
@@ -487,25 +499,27 @@ class CsrDev:
             out = torch.empty((x_nrow, nv), dtype=XT.dtype, device=XT.device)
         if self.nrow == 0:
             return out
-        fn = self._lib.crp_gatv2_attention_csr_f32 if XT.dtype == torch.float32 else self._lib.crp_gatv2_attention_csr_f64
+        fn, drop = _drop_entry(self._lib, "gatv2_attention", "", XT.dtype == torch.float32, dropout, seed)
         x1p, ldx1 = (XS1.data_ptr(), XS1.stride(0)) if XS1 is not None else (None, 0)
         ptr = lambda t: (t.data_ptr() or None) if t is not None else None
         L.check(fn(self.handle, heads, nv // heads, slope, bias, XT.data_ptr(), XT.stride(0), ptr(XS0), XS0.stride(0), x1p, ldx1,
-                   a.data_ptr(), out.data_ptr(), out.stride(0), ptr(lse), ptr(p_out), ptr(out_pos),
+                   a.data_ptr(), out.data_ptr(), out.stride(0), ptr(lse), ptr(p_out), ptr(out_pos), *drop,
                    _stream(out) if stream is None else stream), fn.__name__)
         return out
 
     def gatv2_attention_bwd_row(self, XT, XS0, a, O, dO, lse, XS1=None, slope=0.2, bias=False, dXT=None, da_part=None, delta=None,
-                                ds_out=None, out_pos=None, stream=None, heads=1):
+                                ds_out=None, out_pos=None, stream=None, heads=1, dropout=0.0, seed=0):
         """The row side of the fused backward of ``gatv2_attention`` (crp_gatv2_attention_bwd_row_csr_f64 / _f32), on the handle the
         forward ran on: with ``O`` and ``lse`` as the forward wrote them and the upstream gradient ``dO``, delta[i, h] =
         <dO[i]_h, O[i]_h>, dXT[i]_h[j] = sum_p dS_p * (z_pj > 0 ? a[h, j] : a[h, j] * slope) and da_part[i]_h[j] = sum_p dS_p *
         leaky_relu(z_pj) -- the row's share of the gradient of ``a``, which ``col_sum`` adds over the rows -- with dS_p = p_p
         (<dO[i]_h, XS[c_p]_h> - delta[i, h]) and p_p = exp(s_p - lse[i, h]).  ``dXT``, ``da_part`` (rows, heads * dv) and ``delta``
         contiguous (rows, heads) are allocated when None; ``ds_out`` (optional, contiguous (nnz, heads)) receives dS_p -- at row
-        out_pos[p] when ``out_pos`` is given.  No output may alias an input.  Returns (dXT, da_part, delta)."""
+        out_pos[p] when ``out_pos`` is given.  No output may alias an input.  ``dropout`` and ``seed``: the forward's (``O`` is the
+        dropped output; dP counts as 0 on a dropped edge and as dP / (1 - dropout) on a kept one).  Returns (dXT, da_part, delta)."""
         import torch
         heads = _heads(heads)
+        dropout, seed = _dropout(dropout, seed)
         vops = ([("XT", XT), ("XS0", XS0)] + ([("XS1", XS1)] if XS1 is not None else []) + [("O", O), ("dO", dO)]
                 + [(n_, t) for n_, t in (("dXT", dXT), ("da_part", da_part)) if t is not None])
         vecs = [("lse", lse)] + [(n_, t) for n_, t in (("delta", delta), ("ds_out", ds_out)) if t is not None]
@@ -532,24 +546,27 @@ class CsrDev:
             delta = delta_given.view(-1)
         if self.nrow == 0:
             return dXT, da_part, delta_given
-        fn = self._lib.crp_gatv2_attention_bwd_row_csr_f32 if XT.dtype == torch.float32 else self._lib.crp_gatv2_attention_bwd_row_csr_f64
+        fn, drop = _drop_entry(self._lib, "gatv2_attention", "_bwd_row", XT.dtype == torch.float32, dropout, seed)
         x1p, ldx1 = (XS1.data_ptr(), XS1.stride(0)) if XS1 is not None else (None, 0)
         ptr = lambda t: (t.data_ptr() or None) if t is not None else None
         L.check(fn(self.handle, heads, nv // heads, slope, bias, XT.data_ptr(), XT.stride(0), ptr(XS0), XS0.stride(0), x1p, ldx1,
                    a.data_ptr(), O.data_ptr(), O.stride(0), dO.data_ptr(), dO.stride(0), lse.data_ptr(), dXT.data_ptr(), dXT.stride(0),
-                   da_part.data_ptr(), da_part.stride(0), delta.data_ptr(), ptr(ds_out), ptr(out_pos),
+                   da_part.data_ptr(), da_part.stride(0), delta.data_ptr(), ptr(ds_out), ptr(out_pos), *drop,
                    _stream(dXT) if stream is None else stream), fn.__name__)
         return dXT, da_part, delta_given
 
-    def gatv2_attention_bwd_col(self, XS, XT, a, dO, lse, delta, slope=0.2, bias=False, dXS=None, stream=None, heads=1):
+    def gatv2_attention_bwd_col(self, XS, XT, a, dO, lse, delta, slope=0.2, bias=False, dXS=None, stream=None, heads=1, dropout=0.0,
+                                seed=0):
         """The column side of the fused backward of ``gatv2_attention`` (crp_gatv2_attention_bwd_col_csr_f64 / _f32), on a handle of
         A^T (``from_transpose``): dXS[c]_h = sum_p dS_p * (z_p > 0 ? a_h : a_h * slope) + sum_p p_p dO[i_p]_h over column c of A --
         two sums in this handle's order and one addition -- with ``lse`` from the forward and ``delta`` from
         ``gatv2_attention_bwd_row``.  ``XS`` and ``dXS`` have a row per row of this handle; ``XT``, ``dO``, ``lse``, ``delta`` one per
         column.  With ``bias`` the value added to a score is this handle's own.  ``dXS is XS`` is allowed (same tensor); it is
-        allocated when None.  Returns dXS."""
+        allocated when None.  ``dropout`` and ``seed``: the forward's; this handle draws the bits the forward's handle drew.
+        Returns dXS."""
         import torch
         heads = _heads(heads)
+        dropout, seed = _dropout(dropout, seed)
         vops = [("XS", XS), ("XT", XT), ("dO", dO)] + ([("dXS", dXS)] if dXS is not None else [])
         nv, slope, bias = _gatv2_operands(vops, [("lse", lse), ("delta", delta)], a, slope, bias, heads)
         lse, delta = _gat_flat("lse", lse, heads), _gat_flat("delta", delta, heads)
@@ -568,11 +585,46 @@ class CsrDev:
             dXS = torch.empty((x_nrow, nv), dtype=XS.dtype, device=XS.device)
         if self.nrow == 0:
             return dXS
-        fn = self._lib.crp_gatv2_attention_bwd_col_csr_f32 if XS.dtype == torch.float32 else self._lib.crp_gatv2_attention_bwd_col_csr_f64
+        fn, drop = _drop_entry(self._lib, "gatv2_attention", "_bwd_col", XS.dtype == torch.float32, dropout, seed)
         L.check(fn(self.handle, heads, nv // heads, slope, bias, XS.data_ptr(), XS.stride(0), XT.data_ptr() or None, XT.stride(0),
                    a.data_ptr(), dO.data_ptr() or None, dO.stride(0), lse.data_ptr() or None, delta.data_ptr() or None,
-                   dXS.data_ptr(), dXS.stride(0), _stream(dXS) if stream is None else stream), fn.__name__)
+                   dXS.data_ptr(), dXS.stride(0), *drop, _stream(dXS) if stream is None else stream), fn.__name__)
         return dXS
+
+    def dropout_mask(self, heads, dropout, seed, out=None, out_pos=None, stream=None):
+        """The attention-dropout mask of the fused GAT / GATv2 calls over this handle (crp_dropout_mask_csr): a uint8 cuda tensor
+        (nnz, heads) of keep flags, entry (p, h) -- row out_pos[p] when ``out_pos`` (int32, nnz entries) is given, ``out`` is then
+        required -- 1 iff ``dropout_keep(seed, r, c, h, dropout)`` with (r, c) = (the row after the row map, the column code) on a
+        handle of A and (the entry's column index, this handle's row after its row map) on a ``from_transpose`` handle, so that
+        both handles of a pair flag the same edges.  Duplicate (r, c) entries share a flag.  Returns ``out``."""
+        import torch
+        heads = _heads(heads)
+        dropout, seed = _dropout(dropout, seed)
+        nnz = self.nnz
+        if out is not None:
+            if not (isinstance(out, torch.Tensor) and out.dtype == torch.uint8 and out.is_contiguous()):
+                raise TypeError("out must be a contiguous uint8 torch tensor on the device")
+            if not out.is_cuda:
+                raise TypeError("out must be on the device")
+        if out_pos is not None:
+            if not (isinstance(out_pos, torch.Tensor) and out_pos.dtype == torch.int32 and out_pos.dim() == 1 and out_pos.is_contiguous()):
+                raise TypeError("out_pos must be a contiguous 1-D int32 torch tensor on the device")
+            if out_pos.numel() != nnz:
+                raise ValueError("out_pos has %d entries, the matrix %d nonzeros" % (out_pos.numel(), nnz))
+            if out is None:
+                raise ValueError("out_pos needs an out to write into")
+            if not out_pos.is_cuda or out_pos.device != out.device:
+                raise TypeError("out_pos must be on the device, with out")
+        elif out is not None and out.numel() < nnz * heads:
+            raise ValueError("out has %d rows, the matrix %d nonzeros" % (out.numel() // heads, nnz))
+        if out is None:
+            out = torch.empty((nnz, heads), dtype=torch.uint8, device=torch.device("cuda", torch.cuda.current_device()))
+        if nnz == 0:
+            return out
+        L.check(self._lib.crp_dropout_mask_csr(self.handle, heads, dropout, seed, out.data_ptr(),
+                                               out_pos.data_ptr() if out_pos is not None else None,
+                                               _stream(out) if stream is None else stream), "crp_dropout_mask_csr")
+        return out
 
     def row_softmax(self, s, out=None, stream=None):
         """Row softmax over this matrix's pattern (crp_csr_dev_row_softmax_f64 / _f32, by the dtype of ``s``): for every row,
@@ -790,6 +842,41 @@ def _gat_operands(sops, vops, vecs, slope, bias, heads, cap=True):
     return nv, slope, int(bool(bias))
 
 
+def _dropout(dropout, seed):
+    """(rate, seed) of the attention dropout as the C calls take them, checked before any library call: a rate in [0, 1), a seed
+    of 64 bits"""
+    try:
+        rate = float(dropout)
+    except (TypeError, ValueError):
+        raise TypeError("dropout must be a number, got %r" % (dropout,))
+    if not (0.0 <= rate < 1.0):
+        raise ValueError("dropout must lie in [0, 1), got %r" % (dropout,))
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
+        raise TypeError("seed must be an integer, got %r" % (seed,))
+    if not (0 <= int(seed) < 1 << 64):
+        raise ValueError("seed must lie in [0, 2^64), got %r" % (seed,))
+    return rate, int(seed)
+
+
+def _drop_entry(lib, family, side, f32, dropout, seed):
+    """(entry point, the arguments it takes before the stream) of a GAT / GATv2 call: the plain one for dropout == 0"""
+    dt = "f32" if f32 else "f64"
+    if dropout == 0.0:
+        return getattr(lib, "crp_%s%s_csr_%s" % (family, side, dt)), ()
+    return getattr(lib, "crp_%s_drop%s_csr_%s" % (family, side, dt)), (dropout, seed)
+
+
+def dropout_keep(seed, r, c, h, dropout):
+    """crp_dropout_keep_host: whether the attention dropout of the fused GAT / GATv2 calls keeps edge (r, c) in head h -- word 0
+    of Philox4x32-10 with key = the seed's two words and counter (r, c, h, 0), held against floor(dropout * 2^32).  ``r``: the row
+    of the output; ``c``: the 32-bit column code (a negative code counts as its bit pattern).  Host code: needs no device."""
+    dropout, seed = _dropout(dropout, seed)
+    rc = L.load().crp_dropout_keep_host(seed, int(r) & 0xFFFFFFFF, int(c) & 0xFFFFFFFF, int(h) & 0xFFFFFFFF, dropout)
+    if rc < 0:
+        raise ValueError("crp_dropout_keep_host refused its arguments")
+    return bool(rc)
+
+
 def _gat_flat(name, t, heads):
     """A per-row or per-nonzero tensor of a GAT call -- contiguous (rows, heads), or 1-D with one head -- as a flat view"""
     if t is None:
@@ -965,19 +1052,35 @@ def _sparse_attention_fn():
     return SparseAttention
 
 
-def gat_attention(A, At, el, er, V, slope=0.2, bias=False, heads=1):
+def gat_attention(A, At, el, er, V, slope=0.2, bias=False, heads=1, dropout=0.0, seed=None):
     """The GAT layer's attention, out[i]_h = sum_p softmax_p(leaky_relu(el[i, h] + er[c_p, h], slope) (+ A's values with ``bias``))
     V[c_p]_h, as a differentiable function of el, er and V: ``A`` is the ``CsrDev`` of the pattern, ``At`` the
     ``CsrDev.from_transpose`` of the same CSR (with ``bias`` both hold the same values).  The forward is ``A.gat_attention``,
     which keeps O and lse; the backward is ``A.gat_attention_bwd_row`` and ``At.gat_attention_bwd_col``.  Nothing nnz-sized is
     stored between the two.  ``el`` (rows, heads), ``er`` (columns, heads) and ``V`` (columns, heads * dv) are 2-D row-major cuda
     tensors of one dtype.  The matrix's values are constants here.  ``At`` must be the transpose of ``A``: its shape and nonzero
-    count are checked, its pattern is not."""
+    count are checked, its pattern is not.  ``dropout`` > 0 (training; evaluation passes 0) drops the attention coefficients
+    after the softmax and scales the kept ones by 1 / (1 - dropout); no mask is stored, the backward re-forms it from ``seed``,
+    which is kept beside O and lse.  ``seed`` None draws 64 bits from torch's default host generator once per call, so that
+    ``torch.manual_seed`` reproduces a run."""
     heads = _heads(heads)
     if At.nrow != A.ncol or At.ncol != A.nrow or At.nnz != A.nnz:
         raise ValueError("At is %d x %d with %d nonzeros: not the transpose of A (%d x %d, %d)"
                          % (At.nrow, At.ncol, At.nnz, A.nrow, A.ncol, A.nnz))
-    return _gat_attention_fn().apply(el, er, V, A, At, float(slope), bool(bias), heads)
+    dropout, seed = _autograd_dropout(dropout, seed)
+    return _gat_attention_fn().apply(el, er, V, A, At, float(slope), bool(bias), heads, dropout, seed)
+
+
+def _autograd_dropout(dropout, seed):
+    """(rate, seed) of a differentiable GAT / GATv2 call: without a seed, 64 bits from torch's default host generator"""
+    rate, _ = _dropout(dropout, 0)
+    if seed is None:
+        if rate == 0.0:
+            return rate, 0
+        import torch
+        hi, lo = (int(x) for x in torch.randint(0, 1 << 32, (2,), dtype=torch.int64))
+        return rate, (hi << 32) | lo
+    return _dropout(rate, seed)
 
 
 _GAT_ATTENTION_FN = None
@@ -992,22 +1095,23 @@ def _gat_attention_fn():
 
     class GatAttention(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, el, er, V, A, At, slope, bias, heads):
+        def forward(ctx, el, er, V, A, At, slope, bias, heads, dropout=0.0, seed=0):
             el, er, V = (t if t.dim() != 2 or t.stride(-1) == 1 else t.contiguous() for t in (el.detach(), er.detach(), V.detach()))
             lse = torch.empty((el.shape[0], heads), dtype=el.dtype, device=el.device)
-            O = A.gat_attention(el, er, V, slope=slope, bias=bias, lse=lse, heads=heads)
+            O = A.gat_attention(el, er, V, slope=slope, bias=bias, lse=lse, heads=heads, dropout=dropout, seed=seed)
             ctx.save_for_backward(el, er, V, O, lse)
-            ctx.handles = (A, At, slope, bias, heads)
+            ctx.handles = (A, At, slope, bias, heads, dropout, seed)
             return O
 
         @staticmethod
         def backward(ctx, dO):
             el, er, V, O, lse = ctx.saved_tensors
-            A, At, slope, bias, heads = ctx.handles
+            A, At, slope, bias, heads, dropout, seed = ctx.handles
             dO = dO if dO.stride(-1) == 1 else dO.contiguous()
-            d_el, delta = A.gat_attention_bwd_row(el, er, V, O, dO, lse, slope=slope, bias=bias, heads=heads)
-            d_er, dV = At.gat_attention_bwd_col(er, V, el, dO, lse, delta, slope=slope, bias=bias, heads=heads)
-            return d_el, d_er, dV, None, None, None, None, None
+            d_el, delta = A.gat_attention_bwd_row(el, er, V, O, dO, lse, slope=slope, bias=bias, heads=heads, dropout=dropout, seed=seed)
+            d_er, dV = At.gat_attention_bwd_col(er, V, el, dO, lse, delta, slope=slope, bias=bias, heads=heads, dropout=dropout,
+                                                seed=seed)
+            return d_el, d_er, dV, None, None, None, None, None, None, None
 
     _GAT_ATTENTION_FN = GatAttention
     return GatAttention
@@ -1044,7 +1148,7 @@ def col_sum(src, out=None, stream=None):
     return out
 
 
-def gatv2_attention(A, At, XT, XS, a, slope=0.2, bias=False, heads=1):
+def gatv2_attention(A, At, XT, XS, a, slope=0.2, bias=False, heads=1, dropout=0.0, seed=None):
     """The GATv2 layer's attention, out[i]_h = sum_p softmax_p(sum_j a[h, j] leaky_relu(XT[i]_h[j] + XS[c_p]_h[j], slope) (+ A's
     values with ``bias``)) XS[c_p]_h, as a differentiable function of XT, XS and a: ``A`` is the ``CsrDev`` of the pattern, ``At``
     the ``CsrDev.from_transpose`` of the same CSR (with ``bias`` both hold the same values).  The forward is
@@ -1052,12 +1156,14 @@ def gatv2_attention(A, At, XT, XS, a, slope=0.2, bias=False, heads=1):
     ``col_sum`` of the rows' shares of the gradient of ``a``.  Nothing nnz-sized is stored.  ``XT`` (rows, heads * dv) and ``XS``
     (columns, heads * dv) are 2-D row-major cuda tensors of one dtype, ``a`` holds heads * dv elements (1-D or (heads, dv)).  One
     tensor may be passed as XT and XS (shared weights): its gradient is the sum of both.  The matrix's values are constants here.
-    ``At`` must be the transpose of ``A``: its shape and nonzero count are checked, its pattern is not."""
+    ``At`` must be the transpose of ``A``: its shape and nonzero count are checked, its pattern is not.  ``dropout`` and ``seed``
+    as in ``gat_attention``."""
     heads = _heads(heads)
     if At.nrow != A.ncol or At.ncol != A.nrow or At.nnz != A.nnz:
         raise ValueError("At is %d x %d with %d nonzeros: not the transpose of A (%d x %d, %d)"
                          % (At.nrow, At.ncol, At.nnz, A.nrow, A.ncol, A.nnz))
-    return _gatv2_attention_fn().apply(XT, XS, a, A, At, float(slope), bool(bias), heads)
+    dropout, seed = _autograd_dropout(dropout, seed)
+    return _gatv2_attention_fn().apply(XT, XS, a, A, At, float(slope), bool(bias), heads, dropout, seed)
 
 
 _GATV2_ATTENTION_FN = None
@@ -1072,28 +1178,28 @@ def _gatv2_attention_fn():
 
     class Gatv2Attention(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, XT, XS, a, A, At, slope, bias, heads):
+        def forward(ctx, XT, XS, a, A, At, slope, bias, heads, dropout=0.0, seed=0):
             XT, XS = (t if t.dim() != 2 or t.stride(-1) == 1 else t.contiguous() for t in (XT.detach(), XS.detach()))
             a = a.detach().contiguous()
             lse = torch.empty((XT.shape[0], heads), dtype=XT.dtype, device=XT.device)
-            O = A.gatv2_attention(XT, XS, a, slope=slope, bias=bias, lse=lse, heads=heads)
+            O = A.gatv2_attention(XT, XS, a, slope=slope, bias=bias, lse=lse, heads=heads, dropout=dropout, seed=seed)
             ctx.save_for_backward(XT, XS, a, O, lse)
-            ctx.handles = (A, At, slope, bias, heads)
+            ctx.handles = (A, At, slope, bias, heads, dropout, seed)
             return O
 
         @staticmethod
         def backward(ctx, dO):
             XT, XS, a, O, lse = ctx.saved_tensors
-            A, At, slope, bias, heads = ctx.handles
+            A, At, slope, bias, heads, dropout, seed = ctx.handles
             dO = dO if dO.stride(-1) == 1 else dO.contiguous()
             dXT = da_part = None
             if getattr(A, "_x_nrow", A.nrow) != A.nrow:         # a row subset writes the rows it names: the others are zero
                 dXT, da_part = torch.zeros_like(XT), torch.zeros_like(XT)
             dXT, da_part, delta = A.gatv2_attention_bwd_row(XT, XS, a, O, dO, lse, slope=slope, bias=bias, dXT=dXT, da_part=da_part,
-                                                            heads=heads)
-            dXS = At.gatv2_attention_bwd_col(XS, XT, a, dO, lse, delta, slope=slope, bias=bias, heads=heads)
+                                                            heads=heads, dropout=dropout, seed=seed)
+            dXS = At.gatv2_attention_bwd_col(XS, XT, a, dO, lse, delta, slope=slope, bias=bias, heads=heads, dropout=dropout, seed=seed)
             da = col_sum(da_part).view(a.shape)
-            return dXT, dXS, da, None, None, None, None, None
+            return dXT, dXS, da, None, None, None, None, None, None, None
 
     _GATV2_ATTENTION_FN = Gatv2Attention
     return Gatv2Attention

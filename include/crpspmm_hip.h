@@ -639,6 +639,100 @@ int crp_gatv2_attention_bwd_col_csr_f32(crp_csr_dev_p At, int heads, int dv, dou
                                         const float *dO, long long lddO, const float *lse, const float *delta,
                                         float *dXS, long long lddXS, void *stream);
 
+/* ---- attention dropout in the fused GAT and GATv2 calls, both directions -----------------------------------------------
+ * The crp_gat_attention_*_csr_* and crp_gatv2_attention_*_csr_* calls above with the attention coefficients dropped after the
+ * edge softmax at rate `drop` and rescaled by 1 / (1 - drop): the same argument lists with (drop, seed) before the stream.  No
+ * mask is stored: the keep bit of an edge is a pure function of (seed, r, c, h), so the forward, both sides of the backward and
+ * crp_dropout_mask_csr re-form it, and nothing nnz-sized lies between forward and backward, as before.
+ * The mask.  Philox4x32-10 (multipliers 0xD2511F53 and 0xCD9E8D57, key increments 0x9E3779B9 and 0xBB67AE85, ten rounds, the key
+ * bumped after each) with key = (seed's low word, seed's high word) and counter = (r, c, h, 0); x = output word 0; the edge is kept
+ * iff x >= thr with thr = (uint32) floor(drop 2^32), formed once on the host in double.  r is the index of the row of O / el / XT /
+ * lse the entry belongs to -- on a handle of A after the handle's row map, on a handle of A^T the entry's column index -- and c the
+ * 32-bit column code as stored: on a handle of A the entry's code (a second-source code goes in as its bit pattern), on a handle of
+ * A^T the index of the er / V / XS row after that handle's row map.  On a one-source pair both handles therefore draw the same
+ * bit for the same edge.  Duplicate (r, c) entries share a bit.  For 0 < drop < 2^-32 every edge is kept and the scale still
+ * applies.  rs = (T) (1.0 / (1.0 - drop)), formed in double and rounded once to the dtype.
+ * Forward, with k_p the keep bit: scores, batches, m, f, e_u and l are exactly the plain call's -- the softmax runs over all
+ * edges -- and only the accumulator changes: acc = fma(k_u ? e_u : +0, V[c_u][j], acc), and O = fl(fl(acc / l) rs).  lse and p_out
+ * are untouched by dropout: bit for bit what the call without it writes.  A row whose edges are all dropped but not all masked
+ * gives O = +0 with its finite lse.
+ * Backward: p, s, g and D = < dO, O > as in the plain call (O is the dropped O, so D is the softmax Jacobian's term unchanged);
+ * dP' = k ? fl(dP rs) : +0,  dS = p (dP' - D),  and the value-side weight is w = k ? fl(p rs) : +0, used in
+ * dV[c] = fma(w_u, dO[i_u][j], acc) (GATv2: in accV).  Everything downstream -- dZ, d_el, d_er, dXT, da_part, accZ and
+ * ds_out = dS -- is unchanged.  The two products with rs are roundings of their own, never contracted with the subtraction.
+ * s, p, dP', dS and k have the same bits on the row side and on the column side.
+ * Head h of a heads-head call is NOT the one-head call on head h's views: the key holds h.
+ * drop == 0 takes the plain call's kernels: the same bits at the same cost.  Returns as the plain calls, and -1, before anything
+ * is written, for a drop that is NaN or outside [0, 1).  Error bounds: DESIGN.md 5q. */
+int crp_gat_attention_drop_csr_f64(crp_csr_dev_p A, int heads, int dv, double slope, int bias,
+        const double *el, long long ldel, const double *er0, long long lder0, const double *er1, long long lder1,
+        const double *V0, long long ldV0, const double *V1, long long ldV1,
+        double *O, long long ldO, double *lse, double *p_out, const int *out_pos,
+        double drop, unsigned long long seed, void *stream);
+int crp_gat_attention_drop_bwd_row_csr_f64(crp_csr_dev_p A, int heads, int dv, double slope, int bias,
+        const double *el, long long ldel, const double *er0, long long lder0, const double *er1, long long lder1,
+        const double *V0, long long ldV0, const double *V1, long long ldV1,
+        const double *O, long long ldO, const double *dO, long long lddO, const double *lse,
+        double *d_el, long long ldd_el, double *delta, double *ds_out, const int *out_pos,
+        double drop, unsigned long long seed, void *stream);
+int crp_gat_attention_drop_bwd_col_csr_f64(crp_csr_dev_p At, int heads, int dv, double slope, int bias,
+        const double *er, long long lder, const double *V, long long ldV,
+        const double *el, long long ldel, const double *dO, long long lddO, const double *lse, const double *delta,
+        double *d_er, long long ldd_er, double *dV, long long lddV,
+        double drop, unsigned long long seed, void *stream);
+int crp_gat_attention_drop_csr_f32(crp_csr_dev_p A, int heads, int dv, double slope, int bias,
+        const float *el, long long ldel, const float *er0, long long lder0, const float *er1, long long lder1,
+        const float *V0, long long ldV0, const float *V1, long long ldV1,
+        float *O, long long ldO, float *lse, float *p_out, const int *out_pos,
+        double drop, unsigned long long seed, void *stream);
+int crp_gat_attention_drop_bwd_row_csr_f32(crp_csr_dev_p A, int heads, int dv, double slope, int bias,
+        const float *el, long long ldel, const float *er0, long long lder0, const float *er1, long long lder1,
+        const float *V0, long long ldV0, const float *V1, long long ldV1,
+        const float *O, long long ldO, const float *dO, long long lddO, const float *lse,
+        float *d_el, long long ldd_el, float *delta, float *ds_out, const int *out_pos,
+        double drop, unsigned long long seed, void *stream);
+int crp_gat_attention_drop_bwd_col_csr_f32(crp_csr_dev_p At, int heads, int dv, double slope, int bias,
+        const float *er, long long lder, const float *V, long long ldV,
+        const float *el, long long ldel, const float *dO, long long lddO, const float *lse, const float *delta,
+        float *d_er, long long ldd_er, float *dV, long long lddV,
+        double drop, unsigned long long seed, void *stream);
+int crp_gatv2_attention_drop_csr_f64(crp_csr_dev_p A, int heads, int dv, double slope, int bias,
+        const double *XT, long long ldXT, const double *XS0, long long ldXS0, const double *XS1, long long ldXS1, const double *a,
+        double *O, long long ldO, double *lse, double *p_out, const int *out_pos,
+        double drop, unsigned long long seed, void *stream);
+int crp_gatv2_attention_drop_bwd_row_csr_f64(crp_csr_dev_p A, int heads, int dv, double slope, int bias,
+        const double *XT, long long ldXT, const double *XS0, long long ldXS0, const double *XS1, long long ldXS1, const double *a,
+        const double *O, long long ldO, const double *dO, long long lddO, const double *lse,
+        double *dXT, long long lddXT, double *da_part, long long ldda, double *delta, double *ds_out, const int *out_pos,
+        double drop, unsigned long long seed, void *stream);
+int crp_gatv2_attention_drop_bwd_col_csr_f64(crp_csr_dev_p At, int heads, int dv, double slope, int bias,
+        const double *XS, long long ldXS, const double *XT, long long ldXT, const double *a,
+        const double *dO, long long lddO, const double *lse, const double *delta, double *dXS, long long lddXS,
+        double drop, unsigned long long seed, void *stream);
+int crp_gatv2_attention_drop_csr_f32(crp_csr_dev_p A, int heads, int dv, double slope, int bias,
+        const float *XT, long long ldXT, const float *XS0, long long ldXS0, const float *XS1, long long ldXS1, const float *a,
+        float *O, long long ldO, float *lse, float *p_out, const int *out_pos,
+        double drop, unsigned long long seed, void *stream);
+int crp_gatv2_attention_drop_bwd_row_csr_f32(crp_csr_dev_p A, int heads, int dv, double slope, int bias,
+        const float *XT, long long ldXT, const float *XS0, long long ldXS0, const float *XS1, long long ldXS1, const float *a,
+        const float *O, long long ldO, const float *dO, long long lddO, const float *lse,
+        float *dXT, long long lddXT, float *da_part, long long ldda, float *delta, float *ds_out, const int *out_pos,
+        double drop, unsigned long long seed, void *stream);
+int crp_gatv2_attention_drop_bwd_col_csr_f32(crp_csr_dev_p At, int heads, int dv, double slope, int bias,
+        const float *XS, long long ldXS, const float *XT, long long ldXT, const float *a,
+        const float *dO, long long lddO, const float *lse, const float *delta, float *dXS, long long lddXS,
+        double drop, unsigned long long seed, void *stream);
+
+/* The mask on its own.  crp_dropout_keep_host: the keep bit (1 or 0) of edge (r, c) and head h, pure host code that needs no
+ * device; -1 for a drop that is NaN or outside [0, 1).  crp_dropout_mask_csr: the (nnz, heads) keep flags of a handle as bytes 1 /
+ * 0 in p_out's layout -- entry (pos, h) at pos heads + h with pos = out_pos[p], or p when out_pos is NULL -- with (r, c) of every
+ * entry as stated above, over a handle of A or of A^T (crp_csr_dev_create_t): what the fused calls re-form, for callers who run
+ * the chain of separate calls.  drop == 0 writes ones.  Asynchronous on `stream`.  Returns 0 (a handle without nonzeros: nothing
+ * is launched), a HIP error (> 0), or -1 before anything is written: a NULL handle, heads < 1, a bad drop, a NULL mask. */
+int crp_dropout_keep_host(unsigned long long seed, unsigned r, unsigned c, unsigned h, double drop);
+int crp_dropout_mask_csr(crp_csr_dev_p A, int heads, double drop, unsigned long long seed, unsigned char *mask,
+                         const int *out_pos, void *stream);
+
 /* ---- row softmax over A's pattern (edge softmax) and its Jacobian product ------
  * For every row r with entries p in [rowptr[r], rowptr[r + 1]):
  *   forward :  m = max_p s[p],  e_p = exp(s[p] - m),  y[p] = e_p / sum_q e_q
