@@ -46,7 +46,10 @@
  * device work there and nowhere else, allocate nothing, wait for nothing and touch no other stream, so they may be captured;
  * the only state they may build is the handle's fp32 copy of the values (fp32, bias = 1), by the first call that needs it.
  * The same holds, word for word, for the GAT attention calls (crp_gat_attention_csr_*, crp_gat_attention_bwd_row_csr_*,
- * crp_gat_attention_bwd_col_csr_*).
+ * crp_gat_attention_bwd_col_csr_*), for the GATv2 attention calls (crp_gatv2_attention_csr_*, crp_gatv2_attention_bwd_row_csr_*,
+ * crp_gatv2_attention_bwd_col_csr_*), for the _drop_ forms of both families (crp_gat_attention_drop_*, crp_gatv2_attention_drop_*)
+ * and for crp_dropout_mask_csr, which reads the handle's pattern only and builds no state at all.  crp_col_sum_* take no handle
+ * and work in the caller's scratch: all of their device work on `stream`, nothing else.
  */
 #ifndef CRPSPMM_HIP_H
 #define CRPSPMM_HIP_H

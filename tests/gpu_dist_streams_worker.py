@@ -95,6 +95,20 @@ def main():
         ds = torch.empty((nnz,), dtype=dt, device=dev)
         both("attention_bwd " + name, lambda: eng.attention_bwd(Q, Kk, V, O0, dO, lse0, dQ, dK, dV, scale=0.2, bias=True, ds_out=ds),
              [dQ, dK, dV, ds])
+        # two heads of 12 columns: the multi-head attention and its backward, the GAT and the GATv2 forward
+        hd = 2
+        lse2, p2 = torch.empty((rows, hd), dtype=dt, device=dev), torch.empty((nnz, hd), dtype=dt, device=dev)
+        both("attention heads 2 " + name, lambda: eng.attention(0, Q, Kk, V, O, scale=0.2, bias=True, lse=lse2, p_out=p2, heads=hd),
+             [O, lse2, p2])
+        O1, lse1 = O.clone(), lse2.clone()
+        ds2 = torch.empty((nnz, hd), dtype=dt, device=dev)
+        both("attention_bwd heads 2 " + name,
+             lambda: eng.attention_bwd(Q, Kk, V, O1, dO, lse1, dQ, dK, dV, scale=0.2, bias=True, ds_out=ds2, heads=hd), [dQ, dK, dV, ds2])
+        el, er, av = rnd(21, (rows, hd), ndt), rnd(22, (rows, hd), ndt), rnd(23, (hd, n // hd), ndt)
+        both("gat_attention heads 2 " + name, lambda: eng.gat_attention(0, el, er, V, O, slope=0.2, bias=True, lse=lse2, p_out=p2, heads=hd),
+             [O, lse2, p2])
+        both("gatv2_attention heads 2 " + name,
+             lambda: eng.gatv2_attention(0, Q, av, Kk, O, slope=0.2, bias=True, lse=lse2, p_out=p2, heads=hd), [O, lse2, p2])
         vals = newv.to(dt)
         both("update_values_dev %s, exec" % name, lambda: (eng.update_values_dev(vals), eng.exec(0, Bm, C_)), [C_])
     torch.cuda.synchronize()

@@ -344,6 +344,25 @@ int crp_transpose_f32(int, int, const float *src, long long, float *dst, long lo
         live_csr(At);                                                                                                                       \
         return kernel(#NAME + 4, s, {R{At}, R{K}, R{V}, R{Q}, R{dO}, R{lse}, R{delta}}, {W{dK}, W{dV}});                                    \
     }
+// the fused GAT and GATv2 attention, forward (csrc/rp_gat.cpp): el / XT and a are local, er, V and XS have the two sources of the column code
+#define GAT_STANDIN(NAME, T)                                                                                                                \
+    int NAME(crp_csr_dev_p A, int, int, double, int, const T *el, long long, const T *er0, long long, const T *er1, long long,              \
+             const T *V0, long long, const T *V1, long long, T *O, long long, T *lse, T *p_out, const int *pos, void *s)                    \
+    {                                                                                                                                       \
+        live_csr(A);                                                                                                                        \
+        return kernel(#NAME + 4, s, {R{A}, R{el}, R{A->b0 ? er0 : NULL}, R{A->b1 ? er1 : NULL}, R{A->b0 ? V0 : NULL}, R{A->b1 ? V1 : NULL}, R{pos}}, {W{O}, W{lse}, W{p_out}});   \
+    }
+#define GATV2_STANDIN(NAME, T)                                                                                                              \
+    int NAME(crp_csr_dev_p A, int, int, double, int, const T *XT, long long, const T *XS0, long long, const T *XS1, long long, const T *a,  \
+             T *O, long long, T *lse, T *p_out, const int *pos, void *s)                                                                    \
+    {                                                                                                                                       \
+        live_csr(A);                                                                                                                        \
+        return kernel(#NAME + 4, s, {R{A}, R{XT}, R{a}, R{A->b0 ? XS0 : NULL}, R{A->b1 ? XS1 : NULL}, R{pos}}, {W{O}, W{lse}, W{p_out}});   \
+    }
+GAT_STANDIN(crp_gat_attention_csr_f64, double)
+GAT_STANDIN(crp_gat_attention_csr_f32, float)
+GATV2_STANDIN(crp_gatv2_attention_csr_f64, double)
+GATV2_STANDIN(crp_gatv2_attention_csr_f32, float)
 FWD_STANDIN(crp_attention_csr_f64, double)
 FWD_STANDIN(crp_attention_csr_f32, float)
 FWD_STANDIN(crp_attention_mh_csr_f64, double, int,)

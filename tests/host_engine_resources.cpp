@@ -1,4 +1,4 @@
-// Who releases what in the two engines (csrc/rp_engine.cpp, csrc/para2d_engine.cpp, csrc/dev_owned.h), under AddressSanitizer /
+// Who releases what in the two engines (csrc/rp_engine.cpp, csrc/rp_attention.cpp, csrc/rp_gat.cpp, csrc/para2d_engine.cpp, csrc/dev_owned.h), under AddressSanitizer /
 // UBSan on the CPU; built and run by tests/test_host_sanitizers.py.  The device ABI is a set of host stand-ins: "device" memory is
 // calloc, kernels and matrix handles do no arithmetic, every call is counted, and a free, destroy, copy or stream / event call on
 // something that is not live ends the program.  The engines run over crp_comm_self() on a tiny matrix and on one without
@@ -191,6 +191,21 @@ static void full_engine(const Matrix &A, bool dev_update_first)
     {
         attention_mh<double>(e, A, layout, crp_rp_spmm_attention_mh_ex);
         attention_mh<float>(e, A, layout, crp_rp_spmm_attention_mh_f32_ex);
+    }
+    // the GAT and GATv2 forward (csrc/rp_gat.cpp): el, er, XT and a on the device, V, O, lse and p_out on the host; one GAT call per
+    // dtype, one with another number of heads (the narrow exchange is set up again), one GATv2 call
+    {
+        const size_t mN = (size_t) A.m * N;
+        DevBuf<double> el(mN), er(mN), XT(mN), av(N);
+        DevBuf<float> elf(mN), erf(mN);
+        std::vector<double> V(mN, 1.0), O(mN), lse(mN + 1), p(nnz * N + 1);
+        std::vector<float> Vf(mN, 1.0f), Of(mN), lsef(mN + 1), pf(nnz * N + 1);
+        crp_rp_spmm_gat_ex(e, 0, N, 0.2, 1, el.p, N, er.p, N, V.data(), N, O.data(), N, lse.data(), p.data(), NULL);
+        crp_rp_spmm_gat_f32_ex(e, 1, N, 0.2, 1, elf.p, N, erf.p, N, Vf.data(), A.m, Of.data(), A.m, lsef.data(), pf.data(), NULL);
+        crp_rp_spmm_gat_ex(e, 1, 1, 0.2, 0, el.p, N, er.p, N, V.data(), A.m, O.data(), A.m, lse.data(), p.data(), NULL);
+        crp_rp_spmm_gat_ex(e, 0, N, 0.2, 1, el.p, N, er.p, N, V.data(), N, O.data(), N, lse.data(), p.data(), NULL);
+        crp_rp_spmm_gatv2_ex(e, 0, N, 0.2, 1, XT.p, N, av.p, V.data(), N, O.data(), N, lse.data(), p.data(), NULL);
+        CHECK(crp_rp_spmm_gat_built(e) == 1 && crp_rp_spmm_gatv2_built(e) == 1, "the GAT calls built nothing");
     }
     // device operands with timing off: the exec returns asynchronously and leaves its event behind
     {

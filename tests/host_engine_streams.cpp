@@ -1,4 +1,4 @@
-// The ORDER of the row-parallel engine's device work across streams (csrc/rp_engine.cpp, csrc/rp_attention.cpp), checked on the
+// The ORDER of the row-parallel engine's device work across streams (csrc/rp_engine.cpp, csrc/rp_attention.cpp, csrc/rp_gat.cpp), checked on the
 // CPU under AddressSanitizer / UBSan; built and run by tests/test_host_sanitizers.py.  The device ABI is the set of host stand-ins of
 // tests/host_device_standins.h, which log every call as (call, stream, buffers read, buffers written) and every event record and wait.
 // A single-threaded fake communicator plays rank 0 of 2: it answers the plan's alltoall_i32 / alltoallv_i32 with fabricated but
@@ -134,6 +134,8 @@ int main()
     CHECK(n_int == 2 && n_bnd == 2, "the engine is not split: %d interior, %d boundary rows", n_int, n_bnd);
     crp_rp_spmm_set_timing(e, 0);
     void *caller = NULL, *caller2 = NULL;
+    std::vector<std::pair<size_t, size_t>> gat_calls;      // the log's [first, end) of every GAT / GATv2 call
+    size_t probe = 0;                                      // ... and which of them the GAT negative control takes apart
     crp_stream_create(&caller);
     crp_stream_create(&caller2);
     {
@@ -141,9 +143,23 @@ int main()
             V((size_t) m * N), O((size_t) m * N), lse(m), p(nnz), dO((size_t) m * N), dQ((size_t) m * N), dK((size_t) m * N), dV((size_t) m * N),
             ds(nnz), vals(nnz), vals2(nnz), lse_mh((size_t) m * N), p_mh(nnz * N), ds_mh(nnz * N);      // (_mh: N heads of one column)
         Dev<float> Bf((size_t) m * N), Cf((size_t) m * N), Xf((size_t) m * N), outf(nnz), valsf(nnz);
+        // the GAT and GATv2 calls' own operands: el, er (N heads, one scalar each), XT and a; fp32 lse and p_out for N heads
+        Dev<double> el((size_t) m * N), er((size_t) m * N), XT((size_t) m * N), av(N);
+        Dev<float> elf((size_t) m * N), erf((size_t) m * N), XTf((size_t) m * N), avf(N), lsef((size_t) m * N), pf(nnz * N);
         // what the caller wrote before: on the caller's stream (the engine must order its other streams after it)
-        for (double *b : {B.p, X.p, Q.p, K.p, V.p, dO.p, vals.p}) crp_dev_memset(b, 0, 8, caller);
-        for (float *b : {Bf.p, Xf.p, valsf.p}) crp_dev_memset(b, 0, 4, caller);
+        for (double *b : {B.p, X.p, Q.p, K.p, V.p, dO.p, vals.p, el.p, er.p, XT.p, av.p}) crp_dev_memset(b, 0, 8, caller);
+        for (float *b : {Bf.p, Xf.p, valsf.p, elf.p, erf.p, XTf.p, avf.p}) crp_dev_memset(b, 0, 4, caller);
+        // (heads == N in the rounds; the heads sequence below also passes 1: the buffers hold N entries per row either way)
+        auto gat = [&](int heads, void *s) {
+            const size_t lo = g_log.size();
+            crp_rp_spmm_gat_ex(e, 0, heads, 0.2, 1, el.p, N, er.p, N, V.p, N, O.p, N, lse_mh.p, p_mh.p, s);
+            gat_calls.push_back({lo, g_log.size()});
+        };
+        auto gat_f32 = [&](int heads, void *s) {
+            const size_t lo = g_log.size();
+            crp_rp_spmm_gat_f32_ex(e, 0, heads, 0.2, 1, elf.p, N, erf.p, N, Bf.p, N, Cf.p, N, lsef.p, pf.p, s);
+            gat_calls.push_back({lo, g_log.size()});
+        };
         auto round_of_calls = [&](void *s) {
             crp_rp_spmm_exec_ex(e, 0, B.p, N, C.p, N, s);
             crp_rp_spmm_exec_f32_ex(e, 0, Bf.p, N, Cf.p, N, s);
@@ -155,6 +171,12 @@ int main()
             crp_rp_spmm_attention_bwd_ex(e, 0.5, 1, Q.p, N, K.p, N, V.p, N, O.p, N, dO.p, N, lse.p, dQ.p, N, dK.p, N, dV.p, N, ds.p, s);
             crp_rp_spmm_attention_mh_ex(e, 0, N, 0.5, 1, Q.p, N, K.p, N, V.p, N, O.p, N, lse_mh.p, p_mh.p, s);
             crp_rp_spmm_attention_bwd_mh_ex(e, N, 0.5, 1, Q.p, N, K.p, N, V.p, N, O.p, N, dO.p, N, lse_mh.p, dQ.p, N, dK.p, N, dV.p, N, ds_mh.p, s);
+            gat(N, s);
+            gat_f32(N, s);
+            const size_t lo = g_log.size();
+            crp_rp_spmm_gatv2_ex(e, 0, N, 0.2, 1, XT.p, N, av.p, V.p, N, O.p, N, lse_mh.p, p_mh.p, s);
+            crp_rp_spmm_gatv2_f32_ex(e, 0, N, 0.2, 1, XTf.p, N, avf.p, Bf.p, N, Cf.p, N, lsef.p, pf.p, s);
+            gat_calls.push_back({lo, g_log.size()});
         };
         round_of_calls(caller);                                  // the first calls build what they need
         round_of_calls(caller);                                  // steady state
@@ -173,6 +195,16 @@ int main()
         crp_stream_sync(caller2);
         crp_rp_spmm_update_values_dev(e, vals.p, 0, caller);     // ... and back: after an update on another stream
         round_of_calls(caller);
+        // other numbers of heads behind work in flight on the caller's stream: every call frees the narrow send and receive
+        // buffers, allocates them again and zero-fills them on the null stream; then one steady-state call (the negative control's)
+        for (int heads : {1, N})
+        {
+            gat(heads, caller);
+            gat_f32(heads, caller);
+        }
+        round_of_calls(caller);
+        probe = gat_calls.size();
+        gat(N, caller);
         crp_stream_sync(caller);
         crp_stream_sync(caller2);
     }
@@ -215,7 +247,49 @@ int main()
     CHECK(victim != (size_t) -1, "the caller's stream never waits for an engine stream");
     const std::vector<Race> broken = races(g_log, victim);
     CHECK(!broken.empty(), "the checker does not see the race of a log without wait #%zu", victim);
-    printf("HOST_ENGINE_STREAMS_OK ops=%zu streams=%zu exchanges=%ld cross_stream_waits=%ld needed=%ld control_races=%zu\n", g_log.size(),
-           work_streams.size(), exchanges, cross, needed, broken.size());
+
+    // ---- the GAT and GATv2 calls (csrc/rp_gat.cpp) reached the overlap path: exchanges on the engine's second stream and
+    // cross-stream waits inside their stretches of the log; the heads sequence set the narrow buffers up again
+    long gat_exchanges = 0, gat_waits = 0, gat_zero_fills = 0;
+    for (const std::pair<size_t, size_t> &call : gat_calls)
+        for (size_t i = call.first; i < call.second; i++)
+        {
+            const Op &op = g_log[i];
+            if (op.kind == OP_WORK && strcmp(op.call, "alltoallv_dev_f64") == 0 && op.stream != caller && op.stream != caller2) gat_exchanges++;
+            if (op.kind == OP_WORK && strcmp(op.call, "dev_memset") == 0 && op.stream == NULL) gat_zero_fills++;
+            if (op.kind == OP_WAIT && recorded_on.count(op.event) && recorded_on[op.event] != op.stream) gat_waits++;
+        }
+    CHECK(gat_exchanges > 0 && gat_waits > 0, "the GAT calls made no exchange on the engine's second stream (%ld) or no wait (%ld)", gat_exchanges,
+          gat_waits);
+    // both dtypes, both buffers: the first call and the two calls with another number of heads
+    CHECK(gat_zero_fills == 2 * 2 * 3, "the narrow buffers were zero-filled %ld times", gat_zero_fills);
+
+    // ---- negative control of the GAT call: one steady-state call packs and exchanges V, then er, on the engine's second stream; the
+    // caller's stream then waits for both.  Without that wait the boundary kernel races with the exchanges, and one of the buffers
+    // is the narrow receive buffer, which the call's SECOND alltoallv_dev_f64 wrote: the stand-in reads it
+    CHECK(probe < gat_calls.size(), "no GAT call for the control");
+    const void *narrow_recv = NULL;
+    size_t gat_victim = (size_t) -1;
+    int seen = 0;
+    for (size_t i = gat_calls[probe].first; i < gat_calls[probe].second; i++)
+    {
+        const Op &op = g_log[i];
+        if (op.kind == OP_WORK && strcmp(op.call, "alltoallv_dev_f64") == 0 && ++seen == 2)
+        {
+            CHECK(op.stream != caller && op.writes.size() == 1, "the GAT call's second exchange");
+            narrow_recv = op.writes[0];
+        }
+        if (op.kind == OP_WAIT && seen == 2 && op.stream == caller && gat_victim == (size_t) -1) gat_victim = i;
+    }
+    CHECK(seen == 2 && narrow_recv != NULL && gat_victim != (size_t) -1, "the GAT call made %d exchanges, or the caller's stream does not wait", seen);
+    const std::vector<Race> gat_broken = races(g_log, gat_victim);
+    bool on_narrow = false;
+    for (const Race &r : gat_broken)
+        if (r.buffer == narrow_recv && strncmp(g_log[r.second].call, "gat_attention_csr", 17) == 0) on_narrow = true;
+    CHECK(!gat_broken.empty(), "the checker does not see the race of a GAT call without wait #%zu", gat_victim);
+    CHECK(on_narrow, "none of the %zu races without wait #%zu is the boundary kernel's read of the narrow receive buffer", gat_broken.size(), gat_victim);
+    printf("HOST_ENGINE_STREAMS_OK ops=%zu streams=%zu exchanges=%ld cross_stream_waits=%ld needed=%ld control_races=%zu gat_calls=%zu "
+           "gat_exchanges=%ld gat_cross_stream_waits=%ld gat_zero_fills=%ld gat_control_races=%zu\n", g_log.size(), work_streams.size(), exchanges, cross,
+           needed, broken.size(), gat_calls.size(), gat_exchanges, gat_waits, gat_zero_fills, gat_broken.size());
     return 0;
 }

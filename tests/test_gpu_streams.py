@@ -1,16 +1,23 @@
 """GPU: the stream contract of include/crpspmm_hip.h ("Streams") and include/crp_engine.h, on a held-back non-blocking side
 stream (tests/streams_harness.py, which explains the method).  Measured on the MI355X: the slowest steady-state host call of the
-table is hip.sparse_attention forward + backward at 0.52 ms, the delay is 120 ms (2.39e6 cycles of torch.cuda._sleep per ms).
+table is hip.gatv2_attention forward + backward with dropout at 0.39 ms (the least of three), the delay is 120 ms (2.39e6 cycles
+of torch.cuda._sleep per ms).
 
-TABLE reaches every launcher of the device ABI at least once, on the smallest matrix that reaches it; the kernels' numerics are
-pinned elsewhere.  Every row makes three assertions -- Order, Asynchrony, Control -- and every row that is not `blocking` is also
+What the rows must reach is read from the headers, not kept by hand: every crp_* prototype of include/crpspmm_hip.h and
+include/crp_engine.h with a `void *stream` parameter (stream_entry_points) that is not in EXEMPT -- plumbing and probes, each
+with its reason -- is really called by the reference call of a row of TABLE or ENGINE_ROWS, which is observed on the loaded
+library object (test_every_stream_taking_entry_point_is_reached); an entry point added to a header without a row fails it.
+TABLE also names every product launcher (test_the_table_reaches_every_launcher), each on the smallest matrix that reaches it; the
+kernels' numerics are pinned elsewhere.  Every row makes three assertions -- Order, Asynchrony, Control -- and every row that is not `blocking` is also
 captured into a graph on the side stream and replayed on a second data set.
 
 Order is asserted BIT FOR BIT in every row: the header promises repeatability for every call of the table (crp_spmm_csr_f64:
 "repeated calls are bit-identical"; crp_sddmm_csr_*, the row softmax, crp_scatter_add_rows_*, crp_sum_segments_*: "Repeated calls
 are ... bit-identical"; the attention calls and their backward: "A row's bits depend on (dtype, nk, nv, scale, bias) and the row's
-entries in CSR order ONLY"; the fp32 products are pinned exactly by tests/test_gpu_fp32_kernels.py; the row movers only move), so
-no row falls back to a bound.
+entries in CSR order ONLY"; the GAT and GATv2 calls: "O, lse and p_out are bit for bit what that order gives", every backward sum
+"from +0 in ascending p" or in the handle's CSR order; their _drop_ forms and crp_dropout_mask_csr: "the keep bit of an edge is a
+pure function of (seed, r, c, h)"; crp_col_sum_*: "repeated calls are bit-identical"; the fp32 products are pinned exactly by
+tests/test_gpu_fp32_kernels.py; the row movers only move), so no row falls back to a bound.
 
 BLOCKING holds the only calls that may block, each with the header sentence that says so (test_blocking_rows_quote_the_header);
 they are exempt from Asynchrony and are the calls that are not capturable (NOT_CAPTURABLE is the same table: nothing else is in it).
@@ -39,6 +46,7 @@ BLOCKING = {
     "csr-transpose": "HIP kernels on `stream`, which the call synchronises",
     "first-build": "The first call that builds state on a handle blocks: what it builds is complete on return.",
     "timing-on": "With timing on every call waits for its stream.",
+    "other-heads": "that call blocks, as does a call with another number of heads, which sets them up again",
 }
 NOT_CAPTURABLE = BLOCKING
 
@@ -53,6 +61,70 @@ def test_blocking_rows_quote_the_header():
     assert all(b is None or b in BLOCKING for _, b, _ in TABLE)
 
 
+# ---- completeness: the stream-taking entry points are read from the headers, not kept by hand -------------------------------
+
+# entry points that take a stream and launch no compute kernel: plumbing and probes.  Everything else must be reached by a row.
+EXEMPT = {
+    "crp_dev_memset": "plumbing: hipMemsetAsync on the stream it is given",
+    "crp_dev_memcpy": "plumbing: hipMemcpyAsync on the stream it is given",
+    "crp_dev_memcpy2d": "plumbing: hipMemcpy2DAsync on the stream it is given",
+    "crp_stream_destroy": "plumbing: the stream is the object, not where work goes",
+    "crp_stream_sync": "plumbing: the stream is the object, not where work goes",
+    "crp_stream_wait_event": "plumbing: the stream is the object, not where work goes",
+    "crp_event_record": "plumbing: hipEventRecord on the stream it is given",
+    "crp_probe_stamp": "probe: a one-thread kernel that writes the device clock, a diagnostic of tools/overlap_probe.py",
+    "crp_probe_copy": "probe: a stand-in for a transport's copy kernel with clock stamps, a diagnostic of tools/overlap_probe.py",
+}
+_EXEMPT_KIND = re.compile(r"crp_(dev_mem(set|cpy|cpy2d)|stream_\w+|event_record|probe_\w+)$")
+
+
+def stream_entry_points(header):
+    """every crp_* prototype of include/<header> with a `void *stream` parameter, comments stripped first"""
+    with open(os.path.join(ROOT, "include", header)) as f:
+        text = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S))
+    return {m.group(1) for m in re.finditer(r"\b(crp_\w+)\s*\(([^;{}()]*)\)\s*;", text) if re.search(r"\bvoid\s*\*\s*stream\b", m.group(2))}
+
+
+def test_the_headers_name_their_stream_taking_entry_points():
+    """the parse finds something, old and new: a regular expression that silently matches nothing fails here.  (The counts are the
+    headers' of today; a new entry point changes them, and test_every_stream_taking_entry_point_is_reached then asks for its row.)"""
+    dev, eng = stream_entry_points("crpspmm_hip.h"), stream_entry_points("crp_engine.h")
+    assert {"crp_spmm_csr_f64", "crp_csr_dev_update_values", "crp_gatv2_attention_drop_bwd_col_csr_f32", "crp_dropout_mask_csr",
+            "crp_col_sum_f32"} <= dev, sorted(dev)
+    assert {"crp_rp_spmm_exec_ex", "crp_para2d_spmm_update_values_dev", "crp_rp_spmm_gatv2_f32_ex", "crp_rp_spmm_attention_bwd_mh_ex"} <= eng, sorted(eng)
+    assert len(dev) >= 74 and len(eng) >= 30, (len(dev), len(eng))
+    assert not dev & eng
+    assert set(EXEMPT) <= dev and all(_EXEMPT_KIND.match(name) for name in EXEMPT), sorted(set(EXEMPT) - dev)
+    assert "crp_stream_create" not in dev                      # (takes a void **: where the stream is made, not used)
+
+
+class _observed:
+    """While a call runs, every stream-taking entry point of the loaded library object is wrapped: the names that are REALLY
+    called are added to `reached`.  The wrappers are attributes of the library object, which is where the Python layer looks an
+    entry point up for every call; the originals are put back on exit."""
+
+    def __init__(self, lib, reached):
+        self.lib, self.reached, self.saved = lib, reached, {}
+
+    def __enter__(self):
+        names = (stream_entry_points("crpspmm_hip.h") | stream_entry_points("crp_engine.h")) - set(EXEMPT)
+        for name in names:
+            fn = getattr(self.lib, name)
+
+            def spy(*args, _fn=fn, _name=name):
+                self.reached.add(_name)
+                return _fn(*args)
+            spy.__name__ = name
+            self.saved[name] = fn
+            setattr(self.lib, name, spy)
+        return self
+
+    def __exit__(self, *exc):
+        for name, fn in self.saved.items():
+            setattr(self.lib, name, fn)
+        return False
+
+
 class Ctx:
     """what the rows share: the device, the library, the held-back stream, the matrices and handles (made on first use)"""
 
@@ -64,6 +136,8 @@ class Ctx:
         self.va2 = np.random.default_rng(8).uniform(-2, 2, self.ci.size)
         self.cache, self.keep = {}, []
         self.kernels = set()
+        self.cache_data = {}                 # staging data that takes a forward to make (_gat_data), made once
+        self.reached = set()                 # the stream-taking entry points the rows' reference calls went through (_observed)
 
     def handle(self, key):
         from crp_spmm_amd import hip
@@ -169,55 +243,202 @@ def _sddmm(dt, mode, two_source=False, out_pos=False):
     return build
 
 
-def _attn_data(c, dt, seed, nk=16, nv=24):
-    """Q, K, V, dO and what the forward writes for them on the default stream: O, lse (staging data of the backward rows)"""
+def _attn_data(c, dt, seed, nk=16, nv=24, heads=1):
+    """Q, K, V, dO and what the forward writes for them on the default stream: O, lse (staging data of the backward rows); with
+    `heads` > 1 that many heads of nk / nv columns side by side, lse and delta (rows, heads)"""
     import torch
     import attention_bwd_ref as B
     A = c.handle("B")
+    nk, nv = nk * heads, nv * heads
     Q, Kk, V, dO = (torch.from_numpy(_rnd(seed + i, sh, dt)).to(c.gpu)
                     for i, sh in enumerate(((B.NROW, nk), (B.NCOL, nk), (B.NCOL, nv), (B.NROW, nv))))
-    lse = torch.empty((B.NROW,), dtype=Q.dtype, device=c.gpu)
-    O = A.attention(Q, Kk, V, scale=0.25, bias=True, lse=lse)
-    dQ, delta = A.attention_bwd_q(Q, Kk, V, O, dO, lse, scale=0.25, bias=True)
+    lse = torch.empty((B.NROW,) if heads == 1 else (B.NROW, heads), dtype=Q.dtype, device=c.gpu)
+    O = A.attention(Q, Kk, V, scale=0.25, bias=True, lse=lse, heads=heads)
+    dQ, delta = A.attention_bwd_q(Q, Kk, V, O, dO, lse, scale=0.25, bias=True, heads=heads)
     torch.cuda.synchronize()
     return dict(Q=Q, K=Kk, V=V, dO=dO, O=O, lse=lse, delta=delta)
 
 
-def _attention(dt):
+def _per_head(count, heads):
+    """the shape of a per-row or per-nonzero vector: 1-D with one head, (count, heads) with several"""
+    return (count,) if heads == 1 else (count, heads)
+
+
+def _attention(dt, heads=1):
     def build(c):
         import attention_bwd_ref as B
         ops = H.Operands(c.gpu)
         A = c.handle("B")
-        d0, d1 = _attn_data(c, dt, 10), _attn_data(c, dt, 20)
+        d0, d1 = _attn_data(c, dt, 10, heads=heads), _attn_data(c, dt, 20, heads=heads)
         Q, Kk, V = (ops.dense(d0[k], d1[k]) for k in ("Q", "K", "V"))
-        O, lse, p = ops.out((B.NROW, 24), _tdt(dt)), ops.out((B.NROW,), _tdt(dt)), ops.out((A.nnz,), _tdt(dt))
-        return ops, lambda stream: A.attention(Q, Kk, V, scale=0.25, bias=True, out=O, lse=lse, p_out=p, stream=stream)
+        O, lse, p = (ops.out(sh, _tdt(dt)) for sh in ((B.NROW, 24 * heads), _per_head(B.NROW, heads), _per_head(A.nnz, heads)))
+        return ops, lambda stream: A.attention(Q, Kk, V, scale=0.25, bias=True, out=O, lse=lse, p_out=p, stream=stream, heads=heads)
     return build
 
 
-def _attention_bwd_q(dt):
+def _attention_bwd_q(dt, heads=1):
     def build(c):
         import attention_bwd_ref as B
         ops = H.Operands(c.gpu)
         A = c.handle("B")
-        d0, d1 = _attn_data(c, dt, 10), _attn_data(c, dt, 20)
+        d0, d1 = _attn_data(c, dt, 10, heads=heads), _attn_data(c, dt, 20, heads=heads)
         Q, Kk, V, O, dO, lse = (ops.dense(d0[k], d1[k]) for k in ("Q", "K", "V", "O", "dO", "lse"))
-        dQ, delta, ds = ops.out((B.NROW, 16), _tdt(dt)), ops.out((B.NROW,), _tdt(dt)), ops.out((A.nnz,), _tdt(dt))
+        dQ, delta, ds = (ops.out(sh, _tdt(dt)) for sh in ((B.NROW, 16 * heads), _per_head(B.NROW, heads), _per_head(A.nnz, heads)))
         return ops, lambda stream: A.attention_bwd_q(Q, Kk, V, O, dO, lse, scale=0.25, bias=True, dQ=dQ, delta=delta, ds_out=ds,
-                                                     stream=stream)
+                                                     stream=stream, heads=heads)
     return build
 
 
-def _attention_bwd_kv(dt, in_place=False):
+def _attention_bwd_kv(dt, in_place=False, heads=1):
     def build(c):
         import attention_bwd_ref as B
         ops = H.Operands(c.gpu)
         At = c.handle("Bt")
-        d0, d1 = _attn_data(c, dt, 10), _attn_data(c, dt, 20)
+        d0, d1 = _attn_data(c, dt, 10, heads=heads), _attn_data(c, dt, 20, heads=heads)
         Kk, V = (ops.dense(d0[k], d1[k], inout=in_place) for k in ("K", "V"))
         Q, dO, lse, delta = (ops.dense(d0[k], d1[k]) for k in ("Q", "dO", "lse", "delta"))
-        dK, dV = (Kk, V) if in_place else (ops.out((B.NCOL, 16), _tdt(dt)), ops.out((B.NCOL, 24), _tdt(dt)))
-        return ops, lambda stream: At.attention_bwd_kv(Kk, V, Q, dO, lse, delta, scale=0.25, bias=True, dK=dK, dV=dV, stream=stream)
+        dK, dV = (Kk, V) if in_place else (ops.out((B.NCOL, 16 * heads), _tdt(dt)), ops.out((B.NCOL, 24 * heads), _tdt(dt)))
+        return ops, lambda stream: At.attention_bwd_kv(Kk, V, Q, dO, lse, delta, scale=0.25, bias=True, dK=dK, dV=dV, stream=stream,
+                                                       heads=heads)
+    return build
+
+
+HEADS, DV, SLOPE, SEED = 2, 12, 0.2, 0x5EED5EED12345         # the GAT / GATv2 rows: two heads of 12 columns
+
+
+def _gat_data(c, dt, seed, v2, dropout):
+    """The operands of the GAT (v2: GATv2) rows on the handles "B" / "Bt" and what a real forward and row-side backward write for
+    them on the default stream -- O, lse, delta: staging data of the backward rows, which need them consistent.  Made once."""
+    import torch
+    import attention_bwd_ref as B
+    key = ("gat-data", np.dtype(dt).name, seed, v2, dropout)
+    if key in c.cache_data:
+        return c.cache_data[key]
+    A = c.handle("B")
+    n = HEADS * DV
+    kw = dict(slope=SLOPE, bias=True, heads=HEADS, dropout=dropout, seed=SEED)
+    lse = torch.empty((B.NROW, HEADS), dtype=_tdt(dt), device=c.gpu)
+    T = lambda i, sh: torch.from_numpy(_rnd(seed + i, sh, dt)).to(c.gpu)
+    dO = T(0, (B.NROW, n))
+    if v2:
+        d = dict(XT=T(1, (B.NROW, n)), XS=T(2, (B.NCOL, n)), a=T(3, (HEADS, DV)), dO=dO, lse=lse)
+        d["O"] = A.gatv2_attention(d["XT"], d["XS"], d["a"], lse=lse, **kw)
+        _, d["da_part"], d["delta"] = A.gatv2_attention_bwd_row(d["XT"], d["XS"], d["a"], d["O"], dO, lse, **kw)
+    else:
+        d = dict(el=T(1, (B.NROW, HEADS)), er=T(2, (B.NCOL, HEADS)), V=T(3, (B.NCOL, n)), dO=dO, lse=lse)
+        d["O"] = A.gat_attention(d["el"], d["er"], d["V"], lse=lse, **kw)
+        _, d["delta"] = A.gat_attention_bwd_row(d["el"], d["er"], d["V"], d["O"], dO, lse, **kw)
+    torch.cuda.synchronize()
+    c.cache_data[key] = d
+    return d
+
+
+def _gat(dt, what, dropout, v2=False):
+    """gat_attention / gatv2_attention (what "fwd"), their row side with ds_out ("bwd_row") and their column side ("bwd_col");
+    dropout 0 reaches the plain entry points, dropout > 0 the _drop_ ones"""
+    def build(c):
+        import attention_bwd_ref as B
+        ops = H.Operands(c.gpu)
+        A, At = c.handle("B"), c.handle("Bt")
+        d0, d1 = _gat_data(c, dt, 100, v2, dropout), _gat_data(c, dt, 200, v2, dropout)
+        n, t = HEADS * DV, _tdt(dt)
+        kw = dict(slope=SLOPE, bias=True, heads=HEADS, dropout=dropout, seed=SEED)
+        D = lambda *names: tuple(ops.dense(d0[k], d1[k]) for k in names)
+        if what == "fwd":
+            x = D("XT", "XS", "a") if v2 else D("el", "er", "V")
+            O, lse, p = ops.out((B.NROW, n), t), ops.out((B.NROW, HEADS), t), ops.out((A.nnz, HEADS), t)
+            fn = A.gatv2_attention if v2 else A.gat_attention
+            return ops, lambda stream: fn(*x, out=O, lse=lse, p_out=p, stream=stream, **kw)
+        if what == "bwd_row":
+            x = D("XT", "XS", "a", "O", "dO", "lse") if v2 else D("el", "er", "V", "O", "dO", "lse")
+            delta, ds = ops.out((B.NROW, HEADS), t), ops.out((A.nnz, HEADS), t)
+            if v2:
+                dXT, da_part = ops.out((B.NROW, n), t), ops.out((B.NROW, n), t)
+                return ops, lambda stream: A.gatv2_attention_bwd_row(*x, dXT=dXT, da_part=da_part, delta=delta, ds_out=ds, stream=stream, **kw)
+            d_el = ops.out((B.NROW, HEADS), t)
+            return ops, lambda stream: A.gat_attention_bwd_row(*x, d_el=d_el, delta=delta, ds_out=ds, stream=stream, **kw)
+        if v2:
+            x = D("XS", "XT", "a", "dO", "lse", "delta")
+            dXS = ops.out((B.NCOL, n), t)
+            return ops, lambda stream: At.gatv2_attention_bwd_col(*x, dXS=dXS, stream=stream, **kw)
+        x = D("er", "V", "el", "dO", "lse", "delta")
+        d_er, dV = ops.out((B.NCOL, HEADS), t), ops.out((B.NCOL, n), t)
+        return ops, lambda stream: At.gat_attention_bwd_col(*x, d_er=d_er, dV=dV, stream=stream, **kw)
+    return build
+
+
+def _gat_two_source(v2):
+    """the forward on the two-source handle: er1 / V1 (v2: XS1) are the rows the negative column codes name; p_out through out_pos"""
+    def build(c):
+        import torch
+        ops = H.Operands(c.gpu)
+        A = c.handle("A2")
+        n, t = HEADS * DV, torch.float64
+        pos = torch.from_numpy(np.random.default_rng(6).permutation(A.nnz).astype(np.int32)).to(c.gpu)
+        O, lse, p = ops.out((M, n), t), ops.out((M, HEADS), t), ops.out((A.nnz, HEADS), t)
+        kw = dict(slope=SLOPE, bias=True, heads=HEADS, out=O, lse=lse, p_out=p, out_pos=pos)
+        if v2:
+            XT, XS0, XS1, a = (ops.dense(_rnd(110 + i, sh)) for i, sh in enumerate(((M, n), (HALF, n), (K - HALF, n), (HEADS, DV))))
+            return ops, lambda stream: A.gatv2_attention(XT, XS0, a, XS1=XS1, stream=stream, **kw)
+        el, er0, er1, V0, V1 = (ops.dense(_rnd(120 + i, sh)) for i, sh in
+                                enumerate(((M, HEADS), (HALF, HEADS), (K - HALF, HEADS), (HALF, n), (K - HALF, n))))
+        return ops, lambda stream: A.gat_attention(el, er0, V0, er1=er1, V1=V1, stream=stream, **kw)
+    return build
+
+
+def _col_sum(dt):
+    """hip.col_sum on an operand shaped like da_part of the GATv2 row side (its scratch comes from torch's allocator)"""
+    def build(c):
+        from crp_spmm_amd import hip
+        import attention_bwd_ref as B
+        ops = H.Operands(c.gpu)
+        d0, d1 = _gat_data(c, dt, 100, True, 0.0), _gat_data(c, dt, 200, True, 0.0)
+        src, out = ops.dense(d0["da_part"], d1["da_part"]), ops.out((HEADS * DV,), _tdt(dt))
+        assert tuple(src.shape) == (B.NROW, HEADS * DV)
+        return ops, lambda stream: hip.col_sum(src, out=out, stream=stream)
+    return build
+
+
+def _dropout_mask(c):
+    """dropout_mask has no dense value input: its one operand is the output, whose sentinel fill (int8 -77, handed over as the
+    uint8 view the wrapper takes) lies on the held-back stream, behind a launch that went elsewhere"""
+    import torch
+    ops = H.Operands(c.gpu)
+    A = c.handle("B")
+    out = ops.out((A.nnz, HEADS), torch.int8)
+    return ops, lambda stream: A.dropout_mask(HEADS, 0.25, SEED, out=out.view(torch.uint8), stream=stream)
+
+
+def _gat_autograd(v2, dropout):
+    """hip.gat_attention / hip.gatv2_attention forward and .backward (v2: with col_sum): no stream argument anywhere, the control
+    makes the null stream current"""
+    def build(c):
+        import torch
+        from crp_spmm_amd import hip
+        import attention_bwd_ref as B
+        ops = H.Operands(c.gpu)
+        A, At = c.handle("B"), c.handle("Bt")
+        d0, d1 = _gat_data(c, F64, 100, v2, dropout), _gat_data(c, F64, 200, v2, dropout)
+        n = HEADS * DV
+        names = ("XT", "XS", "a") if v2 else ("el", "er", "V")
+        x = tuple(ops.dense(d0[k], d1[k]) for k in names)
+        dO = ops.dense(d0["dO"], d1["dO"])
+        outs = [ops.out(sh, torch.float64) for sh in ((B.NROW, n),) + tuple(tuple(t.shape) for t in x)]
+        fn = hip.gatv2_attention if v2 else hip.gat_attention
+
+        def run():
+            leaves = tuple(t.detach().requires_grad_(True) for t in x)
+            O = fn(A, At, *leaves, slope=SLOPE, bias=True, heads=HEADS, dropout=dropout, seed=SEED)
+            grads = torch.autograd.grad(O, leaves, dO)
+            for dst, src in zip(outs, (O.detach(),) + tuple(grads)):
+                dst.copy_(src)
+
+        def call(stream):
+            if stream is None:
+                return run()
+            with torch.cuda.stream(torch.cuda.default_stream()):
+                run()
+        return ops, call
     return build
 
 
@@ -285,11 +506,13 @@ def _move(what, dt):
 
 
 def _helper(what, dt):
-    """the device helpers without a Python wrapper: the raw library call on torch's current stream"""
+    """the device helpers without a Python wrapper: the raw library call on torch's current stream (the entry point is looked up
+    on the library object at every call, as the wrappers do)"""
     def build(c):
         import torch
         from crp_spmm_amd import _lib as L
         ops = H.Operands(c.gpu)
+        raw = lambda name, *args: L.check(getattr(c.lib, name)(*args), name)
         sfx = "f32" if np.dtype(dt) == np.float32 else "f64"
         if what == "scatter_add_rows":
             n, nseg, nsrc = 9, 40, 100
@@ -299,19 +522,17 @@ def _helper(what, dt):
             seg_ptr = torch.from_numpy(np.concatenate([[0], np.cumsum(cnt)]).astype(np.int32)).to(c.gpu)
             seg_pos = torch.from_numpy(rng.integers(0, nsrc, int(cnt.sum())).astype(np.int32)).to(c.gpu)
             src, dst = ops.dense(_rnd(15, (nsrc, n), dt)), ops.dense(_rnd(16, (64, n), dt), inout=True)
-            fn = getattr(c.lib, "crp_scatter_add_rows_" + sfx)
-            return ops, lambda stream: L.check(fn(nseg, n, seg_row.data_ptr(), seg_ptr.data_ptr(), seg_pos.data_ptr(), src.data_ptr(), n,
-                                                  dst.data_ptr(), n, _cur(stream)), fn.__name__)
+            return ops, lambda stream: raw("crp_scatter_add_rows_" + sfx, nseg, n, seg_row.data_ptr(), seg_ptr.data_ptr(), seg_pos.data_ptr(),
+                                           src.data_ptr(), n, dst.data_ptr(), n, _cur(stream))
         if what == "gather_vals":
             cnt = 700
             vmap = torch.from_numpy(np.random.default_rng(17).integers(0, 500, cnt).astype(np.int32)).to(c.gpu)
             src, dst = ops.dense(_rnd(18, (500,), dt)), ops.out((cnt,), torch.float64)
-            fn = c.lib.crp_gather_vals_f32_f64 if sfx == "f32" else c.lib.crp_gather_vals_f64
-            return ops, lambda stream: L.check(fn(cnt, vmap.data_ptr(), src.data_ptr(), dst.data_ptr(), _cur(stream)), fn.__name__)
+            name = "crp_gather_vals_f32_f64" if sfx == "f32" else "crp_gather_vals_f64"
+            return ops, lambda stream: raw(name, cnt, vmap.data_ptr(), src.data_ptr(), dst.data_ptr(), _cur(stream))
         nseg, ln = 3, 259
         src, out = ops.dense(_rnd(19, (nseg * ln,), dt)), ops.out((ln,), _tdt(dt))
-        fn = getattr(c.lib, "crp_sum_segments_" + sfx)
-        return ops, lambda stream: L.check(fn(nseg, ln, src.data_ptr(), ln, out.data_ptr(), _cur(stream)), fn.__name__)
+        return ops, lambda stream: raw("crp_sum_segments_" + sfx, nseg, ln, src.data_ptr(), ln, out.data_ptr(), _cur(stream))
     return build
 
 
@@ -378,6 +599,19 @@ TABLE += [("%s-%s" % (what, np.dtype(dt).name), None, _move(what, dt)) for what 
 TABLE += [("%s-%s" % (what, np.dtype(dt).name), None, _helper(what, dt))
           for what in ("scatter_add_rows", "gather_vals", "sum_segments") for dt in (F64, F32)]
 TABLE += [("sparse_attention-forward-backward", None, _sparse_attention)]
+_DT = [(F64, "float64"), (F32, "float32")]
+TABLE += [("attention-heads2-%s" % nm, None, _attention(dt, heads=HEADS)) for dt, nm in _DT]
+TABLE += [("attention_bwd_q-heads2-%s" % nm, None, _attention_bwd_q(dt, heads=HEADS)) for dt, nm in _DT]
+TABLE += [("attention_bwd_kv-heads2-%s" % nm, None, _attention_bwd_kv(dt, heads=HEADS)) for dt, nm in _DT]
+TABLE += [("attention_bwd_kv-heads2-in-place-%s" % nm, None, _attention_bwd_kv(dt, in_place=True, heads=HEADS)) for dt, nm in _DT]
+for _v2, _fam in ((False, "gat_attention"), (True, "gatv2_attention")):
+    TABLE += [("%s%s-%s%s" % (_fam, {"fwd": ""}.get(what, "_" + what), nm, "-dropout" if drop else ""), None, _gat(dt, what, drop, v2=_v2))
+              for what in ("fwd", "bwd_row", "bwd_col") for dt, nm in _DT for drop in (0.0, 0.25)]
+    TABLE += [("%s-two-source" % _fam, None, _gat_two_source(_v2))]
+TABLE += [("col_sum-%s" % nm, None, _col_sum(dt)) for dt, nm in _DT]
+TABLE += [("dropout_mask", None, _dropout_mask)]
+TABLE += [("hip.%s-forward-backward%s" % (_fam, "-dropout" if drop else ""), None, _gat_autograd(_v2, drop))
+          for _v2, _fam in ((False, "gat_attention"), (True, "gatv2_attention")) for drop in (0.0, 0.25)]
 TABLE += [("update_values-host-then-product", "host-values", _update_then_product(False, host=True)),
           ("csr_transpose-device", "csr-transpose", _csr_transpose),
           ("first-product-builds-team2", "first-build", _spmm(5, 64, "team2<f64", fresh=True)),
@@ -391,7 +625,8 @@ LAUNCHERS = {"rowgroup<", "cm", "panel<4", "panel<8", "narrow<", "team2r<4", "te
 def test_order_asynchrony_control(ctx, name, blocking, build):
     ops, call = build(ctx)
     held = ctx.held
-    want = held.reference(ops, call, name=None if blocking else name)
+    with _observed(ctx.lib, ctx.reached):
+        want = held.reference(ops, call, name=None if blocking else name)
     if not blocking:
         held.warm(ops, call)
     got, pending = held.run(ops, call)
@@ -468,6 +703,51 @@ def test_first_fp32_product_on_one_stream_then_a_product_on_another(ctx, variant
     torch.cuda.synchronize()
     assert H.same([C2], [want2]), "the product on the second stream read state the first call had not finished building"
     assert H.same([C1], [want1])
+
+
+def test_first_fp32_gat_attention_on_one_stream_then_a_product_on_another(ctx):
+    """The same case with the fp32 copy of the values built by the first fp32 gat_attention with bias, on a fresh handle on the
+    held-back S1; then an independent fp32 product of the same handle on the free S2, nothing ordering the two: both are correct."""
+    import torch
+    from crp_spmm_amd import hip
+    import attention_bwd_ref as B
+    n = HEADS * DV
+    held = ctx.held
+    rp, ci, nrow = B.matrix()
+    va = np.random.default_rng(3).uniform(-1, 1, ci.size)
+    ops = H.Operands(ctx.gpu)
+    el, er, V = (ops.dense(_rnd(34 + i, sh, np.float32)) for i, sh in enumerate(((nrow, HEADS), (B.NCOL, HEADS), (B.NCOL, n))))
+    O, lse = ops.out((nrow, n), torch.float32), ops.out((nrow, HEADS), torch.float32)
+    B2 = torch.from_numpy(_rnd(37, (B.NCOL, n), np.float32)).to(ctx.gpu)
+    C2 = torch.full((nrow, n), H.SENTINEL, dtype=torch.float32, device=ctx.gpu)
+    gat = lambda h: h.gat_attention(el, er, V, slope=SLOPE, bias=True, out=O, lse=lse, heads=HEADS)
+    W = hip.CsrDev(nrow, B.NCOL, rp, ci, va)                      # the reference: a handle of its own, on the default stream
+    ctx.keep.append(W)
+    ops.load(0)
+    gat(W)
+    hip.spmm_csr_f32(W, B2, C2, variant=1)
+    torch.cuda.synchronize()
+    assert W.last_kernel.startswith("rowgroup_f32<")
+    want1, want2 = ops.snapshot(), C2.clone()
+    A = hip.CsrDev(nrow, B.NCOL, rp, ci, va)
+    ctx.keep.append(A)
+    ops.poison()
+    ops.clear()
+    C2.fill_(H.SENTINEL)
+    torch.cuda.synchronize()
+    S2 = held.second()
+    with torch.cuda.stream(held.S):
+        held.hold()
+        ops.load(0)
+        ops.clear()
+        gat(A)
+    with torch.cuda.stream(S2):
+        hip.spmm_csr_f32(A, B2, C2, variant=1)
+    S2.synchronize()
+    held.S.synchronize()
+    torch.cuda.synchronize()
+    assert H.same([C2], [want2]), "the product on the second stream read values the first gat_attention had not finished converting"
+    assert H.same(ops.snapshot(), want1)
 
 
 def test_first_team2r_product_on_one_stream_then_a_product_on_another(ctx):
@@ -567,26 +847,49 @@ def _engine_rows():
             return lambda stream: e.row_softmax_bwd(s, dy, out=out, stream=stream)
         return b
 
-    def attention(dt):
+    def attention(dt, heads=1):
         def b(e, nnz, k, ops):
             Q, Kk, V = (ops.dense(_rnd(57 + i, sh, dt)) for i, sh in enumerate(((M, EN), (k, EN), (k, EN))))
-            O, lse, p = ops.out((M, EN), _tdt(dt)), ops.out((M,), _tdt(dt)), ops.out((nnz,), _tdt(dt))
-            return lambda stream: e.attention(0, Q, Kk, V, O, scale=0.2, bias=True, lse=lse, p_out=p, stream=stream)
+            O, lse, p = ops.out((M, EN), _tdt(dt)), ops.out(_per_head(M, heads), _tdt(dt)), ops.out(_per_head(nnz, heads), _tdt(dt))
+            return lambda stream: e.attention(0, Q, Kk, V, O, scale=0.2, bias=True, lse=lse, p_out=p, stream=stream, heads=heads)
         return b
 
-    def attention_bwd(dt):
+    def attention_bwd(dt, heads=1):
         def b(e, nnz, k, ops):
             t = [torch.from_numpy(_rnd(60 + i, sh, dt)).to(ops.gpu) for i, sh in enumerate(((M, EN), (k, EN), (k, EN), (M, EN)))]
             d = []
             for sgn in (1.0, -0.5):                               # two consistent data sets: O and lse from the engine's forward
                 Q, Kk, V, dO = (x * sgn for x in t)
-                O, lse = torch.empty((M, EN), dtype=Q.dtype, device=ops.gpu), torch.empty((M,), dtype=Q.dtype, device=ops.gpu)
-                e.attention(0, Q, Kk, V, O, scale=0.2, bias=True, lse=lse)
+                O, lse = torch.empty((M, EN), dtype=Q.dtype, device=ops.gpu), torch.empty(_per_head(M, heads), dtype=Q.dtype, device=ops.gpu)
+                e.attention(0, Q, Kk, V, O, scale=0.2, bias=True, lse=lse, heads=heads)
                 torch.cuda.synchronize()
                 d.append((Q, Kk, V, O, dO, lse))
             Q, Kk, V, O, dO, lse = (ops.dense(a, b_) for a, b_ in zip(*d))
-            dQ, dK, dV, ds = (ops.out(sh, _tdt(dt)) for sh in ((M, EN), (k, EN), (k, EN), (nnz,)))
-            return lambda stream: e.attention_bwd(Q, Kk, V, O, dO, lse, dQ, dK, dV, scale=0.2, bias=True, ds_out=ds, stream=stream)
+            dQ, dK, dV, ds = (ops.out(sh, _tdt(dt)) for sh in ((M, EN), (k, EN), (k, EN), _per_head(nnz, heads)))
+            return lambda stream: e.attention_bwd(Q, Kk, V, O, dO, lse, dQ, dK, dV, scale=0.2, bias=True, ds_out=ds, stream=stream,
+                                                  heads=heads)
+        return b
+
+    def gat(dt, v2, other_heads=False):
+        """the engine's GAT (v2: GATv2) forward with `HEADS` heads; other_heads: two GAT calls, 3 heads into outputs of their own and
+        then HEADS heads, so that every call of the row sets the narrow exchange up again"""
+        def b(e, nnz, k, ops):
+            t = _tdt(dt)
+            O, lse, p = ops.out((M, EN), t), ops.out((M, HEADS), t), ops.out((nnz, HEADS), t)
+            kw = dict(slope=SLOPE, bias=True, lse=lse, p_out=p, heads=HEADS)
+            if v2:
+                XT, XS, a = (ops.dense(_rnd(63 + i, sh, dt)) for i, sh in enumerate(((M, EN), (k, EN), (HEADS, EN // HEADS))))
+                return lambda stream: e.gatv2_attention(0, XT, a, XS, O, stream=stream, **kw)
+            el, er, V = (ops.dense(_rnd(66 + i, sh, dt)) for i, sh in enumerate(((M, HEADS), (k, HEADS), (k, EN))))
+            if not other_heads:
+                return lambda stream: e.gat_attention(0, el, er, V, O, stream=stream, **kw)
+            el3, er3 = ops.dense(_rnd(69, (M, 3), dt)), ops.dense(_rnd(70, (k, 3), dt))
+            O3, lse3 = ops.out((M, EN), t), ops.out((M, 3), t)
+
+            def call(stream):
+                e.gat_attention(0, el3, er3, V, O3, slope=SLOPE, bias=True, lse=lse3, heads=3, stream=stream)
+                e.gat_attention(0, el, er, V, O, stream=stream, **kw)
+            return call
         return b
 
     def update_dev(dt):
@@ -610,7 +913,12 @@ def _engine_rows():
         rows += [("%s-update_values_dev-%s-then-exec" % (eng, np.dtype(dt).name), eng, None, update_dev(dt)) for dt in (F64, F32)]
     rows += [("rp-attention-%s" % np.dtype(dt).name, "rp", None, attention(dt)) for dt in (F64, F32)]
     rows += [("rp-attention_bwd-%s" % np.dtype(dt).name, "rp", None, attention_bwd(dt)) for dt in (F64, F32)]
-    rows += [("rp-exec-timing-on", "rp", "timing-on", exec_(F64))]
+    rows += [("rp-attention-mh-%s" % np.dtype(dt).name, "rp", None, attention(dt, HEADS)) for dt in (F64, F32)]
+    rows += [("rp-attention_bwd-mh-%s" % np.dtype(dt).name, "rp", None, attention_bwd(dt, HEADS)) for dt in (F64, F32)]
+    rows += [("rp-gat_attention-%s" % np.dtype(dt).name, "rp", None, gat(dt, False)) for dt in (F64, F32)]
+    rows += [("rp-gatv2_attention-%s" % np.dtype(dt).name, "rp", None, gat(dt, True)) for dt in (F64, F32)]
+    rows += [("rp-exec-timing-on", "rp", "timing-on", exec_(F64)),
+             ("rp-gat-other-heads", "rp", "other-heads", gat(F64, False, other_heads=True))]
     return rows
 
 
@@ -627,7 +935,8 @@ def test_engine_order_asynchrony_control(ctx, engines, name, which, blocking, bu
     timed = e if which == "rp" else e.rp
     timed.set_timing(blocking == "timing-on")
     try:
-        want = held.reference(ops, call, name=None if blocking else name)
+        with _observed(ctx.lib, ctx.reached):
+            want = held.reference(ops, call, name=None if blocking else name)
         held.warm(ops, call)
         got, pending = held.run(ops, call)
         assert H.same(got, want), "Order"
@@ -638,6 +947,28 @@ def test_engine_order_asynchrony_control(ctx, engines, name, which, blocking, bu
         assert not H.same(bad, want), "Control"
     finally:
         timed.set_timing(False)
+
+
+def test_every_stream_taking_entry_point_is_reached(ctx, engines):
+    """after the rows above (same module, same Ctx): every entry point of both headers that takes a stream and is not in EXEMPT
+    was really called by the reference call of some row (_observed), the blocking rows included.  The 2D engine's rows go through
+    crp_para2d_*, which have rows of their own; the row engine's entry points are reached by the row engine's rows."""
+    if not ctx.reached:                                           # run by itself: the reference call of every row, once
+        with _observed(ctx.lib, ctx.reached):
+            for name, blocking, build in TABLE:
+                ops, call = build(ctx)
+                ctx.held.reference(ops, call)
+            for name, which, blocking, build in ENGINE_ROWS:
+                ops = H.Operands(ctx.gpu)
+                e = engines.rp if which == "rp" else engines.p2
+                nnz, k = (ctx.ci.size, K) if which == "rp" else (engines.sq[1].size, M)
+                ctx.held.reference(ops, build(e, nnz, k, ops))
+    for header in ("crpspmm_hip.h", "crp_engine.h"):
+        need = stream_entry_points(header) - set(EXEMPT)
+        print("%s: %d stream-taking entry points, %d exempt, %d of %d reached by a row"
+              % (header, len(need | (set(EXEMPT) & stream_entry_points(header))), len(set(EXEMPT) & stream_entry_points(header)),
+                 len(need & ctx.reached), len(need)))
+        assert need <= ctx.reached, (header, sorted(need - ctx.reached))
 
 
 def _exec(e, B, k=K):

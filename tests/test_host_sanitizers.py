@@ -50,7 +50,7 @@ def test_engine_resources_under_asan_ubsan(tmp_path):
     if gxx is None:
         pytest.skip("no g++")
     src = os.path.join(ROOT, "crp-spmm_amd", "csrc")
-    files = [os.path.join(src, f) for f in ("rp_engine.cpp", "rp_attention.cpp", "para2d_engine.cpp", "knobs.cpp", "host_support.cpp")]
+    files = [os.path.join(src, f) for f in ("rp_engine.cpp", "rp_attention.cpp", "rp_gat.cpp", "para2d_engine.cpp", "knobs.cpp", "host_support.cpp")]
     exe = str(tmp_path / "host_engine_resources")
     cmd = [gxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
            "-fno-omit-frame-pointer", "-pthread", "-I" + os.path.join(ROOT, "include"), "-I" + src,
@@ -67,14 +67,15 @@ def test_engine_resources_under_asan_ubsan(tmp_path):
 
 def test_engine_stream_order_under_asan_ubsan(tmp_path):
     """The split row engine (a fake communicator of 2 ranks) orders every conflicting pair of device accesses across the caller's
-    stream, its own stream and the exchange stream -- exec, exec_t, sddmm, attention, attention_bwd, update_values and
-    update_values_dev, on two caller streams -- and the same checker reports a race once one stream_wait_event is taken out of
-    the log (tests/host_engine_streams.cpp)."""
+    stream, its own stream and the exchange stream -- exec, exec_t, sddmm, attention, attention_bwd, the GAT and GATv2 forward (csrc/rp_gat.cpp: two
+    packs and two exchanges beside the interior kernel, and the narrow buffers set up again for another number of heads),
+    update_values and update_values_dev, on two caller streams -- and the same checker reports a race once one stream_wait_event
+    is taken out of the log, for a GAT call on the narrow receive buffer among others (tests/host_engine_streams.cpp)."""
     gxx = shutil.which("g++")
     if gxx is None:
         pytest.skip("no g++")
     src = os.path.join(ROOT, "crp-spmm_amd", "csrc")
-    files = [os.path.join(src, f) for f in ("rp_engine.cpp", "rp_attention.cpp", "knobs.cpp", "host_support.cpp")]
+    files = [os.path.join(src, f) for f in ("rp_engine.cpp", "rp_attention.cpp", "rp_gat.cpp", "knobs.cpp", "host_support.cpp")]
     exe = str(tmp_path / "host_engine_streams")
     cmd = [gxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
            "-fno-omit-frame-pointer", "-pthread", "-I" + os.path.join(ROOT, "include"), "-I" + src,
@@ -86,3 +87,4 @@ def test_engine_stream_order_under_asan_ubsan(tmp_path):
     assert r.returncode == 0 and "HOST_ENGINE_STREAMS_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
     stats = dict(kv.split("=") for kv in r.stdout.split()[1:])
     assert int(stats["streams"]) >= 4 and int(stats["exchanges"]) > 0 and int(stats["needed"]) > 0 and int(stats["control_races"]) > 0, r.stdout
+    assert int(stats["gat_exchanges"]) > 0 and int(stats["gat_cross_stream_waits"]) > 0 and int(stats["gat_control_races"]) > 0, r.stdout
