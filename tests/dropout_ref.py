@@ -442,6 +442,36 @@ def gatv2_steep_case(dtype):
     return rp, ci, val, XT, XS, a, dO, gatv2_reference(rp, ci, XT, XS, a, G2.SLOPE, DROP, SEED, val, dO)
 
 
+@functools.lru_cache(maxsize=None)
+def gat_chunk_case(dtype, H, dv, spread, backward=True):
+    """gat_ref.chunk_case's operands under (DROP, SEED): (rp, ci, el, er, V, dO, ref)"""
+    rp, ci, el, er, V, dO, _ = G.chunk_case(dtype, H, dv, spread, backward)
+    return rp, ci, el, er, V, dO, gat_reference(rp, ci, el, er, V, G.SLOPE, DROP, SEED, None, dO)
+
+
+@functools.lru_cache(maxsize=None)
+def gatv2_chunk_case(dtype, H, dv, spread):
+    """gatv2_ref.chunk_case's operands under (DROP, SEED): (rp, ci, XT, XS, a, dO, ref)"""
+    rp, ci, XT, XS, a, dO, _ = G2.chunk_case(dtype, H, dv, spread)
+    return rp, ci, XT, XS, a, dO, gatv2_reference(rp, ci, XT, XS, a, G2.SLOPE, DROP, SEED, None, dO)
+
+
+def chunk_fixture_facts(drop=DROP, seed=SEED):
+    """(ok, the hub's length) on gat_ref.chunk_matrix(): ok when, at every chunk size 8, 16, 32 and 64, every full chunk after the
+    first of every row, and of the hub column (its entries in ascending row), holds keep bits that differ from the first chunk's in
+    some head -- so that keep bits taken from the wrong chunk are wrong bits"""
+    rp, ci = G.chunk_matrix()
+    k = mask_csr(rp, ci, HEADS, drop, seed)
+    tmap = B.transpose(rp, ci, G.CHUNK_NCOL)[2]
+    hub = k[tmap][ci[tmap] == G.CHUNK_HUB]
+    ok = True
+    for kr in [k[rp[i]:rp[i + 1]] for i in range(rp.size - 1)] + [hub]:
+        for lpr in (8, 16, 32, 64):
+            for j in range(lpr, kr.shape[0] - lpr + 1, lpr):
+                ok = ok and bool((kr[j:j + lpr] != kr[:lpr]).any())
+    return ok, int(hub.shape[0])
+
+
 def gat_bound_cases():
     """gat_ref.bound_cases: H = 1, 3; dv = 1, 5, 8 W, 8 W + 1, 33 W, 65 W; scores at two scales"""
     return G.bound_cases()

@@ -191,8 +191,74 @@ def matrix(seed=3):
     return rp, ci
 
 
-def two_source_codes(ci):
-    return np.where(ci < K0, ci, ~(ci - K0)).astype(np.int32)
+def two_source_codes(ci, k0=K0):
+    """the codes of a two-source handle: the columns below k0 as they are, column c >= k0 as ~(c - k0)"""
+    return np.where(ci < k0, ci, ~(ci - k0)).astype(np.int32)
+
+
+# The chunk pattern: every length at which a kernel that walks a row (or a column of A) in chunks of LPR = 8, 16, 32 or 64 entries
+# takes another trip, on both sides
+CHUNK_LENGTHS = (0, 1, 7, 8, 9, 15, 16, 17, 31, 32, 33, 63, 64, 65, 128, 129, 200)      # of the first rows; the last row is empty too
+CHUNK_NROW, CHUNK_NCOL, CHUNK_K0 = 280, 256, 128
+CHUNK_HUB, CHUNK_EMPTY_COL = 5, 17
+CHUNK_COLS = {1: 18, 8: 19, 9: 20, 63: 130, 64: 131, 65: 132}        # length -> the column of exactly that many entries
+CHUNK_SHUFFLED = 65                      # rows from this length on hold their columns in a shuffled order
+
+
+@functools.lru_cache(maxsize=None)
+def chunk_matrix(seed=23):
+    """(rp, ci): CHUNK_NROW rows over CHUNK_NCOL columns.  The first rows have CHUNK_LENGTHS, the last one is empty, the others
+    2 .. 6 entries; every row of two or more entries names CHUNK_HUB (more than four chunks of 64 on the column side); no row names
+    CHUNK_EMPTY_COL and the columns of CHUNK_COLS have exactly 1, 8, 9, 63, 64 and 65 entries, from consecutive short rows; the
+    rows of CHUNK_SHUFFLED entries and more are not in ascending column order; both sides of CHUNK_K0 are named by the long rows"""
+    rng = np.random.default_rng(seed)
+    lens = rng.integers(2, 7, CHUNK_NROW)
+    lens[:len(CHUNK_LENGTHS)] = CHUNK_LENGTHS
+    lens[-1] = 0
+    extra = np.full(CHUNK_NROW, -1)
+    r = 20
+    for n in sorted(CHUNK_COLS):
+        extra[r:r + n] = CHUNK_COLS[n]
+        r += n
+    assert r < CHUNK_NROW - 1
+    pool = np.setdiff1d(np.arange(CHUNK_NCOL), [CHUNK_HUB, CHUNK_EMPTY_COL] + list(CHUNK_COLS.values()))
+    cols = []
+    for r, n in enumerate(lens):
+        n = int(n)
+        if n < 2:
+            cols.append(rng.choice(pool, size=n, replace=False))
+            continue
+        own = [CHUNK_HUB] + ([extra[r]] if extra[r] >= 0 else [])
+        c = np.sort(np.concatenate([own, rng.choice(pool, size=n - len(own), replace=False)]))
+        cols.append(rng.permutation(c) if n >= CHUNK_SHUFFLED else c)
+    rp = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+    ci = np.concatenate(cols).astype(np.int32)
+    rp.setflags(write=False)
+    ci.setflags(write=False)
+    return rp, ci
+
+
+def check_chunk_matrix():
+    """the properties the chunk tests rely on"""
+    rp, ci = chunk_matrix()
+    lens, cnt = np.diff(rp), np.bincount(ci, minlength=CHUNK_NCOL)
+    nspec = len(CHUNK_LENGTHS)
+    assert rp.size - 1 == CHUNK_NROW and cnt.size == CHUNK_NCOL and 1500 <= ci.size <= 3000, (rp.size, cnt.size, ci.size)
+    assert tuple(lens[:nspec]) == CHUNK_LENGTHS and lens[-1] == 0 and (lens == 0).sum() == 2
+    assert lens[nspec:-1].min() >= 2 and lens[nspec:-1].max() <= 6
+    assert {0, 1, 7, 8, 9, 15, 16, 17, 31, 32, 33, 63, 64, 65, 128, 129, 200} <= set(lens.tolist())
+    for i in range(CHUNK_NROW):
+        c = ci[rp[i]:rp[i + 1]]
+        assert np.unique(c).size == c.size, "a row names a column once"
+        assert (lens[i] >= 2) == bool((c == CHUNK_HUB).any()), "every row of two or more entries names the hub, no other"
+        if lens[i] >= CHUNK_SHUFFLED:
+            assert (np.diff(c) < 0).any(), (i, "in ascending order")
+            assert (c < CHUNK_K0).any() and (c >= CHUNK_K0).any(), (i, "names one source only")
+    assert cnt[CHUNK_HUB] == (lens >= 2).sum() > 4 * 64 + 8 and cnt[CHUNK_EMPTY_COL] == 0
+    for n, c in CHUNK_COLS.items():
+        assert cnt[c] == n, (c, cnt[c], n)
+    codes = two_source_codes(ci, CHUNK_K0)
+    assert (codes < 0).any() and (codes >= 0).any() and (~codes[codes < 0]).max() < CHUNK_NCOL - CHUNK_K0
 
 
 def operands(dtype, H, dv, spread, seed, nrow=NROW, ncol=NCOL):
@@ -219,6 +285,42 @@ def second_block_width(dtype):
     return 8 * 64 * w + w
 
 
+# The kernel instance (LPR lanes per unit, P pieces per lane) comes from (dtype, nv) alone, with W = 16 / sizeof(T).  gat_fwd in
+# csrc/gat_kernels.hip:
+#     if (a.nv <= 8 * W)   return launch_gat<T, 8, 1>(a, s);
+#     if (a.nv <= 16 * W)  return launch_gat<T, 16, 1>(a, s);
+#     if (a.nv <= 32 * W)  return launch_gat<T, 32, 1>(a, s);
+#     if (a.nv <= 64 * W)  return launch_gat<T, 64, 1>(a, s);
+#     if (a.nv <= 128 * W) return launch_gat<T, 64, 2>(a, s);
+#     if (a.nv <= 256 * W) return launch_gat<T, 64, 4>(a, s);
+#     return launch_gat<T, 64, 8>(a, s);
+# gat_bwd there and gatv2_any in csrc/gatv2_kernels.hip (launch_gatv2) refuse nv > CAP = 256 W, have the same first five lines and end in
+#     return launch_gat<T, 64, 4>(a, s);
+KINDS = ("gat_fwd", "gat_bwd", "gatv2")
+INSTANCES = ((8, (8, 1)), (16, (16, 1)), (32, (32, 1)), (64, (64, 1)), (128, (64, 2)), (256, (64, 4)))    # (the last width in W, (LPR, P))
+FWD_BLOCK = 512                          # in W: the forward's V block of 8 pieces of 64 lanes
+
+
+def instance_of(kind, dtype, dv):
+    """(LPR, P) of the kernel that serves one head's width dv; kind: one of KINDS"""
+    assert kind in KINDS and dv >= 1
+    w = W[np.dtype(dtype).name]
+    for top, inst in INSTANCES:
+        if dv <= top * w:
+            return inst
+    assert kind == "gat_fwd", (kind, dv, "is over the cap")
+    return 64, 8
+
+
+def chunk_widths(dtype, kind="gat_bwd"):
+    """one head's widths on the chunk pattern: both sides of the thresholds 16 W, 32 W, 64 W and 128 W (8 W is in widths()), the cap
+    256 W (P = 4, full), and one width that is no multiple of W strictly inside the 32-lane and the 64-lane range -- with the + 1
+    widths these are the element path; for the forward of GAT also the first width of P = 8 and its one V block, full"""
+    w = W[np.dtype(dtype).name]
+    out = (16 * w, 16 * w + 1, 17 * w + 1, 32 * w, 32 * w + 1, 40 * w + 1, 64 * w, 64 * w + 1, 128 * w, 128 * w + 1, 256 * w)
+    return out + ((256 * w + 1, FWD_BLOCK * w) if kind == "gat_fwd" else ())
+
+
 SPREADS = (0.5, 6.0)
 SLOPE = 0.2
 
@@ -241,6 +343,31 @@ def case(dtype, H, dv, spread):
     assert ref["T"] <= SR.T_MAX[dt], ref["T"]
     for x in (el, er, V, dO):
         x.setflags(write=False)
+    return rp, ci, el, er, V, dO, ref
+
+
+def chunk_bound_cases():
+    """(dtype, H, dv, spread, backward) on chunk_matrix(): what the chunk tests hold against the bound on the GPU and replay on the
+    CPU.  H = 3 and H = 1 on the widths up to 64 W + 1, H = 1 above (the reference's cost grows with H dv); the widths past the cap
+    are the forward's alone"""
+    for dtype in ("float64", "float32"):
+        w = W[dtype]
+        for i, dv in enumerate(chunk_widths(dtype, "gat_fwd")):
+            for H in ((1, 3) if dv <= 64 * w + 1 else (1,)):
+                yield dtype, H, dv, SPREADS[(i + H) % 2], dv <= 256 * w
+
+
+@functools.lru_cache(maxsize=None)
+def chunk_case(dtype, H, dv, spread, backward=True):
+    """(rp, ci, el, er, V, dO, ref) of one bound case on chunk_matrix(), computed once and read-only (forward only: dO is None)"""
+    dt = np.dtype(dtype)
+    rp, ci = chunk_matrix()
+    el, er, V, dO = operands(dt, H, dv, spread, 3000 * H + dv + (dt == np.float32), nrow=CHUNK_NROW, ncol=CHUNK_NCOL)
+    dO = dO if backward else None
+    ref = reference(rp, ci, el, er, V, SLOPE, None, dO)
+    for x in (el, er, V, dO):
+        if x is not None:
+            x.setflags(write=False)
     return rp, ci, el, er, V, dO, ref
 
 

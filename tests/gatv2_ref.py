@@ -300,6 +300,33 @@ def case(dtype, H, dv, spread, short=False):
     return rp, ci, XT, XS, a, dO, ref
 
 
+def chunk_widths(dtype):
+    """gat_ref.chunk_widths up to the cap: either side of 16 W, 32 W, 64 W and 128 W, 17 W + 1, 40 W + 1 and the cap"""
+    return G.chunk_widths(dtype, "gatv2")
+
+
+def chunk_bound_cases():
+    """(dtype, H, dv, spread) on gat_ref.chunk_matrix(): H = 3 and H = 1 on the widths up to 64 W + 1, H = 1 above (the reference's
+    cost grows with H dv)"""
+    for dtype in ("float64", "float32"):
+        w = W[dtype]
+        for i, dv in enumerate(chunk_widths(dtype)):
+            for H in ((1, 3) if dv <= 64 * w + 1 else (1,)):
+                yield dtype, H, dv, SPREADS[(i + H) % 2]
+
+
+@functools.lru_cache(maxsize=None)
+def chunk_case(dtype, H, dv, spread):
+    """(rp, ci, XT, XS, a, dO, ref) of one bound case on gat_ref.chunk_matrix(), computed once and read-only"""
+    dt = np.dtype(dtype)
+    rp, ci = G.chunk_matrix()
+    XT, XS, a, dO = operands(dt, H, dv, spread, 4000 * H + dv + (dt == np.float32), nrow=G.CHUNK_NROW, ncol=G.CHUNK_NCOL)
+    ref = reference(rp, ci, XT, XS, a, SLOPE, None, dO)
+    for x in (XT, XS, a, dO):
+        x.setflags(write=False)
+    return rp, ci, XT, XS, a, dO, ref
+
+
 @functools.lru_cache(maxsize=None)
 def steep_case(dtype, H=3, dv=20):
     """attention_ref.steep_case's rows -- ascending, descending, late-peak and half-masked, T up to 60 -- with its bias as the

@@ -109,6 +109,35 @@ def test_gatv2_replay_is_inside_the_bound(dtype, H, dv, spread, short):
     assert max(r.values()) <= 1, r
 
 
+def test_chunk_fixture():
+    """under (DROP, SEED) on the chunk pattern every full chunk after the first of a row, and of the hub column, holds other keep bits
+    than the first, at every chunk size: a kernel that takes them from the wrong chunk takes wrong ones"""
+    ok, hub = D.chunk_fixture_facts()
+    assert ok and hub > 4 * 64 + 8, (ok, hub)
+
+
+@pytest.mark.parametrize("dtype,H,dv,spread,backward", list(G.chunk_bound_cases()))
+def test_gat_replay_is_inside_the_bound_on_the_chunk_pattern(dtype, H, dv, spread, backward):
+    rp, ci, el, er, V, dO, ref = D.gat_chunk_case(dtype, H, dv, spread, backward)
+    assert 0 < ref["T"] <= SR.T_MAX[np.dtype(dtype)], (dtype, H, dv, spread, ref["T"])
+    out = D.gat_replay(rp, ci, el, er, V, G.SLOPE, D.DROP, D.SEED, None, dO)
+    r = D.ratios(_got(out, G.FWD_KEYS + (G.BWD_KEYS if backward else ())), ref)
+    print("GAT replay under dropout on the chunk pattern, worst |err| / bound (%s, H = %d, dv = %d, spread %g): %s"
+          % (dtype, H, dv, spread, {k: "%.3g" % v for k, v in r.items()}))
+    assert max(r.values()) <= 1, r
+
+
+@pytest.mark.parametrize("dtype,H,dv,spread", list(G2.chunk_bound_cases()))
+def test_gatv2_replay_is_inside_the_bound_on_the_chunk_pattern(dtype, H, dv, spread):
+    rp, ci, XT, XS, a, dO, ref = D.gatv2_chunk_case(dtype, H, dv, spread)
+    assert 0 < ref["T"] <= SR.T_MAX[np.dtype(dtype)], (dtype, H, dv, spread, ref["T"])
+    out = D.gatv2_replay(rp, ci, XT, XS, a, G2.SLOPE, D.DROP, D.SEED, None, dO)
+    r = D.ratios(_got(out, GATV2_KEYS), ref)
+    print("GATv2 replay under dropout on the chunk pattern, worst |err| / bound (%s, H = %d, dv = %d, spread %g): %s"
+          % (dtype, H, dv, spread, {k: "%.3g" % v for k, v in r.items()}))
+    assert max(r.values()) <= 1, r
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_replay_of_the_steep_rows_and_of_the_second_block(dtype):
     rp, ci, val, el, er, V, dO, ref = D.gat_steep_case(dtype)

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import gat_ref as G
+import softmax_ref as SR
 
 DTYPES = ["float64", "float32"]
 
@@ -20,6 +21,51 @@ def test_the_matrix_has_the_rows_the_tests_rely_on():
     assert np.bincount(ci, minlength=G.NCOL)[G.EMPTY_COL] == 0
     codes = G.two_source_codes(ci)
     assert (codes < 0).any() and (codes >= 0).any() and (~codes[codes < 0]).max() < G.NCOL - G.K0
+
+
+def test_the_chunk_matrix_has_the_lengths_the_tests_rely_on():
+    G.check_chunk_matrix()
+
+
+def _census(dtype, kind, have):
+    """the widths `have` reach every (LPR, P) of kind's dispatch table, both sides of every threshold, the last width of the table,
+    the 16-byte and the element path of every instance, and an element-path width strictly inside the 32- and the 64-lane range"""
+    w = G.W[dtype]
+    fwd = kind == "gat_fwd"
+    tops = [t * w for t, _ in G.INSTANCES]
+    want = [inst for _, inst in G.INSTANCES] + ([(64, 8)] if fwd else [])
+    by = {inst: [dv for dv in have if G.instance_of(kind, dtype, dv) == inst] for inst in want}
+    assert sum(len(v) for v in by.values()) == len(have), (dtype, kind, "a width outside the table")
+    for inst, dvs in by.items():
+        assert any(dv % w == 0 for dv in dvs) and any(dv % w for dv in dvs), (dtype, kind, inst, dvs, "needs a 16-byte and an element width")
+    for t in tops[:-1] + (tops[-1:] if fwd else []):
+        assert t in have and t + 1 in have, (dtype, kind, t, "both sides of the threshold")
+        assert G.instance_of(kind, dtype, t) != G.instance_of(kind, dtype, t + 1)
+    assert tops[-1] in have, (dtype, kind, "P = 4, every piece full")
+    if fwd:
+        assert G.FWD_BLOCK * w in have and G.second_block_width(dtype) in have, (dtype, "P = 8 in one V block, full, and in two")
+    for lo, hi in ((16 * w, 32 * w), (32 * w, 64 * w)):
+        assert any(lo + 1 < dv < hi and dv % w for dv in have), (dtype, kind, lo, hi, "an element-path width inside the range")
+
+
+def test_the_instances_are_the_ones_meant():
+    """gat_ref.instance_of restates the three dispatch tables; widths() and chunk_widths() together reach every instance of every
+    table on both sides of every threshold -- and no width of chunk_widths() can be left out"""
+    assert G.instance_of("gat_fwd", "float64", 512) == (64, 4) and G.instance_of("gat_fwd", "float64", 513) == (64, 8)
+    assert G.instance_of("gat_fwd", "float32", 1025) == (64, 8) and G.instance_of("gat_bwd", "float64", 17) == (16, 1)
+    assert [G.instance_of("gatv2", "float32", dv) for dv in (32, 33, 64, 65, 128, 129, 256, 257, 512, 513, 1024)] == \
+        [(8, 1), (16, 1), (16, 1), (32, 1), (32, 1), (64, 1), (64, 1), (64, 2), (64, 2), (64, 4), (64, 4)]
+    with pytest.raises(AssertionError):
+        G.instance_of("gat_bwd", "float64", 513)
+    for dtype in DTYPES:
+        for kind in G.KINDS:
+            base = set(G.widths(dtype)) | ({G.second_block_width(dtype)} if kind == "gat_fwd" else set())
+            chunk = G.chunk_widths(dtype, kind)
+            assert len(set(chunk)) == len(chunk) and not base & set(chunk)
+            _census(dtype, kind, base | set(chunk))
+            for dv in chunk:
+                with pytest.raises(AssertionError):
+                    _census(dtype, kind, base | (set(chunk) - {dv}))
 
 
 def test_scores_are_rounded_step_by_step():
@@ -41,6 +87,18 @@ def test_replay_is_inside_the_bound(dtype, H, dv, spread):
     out = G.replay(rp, ci, el, er, V, G.SLOPE, None, dO)
     r = G.ratios(_got(out, G.FWD_KEYS + G.BWD_KEYS), ref)
     print("replay, worst |err| / bound (%s, H = %d, dv = %d, spread %g): %s" % (dtype, H, dv, spread, {k: "%.3g" % v for k, v in r.items()}))
+    assert max(r.values()) <= 1, r
+
+
+@pytest.mark.parametrize("dtype,H,dv,spread,backward", list(G.chunk_bound_cases()))
+def test_replay_is_inside_the_bound_on_the_chunk_pattern(dtype, H, dv, spread, backward):
+    """rows of up to 200 entries and a hub column of 277: 5j's data rule on the reference alone, then the replay against the bound"""
+    rp, ci, el, er, V, dO, ref = G.chunk_case(dtype, H, dv, spread, backward)
+    assert 0 < ref["T"] <= SR.T_MAX[np.dtype(dtype)], (dtype, H, dv, spread, ref["T"])
+    out = G.replay(rp, ci, el, er, V, G.SLOPE, None, dO)
+    r = G.ratios(_got(out, G.FWD_KEYS + (G.BWD_KEYS if backward else ())), ref)
+    print("replay on the chunk pattern, worst |err| / bound (%s, H = %d, dv = %d, spread %g): %s"
+          % (dtype, H, dv, spread, {k: "%.3g" % v for k, v in r.items()}))
     assert max(r.values()) <= 1, r
 
 

@@ -84,6 +84,18 @@ def test_replay_is_inside_the_bound(dtype, H, dv, spread, short):
     assert max(r.values()) <= 1, r
 
 
+@pytest.mark.parametrize("dtype,H,dv,spread", list(G2.chunk_bound_cases()))
+def test_replay_is_inside_the_bound_on_the_chunk_pattern(dtype, H, dv, spread):
+    """rows of up to 200 entries and a hub column of 277: 5j's data rule on the reference alone, then the replay against the bound"""
+    rp, ci, XT, XS, a, dO, ref = G2.chunk_case(dtype, H, dv, spread)
+    assert 0 < ref["T"] <= SR.T_MAX[np.dtype(dtype)], (dtype, H, dv, spread, ref["T"])
+    out = G2.replay(rp, ci, XT, XS, a, G2.SLOPE, None, dO)
+    r = G2.ratios(_got(out, KEYS), ref)
+    print("replay on the chunk pattern, worst |err| / bound (%s, H = %d, dv = %d, spread %g): %s"
+          % (dtype, H, dv, spread, {k: "%.3g" % v for k, v in r.items()}))
+    assert max(r.values()) <= 1, r
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_replay_of_the_steep_rows_with_bias(dtype):
     rp, ci, val, XT, XS, a, dO, ref = G2.steep_case(dtype)
