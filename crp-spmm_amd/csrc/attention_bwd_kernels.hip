@@ -42,142 +42,23 @@
 // instances (MH = false) compile none of this.
 //
 // LOADS IN FLIGHT.  Per batch, the gathers of a step (per lane two 16-byte pieces, or one piece by elements, of each of the 8 K
-// rows and of the 8 V rows; kv: Q and dO rows) are all issued before the step's FMAs.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <initializer_list>
-#include <type_traits>
-#include "kernels.h"
+// rows and of the 8 V rows; kv: Q and dO rows) are all issued before the step's FMAs.  The second read of a batch's rows, for the
+// accumulators, goes through rg_again's opaque zero (row_group.h, which says what would fold it and how the build notices).
+//
+// The pieces, the row loads and stores, rg_load8 and the batch's butterfly (rg_reduce8) are row_group.h's (rg_), one definition
+// for this file, gat_kernels.hip and gatv2_kernels.hip; ab_ marks what is this file's own: the two-operand dots and the entry.
+#include "row_group.h"
 
 namespace crp {
 
-constexpr int AB_UNR = 8;
-
-template <typename T> struct AbPiece;
-template <> struct AbPiece<double> { typedef double type __attribute__((ext_vector_type(2))); static constexpr int VW = 2; };
-template <> struct AbPiece<float>  { typedef float type __attribute__((ext_vector_type(4))); static constexpr int VW = 4; };
-
-__device__ __forceinline__ double ab_exp(double x) { return exp(x); }
-__device__ __forceinline__ float  ab_exp(float x) { return expf(x); }
-template <typename T> __device__ __forceinline__ T ab_ninf() { return -__builtin_huge_val(); }
-template <> __device__ __forceinline__ float ab_ninf<float>() { return -__builtin_huge_valf(); }
-
-// pieces per lane and row of one load step: two by 16-byte accesses, one by elements (which cost a register per element AND
-// an address each), so that no instance spills
-template <int P, bool VEC> constexpr int ab_ch = VEC ? (P < 2 ? P : 2) : 1;
-
-// f(integral_constant K) for K = K0, K0 + STEP, ... < END
-template <int K0, int END, int STEP, class F>
-__device__ __forceinline__ void ab_static_for(F &&f)
-{
-    if constexpr (K0 < END)
-    {
-        f(std::integral_constant<int, K0>{});
-        ab_static_for<K0 + STEP, END, STEP>(f);
-    }
-}
-
-// The zero of ab_load8's `again`.  It stays opaque only as long as nothing lets the compiler prove nk >= 0: an assumption or a
-// check on nk ahead of the loops (__builtin_assume, an early return on nk < 1) folds it to 0, the two reads of a batch's rows merge
-// again and the wide instances spill without a warning.  csrc/Makefile compiles this file with the resource-usage remarks and
-// fails the build when any instance reports scratch or LDS.
-template <int VW> __device__ __forceinline__ int ab_again(const int nk) { return VW * (int) (nk < 0); }
-
-template <int LPR>
-__device__ __forceinline__ int ab_bcast_i(int v, int j)
-{
-    if constexpr (LPR == 64) return __builtin_amdgcn_readlane(v, j);
-    else return __shfl(v, j, LPR);
-}
-
-// this lane's NP pieces of a row of n columns: piece q starts at column (q * LPR + lir) * VW; slots past n hold 0
-template <typename T, int LPR, int NP, bool VEC>
-__device__ __forceinline__ void ab_load_row(T (&x)[NP][AbPiece<T>::VW], const T *row, const int n, const int lir)
-{
-    typedef typename AbPiece<T>::type PT;
-    constexpr int VW = AbPiece<T>::VW;
-#pragma unroll
-    for (int v = 0; v < NP; v++)
-    {
-        const int c = (v * LPR + lir) * VW;
-        if constexpr (VEC)
-        {
-            PT t = {};
-            if (c < n) t = *reinterpret_cast<const PT *>(row + c);
-#pragma unroll
-            for (int w = 0; w < VW; w++) x[v][w] = t[w];
-        }
-        else
-        {
-#pragma unroll
-            for (int w = 0; w < VW; w++) x[v][w] = (c + w < n) ? row[c + w] : (T) 0;
-        }
-    }
-}
-
-// ... and the store of them (slots past n are not written)
-template <typename T, int LPR, int NP, bool VEC>
-__device__ __forceinline__ void ab_store_row(const T (&x)[NP][AbPiece<T>::VW], T *row, const int n, const int lir)
-{
-    typedef typename AbPiece<T>::type PT;
-    constexpr int VW = AbPiece<T>::VW;
-#pragma unroll
-    for (int v = 0; v < NP; v++)
-    {
-        const int c = (v * LPR + lir) * VW;
-        if constexpr (VEC)
-        {
-            PT t;
-#pragma unroll
-            for (int w = 0; w < VW; w++) t[w] = x[v][w];
-            if (c < n) *reinterpret_cast<PT *>(row + c) = t;
-        }
-        else
-        {
-#pragma unroll
-            for (int w = 0; w < VW; w++)
-                if (c + w < n) row[c + w] = x[v][w];
-        }
-    }
-}
-
-// this lane's pieces piece0 .. piece0 + CH - 1 of the 8 rows y[u] (slots past n: column 0, a valid address, not used).  again:
-// 0 at run time in a form the compiler cannot see through, added to the row's address -- the second read of a batch's rows (for the
-// accumulators, after the dots) stays a load of its own, a cache hit, instead of 8 rows held in registers across the batch
-template <typename T, int LPR, int CH, bool VEC>
-__device__ __forceinline__ void ab_load8(T (&yv)[AB_UNR][CH][AbPiece<T>::VW], const T *const (&y)[AB_UNR], const int piece0, const int n,
-                                         const int lir, const int again = 0)
-{
-    typedef typename AbPiece<T>::type PT;
-    constexpr int VW = AbPiece<T>::VW;
-#pragma unroll
-    for (int u = 0; u < AB_UNR; u++)
-#pragma unroll
-        for (int v = 0; v < CH; v++)
-        {
-            const int c = ((piece0 + v) * LPR + lir) * VW;
-            if constexpr (VEC)
-            {
-                const PT t = *reinterpret_cast<const PT *>(y[u] + again + (unsigned) ((c < n) ? c : 0));
-#pragma unroll
-                for (int w = 0; w < VW; w++) yv[u][v][w] = t[w];
-            }
-            else
-            {
-#pragma unroll
-                for (int w = 0; w < VW; w++) yv[u][v][w] = (y[u] + again)[(unsigned) ((c + w < n) ? c + w : 0)];
-            }
-        }
-}
-
 // part[u] += < this lane's pieces piece0 .. of x, of row u >: FMAs in column order (the SDDMM's chunk)
 template <typename T, int LPR, int CH, int NP>
-__device__ __forceinline__ void ab_fma_dot(T (&part)[AB_UNR], const T (&x)[NP][AbPiece<T>::VW], const T (&yv)[AB_UNR][CH][AbPiece<T>::VW],
+__device__ __forceinline__ void ab_fma_dot(T (&part)[RG_UNR], const T (&x)[NP][Piece<T>::VW], const T (&yv)[RG_UNR][CH][Piece<T>::VW],
                                            const int piece0, const int n, const int lir)
 {
-    constexpr int VW = AbPiece<T>::VW;
+    constexpr int VW = Piece<T>::VW;
 #pragma unroll
-    for (int u = 0; u < AB_UNR; u++)
+    for (int u = 0; u < RG_UNR; u++)
 #pragma unroll
         for (int v = 0; v < CH; v++)
 #pragma unroll
@@ -190,12 +71,12 @@ __device__ __forceinline__ void ab_fma_dot(T (&part)[AB_UNR], const T (&x)[NP][A
 
 // acc[piece] = fma(coef[u], row u's piece, acc[piece]) for u = 0 .. 7 (slots past the width gather garbage that is never stored)
 template <typename T, int CH, int NP>
-__device__ __forceinline__ void ab_fma_acc(T (&acc)[NP][AbPiece<T>::VW], const T (&coef)[AB_UNR], const T (&yv)[AB_UNR][CH][AbPiece<T>::VW],
+__device__ __forceinline__ void ab_fma_acc(T (&acc)[NP][Piece<T>::VW], const T (&coef)[RG_UNR], const T (&yv)[RG_UNR][CH][Piece<T>::VW],
                                            const int piece0)
 {
-    constexpr int VW = AbPiece<T>::VW;
+    constexpr int VW = Piece<T>::VW;
 #pragma unroll
-    for (int u = 0; u < AB_UNR; u++)
+    for (int u = 0; u < RG_UNR; u++)
 #pragma unroll
         for (int v = 0; v < CH; v++)
 #pragma unroll
@@ -205,48 +86,24 @@ __device__ __forceinline__ void ab_fma_acc(T (&acc)[NP][AbPiece<T>::VW], const T
 // partA[u] = the lane's part of < xa, rows ya[u] > (width na, PA pieces), partB likewise: per step the gathers of both operands
 // (two pieces per lane and row at most) go out before the step's FMAs
 template <typename T, int LPR, int PA, int PB, bool VEC>
-__device__ __forceinline__ void ab_dots2(T (&partA)[AB_UNR], const T (&xa)[PA][AbPiece<T>::VW], const T *const (&ya)[AB_UNR], const int na,
-                                         T (&partB)[AB_UNR], const T (&xb)[PB][AbPiece<T>::VW], const T *const (&yb)[AB_UNR], const int nb,
+__device__ __forceinline__ void ab_dots2(T (&partA)[RG_UNR], const T (&xa)[PA][Piece<T>::VW], const T *const (&ya)[RG_UNR], const int na,
+                                         T (&partB)[RG_UNR], const T (&xb)[PB][Piece<T>::VW], const T *const (&yb)[RG_UNR], const int nb,
                                          const int lir)
 {
-    constexpr int VW = AbPiece<T>::VW;
-    constexpr int CA = ab_ch<PA, VEC>, CB = ab_ch<PB, VEC>, PM = PA > PB ? PA : PB;
+    constexpr int VW = Piece<T>::VW;
+    constexpr int CA = rg_ch<PA, VEC>, CB = rg_ch<PB, VEC>, PM = PA > PB ? PA : PB;
 #pragma unroll
-    for (int u = 0; u < AB_UNR; u++) partA[u] = partB[u] = (T) 0;
-    ab_static_for<0, PM, (VEC ? 2 : 1)>([&](auto kc) {
+    for (int u = 0; u < RG_UNR; u++) partA[u] = partB[u] = (T) 0;
+    rg_static_for<0, PM, (VEC ? 2 : 1)>([&](auto kc) {
         constexpr int K = decltype(kc)::value;
-        T va[AB_UNR][CA][VW], vb[AB_UNR][CB][VW];
-        if constexpr (K < PA) ab_load8<T, LPR, CA, VEC>(va, ya, K, na, lir);
-        if constexpr (K < PB) ab_load8<T, LPR, CB, VEC>(vb, yb, K, nb, lir);
+        T va[RG_UNR][CA][VW], vb[RG_UNR][CB][VW];
+        if constexpr (K < PA) rg_load8<T, LPR, CA, VEC>(va, ya, K, na, lir);
+        if constexpr (K < PB) rg_load8<T, LPR, CB, VEC>(vb, yb, K, nb, lir);
         __builtin_amdgcn_sched_barrier(0);              // every load of the step is in flight before the first FMA waits for one
         if constexpr (K < PA) ab_fma_dot<T, LPR, CA, PA>(partA, xa, va, K, na, lir);
         if constexpr (K < PB) ab_fma_dot<T, LPR, CB, PB>(partB, xb, vb, K, nb, lir);
         if constexpr (!VEC) __builtin_amdgcn_sched_barrier(0);      // (by elements: the next step's loads wait, for the registers)
     });
-}
-
-// reduce-scatter butterfly of the SDDMM: after it lane l holds entry (l & 7) of the batch summed over the group
-template <typename T, int LPR>
-__device__ __forceinline__ T ab_reduce8(const T (&part)[AB_UNR], const int lir)
-{
-    const bool b0 = (lir & 1) != 0, b1 = (lir & 2) != 0, b2 = (lir & 4) != 0;
-    T q4[4], q2[2];
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-    {
-        const T keep = b0 ? part[2 * i + 1] : part[2 * i], send = b0 ? part[2 * i] : part[2 * i + 1];
-        q4[i] = keep + __shfl_xor(send, 1, LPR);
-    }
-#pragma unroll
-    for (int i = 0; i < 2; i++)
-    {
-        const T keep = b1 ? q4[2 * i + 1] : q4[2 * i], send = b1 ? q4[2 * i] : q4[2 * i + 1];
-        q2[i] = keep + __shfl_xor(send, 2, LPR);
-    }
-    T r = (b2 ? q2[1] : q2[0]) + __shfl_xor(b2 ? q2[0] : q2[1], 4, LPR);
-#pragma unroll
-    for (int mask = 8; mask < LPR; mask <<= 1) r = r + __shfl_xor(r, mask, LPR);
-    return r;
 }
 
 // p and dS of one entry from its two dots (see FIXED ORDER); dead: lse == -inf
@@ -256,7 +113,7 @@ __device__ __forceinline__ void ab_entry(const T dot, const T dp, const T scale,
 {
     T s = dot * scale;
     if (val != nullptr) s = s + val[p];
-    const T e = dead ? (T) 0 : ab_exp(s - lse);
+    const T e = dead ? (T) 0 : rg_exp(s - lse);
     *pp = e;
     *ds = (e == (T) 0) ? (T) 0 : e * (dp - delta);
 }
@@ -267,10 +124,10 @@ __device__ __forceinline__ void ab_entry(const T dot, const T dp, const T scale,
 template <typename T, int LPR, int PK, int PV, bool VEC, bool MH = false>
 __global__ __launch_bounds__(256) void attention_bwd_q_kernel(const AttnBwdQArgs<T> a)
 {
-    constexpr int VW  = AbPiece<T>::VW;
+    constexpr int VW  = Piece<T>::VW;
     constexpr int RPB = 256 / LPR;
-    constexpr int UNR = AB_UNR;
-    constexpr int CK  = ab_ch<PK, VEC>;
+    constexpr int UNR = RG_UNR;
+    constexpr int CK  = rg_ch<PK, VEC>;
     const int lir = threadIdx.x % LPR;                  // lane in row group
     int row = blockIdx.x * RPB + threadIdx.x / LPR;
     int64_t nh = 1, h = 0;                              // heads, and this group's
@@ -294,15 +151,15 @@ __global__ __launch_bounds__(256) void attention_bwd_q_kernel(const AttnBwdQArgs
         if constexpr (MH) return pos * nh + h;
         else return pos;
     };
-    const T ninf = ab_ninf<T>();
+    const T ninf = rg_ninf<T>();
 
     // D = < dO[i], O[i] >, the SDDMM's dot for (dtype, nv); every lane of the group ends with the same bits
     T xd[PV][VW];
-    ab_load_row<T, LPR, PV, VEC>(xd, a.dO + orow * a.lddO + hv, nv, lir);
+    rg_load_row<T, LPR, PV, VEC>(xd, a.dO + orow * a.lddO + hv, nv, lir);
     T delta = (T) 0;
     {
         T xo[PV][VW];
-        ab_load_row<T, LPR, PV, VEC>(xo, a.O + orow * a.ldO + hv, nv, lir);
+        rg_load_row<T, LPR, PV, VEC>(xo, a.O + orow * a.ldO + hv, nv, lir);
 #pragma unroll
         for (int v = 0; v < PV; v++)
 #pragma unroll
@@ -322,15 +179,15 @@ __global__ __launch_bounds__(256) void attention_bwd_q_kernel(const AttnBwdQArgs
     const T lse = a.lse[srow];
     if (pb >= pe || lse == ninf)                        // an empty or all-masked row: +0 everywhere; no Q row is read
     {
-        ab_store_row<T, LPR, PK, VEC>(acc, dqrow, nk, lir);
+        rg_store_row<T, LPR, PK, VEC>(acc, dqrow, nk, lir);
         if (a.ds_out != nullptr)
             for (int p = pb + lir; p < pe; p += LPR) a.ds_out[ppos(a.out_pos ? a.out_pos[p] : p)] = (T) 0;
         return;
     }
     T xq[PK][VW];
-    ab_load_row<T, LPR, PK, VEC>(xq, a.Q + orow * a.ldQ + hk, nk, lir);
+    rg_load_row<T, LPR, PK, VEC>(xq, a.Q + orow * a.ldQ + hk, nk, lir);
     const T scale = a.scale;
-    const int again = ab_again<VW>(a.nk);
+    const int again = rg_again<VW>(a.nk);
 
     for (int p0 = pb; p0 < pe; p0 += LPR)
     {
@@ -344,13 +201,13 @@ __global__ __launch_bounds__(256) void attention_bwd_q_kernel(const AttnBwdQArgs
 #pragma unroll
             for (int u = 0; u < UNR; u++)
             {
-                const int cj = ab_bcast_i<LPR>(c, min(j + u, cnt - 1));
+                const int cj = rg_bcast_i<LPR>(c, min(j + u, cnt - 1));
                 krow[u] = ((cj >= 0) ? (a.K0 + (int64_t) cj * a.ldK0) : (a.K1 + (int64_t) (~cj) * a.ldK1)) + hk;
                 vrow[u] = ((cj >= 0) ? (a.V0 + (int64_t) cj * a.ldV0) : (a.V1 + (int64_t) (~cj) * a.ldV1)) + hv;
             }
             T ps[UNR], pp[UNR];
             ab_dots2<T, LPR, PK, PV, VEC>(ps, xq, krow, nk, pp, xd, vrow, nv, lir);
-            const T rs = ab_reduce8<T, LPR>(ps, lir), rp = ab_reduce8<T, LPR>(pp, lir);
+            const T rs = rg_reduce8<T, LPR>(ps, lir), rp = rg_reduce8<T, LPR>(pp, lir);
             // every lane holds both dots of entry (lir & 7) of the batch
             const int mine = j + (lir & 7);
             T prob = (T) 0, ds = (T) 0;
@@ -367,7 +224,7 @@ __global__ __launch_bounds__(256) void attention_bwd_q_kernel(const AttnBwdQArgs
             for (int k = 0; k < PK; k += CK)
             {
                 T kv[UNR][CK][VW];
-                ab_load8<T, LPR, CK, VEC>(kv, krow, k, nk, lir, again);      // (cache hits: the dots read these rows)
+                rg_load8<T, LPR, CK, VEC>(kv, krow, k, nk, lir, again);      // (cache hits: the dots read these rows)
                 __builtin_amdgcn_sched_barrier(0);
                 ab_fma_acc<T, CK, PK>(acc, coef, kv, k);
             }
@@ -377,17 +234,17 @@ __global__ __launch_bounds__(256) void attention_bwd_q_kernel(const AttnBwdQArgs
     for (int v = 0; v < PK; v++)
 #pragma unroll
         for (int w = 0; w < VW; w++) acc[v][w] = acc[v][w] * scale;
-    ab_store_row<T, LPR, PK, VEC>(acc, dqrow, nk, lir);
+    rg_store_row<T, LPR, PK, VEC>(acc, dqrow, nk, lir);
 }
 
 // MH: the unit is (column c, head h); lse and delta of row i of A are read at i * heads + h
 template <typename T, int LPR, int PK, int PV, bool VEC, bool MH = false>
 __global__ __launch_bounds__(256) void attention_bwd_kv_kernel(const AttnBwdKVArgs<T> a)
 {
-    constexpr int VW  = AbPiece<T>::VW;
+    constexpr int VW  = Piece<T>::VW;
     constexpr int RPB = 256 / LPR;
-    constexpr int UNR = AB_UNR;
-    constexpr int CK  = ab_ch<PK, VEC>, CV = ab_ch<PV, VEC>, PM = PK > PV ? PK : PV;
+    constexpr int UNR = RG_UNR;
+    constexpr int CK  = rg_ch<PK, VEC>, CV = rg_ch<PV, VEC>, PM = PK > PV ? PK : PV;
     const int lir = threadIdx.x % LPR;
     int row = blockIdx.x * RPB + threadIdx.x / LPR;
     int64_t nh = 1, h = 0;                              // heads, and this group's
@@ -405,7 +262,7 @@ __global__ __launch_bounds__(256) void attention_bwd_kv_kernel(const AttnBwdKVAr
     if constexpr (LPR == 64) pb = __builtin_amdgcn_readfirstlane(pb);
     const int nk = a.nk, nv = a.nv;
     const int64_t crow = a.rowmap ? a.rowmap[row] : row;
-    const T ninf = ab_ninf<T>();
+    const T ninf = rg_ninf<T>();
     const int64_t hk = h * nk, hv = h * nv;             // the head's first column (MH; else 0)
     T *const dkrow = a.dK + crow * a.lddK + hk;
     T *const dvrow = a.dV + crow * a.lddV + hv;
@@ -421,16 +278,16 @@ __global__ __launch_bounds__(256) void attention_bwd_kv_kernel(const AttnBwdKVAr
         for (int w = 0; w < VW; w++) accV[v][w] = (T) 0;
     if (pb >= pe)                                       // a column no row names: +0; its K and V rows are not read
     {
-        ab_store_row<T, LPR, PK, VEC>(accK, dkrow, nk, lir);
-        ab_store_row<T, LPR, PV, VEC>(accV, dvrow, nv, lir);
+        rg_store_row<T, LPR, PK, VEC>(accK, dkrow, nk, lir);
+        rg_store_row<T, LPR, PV, VEC>(accV, dvrow, nv, lir);
         return;
     }
     // K[c] and V[c] whole, before anything of this row is written (dK == K, dV == V)
     T xk[PK][VW], xv[PV][VW];
-    ab_load_row<T, LPR, PK, VEC>(xk, a.K + crow * a.ldK + hk, nk, lir);
-    ab_load_row<T, LPR, PV, VEC>(xv, a.V + crow * a.ldV + hv, nv, lir);
+    rg_load_row<T, LPR, PK, VEC>(xk, a.K + crow * a.ldK + hk, nk, lir);
+    rg_load_row<T, LPR, PV, VEC>(xv, a.V + crow * a.ldV + hv, nv, lir);
     const T scale = a.scale;
-    const int again = ab_again<VW>(a.nk);
+    const int again = rg_again<VW>(a.nk);
 
     for (int p0 = pb; p0 < pe; p0 += LPR)
     {
@@ -443,13 +300,13 @@ __global__ __launch_bounds__(256) void attention_bwd_kv_kernel(const AttnBwdKVAr
 #pragma unroll
             for (int u = 0; u < UNR; u++)
             {
-                const int ij = ab_bcast_i<LPR>(c, min(j + u, cnt - 1));
+                const int ij = rg_bcast_i<LPR>(c, min(j + u, cnt - 1));
                 qrow[u] = a.Q + (int64_t) ij * a.ldQ + hk;
                 drow[u] = a.dO + (int64_t) ij * a.lddO + hv;
             }
             T ps[UNR], pp[UNR];
             ab_dots2<T, LPR, PK, PV, VEC>(ps, xk, qrow, nk, pp, xv, drow, nv, lir);
-            const T rs = ab_reduce8<T, LPR>(ps, lir), rp = ab_reduce8<T, LPR>(pp, lir);
+            const T rs = rg_reduce8<T, LPR>(ps, lir), rp = rg_reduce8<T, LPR>(pp, lir);
             const int mine = j + (lir & 7);
             const int im = __shfl(c, min(mine, cnt - 1), LPR);          // the row of A of this lane's entry
             T prob = (T) 0, ds = (T) 0;
@@ -469,11 +326,11 @@ __global__ __launch_bounds__(256) void attention_bwd_kv_kernel(const AttnBwdKVAr
                 cs[u] = __shfl(ds, u, LPR);
                 cp[u] = __shfl(prob, u, LPR);
             }
-            ab_static_for<0, PM, (VEC ? 2 : 1)>([&](auto kc) {
+            rg_static_for<0, PM, (VEC ? 2 : 1)>([&](auto kc) {
                 constexpr int K = decltype(kc)::value;
                 T qv[UNR][CK][VW], dv[UNR][CV][VW];
-                if constexpr (K < PK) ab_load8<T, LPR, CK, VEC>(qv, qrow, K, nk, lir, again);      // (cache hits: the dots read these rows)
-                if constexpr (K < PV) ab_load8<T, LPR, CV, VEC>(dv, drow, K, nv, lir, again);
+                if constexpr (K < PK) rg_load8<T, LPR, CK, VEC>(qv, qrow, K, nk, lir, again);      // (cache hits: the dots read these rows)
+                if constexpr (K < PV) rg_load8<T, LPR, CV, VEC>(dv, drow, K, nv, lir, again);
                 __builtin_amdgcn_sched_barrier(0);
                 if constexpr (K < PK) ab_fma_acc<T, CK, PK>(accK, cs, qv, K);
                 if constexpr (K < PV) ab_fma_acc<T, CV, PV>(accV, cp, dv, K);
@@ -485,61 +342,33 @@ __global__ __launch_bounds__(256) void attention_bwd_kv_kernel(const AttnBwdKVAr
     for (int v = 0; v < PK; v++)
 #pragma unroll
         for (int w = 0; w < VW; w++) accK[v][w] = accK[v][w] * scale;
-    ab_store_row<T, LPR, PK, VEC>(accK, dkrow, nk, lir);
-    ab_store_row<T, LPR, PV, VEC>(accV, dvrow, nv, lir);
+    rg_store_row<T, LPR, PK, VEC>(accK, dkrow, nk, lir);
+    rg_store_row<T, LPR, PV, VEC>(accV, dvrow, nv, lir);
 }
 
-static inline bool ab_aligned(std::initializer_list<const void *> ptrs, std::initializer_list<int64_t> lds, int vw)
-{
-    uintptr_t bits = 0;
-    for (const void *p : ptrs) bits |= (uintptr_t) p;
-    bool ok = bits % 16 == 0;
-    for (int64_t ld : lds) ok = ok && ld % vw == 0;
-    return ok;
-}
-
+// (nk % VW == 0 and nv % VW == 0 keep every head's slice on a 16-byte boundary; the leading dimension of a source that is NULL is
+// not read: it counts as 0.  The single-head instances take a.heads as 1, whatever it holds)
 template <typename T, int LPR, int PK, int PV, bool MH>
 static hipError_t launch_bwd(const AttnBwdQArgs<T> &a, hipStream_t s)
 {
-    constexpr int VW = AbPiece<T>::VW, RPB = 256 / LPR;
-    // (the leading dimension of a source that is NULL is not read: it counts as 0)
-    const bool vec = ab_aligned({a.Q, a.K0, a.K1, a.V0, a.V1, a.O, a.dO, a.dQ},
+    const bool vec = rg_aligned({a.Q, a.K0, a.K1, a.V0, a.V1, a.O, a.dO, a.dQ},
                                 {a.nk, a.nv, a.ldQ, a.ldO, a.lddO, a.lddQ, a.K0 ? a.ldK0 : 0, a.K0 ? a.ldV0 : 0, a.K1 ? a.ldK1 : 0,
-                                 a.K1 ? a.ldV1 : 0}, VW);
-    if constexpr (MH)
-    {
-        // (nk % VW == 0 and nv % VW == 0 above keep every head's slice on a 16-byte boundary)
-        const int64_t blocks = ((int64_t) a.nrow * a.heads + RPB - 1) / RPB;
-        if (blocks > INT32_MAX) return hipErrorInvalidValue;            // before anything is written
-        const dim3 grid((unsigned) blocks), block(256);
-        if (vec) hipLaunchKernelGGL((attention_bwd_q_kernel<T, LPR, PK, PV, true, true>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((attention_bwd_q_kernel<T, LPR, PK, PV, false, true>), grid, block, 0, s, a);
-        return hipGetLastError();
-    }
-    const dim3 grid((a.nrow + RPB - 1) / RPB), block(256);
-    if (vec) hipLaunchKernelGGL((attention_bwd_q_kernel<T, LPR, PK, PV, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((attention_bwd_q_kernel<T, LPR, PK, PV, false>), grid, block, 0, s, a);
+                                 a.K1 ? a.ldV1 : 0}, Piece<T>::VW);
+    dim3 grid;
+    if (!rg_grid(a.nrow, MH ? a.heads : 1, 256 / LPR, &grid)) return hipErrorInvalidValue;
+    if (vec) hipLaunchKernelGGL((attention_bwd_q_kernel<T, LPR, PK, PV, true, MH>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((attention_bwd_q_kernel<T, LPR, PK, PV, false, MH>), grid, dim3(256), 0, s, a);
     return hipGetLastError();
 }
 
 template <typename T, int LPR, int PK, int PV, bool MH>
 static hipError_t launch_bwd(const AttnBwdKVArgs<T> &a, hipStream_t s)
 {
-    constexpr int VW = AbPiece<T>::VW, RPB = 256 / LPR;
-    const bool vec = ab_aligned({a.K, a.V, a.Q, a.dO, a.dK, a.dV}, {a.nk, a.nv, a.ldK, a.ldV, a.ldQ, a.lddO, a.lddK, a.lddV}, VW);
-    if constexpr (MH)
-    {
-        // (nk % VW == 0 and nv % VW == 0 above keep every head's slice on a 16-byte boundary)
-        const int64_t blocks = ((int64_t) a.nrow * a.heads + RPB - 1) / RPB;
-        if (blocks > INT32_MAX) return hipErrorInvalidValue;            // before anything is written
-        const dim3 grid((unsigned) blocks), block(256);
-        if (vec) hipLaunchKernelGGL((attention_bwd_kv_kernel<T, LPR, PK, PV, true, true>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((attention_bwd_kv_kernel<T, LPR, PK, PV, false, true>), grid, block, 0, s, a);
-        return hipGetLastError();
-    }
-    const dim3 grid((a.nrow + RPB - 1) / RPB), block(256);
-    if (vec) hipLaunchKernelGGL((attention_bwd_kv_kernel<T, LPR, PK, PV, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((attention_bwd_kv_kernel<T, LPR, PK, PV, false>), grid, block, 0, s, a);
+    const bool vec = rg_aligned({a.K, a.V, a.Q, a.dO, a.dK, a.dV}, {a.nk, a.nv, a.ldK, a.ldV, a.ldQ, a.lddO, a.lddK, a.lddV}, Piece<T>::VW);
+    dim3 grid;
+    if (!rg_grid(a.nrow, MH ? a.heads : 1, 256 / LPR, &grid)) return hipErrorInvalidValue;
+    if (vec) hipLaunchKernelGGL((attention_bwd_kv_kernel<T, LPR, PK, PV, true, MH>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((attention_bwd_kv_kernel<T, LPR, PK, PV, false, MH>), grid, dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

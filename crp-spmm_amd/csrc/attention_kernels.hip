@@ -48,29 +48,13 @@
 // p_out: the lanes 0 .. 7 of the group that hold a batch's scores store them raw (through out_pos); after the row the same lanes
 // -- entry p of a row that starts at pb belongs to lane (p - pb) % 8 -- read their own stores back and overwrite them with the
 // probabilities.  No lane ever reads what another lane wrote.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include "kernels.h"
+//
+// The piece type, exp / log / -inf, the broadcast of a column code and the launcher's alignment and grid checks are row_group.h's
+// (rg_).  The kernel's own lambdas, its inlined butterfly and the online-softmax step stay here: as functions of that header they
+// compile to other instructions (measured), and this file's instructions are not to change.
+#include "row_group.h"
 
 namespace crp {
-
-template <typename T> struct AtPiece;
-template <> struct AtPiece<double> { typedef double type __attribute__((ext_vector_type(2))); };
-template <> struct AtPiece<float>  { typedef float type __attribute__((ext_vector_type(4))); };
-
-__device__ __forceinline__ double at_exp(double x) { return exp(x); }
-__device__ __forceinline__ float  at_exp(float x) { return expf(x); }
-__device__ __forceinline__ double at_log(double x) { return log(x); }
-__device__ __forceinline__ float  at_log(float x) { return logf(x); }
-template <typename T> __device__ __forceinline__ T at_ninf() { return -__builtin_huge_val(); }
-template <> __device__ __forceinline__ float at_ninf<float>() { return -__builtin_huge_valf(); }
-
-template <int LPR>
-__device__ __forceinline__ int at_bcast_i(int v, int j)
-{
-    if constexpr (LPR == 64) return __builtin_amdgcn_readlane(v, j);
-    else return __shfl(v, j, LPR);
-}
 
 // LPR lanes per row; PK pieces of Q per lane in registers (0: any nk); PV pieces of the accumulator per lane and V block.
 // VEC: 16-byte accesses; else single elements.  Every column slot is checked against its width.
@@ -79,7 +63,7 @@ __device__ __forceinline__ int at_bcast_i(int v, int j)
 template <typename T, int LPR, int PK, int PV, bool VEC, bool MH = false>
 __global__ __launch_bounds__(256) void attention_rm_kernel(const AttnArgs<T> a)
 {
-    typedef typename AtPiece<T>::type PT;
+    typedef typename Piece<T>::type PT;
     constexpr int VW  = 16 / (int) sizeof(T);
     constexpr int RPB = 256 / LPR;
     constexpr int UNR = 8;
@@ -104,7 +88,7 @@ __global__ __launch_bounds__(256) void attention_rm_kernel(const AttnArgs<T> a)
     if constexpr (LPR == 64) pb = __builtin_amdgcn_readfirstlane(pb);
     const int nk = a.nk, nv = a.nv;
     const int64_t orow = a.rowmap ? a.rowmap[row] : row;        // rowmap: the Q and O row of every row of a row-subset matrix
-    const T ninf = at_ninf<T>();
+    const T ninf = rg_ninf<T>();
     const int64_t hk = h * nk, hv = h * nv;             // the head's first column (MH; else 0)
     const int64_t srow = MH ? orow * nh + h : orow;     // the unit's entry of lse
     T *const orp = a.O + orow * a.ldO + hv;
@@ -254,7 +238,7 @@ __global__ __launch_bounds__(256) void attention_rm_kernel(const AttnArgs<T> a)
 #pragma unroll
                 for (int u = 0; u < UNR; u++)
                 {
-                    const int cj = at_bcast_i<LPR>(c, min(j + u, cnt - 1));
+                    const int cj = rg_bcast_i<LPR>(c, min(j + u, cnt - 1));
                     krow[u] = ((cj >= 0) ? (a.K0 + (int64_t) cj * a.ldK0) : (a.K1 + (int64_t) (~cj) * a.ldK1)) + hk;
                     vrow[u] = ((cj >= 0) ? (a.V0 + (int64_t) cj * a.ldV0) : (a.V1 + (int64_t) (~cj) * a.ldV1)) + hv;
                 }
@@ -317,8 +301,8 @@ __global__ __launch_bounds__(256) void attention_rm_kernel(const AttnArgs<T> a)
                 T f = (T) 1, e = (T) 0;
                 if (mn != ninf)                         // (else every entry so far is masked: l and acc stay 0)
                 {
-                    f = at_exp(m - mn);
-                    e = at_exp(s - mn);
+                    f = rg_exp(m - mn);
+                    e = rg_exp(s - mn);
                 }
                 m = mn;
                 T eu[UNR];
@@ -357,39 +341,30 @@ __global__ __launch_bounds__(256) void attention_rm_kernel(const AttnArgs<T> a)
         store_o(acc, vb);
         if (first)
         {
-            if (a.lse != nullptr && lir == 0) a.lse[srow] = masked ? ninf : m + at_log(l);
+            if (a.lse != nullptr && lir == 0) a.lse[srow] = masked ? ninf : m + rg_log(l);
             if (a.p_out != nullptr && lir < UNR)
                 for (int p = pb + lir; p < pe; p += UNR)        // this lane's own stores
                 {
                     const auto pos = ppos(a.out_pos ? a.out_pos[p] : p);
                     const T sv = a.p_out[pos];
-                    a.p_out[pos] = masked ? (T) 0 : at_exp(sv - m) / l;
+                    a.p_out[pos] = masked ? (T) 0 : rg_exp(sv - m) / l;
                 }
         }
     }
 }
 
+// (nk % VW == 0 and nv % VW == 0 keep every head's slice on a 16-byte boundary; the leading dimension of a source that is NULL is
+// not read: it counts as 0.  The single-head instances take a.heads as 1, whatever it holds)
 template <typename T, int LPR, int PK, int PV, bool MH>
 static hipError_t launch_attention(const AttnArgs<T> &a, hipStream_t s)
 {
-    constexpr int VW = 16 / (int) sizeof(T), RPB = 256 / LPR;
-    const bool vec = (a.nk % VW == 0) && (a.nv % VW == 0) && (a.ldQ % VW == 0) && (a.ldO % VW == 0) &&
-                     (a.K0 == nullptr || (a.ldK0 % VW == 0 && a.ldV0 % VW == 0)) &&
-                     (a.K1 == nullptr || (a.ldK1 % VW == 0 && a.ldV1 % VW == 0)) &&
-                     (((uintptr_t) a.Q | (uintptr_t) a.O | (uintptr_t) a.K0 | (uintptr_t) a.K1 | (uintptr_t) a.V0 | (uintptr_t) a.V1) % 16 == 0);
-    if constexpr (MH)
-    {
-        // (nk % VW == 0 and nv % VW == 0 above keep every head's slice on a 16-byte boundary)
-        const int64_t blocks = ((int64_t) a.nrow * a.heads + RPB - 1) / RPB;
-        if (blocks > INT32_MAX) return hipErrorInvalidValue;            // before anything is written
-        const dim3 grid((unsigned) blocks), block(256);
-        if (vec) hipLaunchKernelGGL((attention_rm_kernel<T, LPR, PK, PV, true, true>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((attention_rm_kernel<T, LPR, PK, PV, false, true>), grid, block, 0, s, a);
-        return hipGetLastError();
-    }
-    const dim3 grid((a.nrow + RPB - 1) / RPB), block(256);
-    if (vec) hipLaunchKernelGGL((attention_rm_kernel<T, LPR, PK, PV, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((attention_rm_kernel<T, LPR, PK, PV, false>), grid, block, 0, s, a);
+    const bool vec = rg_aligned({a.Q, a.O, a.K0, a.K1, a.V0, a.V1},
+                                {a.nk, a.nv, a.ldQ, a.ldO, a.K0 ? a.ldK0 : 0, a.K0 ? a.ldV0 : 0, a.K1 ? a.ldK1 : 0, a.K1 ? a.ldV1 : 0},
+                                Piece<T>::VW);
+    dim3 grid;
+    if (!rg_grid(a.nrow, MH ? a.heads : 1, 256 / LPR, &grid)) return hipErrorInvalidValue;
+    if (vec) hipLaunchKernelGGL((attention_rm_kernel<T, LPR, PK, PV, true, MH>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((attention_rm_kernel<T, LPR, PK, PV, false, MH>), grid, dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

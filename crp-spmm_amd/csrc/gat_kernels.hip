@@ -5,6 +5,8 @@
 // -- the additive LeakyReLU score of a graph attention layer in place of the scaled dot product of attention_kernels.hip: two
 // scalars per node and head and no K.  From the scores on everything is attention_kernels.hip's: the batches of 8, the online
 // softmax, lse / p_out, the (row, head) units and the column-to-lane assignment.  No atomics, no LDS, no partial result in memory.
+// The pieces, the row loads and stores, the walk over a batch's 8 rows, the batch's butterfly, the keep bits and the launcher are
+// row_group.h's (rg_), one definition for this file, gatv2_kernels.hip and the attention's two; gt_ marks what is this score's own.
 //
 // OPERANDS.  heads = H >= 1 heads of nv columns each lie side by side in V / O / dO / dV: head h owns columns [h nv, (h + 1) nv).
 // el is (rows of O, H) with leading dimension ldel, read through the row map like Q; er0 / er1 are the two sources of the column
@@ -43,36 +45,12 @@
 // scores, batches, m, f, e_u and l are the plain call's -- the softmax runs over all edges -- and only the accumulator changes:
 // acc = fma(k_u ? e_u : +0, V[c_u][j], acc), O = fl(fl(acc / l) rs); lse and p_out keep the plain call's bits.  Backward: p, s, g
 // and D = < dO, O > (O is the dropped O) as above, dP' = k ? fl(dP rs) : +0, dS = p (dP' - D), and the value-side weight of dV is
-// w = k ? fl(p rs) : +0.  The two products with rs are roundings of their own (gt_mul).  The lane that loads the column code of
+// w = k ? fl(p rs) : +0.  The two products with rs are roundings of their own (rg_mul).  The lane that loads the column code of
 // its own entry of a chunk draws that entry's bit -- one draw per entry and (unit, V block) -- and one ballot hands the chunk's
 // bits to the group; a batch takes its 8 bits from that word.  DROP = false compiles to the code without any of this.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <initializer_list>
-#include <type_traits>
-#include "kernels.h"
+#include "row_group.h"
 
 namespace crp {
-
-constexpr int GT_UNR = 8;
-
-template <typename T> struct GtPiece;
-template <> struct GtPiece<double> { typedef double type __attribute__((ext_vector_type(2))); static constexpr int VW = 2; };
-template <> struct GtPiece<float>  { typedef float type __attribute__((ext_vector_type(4))); static constexpr int VW = 4; };
-
-__device__ __forceinline__ double gt_exp(double x) { return exp(x); }
-__device__ __forceinline__ float  gt_exp(float x) { return expf(x); }
-__device__ __forceinline__ double gt_log(double x) { return log(x); }
-__device__ __forceinline__ float  gt_log(float x) { return logf(x); }
-template <typename T> __device__ __forceinline__ T gt_ninf() { return -__builtin_huge_val(); }
-template <> __device__ __forceinline__ float gt_ninf<float>() { return -__builtin_huge_valf(); }
-
-template <int LPR>
-__device__ __forceinline__ int gt_bcast_i(int v, int j)
-{
-    if constexpr (LPR == 64) return __builtin_amdgcn_readlane(v, j);
-    else return __shfl(v, j, LPR);
-}
 
 // s = lrelu(el + er) (+ val): three statements, three roundings.  hipcc contracts across statements by default; here it may not.
 // *g = the derivative of the LeakyReLU at z.
@@ -96,27 +74,6 @@ __device__ __forceinline__ T gt_dz(const T ds, const T g)
     const T dz = ds * g;
     return dz;
 }
-// the products with rs of the DROP instances: roundings of their own, so that dP rs - D never becomes one FMA
-template <typename T>
-__device__ __forceinline__ T gt_mul(const T x, const T y)
-{
-#pragma clang fp contract(off)
-    const T r = x * y;
-    return r;
-}
-
-// The keep bits of a chunk of LPR entries: the lane that holds entry `lir` of the chunk (live: it has one) draws the bit of
-// (r, c, h); bit e of the result is entry e's, the same word in every lane of the group.  Every lane of a group is active here
-// together (the chunk loop's bounds are the group's); lanes of other groups that are not contribute 0 to bits this group drops.
-template <typename T, int LPR>
-__device__ __forceinline__ unsigned long long gt_keep_bits(const DropArgs<T> &d, const bool live, const uint32_t r, const uint32_t c,
-                                                           const uint32_t h, const int lir)
-{
-    const bool k = live && dropout_keep(d.seed_lo, d.seed_hi, r, c, h, d.thr);
-    const unsigned long long all = __ballot(k);
-    if constexpr (LPR == 64) return all;
-    else return all >> ((threadIdx.x & 63u) - (unsigned) lir);
-}
 
 // where the er scalar of column code c and head h lies
 template <typename T>
@@ -130,10 +87,10 @@ __device__ __forceinline__ const T *gt_er(const int c, const int64_t h, const T 
 template <typename T, int LPR, int PV, bool VEC, bool DROP>
 __global__ __launch_bounds__(256) void gat_fwd_kernel(const GatArgs<T> a)
 {
-    typedef typename GtPiece<T>::type PT;
-    constexpr int VW  = GtPiece<T>::VW;
+    typedef typename Piece<T>::type PT;
+    constexpr int VW  = Piece<T>::VW;
     constexpr int RPB = 256 / LPR;
-    constexpr int UNR = GT_UNR;
+    constexpr int UNR = RG_UNR;
     constexpr int VC  = PV < 4 ? PV : 4;                // pieces of V per load chunk (8 VC pieces in flight)
     constexpr int VBW = LPR * VW * PV;                  // columns of a V block
     const int lir = threadIdx.x % LPR;                  // lane in the unit's group
@@ -147,7 +104,7 @@ __global__ __launch_bounds__(256) void gat_fwd_kernel(const GatArgs<T> a)
     if constexpr (LPR == 64) pb = __builtin_amdgcn_readfirstlane(pb);
     const int nv = a.nv;
     const int64_t orow = a.rowmap ? a.rowmap[row] : row;        // rowmap: the el and O row of every row of a row-subset matrix
-    const T ninf = gt_ninf<T>();
+    const T ninf = rg_ninf<T>();
     const int64_t hv = h * nv;                          // the head's first column
     const int64_t srow = orow * nh + h;                 // the unit's entry of lse
     T *const orp = a.O + orow * a.ldO + hv;
@@ -227,7 +184,7 @@ __global__ __launch_bounds__(256) void gat_fwd_kernel(const GatArgs<T> a)
             const int c = (my < pe) ? a.colidx[my] : 0;
             const int cnt = min(LPR, pe - p0);
             unsigned long long km = 0;                  // (DROP: the chunk's keep bits)
-            if constexpr (DROP) km = gt_keep_bits<T, LPR>(a.drop, my < pe, (uint32_t) orow, (uint32_t) c, (uint32_t) h, lir);
+            if constexpr (DROP) km = rg_keep_bits<T, LPR>(a.drop, my < pe, (uint32_t) orow, (uint32_t) c, (uint32_t) h, lir);
             for (int j = 0; j < cnt; j += UNR)
             {
                 // the scalar of this lane's entry (lir & 7) of the batch goes out first: a tiny gather under the V loads.
@@ -241,7 +198,7 @@ __global__ __launch_bounds__(256) void gat_fwd_kernel(const GatArgs<T> a)
 #pragma unroll
                 for (int q = 0; q < UNR; q++)
                 {
-                    const int cj = gt_bcast_i<LPR>(c, min(j + q, cnt - 1));
+                    const int cj = rg_bcast_i<LPR>(c, min(j + q, cnt - 1));
                     vrow[q] = ((cj >= 0) ? (a.V0 + (int64_t) cj * a.ldV0) : (a.V1 + (int64_t) (~cj) * a.ldV1)) + hv;
                 }
                 // the first V pieces of the batch go out before the exponentials
@@ -267,8 +224,8 @@ __global__ __launch_bounds__(256) void gat_fwd_kernel(const GatArgs<T> a)
                 T f = (T) 1, e = (T) 0;
                 if (mn != ninf)                         // (else every entry so far is masked: l and acc stay 0)
                 {
-                    f = gt_exp(m - mn);
-                    e = gt_exp(s - mn);
+                    f = rg_exp(m - mn);
+                    e = rg_exp(s - mn);
                 }
                 m = mn;
                 T eu[UNR];
@@ -312,170 +269,34 @@ __global__ __launch_bounds__(256) void gat_fwd_kernel(const GatArgs<T> a)
             for (int w = 0; w < VW; w++)
             {
                 acc[v][w] = masked ? (T) 0 : acc[v][w] / l;
-                if constexpr (DROP) acc[v][w] = gt_mul<T>(acc[v][w], a.drop.rs);
+                if constexpr (DROP) acc[v][w] = rg_mul<T>(acc[v][w], a.drop.rs);
             }
         store_o(acc, vb);
         if (first)
         {
-            if (a.lse != nullptr && lir == 0) a.lse[srow] = masked ? ninf : m + gt_log(l);
+            if (a.lse != nullptr && lir == 0) a.lse[srow] = masked ? ninf : m + rg_log(l);
             if (a.p_out != nullptr && lir < UNR)
                 for (int p = pb + lir; p < pe; p += UNR)        // this lane's own stores
                 {
                     const int64_t pos = (int64_t) (a.out_pos ? a.out_pos[p] : p) * nh + h;
                     const T sv = a.p_out[pos];
-                    a.p_out[pos] = masked ? (T) 0 : gt_exp(sv - m) / l;
+                    a.p_out[pos] = masked ? (T) 0 : rg_exp(sv - m) / l;
                 }
         }
     }
 }
 
-// ---- backward: the pieces (attention_bwd_kernels.hip's, without the K side) ---------------------------------------------------
-// pieces per lane and row of one load step: two by 16-byte accesses, one by elements, so that no instance spills
-template <int P, bool VEC> constexpr int gt_ch = VEC ? (P < 2 ? P : 2) : 1;
-
-template <int K0, int END, int STEP, class F>
-__device__ __forceinline__ void gt_static_for(F &&f)
-{
-    if constexpr (K0 < END)
-    {
-        f(std::integral_constant<int, K0>{});
-        gt_static_for<K0 + STEP, END, STEP>(f);
-    }
-}
-
-// The zero of gt_load8's `again`: opaque as long as nothing lets the compiler prove nv >= 0, so that the second read of a batch's
-// rows stays a load of its own (a cache hit) instead of 8 rows held in registers across the batch.
-template <int VW> __device__ __forceinline__ int gt_again(const int nv) { return VW * (int) (nv < 0); }
-
-// this lane's NP pieces of a row of n columns: piece q starts at column (q * LPR + lir) * VW; slots past n hold 0
+// ---- backward: the pieces (row_group.h's, and the score's own) ----------------------------------------------------------------
+// part[q] = the lane's part of < x, row y[q] > (width n, NP pieces): rg_walk8's trip, FMAs in column order from +0
 template <typename T, int LPR, int NP, bool VEC>
-__device__ __forceinline__ void gt_load_row(T (&x)[NP][GtPiece<T>::VW], const T *row, const int n, const int lir)
-{
-    typedef typename GtPiece<T>::type PT;
-    constexpr int VW = GtPiece<T>::VW;
-#pragma unroll
-    for (int v = 0; v < NP; v++)
-    {
-        const int c = (v * LPR + lir) * VW;
-        if constexpr (VEC)
-        {
-            PT t = {};
-            if (c < n) t = *reinterpret_cast<const PT *>(row + c);
-#pragma unroll
-            for (int w = 0; w < VW; w++) x[v][w] = t[w];
-        }
-        else
-        {
-#pragma unroll
-            for (int w = 0; w < VW; w++) x[v][w] = (c + w < n) ? row[c + w] : (T) 0;
-        }
-    }
-}
-
-// ... and the store of them (slots past n are not written)
-template <typename T, int LPR, int NP, bool VEC>
-__device__ __forceinline__ void gt_store_row(const T (&x)[NP][GtPiece<T>::VW], T *row, const int n, const int lir)
-{
-    typedef typename GtPiece<T>::type PT;
-    constexpr int VW = GtPiece<T>::VW;
-#pragma unroll
-    for (int v = 0; v < NP; v++)
-    {
-        const int c = (v * LPR + lir) * VW;
-        if constexpr (VEC)
-        {
-            PT t;
-#pragma unroll
-            for (int w = 0; w < VW; w++) t[w] = x[v][w];
-            if (c < n) *reinterpret_cast<PT *>(row + c) = t;
-        }
-        else
-        {
-#pragma unroll
-            for (int w = 0; w < VW; w++)
-                if (c + w < n) row[c + w] = x[v][w];
-        }
-    }
-}
-
-// this lane's pieces piece0 .. piece0 + CH - 1 of the 8 rows y[q] (slots past n: column 0, a valid address, not used)
-template <typename T, int LPR, int CH, bool VEC>
-__device__ __forceinline__ void gt_load8(T (&yv)[GT_UNR][CH][GtPiece<T>::VW], const T *const (&y)[GT_UNR], const int piece0, const int n,
-                                         const int lir, const int again = 0)
-{
-    typedef typename GtPiece<T>::type PT;
-    constexpr int VW = GtPiece<T>::VW;
-#pragma unroll
-    for (int q = 0; q < GT_UNR; q++)
-#pragma unroll
-        for (int v = 0; v < CH; v++)
-        {
-            const int c = ((piece0 + v) * LPR + lir) * VW;
-            if constexpr (VEC)
-            {
-                const PT t = *reinterpret_cast<const PT *>(y[q] + again + (unsigned) ((c < n) ? c : 0));
-#pragma unroll
-                for (int w = 0; w < VW; w++) yv[q][v][w] = t[w];
-            }
-            else
-            {
-#pragma unroll
-                for (int w = 0; w < VW; w++) yv[q][v][w] = (y[q] + again)[(unsigned) ((c + w < n) ? c + w : 0)];
-            }
-        }
-}
-
-// part[q] = the lane's part of < x, row y[q] > (width n, NP pieces): per step the gathers go out before the step's FMAs, which
-// run in column order (the SDDMM's chunk)
-template <typename T, int LPR, int NP, bool VEC>
-__device__ __forceinline__ void gt_dots(T (&part)[GT_UNR], const T (&x)[NP][GtPiece<T>::VW], const T *const (&y)[GT_UNR], const int n,
+__device__ __forceinline__ void gt_dots(T (&part)[RG_UNR], const T (&x)[NP][Piece<T>::VW], const T *const (&y)[RG_UNR], const int n,
                                         const int lir)
 {
-    constexpr int VW = GtPiece<T>::VW;
-    constexpr int CH = gt_ch<NP, VEC>;
 #pragma unroll
-    for (int q = 0; q < GT_UNR; q++) part[q] = (T) 0;
-    gt_static_for<0, NP, (VEC ? 2 : 1)>([&](auto kc) {
-        constexpr int K = decltype(kc)::value;
-        T yv[GT_UNR][CH][VW];
-        gt_load8<T, LPR, CH, VEC>(yv, y, K, n, lir);
-        __builtin_amdgcn_sched_barrier(0);              // every load of the step is in flight before the first FMA waits for one
-#pragma unroll
-        for (int q = 0; q < GT_UNR; q++)
-#pragma unroll
-            for (int v = 0; v < CH; v++)
-#pragma unroll
-                for (int w = 0; w < VW; w++)
-                {
-                    const int c = ((K + v) * LPR + lir) * VW + w;
-                    if (c < n) part[q] = fma(x[K + v][w], yv[q][v][w], part[q]);
-                }
-        if constexpr (!VEC) __builtin_amdgcn_sched_barrier(0);      // (by elements: the next step's loads wait, for the registers)
+    for (int q = 0; q < RG_UNR; q++) part[q] = (T) 0;
+    rg_walk8<T, LPR, NP, VEC>(y, n, lir, 0, [&](const int q, const int v, const int w, const bool in, const T yv) {
+        if (in) part[q] = fma(x[v][w], yv, part[q]);
     });
-}
-
-// reduce-scatter butterfly of the SDDMM: after it lane l holds entry (l & 7) of the batch summed over the group
-template <typename T, int LPR>
-__device__ __forceinline__ T gt_reduce8(const T (&part)[GT_UNR], const int lir)
-{
-    const bool b0 = (lir & 1) != 0, b1 = (lir & 2) != 0, b2 = (lir & 4) != 0;
-    T q4[4], q2[2];
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-    {
-        const T keep = b0 ? part[2 * i + 1] : part[2 * i], send = b0 ? part[2 * i] : part[2 * i + 1];
-        q4[i] = keep + __shfl_xor(send, 1, LPR);
-    }
-#pragma unroll
-    for (int i = 0; i < 2; i++)
-    {
-        const T keep = b1 ? q4[2 * i + 1] : q4[2 * i], send = b1 ? q4[2 * i] : q4[2 * i + 1];
-        q2[i] = keep + __shfl_xor(send, 2, LPR);
-    }
-    T r = (b2 ? q2[1] : q2[0]) + __shfl_xor(b2 ? q2[0] : q2[1], 4, LPR);
-#pragma unroll
-    for (int mask = 8; mask < LPR; mask <<= 1) r = r + __shfl_xor(r, mask, LPR);
-    return r;
 }
 
 // p, dS and dZ of one entry from its score, the LeakyReLU's derivative and dP (see FIXED ORDER); dead: lse == -inf.  DROP: dP
@@ -484,11 +305,11 @@ template <typename T, bool DROP>
 __device__ __forceinline__ void gt_entry(const T s, const T g, T dp, const T lse, const T delta, const bool dead, const bool keep, const T rs,
                                          T *pp, T *ds, T *dz)
 {
-    const T e = dead ? (T) 0 : gt_exp(s - lse);
+    const T e = dead ? (T) 0 : rg_exp(s - lse);
     if constexpr (DROP)
     {
-        dp = keep ? gt_mul<T>(dp, rs) : (T) 0;
-        *pp = keep ? gt_mul<T>(e, rs) : (T) 0;
+        dp = keep ? rg_mul<T>(dp, rs) : (T) 0;
+        *pp = keep ? rg_mul<T>(e, rs) : (T) 0;
     }
     else *pp = e;
     *ds = (e == (T) 0) ? (T) 0 : e * (dp - delta);
@@ -499,9 +320,9 @@ __device__ __forceinline__ void gt_entry(const T s, const T g, T dp, const T lse
 template <typename T, int LPR, int PV, bool VEC, bool DROP>
 __global__ __launch_bounds__(256) void gat_bwd_row_kernel(const GatBwdRowArgs<T> a)
 {
-    constexpr int VW  = GtPiece<T>::VW;
+    constexpr int VW  = Piece<T>::VW;
     constexpr int RPB = 256 / LPR;
-    constexpr int UNR = GT_UNR;
+    constexpr int UNR = RG_UNR;
     const int lir = threadIdx.x % LPR;
     const int64_t u = (int64_t) blockIdx.x * RPB + threadIdx.x / LPR;
     const int64_t nh = a.heads;
@@ -515,15 +336,15 @@ __global__ __launch_bounds__(256) void gat_bwd_row_kernel(const GatBwdRowArgs<T>
     const int64_t orow = a.rowmap ? a.rowmap[row] : row;
     const int64_t hv = h * nv;
     const int64_t srow = orow * nh + h;                 // the unit's entry of lse and delta
-    const T ninf = gt_ninf<T>();
+    const T ninf = rg_ninf<T>();
 
     // D = < dO[i]_h, O[i]_h >, the SDDMM's dot for (dtype, nv); every lane of the group ends with the same bits
     T xd[PV][VW];
-    gt_load_row<T, LPR, PV, VEC>(xd, a.dO + orow * a.lddO + hv, nv, lir);
+    rg_load_row<T, LPR, PV, VEC>(xd, a.dO + orow * a.lddO + hv, nv, lir);
     T delta = (T) 0;
     {
         T xo[PV][VW];
-        gt_load_row<T, LPR, PV, VEC>(xo, a.O + orow * a.ldO + hv, nv, lir);
+        rg_load_row<T, LPR, PV, VEC>(xo, a.O + orow * a.ldO + hv, nv, lir);
 #pragma unroll
         for (int v = 0; v < PV; v++)
 #pragma unroll
@@ -554,7 +375,7 @@ __global__ __launch_bounds__(256) void gat_bwd_row_kernel(const GatBwdRowArgs<T>
         const int c = (my < pe) ? a.colidx[my] : 0;
         const int cnt = min(LPR, pe - p0);
         unsigned long long km = 0;                      // (DROP: the chunk's keep bits)
-        if constexpr (DROP) km = gt_keep_bits<T, LPR>(a.drop, my < pe, (uint32_t) orow, (uint32_t) c, (uint32_t) h, lir);
+        if constexpr (DROP) km = rg_keep_bits<T, LPR>(a.drop, my < pe, (uint32_t) orow, (uint32_t) c, (uint32_t) h, lir);
         for (int j = 0; j < cnt; j += UNR)
         {
             // indices past the row end are clamped to the row's last entry: a valid row whose dS counts as +0
@@ -567,12 +388,12 @@ __global__ __launch_bounds__(256) void gat_bwd_row_kernel(const GatBwdRowArgs<T>
 #pragma unroll
             for (int q = 0; q < UNR; q++)
             {
-                const int cj = gt_bcast_i<LPR>(c, min(j + q, cnt - 1));
+                const int cj = rg_bcast_i<LPR>(c, min(j + q, cnt - 1));
                 vrow[q] = ((cj >= 0) ? (a.V0 + (int64_t) cj * a.ldV0) : (a.V1 + (int64_t) (~cj) * a.ldV1)) + hv;
             }
             T pp[UNR];
             gt_dots<T, LPR, PV, VEC>(pp, xd, vrow, nv, lir);
-            const T rp = gt_reduce8<T, LPR>(pp, lir);
+            const T rp = rg_reduce8<T, LPR>(pp, lir);
             // every lane holds the score and dP of entry (lir & 7) of the batch
             T prob = (T) 0, ds = (T) 0, dz = (T) 0;
             if (mine < cnt)
@@ -597,10 +418,10 @@ __global__ __launch_bounds__(256) void gat_bwd_row_kernel(const GatBwdRowArgs<T>
 template <typename T, int LPR, int PV, bool VEC, bool DROP>
 __global__ __launch_bounds__(256) void gat_bwd_col_kernel(const GatBwdColArgs<T> a)
 {
-    constexpr int VW  = GtPiece<T>::VW;
+    constexpr int VW  = Piece<T>::VW;
     constexpr int RPB = 256 / LPR;
-    constexpr int UNR = GT_UNR;
-    constexpr int CV  = gt_ch<PV, VEC>;
+    constexpr int UNR = RG_UNR;
+    constexpr int CV  = rg_ch<PV, VEC>;
     const int lir = threadIdx.x % LPR;
     const int64_t u = (int64_t) blockIdx.x * RPB + threadIdx.x / LPR;
     const int64_t nh = a.heads;
@@ -612,7 +433,7 @@ __global__ __launch_bounds__(256) void gat_bwd_col_kernel(const GatBwdColArgs<T>
     if constexpr (LPR == 64) pb = __builtin_amdgcn_readfirstlane(pb);
     const int nv = a.nv;
     const int64_t crow = a.rowmap ? a.rowmap[row] : row;
-    const T ninf = gt_ninf<T>();
+    const T ninf = rg_ninf<T>();
     const int64_t hv = h * nv;
     T *const dvrow = a.dV + crow * a.lddV + hv;
     T *const derp = a.d_er + crow * a.ldd_er + h;
@@ -624,17 +445,17 @@ __global__ __launch_bounds__(256) void gat_bwd_col_kernel(const GatBwdColArgs<T>
         for (int w = 0; w < VW; w++) accV[v][w] = (T) 0;
     if (pb >= pe)                                       // a column no row names: +0; its er and V row are not read
     {
-        gt_store_row<T, LPR, PV, VEC>(accV, dvrow, nv, lir);
+        rg_store_row<T, LPR, PV, VEC>(accV, dvrow, nv, lir);
         if (lir == 0) *derp = (T) 0;
         return;
     }
     // er[c][h] and V[c]_h whole, before anything of this unit is written (dV == V)
     T xv[PV][VW];
-    gt_load_row<T, LPR, PV, VEC>(xv, a.V + crow * a.ldV + hv, nv, lir);
+    rg_load_row<T, LPR, PV, VEC>(xv, a.V + crow * a.ldV + hv, nv, lir);
     const T erv = a.er[crow * a.lder + h];
     const T slope = a.slope;
     const bool bias = a.val != nullptr;
-    const int again = gt_again<VW>(a.nv);
+    const int again = rg_again<VW>(a.nv);
     T sum = (T) 0;                                      // d_er: the same bits in every lane
 
     for (int p0 = pb; p0 < pe; p0 += LPR)
@@ -643,7 +464,7 @@ __global__ __launch_bounds__(256) void gat_bwd_col_kernel(const GatBwdColArgs<T>
         const int c = (my < pe) ? a.colidx[my] : 0;
         const int cnt = min(LPR, pe - p0);
         unsigned long long km = 0;                      // (DROP: the chunk's keep bits; the entry's row of A is r, this unit's row c)
-        if constexpr (DROP) km = gt_keep_bits<T, LPR>(a.drop, my < pe, (uint32_t) c, (uint32_t) crow, (uint32_t) h, lir);
+        if constexpr (DROP) km = rg_keep_bits<T, LPR>(a.drop, my < pe, (uint32_t) c, (uint32_t) crow, (uint32_t) h, lir);
         for (int j = 0; j < cnt; j += UNR)
         {
             const int mine = j + (lir & 7);
@@ -657,12 +478,12 @@ __global__ __launch_bounds__(256) void gat_bwd_col_kernel(const GatBwdColArgs<T>
 #pragma unroll
             for (int q = 0; q < UNR; q++)
             {
-                const int ij = gt_bcast_i<LPR>(c, min(j + q, cnt - 1));
+                const int ij = rg_bcast_i<LPR>(c, min(j + q, cnt - 1));
                 drow[q] = a.dO + (int64_t) ij * a.lddO + hv;
             }
             T pp[UNR];
             gt_dots<T, LPR, PV, VEC>(pp, xv, drow, nv, lir);
-            const T rp = gt_reduce8<T, LPR>(pp, lir);
+            const T rp = rg_reduce8<T, LPR>(pp, lir);
             T prob = (T) 0, ds = (T) 0, dz = (T) 0;
             if (mine < cnt)
             {
@@ -677,10 +498,10 @@ __global__ __launch_bounds__(256) void gat_bwd_col_kernel(const GatBwdColArgs<T>
                 sum = sum + __shfl(dz, q, LPR);
                 cp[q] = __shfl(prob, q, LPR);
             }
-            gt_static_for<0, PV, (VEC ? 2 : 1)>([&](auto kc) {
+            rg_static_for<0, PV, (VEC ? 2 : 1)>([&](auto kc) {
                 constexpr int K = decltype(kc)::value;
                 T dv[UNR][CV][VW];
-                gt_load8<T, LPR, CV, VEC>(dv, drow, K, nv, lir, again);        // (cache hits: the dots read these rows)
+                rg_load8<T, LPR, CV, VEC>(dv, drow, K, nv, lir, again);        // (cache hits: the dots read these rows)
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int q = 0; q < UNR; q++)
@@ -692,77 +513,31 @@ __global__ __launch_bounds__(256) void gat_bwd_col_kernel(const GatBwdColArgs<T>
             });
         }
     }
-    gt_store_row<T, LPR, PV, VEC>(accV, dvrow, nv, lir);
+    rg_store_row<T, LPR, PV, VEC>(accV, dvrow, nv, lir);
     if (lir == 0) *derp = sum;
 }
 
+
 // ---- launchers ----------------------------------------------------------------------------------------------------------------
-static inline bool gt_aligned(std::initializer_list<const void *> ptrs, std::initializer_list<int64_t> lds, int vw)
-{
-    uintptr_t bits = 0;
-    for (const void *p : ptrs) bits |= (uintptr_t) p;
-    bool ok = bits % 16 == 0;
-    for (int64_t ld : lds) ok = ok && ld % vw == 0;
-    return ok;
-}
-
-// the grid of nrow * heads units, RPB per block; false when it does not fit one launch (before anything is written)
-static inline bool gt_grid(int nrow, int heads, int rpb, dim3 *grid)
-{
-    const int64_t blocks = ((int64_t) nrow * heads + rpb - 1) / rpb;
-    if (blocks > INT32_MAX) return false;
-    *grid = dim3((unsigned) blocks);
-    return true;
-}
-
-// (nv % VW == 0 keeps every head's slice on a 16-byte boundary; the leading dimension of a source that is NULL is not read)
+// Per argument list: which pointers and which leading dimensions decide VEC (nv % VW == 0 keeps every head's slice on a 16-byte
+// boundary; the leading dimension of a source that is NULL is not read), and the kernel family; rg_launch does the rest.
 template <typename T, int LPR, int PV>
 static hipError_t launch_gat(const GatArgs<T> &a, hipStream_t s)
 {
-    constexpr int VW = GtPiece<T>::VW;
-    const bool vec = gt_aligned({a.V0, a.V1, a.O}, {a.nv, a.ldO, a.V0 ? a.ldV0 : 0, a.V1 ? a.ldV1 : 0}, VW);
-    dim3 grid;
-    if (!gt_grid(a.nrow, a.heads, 256 / LPR, &grid)) return hipErrorInvalidValue;
-    if (a.drop.on)
-    {
-        if (vec) hipLaunchKernelGGL((gat_fwd_kernel<T, LPR, PV, true, true>), grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((gat_fwd_kernel<T, LPR, PV, false, true>), grid, dim3(256), 0, s, a);
-    }
-    else if (vec) hipLaunchKernelGGL((gat_fwd_kernel<T, LPR, PV, true, false>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((gat_fwd_kernel<T, LPR, PV, false, false>), grid, dim3(256), 0, s, a);
-    return hipGetLastError();
+    return rg_launch<T, LPR>(a, s, {a.V0, a.V1, a.O}, {a.nv, a.ldO, a.V0 ? a.ldV0 : 0, a.V1 ? a.ldV1 : 0},
+                             [](auto v, auto d) { return gat_fwd_kernel<T, LPR, PV, decltype(v)::value, decltype(d)::value>; });
 }
 template <typename T, int LPR, int PV>
 static hipError_t launch_gat(const GatBwdRowArgs<T> &a, hipStream_t s)
 {
-    constexpr int VW = GtPiece<T>::VW;
-    const bool vec = gt_aligned({a.V0, a.V1, a.O, a.dO}, {a.nv, a.ldO, a.lddO, a.V0 ? a.ldV0 : 0, a.V1 ? a.ldV1 : 0}, VW);
-    dim3 grid;
-    if (!gt_grid(a.nrow, a.heads, 256 / LPR, &grid)) return hipErrorInvalidValue;
-    if (a.drop.on)
-    {
-        if (vec) hipLaunchKernelGGL((gat_bwd_row_kernel<T, LPR, PV, true, true>), grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((gat_bwd_row_kernel<T, LPR, PV, false, true>), grid, dim3(256), 0, s, a);
-    }
-    else if (vec) hipLaunchKernelGGL((gat_bwd_row_kernel<T, LPR, PV, true, false>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((gat_bwd_row_kernel<T, LPR, PV, false, false>), grid, dim3(256), 0, s, a);
-    return hipGetLastError();
+    return rg_launch<T, LPR>(a, s, {a.V0, a.V1, a.O, a.dO}, {a.nv, a.ldO, a.lddO, a.V0 ? a.ldV0 : 0, a.V1 ? a.ldV1 : 0},
+                             [](auto v, auto d) { return gat_bwd_row_kernel<T, LPR, PV, decltype(v)::value, decltype(d)::value>; });
 }
 template <typename T, int LPR, int PV>
 static hipError_t launch_gat(const GatBwdColArgs<T> &a, hipStream_t s)
 {
-    constexpr int VW = GtPiece<T>::VW;
-    const bool vec = gt_aligned({a.V, a.dO, a.dV}, {a.nv, a.ldV, a.lddO, a.lddV}, VW);
-    dim3 grid;
-    if (!gt_grid(a.nrow, a.heads, 256 / LPR, &grid)) return hipErrorInvalidValue;
-    if (a.drop.on)
-    {
-        if (vec) hipLaunchKernelGGL((gat_bwd_col_kernel<T, LPR, PV, true, true>), grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((gat_bwd_col_kernel<T, LPR, PV, false, true>), grid, dim3(256), 0, s, a);
-    }
-    else if (vec) hipLaunchKernelGGL((gat_bwd_col_kernel<T, LPR, PV, true, false>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((gat_bwd_col_kernel<T, LPR, PV, false, false>), grid, dim3(256), 0, s, a);
-    return hipGetLastError();
+    return rg_launch<T, LPR>(a, s, {a.V, a.dO, a.dV}, {a.nv, a.ldV, a.lddO, a.lddV},
+                             [](auto v, auto d) { return gat_bwd_col_kernel<T, LPR, PV, decltype(v)::value, decltype(d)::value>; });
 }
 
 // The instance, from (dtype, nv) alone (the rule is stated at the top of this file)

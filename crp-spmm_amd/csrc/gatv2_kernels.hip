@@ -5,7 +5,9 @@
 // -- the LeakyReLU INSIDE the dot with a, where gat_kernels.hip has it outside a sum of two scalars.  The gathered row XS[c] is the
 // score operand and the value operand: one gather per entry.  From the scores on everything is attention_kernels.hip's: the batches
 // of 8, the online softmax, lse / p_out, the (row, head) units and the column-to-lane assignment.  No atomics, no LDS, no partial
-// result in memory.
+// result in memory.  The pieces, the row loads and stores, the walk over a batch's 8 rows (rg_walk8), the batch's butterfly
+// (rg_reduce8), the keep bits and the launcher are row_group.h's (rg_), one definition for this file, gat_kernels.hip and the
+// attention's two; g2_ marks what is this score's own.
 //
 // OPERANDS.  heads = H >= 1 heads of nv columns each lie side by side in XT / XS / a / O / dO / dXT / da_part / dXS: head h owns
 // columns [h nv, (h + 1) nv).  XT is (rows of O, H nv), read through the row map like Q; XS0 / XS1 are the two sources of the column
@@ -20,15 +22,16 @@
 //
 // SCORES.  Per batch of 8 entries a lane forms its part of the 8 dots from its pieces of the 8 gathered rows -- z and r rounded one
 // by one (g2_lrelu compiles with contraction off, so slope * z never meets the product with a in one instruction), then
-// part = fma(a_j, r_j, part) in ascending j from +0 -- and the SDDMM's reduce-scatter butterfly leaves the dot of entry u in lane u
-// of every block of 8 lanes: the bits of crp_sddmm_csr_* for (dtype, nv) on the rows a and r.  s = dot (bias: + val, one rounding).
+// part = fma(a_j, r_j, part) in ascending j from +0 -- and the SDDMM's reduce-scatter butterfly (rg_reduce8) leaves the dot of
+// entry u in lane u of every block of 8 lanes: the bits of crp_sddmm_csr_* for (dtype, nv) on the rows a and r.  s = dot (bias:
+// + val, one rounding).
 //
 // LOADS.  Forward, P = 1: the 8 row pieces loaded for the dots stay in registers and serve the accumulator FMAs.  Backward, P = 1
 // in fp64: what the second trip over a batch needs stays in registers -- row side r and the branch bits, column side the dO
 // pieces and the branch bits -- and nothing is formed or fetched twice.  In fp32 the same 32 + 32 registers take the row side
 // from 4 waves per SIMD to 2, and the backward measured 10 - 17 % slower with them than without, so fp32 does
 // as P = 2 and 4 do in both directions: holding 8 rows x P pieces across the exponentials would spill, so the rows are read again
-// through g2_again's opaque zero -- cache hits, the dots read these lines a moment ago -- and z, the branch and r are formed
+// through rg_again's opaque zero -- cache hits, the dots read these lines a moment ago -- and z, the branch and r are formed
 // again, with the same bits.  Per step at most 8 x 2 pieces by 16-byte accesses (8 x 1 by elements) are in flight, issued ahead
 // of the step's FMAs.
 //
@@ -52,36 +55,12 @@
 // scores, batches, m, f, e_u and l are the plain call's -- the softmax runs over all edges -- and only the accumulator changes:
 // acc = fma(k_u ? e_u : +0, XS[c_u][j], acc), O = fl(fl(acc / l) rs); lse and p_out keep the plain call's bits.  Backward: p, s
 // and D = < dO, O > (O is the dropped O) as above, dP' = k ? fl(dP rs) : +0, dS = p (dP' - D), and accV takes the weight
-// w = k ? fl(p rs) : +0 in the place of p.  The two products with rs are roundings of their own (g2_mul).  The lane that loads the
+// w = k ? fl(p rs) : +0 in the place of p.  The two products with rs are roundings of their own (rg_mul).  The lane that loads the
 // column code of its own entry of a chunk draws that entry's bit, one ballot hands the chunk's bits to the group, and a batch takes
 // its 8 bits from that word.  DROP = false compiles to the code without any of this.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <initializer_list>
-#include <type_traits>
-#include "kernels.h"
+#include "row_group.h"
 
 namespace crp {
-
-constexpr int G2_UNR = 8;
-
-template <typename T> struct G2Piece;
-template <> struct G2Piece<double> { typedef double type __attribute__((ext_vector_type(2))); static constexpr int VW = 2; };
-template <> struct G2Piece<float>  { typedef float type __attribute__((ext_vector_type(4))); static constexpr int VW = 4; };
-
-__device__ __forceinline__ double g2_exp(double x) { return exp(x); }
-__device__ __forceinline__ float  g2_exp(float x) { return expf(x); }
-__device__ __forceinline__ double g2_log(double x) { return log(x); }
-__device__ __forceinline__ float  g2_log(float x) { return logf(x); }
-template <typename T> __device__ __forceinline__ T g2_ninf() { return -__builtin_huge_val(); }
-template <> __device__ __forceinline__ float g2_ninf<float>() { return -__builtin_huge_valf(); }
-
-template <int LPR>
-__device__ __forceinline__ int g2_bcast_i(int v, int j)
-{
-    if constexpr (LPR == 64) return __builtin_amdgcn_readlane(v, j);
-    else return __shfl(v, j, LPR);
-}
 
 // r = lrelu(xt + xs): two statements, two roundings; the caller's fma(a, r, .) is a third.  hipcc contracts across statements by
 // default; here it may not.  *pos: z > 0, which chooses a or as in the backward.
@@ -94,174 +73,12 @@ __device__ __forceinline__ T g2_lrelu(const T xt, const T xs, const T slope, boo
     *pos = z > (T) 0;
     return *pos ? z : sz;
 }
-// as = a * slope, rounded before it is used in anything; the products with rs of the DROP instances likewise
-template <typename T>
-__device__ __forceinline__ T g2_mul(const T x, const T y)
-{
-#pragma clang fp contract(off)
-    const T r = x * y;
-    return r;
-}
 // s = dot (+ val), and accZ + accV: additions of their own
 template <typename T>
 __device__ __forceinline__ T g2_add(const T x, const T y)
 {
 #pragma clang fp contract(off)
     const T r = x + y;
-    return r;
-}
-
-// The keep bits of a chunk of LPR entries: the lane that holds entry `lir` of the chunk (live: it has one) draws the bit of
-// (r, c, h); bit e of the result is entry e's, the same word in every lane of the group.  Every lane of a group is active here
-// together (the chunk loop's bounds are the group's); lanes of other groups that are not contribute 0 to bits this group drops.
-template <typename T, int LPR>
-__device__ __forceinline__ unsigned long long g2_keep_bits(const DropArgs<T> &d, const bool live, const uint32_t r, const uint32_t c,
-                                                           const uint32_t h, const int lir)
-{
-    const bool k = live && dropout_keep(d.seed_lo, d.seed_hi, r, c, h, d.thr);
-    const unsigned long long all = __ballot(k);
-    if constexpr (LPR == 64) return all;
-    else return all >> ((threadIdx.x & 63u) - (unsigned) lir);
-}
-
-// pieces per lane and row of one load step: two by 16-byte accesses, one by elements, so that no instance spills
-template <int P, bool VEC> constexpr int g2_ch = VEC ? (P < 2 ? P : 2) : 1;
-
-template <int K0, int END, int STEP, class F>
-__device__ __forceinline__ void g2_static_for(F &&f)
-{
-    if constexpr (K0 < END)
-    {
-        f(std::integral_constant<int, K0>{});
-        g2_static_for<K0 + STEP, END, STEP>(f);
-    }
-}
-
-// The zero of g2_load8's `again`: opaque as long as nothing lets the compiler prove nv >= 0, so that the second read of a batch's
-// rows stays a load of its own (a cache hit) instead of 8 rows held in registers across the batch.
-template <int VW> __device__ __forceinline__ int g2_again(const int nv) { return VW * (int) (nv < 0); }
-
-// this lane's NP pieces of a row of n columns: piece q starts at column (q * LPR + lir) * VW; slots past n hold 0
-template <typename T, int LPR, int NP, bool VEC>
-__device__ __forceinline__ void g2_load_row(T (&x)[NP][G2Piece<T>::VW], const T *row, const int n, const int lir)
-{
-    typedef typename G2Piece<T>::type PT;
-    constexpr int VW = G2Piece<T>::VW;
-#pragma unroll
-    for (int v = 0; v < NP; v++)
-    {
-        const int c = (v * LPR + lir) * VW;
-        if constexpr (VEC)
-        {
-            PT t = {};
-            if (c < n) t = *reinterpret_cast<const PT *>(row + c);
-#pragma unroll
-            for (int w = 0; w < VW; w++) x[v][w] = t[w];
-        }
-        else
-        {
-#pragma unroll
-            for (int w = 0; w < VW; w++) x[v][w] = (c + w < n) ? row[c + w] : (T) 0;
-        }
-    }
-}
-
-// ... and the store of them (slots past n are not written)
-template <typename T, int LPR, int NP, bool VEC>
-__device__ __forceinline__ void g2_store_row(const T (&x)[NP][G2Piece<T>::VW], T *row, const int n, const int lir)
-{
-    typedef typename G2Piece<T>::type PT;
-    constexpr int VW = G2Piece<T>::VW;
-#pragma unroll
-    for (int v = 0; v < NP; v++)
-    {
-        const int c = (v * LPR + lir) * VW;
-        if constexpr (VEC)
-        {
-            PT t;
-#pragma unroll
-            for (int w = 0; w < VW; w++) t[w] = x[v][w];
-            if (c < n) *reinterpret_cast<PT *>(row + c) = t;
-        }
-        else
-        {
-#pragma unroll
-            for (int w = 0; w < VW; w++)
-                if (c + w < n) row[c + w] = x[v][w];
-        }
-    }
-}
-
-// this lane's pieces piece0 .. piece0 + CH - 1 of the 8 rows y[q] (slots past n: column 0, a valid address, not used)
-template <typename T, int LPR, int CH, bool VEC>
-__device__ __forceinline__ void g2_load8(T (&yv)[G2_UNR][CH][G2Piece<T>::VW], const T *const (&y)[G2_UNR], const int piece0, const int n,
-                                         const int lir, const int again = 0)
-{
-    typedef typename G2Piece<T>::type PT;
-    constexpr int VW = G2Piece<T>::VW;
-#pragma unroll
-    for (int q = 0; q < G2_UNR; q++)
-#pragma unroll
-        for (int v = 0; v < CH; v++)
-        {
-            const int c = ((piece0 + v) * LPR + lir) * VW;
-            if constexpr (VEC)
-            {
-                const PT t = *reinterpret_cast<const PT *>(y[q] + again + (unsigned) ((c < n) ? c : 0));
-#pragma unroll
-                for (int w = 0; w < VW; w++) yv[q][v][w] = t[w];
-            }
-            else
-            {
-#pragma unroll
-                for (int w = 0; w < VW; w++) yv[q][v][w] = (y[q] + again)[(unsigned) ((c + w < n) ? c + w : 0)];
-            }
-        }
-}
-
-// One trip over this lane's NP pieces of the 8 rows y[q]: per step the gathers go out before the step's arithmetic, which runs in
-// the order (q, piece, element) -- per q in column order, the SDDMM's chunk.  f(q, piece, element, in-range, value).
-template <typename T, int LPR, int NP, bool VEC, class F>
-__device__ __forceinline__ void g2_walk8(const T *const (&y)[G2_UNR], const int n, const int lir, const int again, F &&f)
-{
-    constexpr int VW = G2Piece<T>::VW;
-    constexpr int CH = g2_ch<NP, VEC>;
-    g2_static_for<0, NP, (VEC ? 2 : 1)>([&](auto kc) {
-        constexpr int K = decltype(kc)::value;
-        T yv[G2_UNR][CH][VW];
-        g2_load8<T, LPR, CH, VEC>(yv, y, K, n, lir, again);
-        __builtin_amdgcn_sched_barrier(0);              // every load of the step is in flight before the first FMA waits for one
-#pragma unroll
-        for (int q = 0; q < G2_UNR; q++)
-#pragma unroll
-            for (int v = 0; v < CH; v++)
-#pragma unroll
-                for (int w = 0; w < VW; w++) f(q, K + v, w, ((K + v) * LPR + lir) * VW + w < n, yv[q][v][w]);
-        if constexpr (!VEC) __builtin_amdgcn_sched_barrier(0);      // (by elements: the next step's loads wait, for the registers)
-    });
-}
-
-// reduce-scatter butterfly of the SDDMM: after it lane l holds entry (l & 7) of the batch summed over the group
-template <typename T, int LPR>
-__device__ __forceinline__ T g2_reduce8(const T (&part)[G2_UNR], const int lir)
-{
-    const bool b0 = (lir & 1) != 0, b1 = (lir & 2) != 0, b2 = (lir & 4) != 0;
-    T q4[4], q2[2];
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-    {
-        const T keep = b0 ? part[2 * i + 1] : part[2 * i], send = b0 ? part[2 * i] : part[2 * i + 1];
-        q4[i] = keep + __shfl_xor(send, 1, LPR);
-    }
-#pragma unroll
-    for (int i = 0; i < 2; i++)
-    {
-        const T keep = b1 ? q4[2 * i + 1] : q4[2 * i], send = b1 ? q4[2 * i] : q4[2 * i + 1];
-        q2[i] = keep + __shfl_xor(send, 2, LPR);
-    }
-    T r = (b2 ? q2[1] : q2[0]) + __shfl_xor(b2 ? q2[0] : q2[1], 4, LPR);
-#pragma unroll
-    for (int mask = 8; mask < LPR; mask <<= 1) r = r + __shfl_xor(r, mask, LPR);
     return r;
 }
 
@@ -278,11 +95,11 @@ template <typename T, bool DROP>
 __device__ __forceinline__ void g2_entry(const T s, T dp, const T lse, const T delta, const bool dead, const bool keep, const T rs, T *pp,
                                          T *ds)
 {
-    const T e = dead ? (T) 0 : g2_exp(s - lse);
+    const T e = dead ? (T) 0 : rg_exp(s - lse);
     if constexpr (DROP)
     {
-        dp = keep ? g2_mul<T>(dp, rs) : (T) 0;
-        *pp = keep ? g2_mul<T>(e, rs) : (T) 0;
+        dp = keep ? rg_mul<T>(dp, rs) : (T) 0;
+        *pp = keep ? rg_mul<T>(e, rs) : (T) 0;
     }
     else *pp = e;
     *ds = (e == (T) 0) ? (T) 0 : e * (dp - delta);
@@ -293,9 +110,9 @@ __device__ __forceinline__ void g2_entry(const T s, T dp, const T lse, const T d
 template <typename T, int LPR, int P, bool VEC, bool DROP>
 __global__ __launch_bounds__(256) void gatv2_fwd_kernel(const Gatv2Args<T> a)
 {
-    constexpr int VW  = G2Piece<T>::VW;
+    constexpr int VW  = Piece<T>::VW;
     constexpr int RPB = 256 / LPR;
-    constexpr int UNR = G2_UNR;
+    constexpr int UNR = RG_UNR;
     constexpr bool HOLD = P == 1;                       // the rows of a batch stay in registers from the dots to the accumulator
     const int lir = threadIdx.x % LPR;                  // lane in the unit's group
     const int64_t u = (int64_t) blockIdx.x * RPB + threadIdx.x / LPR;
@@ -308,7 +125,7 @@ __global__ __launch_bounds__(256) void gatv2_fwd_kernel(const Gatv2Args<T> a)
     if constexpr (LPR == 64) pb = __builtin_amdgcn_readfirstlane(pb);
     const int nv = a.nv;
     const int64_t orow = a.rowmap ? a.rowmap[row] : row;        // rowmap: the XT and O row of every row of a row-subset matrix
-    const T ninf = g2_ninf<T>();
+    const T ninf = rg_ninf<T>();
     const int64_t hv = h * nv;                          // the head's first column
     const int64_t srow = orow * nh + h;                 // the unit's entry of lse
     T *const orp = a.O + orow * a.ldO + hv;
@@ -320,16 +137,16 @@ __global__ __launch_bounds__(256) void gatv2_fwd_kernel(const Gatv2Args<T> a)
         for (int w = 0; w < VW; w++) acc[v][w] = (T) 0;
     if (pb >= pe)                                       // an empty row: zeros; XT is not read
     {
-        g2_store_row<T, LPR, P, VEC>(acc, orp, nv, lir);
+        rg_store_row<T, LPR, P, VEC>(acc, orp, nv, lir);
         if (a.lse != nullptr && lir == 0) a.lse[srow] = ninf;
         return;
     }
     T xt[P][VW], av[P][VW];                             // kept for the row
-    g2_load_row<T, LPR, P, VEC>(xt, a.XT + orow * a.ldXT + hv, nv, lir);
-    g2_load_row<T, LPR, P, VEC>(av, a.av + hv, nv, lir);
+    rg_load_row<T, LPR, P, VEC>(xt, a.XT + orow * a.ldXT + hv, nv, lir);
+    rg_load_row<T, LPR, P, VEC>(av, a.av + hv, nv, lir);
     const T slope = a.slope;
     const bool bias = a.val != nullptr;
-    const int again = g2_again<VW>(a.nv);
+    const int again = rg_again<VW>(a.nv);
     T m = ninf, l = (T) 0;
 
     for (int p0 = pb; p0 < pe; p0 += LPR)
@@ -338,7 +155,7 @@ __global__ __launch_bounds__(256) void gatv2_fwd_kernel(const Gatv2Args<T> a)
         const int c = (my < pe) ? a.colidx[my] : 0;
         const int cnt = min(LPR, pe - p0);
         unsigned long long km = 0;                      // (DROP: the chunk's keep bits)
-        if constexpr (DROP) km = g2_keep_bits<T, LPR>(a.drop, my < pe, (uint32_t) orow, (uint32_t) c, (uint32_t) h, lir);
+        if constexpr (DROP) km = rg_keep_bits<T, LPR>(a.drop, my < pe, (uint32_t) orow, (uint32_t) c, (uint32_t) h, lir);
         for (int j = 0; j < cnt; j += UNR)
         {
             // indices past the row end are clamped to the row's last entry: a valid row whose score counts as -inf
@@ -347,7 +164,7 @@ __global__ __launch_bounds__(256) void gatv2_fwd_kernel(const Gatv2Args<T> a)
             const T bv = bias ? a.val[p0 + mcl] : (T) 0;
             const T *xrow[UNR];
 #pragma unroll
-            for (int q = 0; q < UNR; q++) xrow[q] = g2_xs<T>(g2_bcast_i<LPR>(c, min(j + q, cnt - 1)), hv, a.XS0, a.ldXS0, a.XS1, a.ldXS1);
+            for (int q = 0; q < UNR; q++) xrow[q] = g2_xs<T>(rg_bcast_i<LPR>(c, min(j + q, cnt - 1)), hv, a.XS0, a.ldXS0, a.XS1, a.ldXS1);
 
             T part[UNR];
 #pragma unroll
@@ -355,7 +172,7 @@ __global__ __launch_bounds__(256) void gatv2_fwd_kernel(const Gatv2Args<T> a)
             T hold[UNR][1][VW];                         // (P == 1: the batch's pieces; else not used)
             if constexpr (HOLD)
             {
-                g2_load8<T, LPR, 1, VEC>(hold, xrow, 0, nv, lir);
+                rg_load8<T, LPR, 1, VEC>(hold, xrow, 0, nv, lir);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int q = 0; q < UNR; q++)
@@ -370,7 +187,7 @@ __global__ __launch_bounds__(256) void gatv2_fwd_kernel(const Gatv2Args<T> a)
             }
             else
             {
-                g2_walk8<T, LPR, P, VEC>(xrow, nv, lir, 0, [&](const int q, const int v, const int w, const bool in, const T y) {
+                rg_walk8<T, LPR, P, VEC>(xrow, nv, lir, 0, [&](const int q, const int v, const int w, const bool in, const T y) {
                     if (in)
                     {
                         bool pos;
@@ -379,7 +196,7 @@ __global__ __launch_bounds__(256) void gatv2_fwd_kernel(const Gatv2Args<T> a)
                     }
                 });
             }
-            const T dot = g2_reduce8<T, LPR>(part, lir);
+            const T dot = rg_reduce8<T, LPR>(part, lir);
 
             // every lane holds the score of entry (lir & 7) of the batch
             T s = ninf;
@@ -399,8 +216,8 @@ __global__ __launch_bounds__(256) void gatv2_fwd_kernel(const Gatv2Args<T> a)
             T f = (T) 1, e = (T) 0;
             if (mn != ninf)                             // (else every entry so far is masked: l and acc stay 0)
             {
-                f = g2_exp(m - mn);
-                e = g2_exp(s - mn);
+                f = rg_exp(m - mn);
+                e = rg_exp(s - mn);
             }
             m = mn;
             T eu[UNR];
@@ -429,7 +246,7 @@ __global__ __launch_bounds__(256) void gatv2_fwd_kernel(const Gatv2Args<T> a)
             else
             {
                 // (cache hits: the dots read these rows)
-                g2_walk8<T, LPR, P, VEC>(xrow, nv, lir, again, [&](const int q, const int v, const int w, const bool, const T y) {
+                rg_walk8<T, LPR, P, VEC>(xrow, nv, lir, again, [&](const int q, const int v, const int w, const bool, const T y) {
                     acc[v][w] = fma(eu[q], y, acc[v][w]);
                 });
             }
@@ -443,16 +260,16 @@ __global__ __launch_bounds__(256) void gatv2_fwd_kernel(const Gatv2Args<T> a)
         for (int w = 0; w < VW; w++)
         {
             acc[v][w] = masked ? (T) 0 : acc[v][w] / l;
-            if constexpr (DROP) acc[v][w] = g2_mul<T>(acc[v][w], a.drop.rs);
+            if constexpr (DROP) acc[v][w] = rg_mul<T>(acc[v][w], a.drop.rs);
         }
-    g2_store_row<T, LPR, P, VEC>(acc, orp, nv, lir);
-    if (a.lse != nullptr && lir == 0) a.lse[srow] = masked ? ninf : m + g2_log(l);
+    rg_store_row<T, LPR, P, VEC>(acc, orp, nv, lir);
+    if (a.lse != nullptr && lir == 0) a.lse[srow] = masked ? ninf : m + rg_log(l);
     if (a.p_out != nullptr && lir < UNR)
         for (int p = pb + lir; p < pe; p += UNR)        // this lane's own stores
         {
             const int64_t pos = (int64_t) (a.out_pos ? a.out_pos[p] : p) * nh + h;
             const T sv = a.p_out[pos];
-            a.p_out[pos] = masked ? (T) 0 : g2_exp(sv - m) / l;
+            a.p_out[pos] = masked ? (T) 0 : rg_exp(sv - m) / l;
         }
 }
 
@@ -460,9 +277,9 @@ __global__ __launch_bounds__(256) void gatv2_fwd_kernel(const Gatv2Args<T> a)
 template <typename T, int LPR, int P, bool VEC, bool DROP>
 __global__ __launch_bounds__(256) void gatv2_bwd_row_kernel(const Gatv2BwdRowArgs<T> a)
 {
-    constexpr int VW  = G2Piece<T>::VW;
+    constexpr int VW  = Piece<T>::VW;
     constexpr int RPB = 256 / LPR;
-    constexpr int UNR = G2_UNR;
+    constexpr int UNR = RG_UNR;
     constexpr bool HOLD = P == 1 && sizeof(T) == 8;     // what the second trip over a batch needs stays in registers (see LOADS)
     const int lir = threadIdx.x % LPR;
     const int64_t u = (int64_t) blockIdx.x * RPB + threadIdx.x / LPR;
@@ -477,15 +294,15 @@ __global__ __launch_bounds__(256) void gatv2_bwd_row_kernel(const Gatv2BwdRowArg
     const int64_t orow = a.rowmap ? a.rowmap[row] : row;
     const int64_t hv = h * nv;
     const int64_t srow = orow * nh + h;                 // the unit's entry of lse and delta
-    const T ninf = g2_ninf<T>();
+    const T ninf = rg_ninf<T>();
 
     // D = < dO[i]_h, O[i]_h >, the SDDMM's dot for (dtype, nv); every lane of the group ends with the same bits
     T xd[P][VW];
-    g2_load_row<T, LPR, P, VEC>(xd, a.dO + orow * a.lddO + hv, nv, lir);
+    rg_load_row<T, LPR, P, VEC>(xd, a.dO + orow * a.lddO + hv, nv, lir);
     T delta = (T) 0;
     {
         T xo[P][VW];
-        g2_load_row<T, LPR, P, VEC>(xo, a.O + orow * a.ldO + hv, nv, lir);
+        rg_load_row<T, LPR, P, VEC>(xo, a.O + orow * a.ldO + hv, nv, lir);
 #pragma unroll
         for (int v = 0; v < P; v++)
 #pragma unroll
@@ -506,22 +323,22 @@ __global__ __launch_bounds__(256) void gatv2_bwd_row_kernel(const Gatv2BwdRowArg
     const T lse = a.lse[srow];
     if (pb >= pe || lse == ninf)                        // an empty or all-masked row: +0 everywhere; XT is not read
     {
-        g2_store_row<T, LPR, P, VEC>(dxt, dxrow, nv, lir);
-        g2_store_row<T, LPR, P, VEC>(dap, darow, nv, lir);
+        rg_store_row<T, LPR, P, VEC>(dxt, dxrow, nv, lir);
+        rg_store_row<T, LPR, P, VEC>(dap, darow, nv, lir);
         if (a.ds_out != nullptr)
             for (int p = pb + lir; p < pe; p += LPR) a.ds_out[(int64_t) (a.out_pos ? a.out_pos[p] : p) * nh + h] = (T) 0;
         return;
     }
     const T slope = a.slope;
     T xt[P][VW], av[P][VW], as[P][VW];
-    g2_load_row<T, LPR, P, VEC>(xt, a.XT + orow * a.ldXT + hv, nv, lir);
-    g2_load_row<T, LPR, P, VEC>(av, a.av + hv, nv, lir);
+    rg_load_row<T, LPR, P, VEC>(xt, a.XT + orow * a.ldXT + hv, nv, lir);
+    rg_load_row<T, LPR, P, VEC>(av, a.av + hv, nv, lir);
 #pragma unroll
     for (int v = 0; v < P; v++)
 #pragma unroll
-        for (int w = 0; w < VW; w++) as[v][w] = g2_mul<T>(av[v][w], slope);
+        for (int w = 0; w < VW; w++) as[v][w] = rg_mul<T>(av[v][w], slope);
     const bool bias = a.val != nullptr;
-    const int again = g2_again<VW>(a.nv);
+    const int again = rg_again<VW>(a.nv);
 
     for (int p0 = pb; p0 < pe; p0 += LPR)
     {
@@ -529,7 +346,7 @@ __global__ __launch_bounds__(256) void gatv2_bwd_row_kernel(const Gatv2BwdRowArg
         const int c = (my < pe) ? a.colidx[my] : 0;
         const int cnt = min(LPR, pe - p0);
         unsigned long long km = 0;                      // (DROP: the chunk's keep bits)
-        if constexpr (DROP) km = g2_keep_bits<T, LPR>(a.drop, my < pe, (uint32_t) orow, (uint32_t) c, (uint32_t) h, lir);
+        if constexpr (DROP) km = rg_keep_bits<T, LPR>(a.drop, my < pe, (uint32_t) orow, (uint32_t) c, (uint32_t) h, lir);
         for (int j = 0; j < cnt; j += UNR)
         {
             // indices past the row end are clamped to the row's last entry: a valid row whose dS counts as +0
@@ -538,7 +355,7 @@ __global__ __launch_bounds__(256) void gatv2_bwd_row_kernel(const Gatv2BwdRowArg
             const T bv = bias ? a.val[p0 + mcl] : (T) 0;
             const T *xrow[UNR];
 #pragma unroll
-            for (int q = 0; q < UNR; q++) xrow[q] = g2_xs<T>(g2_bcast_i<LPR>(c, min(j + q, cnt - 1)), hv, a.XS0, a.ldXS0, a.XS1, a.ldXS1);
+            for (int q = 0; q < UNR; q++) xrow[q] = g2_xs<T>(rg_bcast_i<LPR>(c, min(j + q, cnt - 1)), hv, a.XS0, a.ldXS0, a.XS1, a.ldXS1);
 
             // one trip serves both dots: the score's and dP's
             T sp[UNR], dp[UNR];
@@ -549,7 +366,7 @@ __global__ __launch_bounds__(256) void gatv2_bwd_row_kernel(const Gatv2BwdRowArg
             if constexpr (HOLD)
             {
                 T y[UNR][1][VW];
-                g2_load8<T, LPR, 1, VEC>(y, xrow, 0, nv, lir);
+                rg_load8<T, LPR, 1, VEC>(y, xrow, 0, nv, lir);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int q = 0; q < UNR; q++)
@@ -569,7 +386,7 @@ __global__ __launch_bounds__(256) void gatv2_bwd_row_kernel(const Gatv2BwdRowArg
             }
             else
             {
-                g2_walk8<T, LPR, P, VEC>(xrow, nv, lir, 0, [&](const int q, const int v, const int w, const bool in, const T y) {
+                rg_walk8<T, LPR, P, VEC>(xrow, nv, lir, 0, [&](const int q, const int v, const int w, const bool in, const T y) {
                     if (in)
                     {
                         bool pos;
@@ -579,8 +396,8 @@ __global__ __launch_bounds__(256) void gatv2_bwd_row_kernel(const Gatv2BwdRowArg
                     }
                 });
             }
-            const T dot = g2_reduce8<T, LPR>(sp, lir);
-            const T rp = g2_reduce8<T, LPR>(dp, lir);
+            const T dot = rg_reduce8<T, LPR>(sp, lir);
+            const T rp = rg_reduce8<T, LPR>(dp, lir);
             // every lane holds the score and dP of entry (lir & 7) of the batch
             T prob = (T) 0, ds = (T) 0;
             if (mine < cnt)
@@ -611,7 +428,7 @@ __global__ __launch_bounds__(256) void gatv2_bwd_row_kernel(const Gatv2BwdRowArg
             else
             {
                 // (cache hits: the dots read these rows)
-                g2_walk8<T, LPR, P, VEC>(xrow, nv, lir, again, [&](const int q, const int v, const int w, const bool, const T y) {
+                rg_walk8<T, LPR, P, VEC>(xrow, nv, lir, again, [&](const int q, const int v, const int w, const bool, const T y) {
                     bool pos;
                     const T r = g2_lrelu<T>(xt[v][w], y, slope, &pos);
                     const T ag = pos ? av[v][w] : as[v][w];
@@ -621,17 +438,17 @@ __global__ __launch_bounds__(256) void gatv2_bwd_row_kernel(const Gatv2BwdRowArg
             }
         }
     }
-    g2_store_row<T, LPR, P, VEC>(dxt, dxrow, nv, lir);
-    g2_store_row<T, LPR, P, VEC>(dap, darow, nv, lir);
+    rg_store_row<T, LPR, P, VEC>(dxt, dxrow, nv, lir);
+    rg_store_row<T, LPR, P, VEC>(dap, darow, nv, lir);
 }
 
 // ---- backward, column side: dXS over a handle of A^T (the unit is (column c, head h)) ------------------------------------------
 template <typename T, int LPR, int P, bool VEC, bool DROP>
 __global__ __launch_bounds__(256) void gatv2_bwd_col_kernel(const Gatv2BwdColArgs<T> a)
 {
-    constexpr int VW  = G2Piece<T>::VW;
+    constexpr int VW  = Piece<T>::VW;
     constexpr int RPB = 256 / LPR;
-    constexpr int UNR = G2_UNR;
+    constexpr int UNR = RG_UNR;
     constexpr bool HOLD = P == 1 && sizeof(T) == 8;     // what the second trip over a batch needs stays in registers (see LOADS)
     const int lir = threadIdx.x % LPR;
     const int64_t u = (int64_t) blockIdx.x * RPB + threadIdx.x / LPR;
@@ -644,7 +461,7 @@ __global__ __launch_bounds__(256) void gatv2_bwd_col_kernel(const Gatv2BwdColArg
     if constexpr (LPR == 64) pb = __builtin_amdgcn_readfirstlane(pb);
     const int nv = a.nv;
     const int64_t crow = a.rowmap ? a.rowmap[row] : row;
-    const T ninf = g2_ninf<T>();
+    const T ninf = rg_ninf<T>();
     const int64_t hv = h * nv;
     T *const dxrow = a.dXS + crow * a.lddXS + hv;
 
@@ -655,20 +472,20 @@ __global__ __launch_bounds__(256) void gatv2_bwd_col_kernel(const Gatv2BwdColArg
         for (int w = 0; w < VW; w++) accZ[v][w] = accV[v][w] = (T) 0;
     if (pb >= pe)                                       // a column no row names: +0; its XS row is not read
     {
-        g2_store_row<T, LPR, P, VEC>(accZ, dxrow, nv, lir);
+        rg_store_row<T, LPR, P, VEC>(accZ, dxrow, nv, lir);
         return;
     }
     // XS[c]_h whole, before anything of this unit is written (dXS == XS)
     const T slope = a.slope;
     T xs[P][VW], av[P][VW], as[P][VW];
-    g2_load_row<T, LPR, P, VEC>(xs, a.XS + crow * a.ldXS + hv, nv, lir);
-    g2_load_row<T, LPR, P, VEC>(av, a.av + hv, nv, lir);
+    rg_load_row<T, LPR, P, VEC>(xs, a.XS + crow * a.ldXS + hv, nv, lir);
+    rg_load_row<T, LPR, P, VEC>(av, a.av + hv, nv, lir);
 #pragma unroll
     for (int v = 0; v < P; v++)
 #pragma unroll
-        for (int w = 0; w < VW; w++) as[v][w] = g2_mul<T>(av[v][w], slope);
+        for (int w = 0; w < VW; w++) as[v][w] = rg_mul<T>(av[v][w], slope);
     const bool bias = a.val != nullptr;
-    const int again = g2_again<VW>(a.nv);
+    const int again = rg_again<VW>(a.nv);
 
     for (int p0 = pb; p0 < pe; p0 += LPR)
     {
@@ -676,7 +493,7 @@ __global__ __launch_bounds__(256) void gatv2_bwd_col_kernel(const Gatv2BwdColArg
         const int c = (my < pe) ? a.colidx[my] : 0;
         const int cnt = min(LPR, pe - p0);
         unsigned long long km = 0;                      // (DROP: the chunk's keep bits; the entry's row of A is r, this unit's row c)
-        if constexpr (DROP) km = g2_keep_bits<T, LPR>(a.drop, my < pe, (uint32_t) c, (uint32_t) crow, (uint32_t) h, lir);
+        if constexpr (DROP) km = rg_keep_bits<T, LPR>(a.drop, my < pe, (uint32_t) c, (uint32_t) crow, (uint32_t) h, lir);
         for (int j = 0; j < cnt; j += UNR)
         {
             const int mine = j + (lir & 7);
@@ -689,7 +506,7 @@ __global__ __launch_bounds__(256) void gatv2_bwd_col_kernel(const Gatv2BwdColArg
 #pragma unroll
             for (int q = 0; q < UNR; q++)
             {
-                const int ij = g2_bcast_i<LPR>(c, min(j + q, cnt - 1));
+                const int ij = rg_bcast_i<LPR>(c, min(j + q, cnt - 1));
                 trow[q] = a.XT + (int64_t) ij * a.ldXT + hv;
                 drow[q] = a.dO + (int64_t) ij * a.lddO + hv;
             }
@@ -701,8 +518,8 @@ __global__ __launch_bounds__(256) void gatv2_bwd_col_kernel(const Gatv2BwdColArg
             if constexpr (HOLD)
             {
                 T ty[UNR][1][VW];
-                g2_load8<T, LPR, 1, VEC>(ty, trow, 0, nv, lir);
-                g2_load8<T, LPR, 1, VEC>(dy, drow, 0, nv, lir);
+                rg_load8<T, LPR, 1, VEC>(ty, trow, 0, nv, lir);
+                rg_load8<T, LPR, 1, VEC>(dy, drow, 0, nv, lir);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int q = 0; q < UNR; q++)
@@ -721,7 +538,7 @@ __global__ __launch_bounds__(256) void gatv2_bwd_col_kernel(const Gatv2BwdColArg
             }
             else
             {
-                g2_walk8<T, LPR, P, VEC>(trow, nv, lir, 0, [&](const int q, const int v, const int w, const bool in, const T y) {
+                rg_walk8<T, LPR, P, VEC>(trow, nv, lir, 0, [&](const int q, const int v, const int w, const bool in, const T y) {
                     if (in)
                     {
                         bool pos;
@@ -729,12 +546,12 @@ __global__ __launch_bounds__(256) void gatv2_bwd_col_kernel(const Gatv2BwdColArg
                         sp[q] = fma(av[v][w], r, sp[q]);
                     }
                 });
-                g2_walk8<T, LPR, P, VEC>(drow, nv, lir, 0, [&](const int q, const int v, const int w, const bool in, const T y) {
+                rg_walk8<T, LPR, P, VEC>(drow, nv, lir, 0, [&](const int q, const int v, const int w, const bool in, const T y) {
                     if (in) dp[q] = fma(y, xs[v][w], dp[q]);
                 });
             }
-            const T dot = g2_reduce8<T, LPR>(sp, lir);
-            const T rp = g2_reduce8<T, LPR>(dp, lir);
+            const T dot = rg_reduce8<T, LPR>(sp, lir);
+            const T rp = rg_reduce8<T, LPR>(dp, lir);
             T prob = (T) 0, ds = (T) 0;
             if (mine < cnt)
             {
@@ -763,13 +580,13 @@ __global__ __launch_bounds__(256) void gatv2_bwd_col_kernel(const Gatv2BwdColArg
             else
             {
                 // (cache hits: the dots read these rows)
-                g2_walk8<T, LPR, P, VEC>(trow, nv, lir, again, [&](const int q, const int v, const int w, const bool, const T y) {
+                rg_walk8<T, LPR, P, VEC>(trow, nv, lir, again, [&](const int q, const int v, const int w, const bool, const T y) {
                     bool pos;
                     (void) g2_lrelu<T>(y, xs[v][w], slope, &pos);
                     const T ag = pos ? av[v][w] : as[v][w];
                     accZ[v][w] = fma(dsu[q], ag, accZ[v][w]);
                 });
-                g2_walk8<T, LPR, P, VEC>(drow, nv, lir, again, [&](const int q, const int v, const int w, const bool, const T y) {
+                rg_walk8<T, LPR, P, VEC>(drow, nv, lir, again, [&](const int q, const int v, const int w, const bool, const T y) {
                     accV[v][w] = fma(pu[q], y, accV[v][w]);
                 });
             }
@@ -779,78 +596,31 @@ __global__ __launch_bounds__(256) void gatv2_bwd_col_kernel(const Gatv2BwdColArg
     for (int v = 0; v < P; v++)
 #pragma unroll
         for (int w = 0; w < VW; w++) accZ[v][w] = g2_add<T>(accZ[v][w], accV[v][w]);
-    g2_store_row<T, LPR, P, VEC>(accZ, dxrow, nv, lir);
+    rg_store_row<T, LPR, P, VEC>(accZ, dxrow, nv, lir);
 }
 
 // ---- launchers ----------------------------------------------------------------------------------------------------------------
-static inline bool g2_aligned(std::initializer_list<const void *> ptrs, std::initializer_list<int64_t> lds, int vw)
-{
-    uintptr_t bits = 0;
-    for (const void *p : ptrs) bits |= (uintptr_t) p;
-    bool ok = bits % 16 == 0;
-    for (int64_t ld : lds) ok = ok && ld % vw == 0;
-    return ok;
-}
-
-// the grid of nrow * heads units, RPB per block; false when it does not fit one launch (before anything is written)
-static inline bool g2_grid(int nrow, int heads, int rpb, dim3 *grid)
-{
-    const int64_t blocks = ((int64_t) nrow * heads + rpb - 1) / rpb;
-    if (blocks > INT32_MAX) return false;
-    *grid = dim3((unsigned) blocks);
-    return true;
-}
-
-// (nv % VW == 0 keeps every head's slice on a 16-byte boundary; the leading dimension of a source that is NULL is not read)
+// Per argument list: which pointers and which leading dimensions decide VEC (nv % VW == 0 keeps every head's slice on a 16-byte
+// boundary; the leading dimension of a source that is NULL is not read), and the kernel family; rg_launch does the rest.
 template <typename T, int LPR, int P>
 static hipError_t launch_gatv2(const Gatv2Args<T> &a, hipStream_t s)
 {
-    constexpr int VW = G2Piece<T>::VW;
-    const bool vec = g2_aligned({a.XT, a.XS0, a.XS1, a.av, a.O}, {a.nv, a.ldXT, a.ldO, a.XS0 ? a.ldXS0 : 0, a.XS1 ? a.ldXS1 : 0}, VW);
-    dim3 grid;
-    if (!g2_grid(a.nrow, a.heads, 256 / LPR, &grid)) return hipErrorInvalidValue;
-    if (a.drop.on)
-    {
-        if (vec) hipLaunchKernelGGL((gatv2_fwd_kernel<T, LPR, P, true, true>), grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((gatv2_fwd_kernel<T, LPR, P, false, true>), grid, dim3(256), 0, s, a);
-    }
-    else if (vec) hipLaunchKernelGGL((gatv2_fwd_kernel<T, LPR, P, true, false>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((gatv2_fwd_kernel<T, LPR, P, false, false>), grid, dim3(256), 0, s, a);
-    return hipGetLastError();
+    return rg_launch<T, LPR>(a, s, {a.XT, a.XS0, a.XS1, a.av, a.O}, {a.nv, a.ldXT, a.ldO, a.XS0 ? a.ldXS0 : 0, a.XS1 ? a.ldXS1 : 0},
+                             [](auto v, auto d) { return gatv2_fwd_kernel<T, LPR, P, decltype(v)::value, decltype(d)::value>; });
 }
 template <typename T, int LPR, int P>
 static hipError_t launch_gatv2(const Gatv2BwdRowArgs<T> &a, hipStream_t s)
 {
-    constexpr int VW = G2Piece<T>::VW;
-    const bool vec = g2_aligned({a.XT, a.XS0, a.XS1, a.av, a.O, a.dO, a.dXT, a.da_part},
-                                {a.nv, a.ldXT, a.ldO, a.lddO, a.lddXT, a.ldda, a.XS0 ? a.ldXS0 : 0, a.XS1 ? a.ldXS1 : 0}, VW);
-    dim3 grid;
-    if (!g2_grid(a.nrow, a.heads, 256 / LPR, &grid)) return hipErrorInvalidValue;
-    if (a.drop.on)
-    {
-        if (vec) hipLaunchKernelGGL((gatv2_bwd_row_kernel<T, LPR, P, true, true>), grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((gatv2_bwd_row_kernel<T, LPR, P, false, true>), grid, dim3(256), 0, s, a);
-    }
-    else if (vec) hipLaunchKernelGGL((gatv2_bwd_row_kernel<T, LPR, P, true, false>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((gatv2_bwd_row_kernel<T, LPR, P, false, false>), grid, dim3(256), 0, s, a);
-    return hipGetLastError();
+    return rg_launch<T, LPR>(a, s, {a.XT, a.XS0, a.XS1, a.av, a.O, a.dO, a.dXT, a.da_part},
+                             {a.nv, a.ldXT, a.ldO, a.lddO, a.lddXT, a.ldda, a.XS0 ? a.ldXS0 : 0, a.XS1 ? a.ldXS1 : 0},
+                             [](auto v, auto d) { return gatv2_bwd_row_kernel<T, LPR, P, decltype(v)::value, decltype(d)::value>; });
 }
 template <typename T, int LPR, int P>
 static hipError_t launch_gatv2(const Gatv2BwdColArgs<T> &a, hipStream_t s)
 {
-    constexpr int VW = G2Piece<T>::VW;
     // (XT and dO are not read when the handle has no nonzero, and may then be NULL)
-    const bool vec = g2_aligned({a.XS, a.XT, a.av, a.dO, a.dXS}, {a.nv, a.ldXS, a.XT ? a.ldXT : 0, a.dO ? a.lddO : 0, a.lddXS}, VW);
-    dim3 grid;
-    if (!g2_grid(a.nrow, a.heads, 256 / LPR, &grid)) return hipErrorInvalidValue;
-    if (a.drop.on)
-    {
-        if (vec) hipLaunchKernelGGL((gatv2_bwd_col_kernel<T, LPR, P, true, true>), grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((gatv2_bwd_col_kernel<T, LPR, P, false, true>), grid, dim3(256), 0, s, a);
-    }
-    else if (vec) hipLaunchKernelGGL((gatv2_bwd_col_kernel<T, LPR, P, true, false>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((gatv2_bwd_col_kernel<T, LPR, P, false, false>), grid, dim3(256), 0, s, a);
-    return hipGetLastError();
+    return rg_launch<T, LPR>(a, s, {a.XS, a.XT, a.av, a.dO, a.dXS}, {a.nv, a.ldXS, a.XT ? a.ldXT : 0, a.dO ? a.lddO : 0, a.lddXS},
+                             [](auto v, auto d) { return gatv2_bwd_col_kernel<T, LPR, P, decltype(v)::value, decltype(d)::value>; });
 }
 
 // The instance, from (dtype, nv) alone (the rule is stated at the top of this file)

@@ -17,22 +17,9 @@
 // count are picked from (dtype, n) alone.  Operands that cannot be read in 16-byte pieces (odd n or ld, unaligned
 // pointers) are read element by element into the SAME assignment.  Hence an entry's bits depend on (dtype, n) and the
 // two rows only: not on alignment, leading dimensions, the source of the Y row, the handle, or the entry's position.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include "kernels.h"
+#include "row_group.h"
 
 namespace crp {
-
-template <typename T> struct Piece;
-template <> struct Piece<double> { typedef double type __attribute__((ext_vector_type(2))); };
-template <> struct Piece<float>  { typedef float type __attribute__((ext_vector_type(4))); };
-
-template <int LPR>
-__device__ __forceinline__ int sd_bcast_i(int v, int j)
-{
-    if constexpr (LPR == 64) return __builtin_amdgcn_readlane(v, j);
-    else return __shfl(v, j, LPR);
-}
 
 // LPR lanes per row, NV 16-byte pieces per lane and column chunk => chunks of TW = LPR * VW * NV columns.
 // NCH > 0: the operands are NCH chunks wide at most and the whole slice of X[i] stays in registers for the row;
@@ -138,7 +125,7 @@ __global__ __launch_bounds__(256) void sddmm_rm_kernel(
 #pragma unroll
             for (int u = 0; u < UNR; u++)
             {
-                const int cj = sd_bcast_i<LPR>(c, min(j + u, cnt - 1));
+                const int cj = rg_bcast_i<LPR>(c, min(j + u, cnt - 1));
                 yrow[u] = (cj >= 0) ? (Y0 + (int64_t) cj * ldY0) : (Y1 + (int64_t) (~cj) * ldY1);
             }
             T part[UNR];

@@ -29,19 +29,12 @@
 // ALIASING.  Exact aliasing is allowed (y == s; ds == dy or ds == y), partial overlap is not.  Every element is read and
 // later written by the same lane.  A row kept in registers is read entirely before its first write; in a longer row every
 // element's last read precedes its own write.  Hence no __restrict__ on the value arrays.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
 #include <algorithm>
-#include "kernels.h"
+#include "row_group.h"
 
 namespace crp {
 
 constexpr int SM_KEEP = 8;                  // values a lane keeps of a register row
-
-__device__ __forceinline__ double sm_exp(double x) { return exp(x); }
-__device__ __forceinline__ float  sm_exp(float x) { return expf(x); }
-template <typename T> __device__ __forceinline__ T sm_ninf() { return -__builtin_huge_val(); }
-template <> __device__ __forceinline__ float sm_ninf<float>() { return -__builtin_huge_valf(); }
 
 template <typename T, int LPR>
 __device__ __forceinline__ T sm_group_max(T m)
@@ -72,7 +65,7 @@ __device__ __forceinline__ void softmax_fwd_rows(const int nrow, const int *__re
 {
     constexpr int A = 64 / LPR, RPB = 256 / LPR;
     const int l = threadIdx.x % LPR;
-    const T ninf = sm_ninf<T>();
+    const T ninf = rg_ninf<T>();
     for (int64_t row = (int64_t) blockIdx.x * RPB + threadIdx.x / LPR; row < nrow; row += (int64_t) gridDim.x * RPB)
     {
         const int p0 = rowptr[row];
@@ -107,7 +100,7 @@ __device__ __forceinline__ void softmax_fwd_rows(const int nrow, const int *__re
             {
                 if (r * LPR < L)                            // (group-uniform; a skipped step would add +0)
                 {
-                    v[r] = sm_exp(v[r] - m);                // past the end: exp(-inf) = +0
+                    v[r] = rg_exp(v[r] - m);                // past the end: exp(-inf) = +0
                     acc[r % A] = acc[r % A] + v[r];
                 }
             }
@@ -137,10 +130,10 @@ __device__ __forceinline__ void softmax_fwd_rows(const int nrow, const int *__re
                 for (int j = 0; j < A; j++)
                 {
                     const int64_t i = base + j * LPR + l;
-                    acc[j] = acc[j] + sm_exp(((i < L) ? sr[i] : ninf) - m);
+                    acc[j] = acc[j] + rg_exp(((i < L) ? sr[i] : ninf) - m);
                 }
             const T sum = sm_group_sum<T, LPR>(acc);
-            for (int64_t i = l; i < L; i += LPR) yr[i] = sm_exp(sr[i] - m) / sum;
+            for (int64_t i = l; i < L; i += LPR) yr[i] = rg_exp(sr[i] - m) / sum;
         }
     }
 }

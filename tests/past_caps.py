@@ -28,7 +28,7 @@ WAVE = 64                             # csrc/scan_sort.h:11
 LONG_GRID = 256                       # csrc/transpose_kernels.hip:236, csrc/permute_kernels.hip:224: min(n_long, 256, budget / ..)
 LONG_BUDGET = 256 << 20               # csrc/transpose_kernels.hip:235, csrc/permute_kernels.hip:223: bytes of scratch per call
 LONG_FULL_GRID_MAX = LONG_BUDGET // (LONG_GRID * 8)        # 131 072: a longer row's slice leaves the budget fewer than 256 slices
-SM_GRID = 2048                        # csrc/softmax_kernels.hip:238  sm_grid: min((nrow + 3) / 4, 2048) workgroups of 256 threads
+SM_GRID = 2048                        # csrc/softmax_kernels.hip:231  sm_grid: min((nrow + 3) / 4, 2048) workgroups of 256 threads
 GATHER_CAP = 65536 * 4                # csrc/hip_api.hip:640 (gather_row_vals_kernel), csrc/row_kernels.hip:537 (comm_mark_kernel):
 #                                       min((nrow + 3) / 4, 65536) blocks of 4 waves, one wave per row
 COUNT_WORDS_CAP = 1024 * 256          # csrc/row_kernels.hip:542 (comm_count_kernel): min(.., 1024) blocks of 256 threads, one word each
