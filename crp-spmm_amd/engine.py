@@ -62,11 +62,17 @@ def _ptr_ld(x, layout, f32=False):
         if isinstance(x, torch.Tensor):
             if x.dtype != (torch.float32 if f32 else torch.float64) or x.dim() != 2:
                 raise TypeError("B and C must be 2-D %s" % name)
+            if x.numel() == 0:          # (as below: a tensor made from an empty numpy array keeps its strides of 0)
+                return x.data_ptr(), max(int(x.stride(0)), int(x.shape[1]), 1), x
             if x.stride(1) != 1:
                 raise ValueError("operand must be contiguous along its fast dimension")
             return x.data_ptr(), x.stride(0), x
     except ImportError:
         pass
+    if isinstance(x, np.ndarray) and x.dtype == np.dtype(name) and x.ndim == 2 and x.size == 0:
+        # a rank without rows: numpy gives an array without elements strides of 0; nothing of it is read (csrc/operand_view.h), and its
+        # leading dimension is its row length
+        return x.ctypes.data, max(int(x.shape[1]), 1), x
     if not isinstance(x, np.ndarray) or x.dtype != np.dtype(name) or x.ndim != 2 or x.strides[1] != isz:
         raise TypeError("B and C must be 2-D %s torch tensors or numpy arrays, contiguous along the fast dimension" % name)
     return x.ctypes.data, x.strides[0] // isz, x
