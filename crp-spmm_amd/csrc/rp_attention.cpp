@@ -5,12 +5,16 @@
 // row and per nonzero).  Only the part kernels and those sizes know; the exchange moves whole rows of K and V either way.  Which
 // device entry point that is, is dtype_calls.h's business (crp::attention, crp::attention_bwd_q, crp::attention_bwd_kv).
 //
-// Data flow of the backward, every piece of which the engine has: the forward exchange of K then V, as the forward attention does it
-// (pack_exchange_run2: K's rows land in the forward receive buffer, V's in the attention's second one); bwd_q on the parts, through
+//
+// Both directions hand two travellers to the schedule of rp_engine_impl.h (pack_exchange_run, packed on the exchange stream): K, whose
+// rows land in the forward receive buffer, then V, whose rows land in the attention's second one, both through the forward send
+// buffer, which is reused in stream order.
+//
+// Data flow of the backward, every piece of which the engine has: that exchange of K then V; bwd_q on the parts, through
 // their row maps and their positions in A_val; the transposed matrices of exec_t (build_transposed) -- bwd_kv on At_rem reads K[c],
 // V[c] from the two receive buffers and writes dK, dV IN PLACE over them (crpspmm_hip.h: dK == K, dV == V is legal), bwd_kv on
-// At_loc writes this rank's dK, dV; then the forward plan run backwards twice, as exec_t does once, each followed by the
-// accumulate into dK, then dV, through the shared send buffer in stream order.
+// At_loc writes this rank's dK, dV; then the forward plan run backwards twice, as exec_t does once (reverse_exchange_rows), each
+// followed by the accumulate into dK, then dV (accumulate_rows), through the shared send buffer in stream order.
 #include "rp_engine_impl.h"
 
 // heads of a multi-head call as the implementations take it: positive and a divisor of glb_n (0, theirs for the single-head calls,
@@ -22,7 +26,7 @@ static int mh_heads(const crp_rp_spmm *e, int heads, const char *what)
     return heads;
 }
 
-// ---- what the forward and the backward share: the second receive buffer and the two-operand exchange ---------------------------------
+// ---- what the forward and the backward share: the second receive buffer ------------------------------------------------------------------
 // first attention call of a dtype: the second receive buffer (rows of x.ld elements, zeroed once: the fp32 rows' pad columns are
 // never written again), and the parts' positions in A_val; blocks
 template <class T>
@@ -40,42 +44,6 @@ static T *attention_recv(crp_rp_spmm *e, const Xchg &x, crp::DevArray<T> &buf, b
 static double *attention_recv(crp_rp_spmm *e, const Xchg &x, const double *) { return attention_recv(e, x, e->at_recv_dev, &e->at_ready64); }
 static float *attention_recv(crp_rp_spmm *e, const Xchg &x, const float *) { return attention_recv(e, x, e->at_recv32_dev, &e->at_ready32); }
 
-// pack_exchange_run (rp_engine.cpp) for two operands partitioned like B: the rows of Kd travel into x.recv, then those of Vd into
-// recv2, both through x.send, which is reused in stream order.  With timing off and a split engine the interior part is enqueued on
-// s first and both packs and both exchanges run beside it on the engine's second stream, from the point of s where the operands
-// are ready; the boundary part follows on s after the second exchange has landed.  Otherwise everything runs on s in sequence and,
-// with timing on, bills to t_pack and t_a2a (t0 is left at the start of the kernels).
-template <class T, class F>
-static void pack_exchange_run2(crp_rp_spmm *e, const Xchg &x, void *recv2, const T *Kd, long long ldKd, const T *Vd, long long ldVd, void *s,
-                               double &t0, F &&product)
-{
-    const bool timing = e->timing != 0;
-    if (timing) { HIP_OK(crp_stream_sync(s)); }
-    t0 = get_wtime_sec();
-    if (e->A_int != nullptr && !timing)
-    {
-        HIP_OK(crp_event_record(e->ev_packed, s));          // (here: the operands are ready)
-        product(e->A_int, 1);
-        HIP_OK(crp_stream_wait_event(e->xstream, e->ev_packed));
-        pack_rows(e, x, Kd, ldKd, e->xstream);
-        exchange_rows(e, x, x.recv, e->xstream);
-        pack_rows(e, x, Vd, ldVd, e->xstream);
-        exchange_rows(e, x, recv2, e->xstream);
-        HIP_OK(crp_event_record(e->ev_landed, e->xstream));
-        HIP_OK(crp_stream_wait_event(s, e->ev_landed));
-        product(e->A_bnd, 2);
-        return;
-    }
-    for (int op = 0; op < 2; op++)
-    {
-        pack_rows(e, x, op == 0 ? Kd : Vd, op == 0 ? ldKd : ldVd, s);
-        lap(e, s, t0, &e->t_pack);
-        if (e->nproc > 1) exchange_rows(e, x, op == 0 ? x.recv : recv2, s);
-        lap(e, s, t0, &e->t_a2a);
-    }
-    run_parts(e, product);
-}
-
 // ---- O = softmax_row(scale (Q K^T)|pattern(A) (+ A's values)) V over this rank's rows of A -------------------------------------------
 template <class T>
 static void attention_impl(crp_rp_spmm *e, int layout, int heads, double scale, int bias, const T *Q, long long ldQ, const T *K, long long ldK,
@@ -83,10 +51,8 @@ static void attention_impl(crp_rp_spmm *e, int layout, int heads, double scale, 
 {
     if (e == NULL) return;
     const size_t nh = heads >= 1 ? (size_t) heads : 1;
-    ASSERT_PRINTF(!e->plan_only, "rp_spmm_attention on a plan-only engine (no device state)\n");
-    ASSERT_PRINTF(layout == 0 || layout == 1, "layout must be 0 or 1\n");
-    ASSERT_PRINTF(bias == 0 || bias == 1, "bias must be 0 or 1\n");
-    ASSERT_PRINTF(scale - scale == 0.0, "scale must be finite\n");
+    check_call(e, "rp_spmm_attention", "layout", layout);
+    check_scores(bias, scale, "scale");
     const double t_begin = get_wtime_sec();
     void *s = stream_;
     const int n = e->glb_n, kb = e->loc_B_nrow, m = e->A_nrow;
@@ -96,7 +62,6 @@ static void attention_impl(crp_rp_spmm *e, int layout, int heads, double scale, 
     double t0;
 
     const bool Q_on_dev = on_device(Q), K_on_dev = on_device(K), V_on_dev = on_device(V), O_on_dev = on_device(O);
-    const bool lse_host = lse != NULL && m > 0 && !on_device(lse), p_host = p_out != NULL && nnz > 0 && !on_device(p_out);
 
     // ---- operands as device-resident row-major views: K takes B's buffers and the forward exchange, O takes C's
     const Xchg x = exchange_of(e, K);
@@ -105,23 +70,20 @@ static void attention_impl(crp_rp_spmm *e, int layout, int heads, double scale, 
     const crp::InView<T> Vv = crp::operand_in(layout, V, ldV, kb, n, V_on_dev, e->V_stage, e->V_rm, s);
     const crp::InView<T> Qv = crp::operand_in(layout, Q, ldQ, m, n, Q_on_dev, e->Q_stage, e->Q_rm, s);
     const crp::OutView<T> Ov = crp::operand_out(layout, O, ldO, m, n, O_on_dev, e->C_stage, e->C_rm);
-    T *lsed = lse_host ? e->at_lse.grow<T>((size_t) m * nh) : lse;
-    T *pd = p_host ? e->sd_out.grow<T>(nnz * nh) : p_out;
+    const HostVec<T> lsev = host_vec(lse, lse != NULL ? (size_t) m * nh : 0, e->at_lse);
+    const HostVec<T> pv = host_vec(p_out, p_out != NULL ? nnz * nh : 0, e->sd_out);
 
     // ---- pack and exchange K, then V; the kernels: the parts of a split engine write O and lse through their row maps and p_out
     // through their positions in A_val
-    pack_exchange_run2(e, x, recv2, Kv.p, Kv.ld, Vv.p, Vv.ld, s, t0, [&](crp_csr_dev_p A, int part) {
+    const Traveller<T> travellers[] = {{x, Kv.p, Kv.ld, x.recv}, {x, Vv.p, Vv.ld, recv2}};
+    pack_exchange_run(e, s, t0, PACK_ON_EXCHANGE, travellers, [&](crp_csr_dev_p A, int part) {
         if (n == 0 || crp_csr_dev_nrow(A) == 0) return;
-        const int *pos = part == 1 ? e->sd_int_pos.get() : (part == 2 ? e->sd_bnd_pos.get() : nullptr);
         HIP_OK(crp::attention(A, heads, d, scale, bias, Qv.p, Qv.ld, Kv.p, Kv.ld, (const T *) x.recv, x.ld, Vv.p, Vv.ld, (const T *) recv2, x.ld,
-                              Ov.p, Ov.ld, lsed, pd, pos, s));
+                              Ov.p, Ov.ld, lsev.dev, pv.dev, part_positions(e, part), s));
     });
-    if (lse_host) HIP_OK(crp_dev_memcpy(lse, lsed, (size_t) m * nh * sizeof(T), 1, s));
-    if (p_host) HIP_OK(crp_dev_memcpy(p_out, pd, nnz * nh * sizeof(T), 1, s));
-    const bool synced = crp::finish(Ov, s, [&] { lap(e, s, t0, &e->t_spmm); });
-    complete(e, s, synced, lse_host || p_host || !Q_on_dev || !K_on_dev || !V_on_dev || timing);
-    e->t_exec += get_wtime_sec() - t_begin;
-    e->n_exec++;
+    lsev.download(s);
+    pv.download(s);
+    finish_call(e, Ov, s, t0, lsev.staged || pv.staged || !Q_on_dev || !K_on_dev || !V_on_dev || timing, t_begin);
 }
 
 // ---- the backward ---------------------------------------------------------------------------------------------------------------------
@@ -143,9 +105,8 @@ static void attention_bwd_impl(crp_rp_spmm *e, int heads, double scale, int bias
 {
     if (e == NULL) return;
     const size_t nh = heads >= 1 ? (size_t) heads : 1;
-    ASSERT_PRINTF(!e->plan_only, "rp_spmm_attention_bwd on a plan-only engine (no device state)\n");
-    ASSERT_PRINTF(bias == 0 || bias == 1, "bias must be 0 or 1\n");
-    ASSERT_PRINTF(scale - scale == 0.0, "scale must be finite\n");
+    check_call(e, "rp_spmm_attention_bwd");
+    check_scores(bias, scale, "scale");
     const int n = e->glb_n, kb = e->loc_B_nrow, m = e->A_nrow;
     const int d = n / (int) nh;                         // one head's width, to which the cap applies
     ASSERT_PRINTF(d <= 64 * 64 / (int) sizeof(T), "rp_spmm_attention_bwd: %d columns pass the fused backward's cap (%d)\n", d,
@@ -179,27 +140,17 @@ static void attention_bwd_impl(crp_rp_spmm *e, int heads, double scale, int bias
     }
 
     // ---- K then V travel as in the forward; the row side on the parts
-    pack_exchange_run2(e, x, recv2, K, ldK, V, ldV, s, t0, [&](crp_csr_dev_p A, int part) {
+    const Traveller<T> travellers[] = {{x, K, ldK, x.recv}, {x, V, ldV, recv2}};
+    pack_exchange_run(e, s, t0, PACK_ON_EXCHANGE, travellers, [&](crp_csr_dev_p A, int part) {
         if (crp_csr_dev_nrow(A) == 0) return;
-        const int *pos = part == 1 ? e->sd_int_pos.get() : (part == 2 ? e->sd_bnd_pos.get() : nullptr);
         HIP_OK(crp::attention_bwd_q(A, heads, d, scale, bias, Q, ldQ, K, ldK, (const T *) x.recv, x.ld, V, ldV, (const T *) recv2, x.ld, O, ldO,
-                                    dO, lddO, lse, dQ, lddQ, delta, ds_out, pos, s));
+                                    dO, lddO, lse, dQ, lddQ, delta, ds_out, part_positions(e, part), s));
     });
     lap(e, s, t0, &e->t_spmm);
 
     // ---- the column side: the rows owed to peers in place over the received K and V rows, this rank's own directly
     auto kv = [&](crp_csr_dev_p At, const T *Kr, long long ldKr, const T *Vr, long long ldVr, T *dKr, long long lddKr, T *dVr, long long lddVr) {
         HIP_OK(crp::attention_bwd_kv(At, heads, d, scale, bias, Kr, ldKr, Vr, ldVr, Q, ldQ, dO, lddO, lse, delta, dKr, lddKr, dVr, lddVr, s));
-    };
-    auto reverse_exchange = [&](const void *from, void *xs) {
-        const double tx0 = get_wtime_sec();
-        e->comm->alltoallv_dev_f64(e->comm->ctx, (const double *) from, x.rc, x.rd, (double *) x.send, x.sc, x.sd, xs);
-        e->t_a2a_host += get_wtime_sec() - tx0;
-    };
-    auto accumulate = [&](T *dst, long long ldd) {
-        if (e->n_acc == 0) return;
-        const int *acc_row = e->acc_dev, *acc_ptr = acc_row + e->n_acc, *acc_pos = acc_ptr + e->n_acc + 1;
-        HIP_OK(crp::scatter_add(e->n_acc, n, acc_row, acc_ptr, acc_pos, (const T *) x.send, x.ld, dst, ldd, s));
     };
     if (e->At_rem != nullptr) kv(e->At_rem, (const T *) x.recv, x.ld, recv2, x.ld, (T *) x.recv, x.ld, recv2, x.ld);
     if (e->nproc > 1 && !timing)
@@ -209,12 +160,12 @@ static void attention_bwd_impl(crp_rp_spmm *e, int heads, double scale, int bias
         HIP_OK(crp_event_record(e->ev_packed, s));
         if (kb > 0) kv(e->At_loc, K, ldK, V, ldV, dK, lddK, dV, lddV);
         HIP_OK(crp_stream_wait_event(e->xstream, e->ev_packed));
-        reverse_exchange(x.recv, e->xstream);
+        reverse_exchange_rows(e, x, x.recv, e->xstream);
         HIP_OK(crp_event_record(e->ev_landed, e->xstream));
         HIP_OK(crp_stream_wait_event(s, e->ev_landed));
-        accumulate(dK, lddK);
-        reverse_exchange(recv2, s);
-        accumulate(dV, lddV);
+        accumulate_rows(e, x, dK, lddK, s);
+        reverse_exchange_rows(e, x, recv2, s);
+        accumulate_rows(e, x, dV, lddV, s);
     }
     else
     {
@@ -223,15 +174,13 @@ static void attention_bwd_impl(crp_rp_spmm *e, int heads, double scale, int bias
         lap(e, s, t0, &e->t_spmm);
         for (int op = 0; op < 2; op++)
         {
-            if (e->nproc > 1) reverse_exchange(op == 0 ? x.recv : (void *) recv2, s);
+            if (e->nproc > 1) reverse_exchange_rows(e, x, op == 0 ? x.recv : (void *) recv2, s);
             lap(e, s, t0, &e->t_a2a);
-            accumulate(op == 0 ? dK : dV, op == 0 ? lddK : lddV);
+            accumulate_rows(e, x, op == 0 ? dK : dV, op == 0 ? lddK : lddV, s);
             lap(e, s, t0, &e->t_unpack);
         }
     }
-    complete(e, s, false, timing);
-    e->t_exec += get_wtime_sec() - t_begin;
-    e->n_exec++;
+    close_call(e, s, false, timing, t_begin);
 }
 
 extern "C" {

@@ -7,8 +7,10 @@
 //         communicator's alltoall(v); A is uploaded once with a two-source column
 //         index (local B row | row of the receive buffer), so exec never copies
 //         locally owned B rows and never unpacks.
-//   exec  (reference :212-422): gather kernel -> device all-to-all -> SpMM kernel
-//         on one stream; no allocation, no sparse-handle creation.
+//   exec  (reference :212-422): gather kernel -> device all-to-all -> SpMM kernel;
+//         no allocation, no sparse-handle creation.  Exec and sddmm hand their one
+//         travelling operand to the schedule all calls share (pack_exchange_run,
+//         rp_engine_impl.h); exec_t runs the plan backwards with that file's helpers.
 // Public plan fields keep the reference's meaning (crp_rp_plan_view_t).
 #include "rp_engine_impl.h"
 
@@ -273,46 +275,12 @@ static int spmm(crp_rp_spmm *e, crp_csr_dev_p A, int n, const float *B0, long lo
     return crp_spmm_csr_f32(A, n, B0, ldB0, B1, ldB1, C, ldC, e->variant_f32, s);
 }
 
-// The half that exec and sddmm share: pack the rows of the row-major device operand Bd that other ranks asked for, exchange them
-// (the received rows land in x.recv in final order), and run the local kernels.  With timing off and a split engine the interior
-// part is enqueued on s beside the exchange, which runs on the engine's second stream, and the boundary part after the rows have
-// landed; with timing on the phases run in sequence and bill to t_pack and t_a2a (t0 is left at the start of the kernels, which
-// the caller bills).
-template <class T, class F>
-static void pack_exchange_run(crp_rp_spmm *e, const Xchg &x, const T *Bd, long long ldBd, void *s, double &t0, F &&product)
-{
-    const bool timing = e->timing != 0;
-    if (timing) { HIP_OK(crp_stream_sync(s)); }
-    t0 = get_wtime_sec();
-    pack_rows(e, x, Bd, ldBd, s);
-    lap(e, s, t0, &e->t_pack);
-    if (e->A_int != nullptr && !timing)
-    {
-        // The exchange runs on its own stream beside the interior rows' product.  The product is ENQUEUED FIRST: it does not
-        // depend on the exchange, and issuing a group of sends / receives can hold the host for a while (a non-blocking RCCL
-        // communicator is polled until the group is on the stream) -- with the exchange first, the whole interior product
-        // (0.06 - 0.2 ms per GPU at pwtk size) could have passed before its launch was even issued.
-        HIP_OK(crp_event_record(e->ev_packed, s));
-        product(e->A_int, 1);
-        HIP_OK(crp_stream_wait_event(e->xstream, e->ev_packed));
-        exchange_rows(e, x, x.recv, e->xstream);
-        HIP_OK(crp_event_record(e->ev_landed, e->xstream));
-        HIP_OK(crp_stream_wait_event(s, e->ev_landed));
-        product(e->A_bnd, 2);
-        return;
-    }
-    if (e->nproc > 1) exchange_rows(e, x, x.recv, s);
-    lap(e, s, t0, &e->t_a2a);
-    run_parts(e, product);
-}
-
-// C := A * B on this rank, one dtype (crp_rp_spmm_exec_ex / crp_rp_spmm_exec_f32_ex)
+// C := A * B on this rank, one dtype (crp_rp_spmm_exec_ex / crp_rp_spmm_exec_f32_ex): B travels, packed on the caller's stream
 template <class T>
 static void exec_impl(crp_rp_spmm *e, int BC_layout, const T *B, long long ldB, T *C, long long ldC, void *stream_)
 {
     if (e == NULL) return;
-    ASSERT_PRINTF(!e->plan_only, "rp_spmm_exec on a plan-only engine (no device state)\n");
-    ASSERT_PRINTF(BC_layout == 0 || BC_layout == 1, "BC_layout must be 0 or 1\n");
+    check_call(e, "rp_spmm_exec", "BC_layout", BC_layout);
     const double t_begin = get_wtime_sec();
     void *s = stream_;   // taken literally: NULL is the HIP null stream (torch's default stream)
     const int n = e->glb_n, kb = e->loc_B_nrow, m = e->A_nrow;
@@ -327,11 +295,10 @@ static void exec_impl(crp_rp_spmm *e, int BC_layout, const T *B, long long ldB, 
     const crp::OutView<T> Cv = crp::operand_out(BC_layout, C, ldC, m, n, C_on_dev, e->C_stage, e->C_rm);
 
     // ---- 1 - 3. pack, exchange, local SpMM
-    pack_exchange_run(e, x, Bv.p, Bv.ld, s, t0, [&](crp_csr_dev_p A, int) { HIP_OK(spmm(e, A, n, Bv.p, Bv.ld, (const T *) x.recv, x.ld, Cv.p, Cv.ld, s)); });
-    const bool synced = crp::finish(Cv, s, [&] { lap(e, s, t0, &e->t_spmm); });
-    complete(e, s, synced, !B_on_dev || timing);
-    e->t_exec += get_wtime_sec() - t_begin;
-    e->n_exec++;
+    const Traveller<T> travellers[] = {{x, Bv.p, Bv.ld, x.recv}};
+    pack_exchange_run(e, s, t0, PACK_ON_CALLER, travellers,
+                      [&](crp_csr_dev_p A, int) { HIP_OK(spmm(e, A, n, Bv.p, Bv.ld, (const T *) x.recv, x.ld, Cv.p, Cv.ld, s)); });
+    finish_call(e, Cv, s, t0, !B_on_dev || timing, t_begin);
 }
 
 // ---- out[p] = < X[row(p)], Y[col(p)] > over this rank's rows of A (crp_rp_spmm_sddmm_ex / _f32_ex); the helpers: rp_engine_impl.h
@@ -339,8 +306,7 @@ template <class T>
 static void sddmm_impl(crp_rp_spmm *e, int layout, const T *X, long long ldX, const T *Y, long long ldY, T *out, int mode, void *stream_)
 {
     if (e == NULL) return;
-    ASSERT_PRINTF(!e->plan_only, "rp_spmm_sddmm on a plan-only engine (no device state)\n");
-    ASSERT_PRINTF(layout == 0 || layout == 1, "layout must be 0 or 1\n");
+    check_call(e, "rp_spmm_sddmm", "layout", layout);
     ASSERT_PRINTF(mode == 0 || mode == 1, "mode must be 0 or 1\n");
     const double t_begin = get_wtime_sec();
     if (!e->sd_built)
@@ -354,30 +320,25 @@ static void sddmm_impl(crp_rp_spmm *e, int layout, const T *X, long long ldX, co
     const bool timing = e->timing != 0;
     double t0;
 
-    const bool X_on_dev = on_device(X), Y_on_dev = on_device(Y), out_on_dev = on_device(out);
+    const bool X_on_dev = on_device(X), Y_on_dev = on_device(Y);
 
     // ---- operands as device-resident row-major views: Y takes B's buffers, X takes C's
     const Xchg x = exchange_of(e, Y);
     const crp::InView<T> Yv = crp::operand_in(layout, Y, ldY, kb, n, Y_on_dev, e->B_stage, e->B_rm, s);
     const crp::InView<T> Xv = crp::operand_in(layout, X, ldX, m, n, X_on_dev, e->C_stage, e->C_rm, s);
-    T *outd = out;
-    if (!out_on_dev && nnz > 0) outd = e->sd_out.grow<T>(nnz);
+    const HostVec<T> outv = host_vec(out, nnz, e->sd_out);
 
-    if (n == 0 && nnz > 0) HIP_OK(crp_dev_memset(outd, 0, nnz * sizeof(T), s));      // empty dots
+    if (n == 0 && nnz > 0) HIP_OK(crp_dev_memset(outv.dev, 0, nnz * sizeof(T), s));      // empty dots
 
-    // ---- pack Y, exchange, the kernels: the parts of a split engine write through their positions in A_val
-    pack_exchange_run(e, x, Yv.p, Yv.ld, s, t0, [&](crp_csr_dev_p A, int part) {
+    // ---- pack Y on the caller's stream, exchange, the kernels: the parts of a split engine write through their positions in A_val
+    const Traveller<T> travellers[] = {{x, Yv.p, Yv.ld, x.recv}};
+    pack_exchange_run(e, s, t0, PACK_ON_CALLER, travellers, [&](crp_csr_dev_p A, int part) {
         if (n == 0 || crp_csr_dev_nnz(A) == 0) return;
-        const int *pos = part == 1 ? e->sd_int_pos.get() : (part == 2 ? e->sd_bnd_pos.get() : nullptr);
-        HIP_OK(crp::sddmm(A, n, Xv.p, Xv.ld, Yv.p, Yv.ld, (const T *) x.recv, x.ld, outd, pos, mode, s));
+        HIP_OK(crp::sddmm(A, n, Xv.p, Xv.ld, Yv.p, Yv.ld, (const T *) x.recv, x.ld, outv.dev, part_positions(e, part), mode, s));
     });
     lap(e, s, t0, &e->t_spmm);
-
-    const bool download = !out_on_dev && nnz > 0;
-    if (download) HIP_OK(crp_dev_memcpy(out, outd, nnz * sizeof(T), 1, s));
-    complete(e, s, false, download || !X_on_dev || !Y_on_dev || timing);
-    e->t_exec += get_wtime_sec() - t_begin;
-    e->n_exec++;
+    outv.download(s);
+    close_call(e, s, false, outv.staged || !X_on_dev || !Y_on_dev || timing, t_begin);
 }
 
 // ---- C := A^T * B (crp_rp_spmm_exec_t_ex); build_transposed: rp_engine_impl.h
@@ -400,8 +361,7 @@ template <class T>
 static void exec_t_impl(crp_rp_spmm *e, int BC_layout, const T *B, long long ldB, T *C, long long ldC, void *stream_)
 {
     if (e == NULL) return;
-    ASSERT_PRINTF(!e->plan_only, "rp_spmm_exec_t on a plan-only engine (no device state)\n");
-    ASSERT_PRINTF(BC_layout == 0 || BC_layout == 1, "BC_layout must be 0 or 1\n");
+    check_call(e, "rp_spmm_exec_t", "BC_layout", BC_layout);
     const double t_begin = get_wtime_sec();
     if (!e->t_built) build_transposed(e);
     void *s = stream_;
@@ -417,18 +377,7 @@ static void exec_t_impl(crp_rp_spmm *e, int BC_layout, const T *B, long long ldB
     const crp::InView<T> Bv = crp::operand_in(BC_layout, B, ldB, mb, n, B_on_dev, e->B_stage, e->B_rm, s);
     const crp::OutView<T> Cv = crp::operand_out(BC_layout, C, ldC, mc, n, C_on_dev, e->C_stage, e->C_rm);
 
-    auto reverse_exchange = [&](void *xs) {
-        // the forward plan backwards: what this rank receives there it sends here, from the receive into the send buffer
-        const double tx0 = get_wtime_sec();
-        e->comm->alltoallv_dev_f64(e->comm->ctx, (const double *) x.recv, x.rc, x.rd, (double *) x.send, x.sc, x.sd, xs);
-        e->t_a2a_host += get_wtime_sec() - tx0;
-    };
     auto product = [&](crp_csr_dev_p A, T *out, long long ldo) { HIP_OK(spmm(e, A, n, Bv.p, Bv.ld, (const T *) NULL, 0, out, ldo, s)); };
-    auto accumulate = [&]() {
-        if (e->n_acc == 0 || n == 0) return;
-        const int *acc_row = e->acc_dev, *acc_ptr = acc_row + e->n_acc, *acc_pos = acc_ptr + e->n_acc + 1;
-        HIP_OK(crp::scatter_add(e->n_acc, n, acc_row, acc_ptr, acc_pos, (const T *) x.send, x.ld, Cv.p, Cv.ld, s));
-    };
 
     if (timing) { HIP_OK(crp_stream_sync(s)); }
     t0 = get_wtime_sec();
@@ -439,26 +388,23 @@ static void exec_t_impl(crp_rp_spmm *e, int BC_layout, const T *B, long long ldB
         HIP_OK(crp_event_record(e->ev_packed, s));
         product(e->At_loc, Cv.p, Cv.ld);
         HIP_OK(crp_stream_wait_event(e->xstream, e->ev_packed));
-        reverse_exchange(e->xstream);
+        reverse_exchange_rows(e, x, x.recv, e->xstream);
         HIP_OK(crp_event_record(e->ev_landed, e->xstream));
         HIP_OK(crp_stream_wait_event(s, e->ev_landed));
-        accumulate();
+        accumulate_rows(e, x, Cv.p, Cv.ld, s);
     }
     else
     {
         if (e->At_rem != nullptr) product(e->At_rem, (T *) x.recv, x.ld);
         lap(e, s, t0, &e->t_spmm);
-        if (e->nproc > 1) reverse_exchange(s);
+        if (e->nproc > 1) reverse_exchange_rows(e, x, x.recv, s);
         lap(e, s, t0, &e->t_a2a);
         product(e->At_loc, Cv.p, Cv.ld);
         lap(e, s, t0, &e->t_spmm);
-        accumulate();
+        accumulate_rows(e, x, Cv.p, Cv.ld, s);
         lap(e, s, t0, &e->t_unpack);
     }
-    const bool synced = crp::finish(Cv, s, [&] { lap(e, s, t0, &e->t_spmm); });
-    complete(e, s, synced, !B_on_dev || timing);
-    e->t_exec += get_wtime_sec() - t_begin;
-    e->n_exec++;
+    finish_call(e, Cv, s, t0, !B_on_dev || timing, t_begin);
 }
 
 extern "C" {
@@ -629,7 +575,7 @@ static void build_dev_update(crp_rp_spmm *e)
 void crp_rp_spmm_update_values_dev(crp_rp_spmm_p e, const void *A_val_dev, int f32, void *stream)
 {
     if (e == NULL) return;
-    ASSERT_PRINTF(!e->plan_only, "rp_spmm_update_values_dev on a plan-only engine (no device state)\n");
+    check_call(e, "rp_spmm_update_values_dev");
     ASSERT_PRINTF(f32 == 0 || f32 == 1, "rp_spmm_update_values_dev: f32 must be 0 or 1\n");
     const size_t nnz = e->A_val.size();
     if (nnz == 0) return;

@@ -1,6 +1,12 @@
-// rp_engine_impl.h -- the row engine's state (struct crp_rp_spmm) and the helpers that its translation units share: rp_engine.cpp
-// (init, exec, exec_t, sddmm, value updates), rp_attention.cpp (the fused attention, forward and backward, single- and
-// multi-head) and rp_gat.cpp (the fused GAT and GATv2 attention, forward).  Internal: nothing outside csrc/ includes it.
+// rp_engine_impl.h -- the row engine's state (struct crp_rp_spmm) and what its translation units share: rp_engine.cpp (init, exec,
+// exec_t, sddmm, value updates), rp_attention.cpp (the fused attention, forward and backward, single- and multi-head) and
+// rp_gat.cpp (the fused GAT and GATv2 attention, forward).  Internal: nothing outside csrc/ includes it.
+//
+// Every call that moves rows of a dense operand to the ranks that asked for them runs ONE schedule, pack_exchange_run below: the
+// call names its travelling operands (Traveller: an Xchg, the source, the receive buffer), says where they are packed (PackOn) and
+// gives the part kernel as product(A, part).  Around it, one definition each: the opening checks (check_call, check_scores), a
+// part's positions array (part_positions), a host result vector staged on the device (HostVec), the way back of exec_t and the
+// attention backward (reverse_exchange_rows, accumulate_rows) and the end of a call (finish_call, close_call).
 #ifndef CRP_RP_ENGINE_IMPL_H
 #define CRP_RP_ENGINE_IMPL_H
 
@@ -16,14 +22,25 @@
 #include "par.h"
 #include <algorithm>
 
-// The narrow exchange of the GAT attention's er (rp_gat.cpp): rows of ld elements -- `heads` of them, fp32 rows padded to whole
-// 8-byte words -- through buffers of their own, with the forward plan's per-peer counts and displacements taken by rows
+// One exchange of packed rows over the forward plan's peers: `cols` elements of every row travel, in rows of ld elements (a
+// whole number of 8-byte words) from send to recv.  A view: the engine owns the buffers and the count vectors.
+struct Xchg
+{
+    void *send, *recv;
+    int cols;
+    long long ld;
+    const long long *sc, *sd, *rc, *rd;           // counts / displacements in 8-byte words, as alltoallv_dev_f64 takes them
+};
+
+// The storage of the GAT attention's narrow exchange of er (rp_gat.cpp): rows of `heads` elements, fp32 rows padded to whole 8-byte
+// words, through buffers of their own
 template <class T> struct GatXchg
 {
     int heads = 0;                               // 0: not set up
     long long ld = 0;
-    std::vector<long long> sc, sd, rc, rd;       // in 8-byte words, as alltoallv_dev_f64 takes them
+    std::vector<long long> sc, sd, rc, rd;
     crp::DevArray<T> recv, send;
+    Xchg view() { return Xchg{send.get(), recv.get(), heads, ld, sc.data(), sd.data(), rc.data(), rd.data()}; }
 };
 
 struct crp_rp_spmm
@@ -127,40 +144,40 @@ struct crp_rp_spmm
 // arithmetic on the payload, so crp_comm_t stays as it is.
 static inline long long ld32_of(int n) { return ((long long) n + 3) / 4 * 4; }
 
-struct Xchg
-{
-    void *send, *recv;                            // packed rows of ld elements
-    long long ld;
-    const long long *sc, *sd, *rc, *rd;           // counts / displacements in 8-byte words, as alltoallv_dev_f64 takes them
-};
-
 static inline Xchg exchange_of(crp_rp_spmm *e, const double *)
 {
-    return Xchg{e->sendbuf_dev, e->recvbuf_dev, (long long) e->glb_n, e->rB_scnts.data(), e->rB_sdispls.data(),
+    return Xchg{e->sendbuf_dev, e->recvbuf_dev, e->glb_n, (long long) e->glb_n, e->rB_scnts.data(), e->rB_sdispls.data(),
                 e->rB_rcnts.data(), e->rB_rdispls.data()};
 }
 
-// first fp32 exec: word counts (rows * ld32 / 2) and the fp32 exchange buffers
+// the forward plan's per-peer counts and displacements (rB_*: rows * glb_n elements) for rows of `words` 8-byte words
+static inline void plan_words(const crp_rp_spmm *e, long long words, std::vector<long long> &sc, std::vector<long long> &sd,
+                              std::vector<long long> &rc, std::vector<long long> &rd)
+{
+    const long long n = e->glb_n;
+    auto by_rows = [&](const std::vector<long long> &v, std::vector<long long> &out) {
+        out.resize(v.size());
+        for (size_t q = 0; q < v.size(); q++) out[q] = n > 0 ? v[q] / n * words : 0;
+    };
+    by_rows(e->rB_scnts, sc);
+    by_rows(e->rB_sdispls, sd);
+    by_rows(e->rB_rcnts, rc);
+    by_rows(e->rB_rdispls, rd);
+}
+
+// first fp32 exec: word counts (rows of ld32 / 2 words) and the fp32 exchange buffers
 static inline Xchg exchange_of(crp_rp_spmm *e, const float *)
 {
     const long long ld = ld32_of(e->glb_n);
     if (!e->x32_ready)
     {
-        const long long n = e->glb_n;     // rB_* hold rows * glb_n elements
-        auto words = [&](const std::vector<long long> &v, std::vector<long long> &out) {
-            out.resize(v.size());
-            for (size_t q = 0; q < v.size(); q++) out[q] = n > 0 ? v[q] / n * ld / 2 : 0;
-        };
-        words(e->rB_scnts, e->x32_scnts);
-        words(e->rB_sdispls, e->x32_sdispls);
-        words(e->rB_rcnts, e->x32_rcnts);
-        words(e->rB_rdispls, e->x32_rdispls);
+        plan_words(e, ld / 2, e->x32_scnts, e->x32_sdispls, e->x32_rcnts, e->x32_rdispls);
         // the pad columns are zeroed here and never written again: no uninitialised byte crosses a link
         if (e->n_send_rows > 0 && ld > 0) e->sendbuf32_dev.zeroed((size_t) e->n_send_rows * (size_t) ld);
         if (e->n_recv_rows > 0 && ld > 0) e->recvbuf32_dev.zeroed((size_t) e->n_recv_rows * (size_t) ld);
         e->x32_ready = true;
     }
-    return Xchg{e->sendbuf32_dev, e->recvbuf32_dev, ld, e->x32_scnts.data(), e->x32_sdispls.data(), e->x32_rcnts.data(),
+    return Xchg{e->sendbuf32_dev, e->recvbuf32_dev, e->glb_n, ld, e->x32_scnts.data(), e->x32_sdispls.data(), e->x32_rcnts.data(),
                 e->x32_rdispls.data()};
 }
 
@@ -193,22 +210,6 @@ static inline void complete(crp_rp_spmm *e, void *s, bool synced, bool must_sync
     e->exec_pending = true;
 }
 
-// ---- the pieces pack_exchange_run (rp_engine.cpp) and pack_exchange_run2 (rp_attention.cpp) share ---------------------------------------------------------------------
-// pack the rows of the row-major device operand Bd that other ranks asked for into x.send, on st (reference :232-262)
-template <class T>
-static inline void pack_rows(crp_rp_spmm *e, const Xchg &x, const T *Bd, long long ldBd, void *st)
-{
-    if (e->n_send_rows > 0 && e->glb_n > 0) HIP_OK(crp::gather((int) e->n_send_rows, e->glb_n, e->sridxs_dev, Bd, ldBd, (T *) x.send, x.ld, st));
-}
-
-// the exchange call on st (reference :275-309), its host time billed to t_a2a_host; the received rows land in recv in final order
-static inline void exchange_rows(crp_rp_spmm *e, const Xchg &x, void *recv, void *st)
-{
-    const double tx0 = get_wtime_sec();
-    e->comm->alltoallv_dev_f64(e->comm->ctx, (const double *) x.send, x.sc, x.sd, (double *) recv, x.rc, x.rd, st);
-    e->t_a2a_host += get_wtime_sec() - tx0;
-}
-
 // with timing on: wait for s and bill the time since t0 to *bucket
 static inline void lap(crp_rp_spmm *e, void *s, double &t0, double *bucket)
 {
@@ -217,6 +218,93 @@ static inline void lap(crp_rp_spmm *e, void *s, double &t0, double *bucket)
     const double t1 = get_wtime_sec();
     *bucket += t1 - t0;
     t0 = t1;
+}
+
+// ---- the opening and the end of a call ----------------------------------------------------------------------------------------------
+// what every call refuses first; layout_name: what the call's ABI names its layout argument (nullptr: it takes none)
+static inline void check_call(const crp_rp_spmm *e, const char *what, const char *layout_name = nullptr, int layout = 0)
+{
+    ASSERT_PRINTF(!e->plan_only, "%s on a plan-only engine (no device state)\n", what);
+    ASSERT_PRINTF(layout_name == nullptr || layout == 0 || layout == 1, "%s must be 0 or 1\n", layout_name);
+}
+// ... and the attention family after it: bias, and the scalar of its scores (scale, slope)
+static inline void check_scores(int bias, double scalar, const char *scalar_name)
+{
+    ASSERT_PRINTF(bias == 0 || bias == 1, "bias must be 0 or 1\n");
+    ASSERT_PRINTF(scalar - scalar == 0.0, "%s must be finite\n", scalar_name);
+}
+
+// The end of a call: complete() unless the stream was synchronised already, then the call's host time and count.
+static inline void close_call(crp_rp_spmm *e, void *s, bool synced, bool must_sync, double t_begin)
+{
+    complete(e, s, synced, must_sync);
+    e->t_exec += get_wtime_sec() - t_begin;
+    e->n_exec++;
+}
+
+// ... of a call with a dense result: the result back in the caller's layout and memory first, the kernels billed to t_spmm between
+// the transpose and the copy to the host
+template <class T>
+static inline void finish_call(crp_rp_spmm *e, const crp::OutView<T> &v, void *s, double &t0, bool must_sync, double t_begin)
+{
+    const bool synced = crp::finish(v, s, [&] { lap(e, s, t0, &e->t_spmm); });
+    close_call(e, s, synced, must_sync, t_begin);
+}
+
+// ---- a result vector of the call's (lse, p_out, sddmm's out): n entries at p, on the host or on the device ------------------------------
+// A host vector is computed in `scratch` on the device and downloaded after the kernels; the call then has to wait for its stream.
+template <class T> struct HostVec
+{
+    T *host, *dev;        // dev: where the kernels write
+    size_t n;
+    bool staged;
+    void download(void *s) const { if (staged) HIP_OK(crp_dev_memcpy(host, dev, n * sizeof(T), 1, s)); }
+};
+// (n == 0: the caller did not ask for it, or it has no entries -- the pointer passes through, nothing is staged)
+template <class T>
+static inline HostVec<T> host_vec(T *p, size_t n, crp::DevScratch &scratch)
+{
+    const bool staged = n > 0 && !on_device(p);
+    return HostVec<T>{p, staged ? scratch.grow<T>(n) : p, n, staged};
+}
+
+// ---- the schedule: pack, exchange, and the part kernels beside or after them ---------------------------------------------------------------
+// One operand on its way to the ranks that asked for its rows: x.cols columns of the row-major device operand src (leading dimension
+// ld) are packed into x.send and land in recv in final order (x.recv, or a buffer of the same shape: several operands may share x)
+template <class T> struct Traveller
+{
+    Xchg x;
+    const T *src;
+    long long ld;
+    void *recv;
+};
+
+// Where the overlapped path packs.  ON_CALLER: on the caller's stream, ahead of ev_packed, so the exchange stream starts with
+// packed rows (exec, sddmm; one traveller only: the send buffer is not reused).  ON_EXCHANGE: on the exchange stream behind the
+// ev_packed wait, every traveller's pack in front of its exchange, so travellers may share a send buffer in stream order (the
+// attention family).  The two are as measured and not interchangeable without measuring again.
+enum PackOn { PACK_ON_CALLER, PACK_ON_EXCHANGE };
+
+// pack the rows of t.src that other ranks asked for into t.x.send, on st (reference :232-262)
+template <class T>
+static inline void pack_rows(crp_rp_spmm *e, const Traveller<T> &t, void *st)
+{
+    if (e->n_send_rows > 0 && t.x.cols > 0)
+        HIP_OK(crp::gather((int) e->n_send_rows, t.x.cols, e->sridxs_dev, t.src, t.ld, (T *) t.x.send, t.x.ld, st));
+}
+
+// the exchange call on st (reference :275-309), its host time billed to t_a2a_host: x's counts, from -> to
+static inline void exchange(crp_rp_spmm *e, const void *from, const long long *fc, const long long *fd, void *to, const long long *tc,
+                            const long long *td, void *st)
+{
+    const double tx0 = get_wtime_sec();
+    e->comm->alltoallv_dev_f64(e->comm->ctx, (const double *) from, fc, fd, (double *) to, tc, td, st);
+    e->t_a2a_host += get_wtime_sec() - tx0;
+}
+template <class T>
+static inline void exchange_rows(crp_rp_spmm *e, const Traveller<T> &t, void *st)
+{
+    exchange(e, t.x.send, t.x.sc, t.x.sd, t.recv, t.x.rc, t.x.rd, st);
 }
 
 // the local kernels after the exchange (reference :388-408): product(A, part) once for A_dev (part 0), or for A_int (1) and A_bnd (2)
@@ -229,6 +317,69 @@ static inline void run_parts(crp_rp_spmm *e, F &&product)
         product(e->A_bnd, 2);
     }
     else product(e->A_dev, 0);
+}
+
+// the positions in A_val through which that part writes per-nonzero results (sddmm's out, p_out, ds_out); part 0: in place
+static inline const int *part_positions(const crp_rp_spmm *e, int part)
+{
+    return part == 1 ? e->sd_int_pos.get() : (part == 2 ? e->sd_bnd_pos.get() : nullptr);
+}
+
+// The schedule.  With timing off and a split engine the interior part is enqueued on s while the packs (PACK_ON_EXCHANGE) and the
+// exchanges run on the engine's second stream, from the point of s where the operands are ready (ev_packed); the boundary part
+// follows on s after the last exchange has landed (ev_landed).  Otherwise everything runs on s in sequence, traveller by traveller,
+// and with timing on bills to t_pack and t_a2a.  t0 is left at the start of the kernels, which the caller bills.
+template <class T, size_t N, class F>
+static inline void pack_exchange_run(crp_rp_spmm *e, void *s, double &t0, PackOn where, const Traveller<T> (&travellers)[N], F &&product)
+{
+    const bool timing = e->timing != 0;
+    if (timing) { HIP_OK(crp_stream_sync(s)); }
+    t0 = get_wtime_sec();
+    if (e->A_int == nullptr || timing)
+    {
+        for (const Traveller<T> &t : travellers)
+        {
+            pack_rows(e, t, s);
+            lap(e, s, t0, &e->t_pack);
+            if (e->nproc > 1) exchange_rows(e, t, s);
+            lap(e, s, t0, &e->t_a2a);
+        }
+        run_parts(e, product);
+        return;
+    }
+    if (where == PACK_ON_CALLER)
+        for (const Traveller<T> &t : travellers) pack_rows(e, t, s);
+    // The exchange runs on its own stream beside the interior rows' product.  The product is ENQUEUED FIRST: it does not
+    // depend on the exchange, and issuing a group of sends / receives can hold the host for a while (a non-blocking RCCL
+    // communicator is polled until the group is on the stream) -- with the exchange first, the whole interior product
+    // (0.06 - 0.2 ms per GPU at pwtk size) could have passed before its launch was even issued.
+    HIP_OK(crp_event_record(e->ev_packed, s));
+    product(e->A_int, 1);
+    HIP_OK(crp_stream_wait_event(e->xstream, e->ev_packed));
+    for (const Traveller<T> &t : travellers)
+    {
+        if (where == PACK_ON_EXCHANGE) pack_rows(e, t, e->xstream);
+        exchange_rows(e, t, e->xstream);
+    }
+    HIP_OK(crp_event_record(e->ev_landed, e->xstream));
+    HIP_OK(crp_stream_wait_event(s, e->ev_landed));
+    product(e->A_bnd, 2);
+}
+
+// ---- the way back (exec_t, the attention backward): the forward plan run backwards -------------------------------------------------------
+// what this rank receives in the forward exchange it sends here, from `from` (a receive buffer of x's shape) into x.send, on st
+static inline void reverse_exchange_rows(crp_rp_spmm *e, const Xchg &x, const void *from, void *st)
+{
+    exchange(e, from, x.rc, x.rd, x.send, x.sc, x.sd, st);
+}
+
+// ... and the rows that came back (x.send) added to the rows of dst they belong to (acc_dev: build_transposed), on s
+template <class T>
+static inline void accumulate_rows(crp_rp_spmm *e, const Xchg &x, T *dst, long long ldd, void *s)
+{
+    if (e->n_acc == 0 || x.cols == 0) return;
+    const int *acc_row = e->acc_dev, *acc_ptr = acc_row + e->n_acc, *acc_pos = acc_ptr + e->n_acc + 1;
+    HIP_OK(crp::scatter_add(e->n_acc, x.cols, acc_row, acc_ptr, acc_pos, (const T *) x.send, x.ld, dst, ldd, s));
 }
 
 // ---- the parts' positions in A_val and the host copy of the values --------------------------------------------------------------

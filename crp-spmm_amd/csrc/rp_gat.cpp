@@ -1,8 +1,10 @@
 // rp_gat.cpp -- the row engine's fused GAT and GATv2 attention, forward (crp_rp_spmm_gat{,_f32}_ex, crp_rp_spmm_gatv2{,_f32}_ex,
-// include/crp_engine.h): one implementation each, templated over the dtype.  GAT:  V travels as B does, through the forward exchange; er -- `heads` scalars per row of B -- travels in a
-// narrow exchange of its own (GatXchg, rp_engine_impl.h): the forward plan's row indices and peers, rows of `heads` elements.
-// The part kernels are crp_gat_attention_csr_* on the engine's device matrices, whose two-source column codes name this rank's
-// rows of er / V and the received ones.
+// include/crp_engine.h): one implementation each, templated over the dtype.  Both hand their travellers to the schedule of
+// rp_engine_impl.h (pack_exchange_run, packed on the exchange stream).  GAT has two: V travels as B does, through the forward
+// exchange; er -- `heads` scalars per row of B -- travels in a narrow exchange of its own (GatXchg: the forward plan's row indices
+// and peers, rows of `heads` elements), which the schedule sees as one more Xchg.  GATv2 has one, XS.  The part kernels are
+// crp_gat_attention_csr_* / crp_gatv2_attention_csr_* on the engine's device matrices, whose two-source column codes name this
+// rank's rows of er / V / XS and the received ones.
 #include "rp_engine_impl.h"
 
 static GatXchg<double> &gat_xchg_of(crp_rp_spmm *e, const double *) { return e->gt_x64; }
@@ -21,15 +23,7 @@ static GatXchg<T> &gat_exchange(crp_rp_spmm *e, int heads, const T *like)
     }
     if (g.heads == heads) return g;
     const long long words = ((long long) heads * (long long) sizeof(T) + 7) / 8;       // 8-byte words per row
-    const long long n = e->glb_n;                       // rB_* hold rows * glb_n elements
-    auto by_rows = [&](const std::vector<long long> &v, std::vector<long long> &out) {
-        out.resize(v.size());
-        for (size_t q = 0; q < v.size(); q++) out[q] = n > 0 ? v[q] / n * words : 0;
-    };
-    by_rows(e->rB_scnts, g.sc);
-    by_rows(e->rB_sdispls, g.sd);
-    by_rows(e->rB_rcnts, g.rc);
-    by_rows(e->rB_rdispls, g.rd);
+    plan_words(e, words, g.sc, g.sd, g.rc, g.rd);
     g.ld = words * 8 / (long long) sizeof(T);
     g.send.reset();
     g.recv.reset();
@@ -44,10 +38,8 @@ static void gat_impl(crp_rp_spmm *e, int layout, int heads, double slope, int bi
                      const T *V, long long ldV, T *O, long long ldO, T *lse, T *p_out, void *stream_)
 {
     if (e == NULL) return;
-    ASSERT_PRINTF(!e->plan_only, "rp_spmm_gat on a plan-only engine (no device state)\n");
-    ASSERT_PRINTF(layout == 0 || layout == 1, "layout must be 0 or 1\n");
-    ASSERT_PRINTF(bias == 0 || bias == 1, "bias must be 0 or 1\n");
-    ASSERT_PRINTF(slope - slope == 0.0, "slope must be finite\n");
+    check_call(e, "rp_spmm_gat", "layout", layout);
+    check_scores(bias, slope, "slope");
     ASSERT_PRINTF(heads >= 1 && e->glb_n % heads == 0, "rp_spmm_gat: heads (%d) must be positive and divide the %d columns\n", heads, e->glb_n);
     const int n = e->glb_n, kb = e->loc_B_nrow, m = e->A_nrow;
     const int d = n / heads;                            // one head's width
@@ -61,74 +53,31 @@ static void gat_impl(crp_rp_spmm *e, int layout, int heads, double slope, int bi
     double t0;
 
     const Xchg x = exchange_of(e, V);
-    GatXchg<T> &g = gat_exchange(e, heads, V);
+    const Xchg gx = gat_exchange(e, heads, V).view();
     if (n == 0)
     {
         e->n_exec++;
         return;
     }
     const bool V_on_dev = on_device(V), O_on_dev = on_device(O);
-    const bool lse_host = lse != NULL && m > 0 && !on_device(lse), p_host = p_out != NULL && nnz > 0 && !on_device(p_out);
 
     // ---- V and O as device-resident row-major views: V takes B's buffers and the forward exchange, O takes C's
     const crp::InView<T> Vv = crp::operand_in(layout, V, ldV, kb, n, V_on_dev, e->B_stage, e->B_rm, s);
     const crp::OutView<T> Ov = crp::operand_out(layout, O, ldO, m, n, O_on_dev, e->C_stage, e->C_rm);
-    T *lsed = lse_host ? e->at_lse.grow<T>((size_t) m * nh) : lse;
-    T *pd = p_host ? e->sd_out.grow<T>(nnz * nh) : p_out;
+    const HostVec<T> lsev = host_vec(lse, lse != NULL ? (size_t) m * nh : 0, e->at_lse);
+    const HostVec<T> pv = host_vec(p_out, p_out != NULL ? nnz * nh : 0, e->sd_out);
 
-    auto pack_er = [&](void *st) {
-        if (e->n_send_rows > 0) HIP_OK(crp::gather((int) e->n_send_rows, heads, e->sridxs_dev, er, lder, g.send.get(), g.ld, st));
-    };
-    auto exchange_er = [&](void *st) {
-        const double tx0 = get_wtime_sec();
-        e->comm->alltoallv_dev_f64(e->comm->ctx, (const double *) g.send.get(), g.sc.data(), g.sd.data(), (double *) g.recv.get(), g.rc.data(),
-                                   g.rd.data(), st);
-        e->t_a2a_host += get_wtime_sec() - tx0;
-    };
-    // the parts of a split engine write O and lse through their row maps and p_out through their positions in A_val
-    auto product = [&](crp_csr_dev_p A, int part) {
+    // ---- pack and exchange V, then er; the kernels: the parts of a split engine write O and lse through their row maps and p_out
+    // through their positions in A_val
+    const Traveller<T> travellers[] = {{x, Vv.p, Vv.ld, x.recv}, {gx, er, lder, gx.recv}};
+    pack_exchange_run(e, s, t0, PACK_ON_EXCHANGE, travellers, [&](crp_csr_dev_p A, int part) {
         if (crp_csr_dev_nrow(A) == 0) return;
-        const int *pos = part == 1 ? e->sd_int_pos.get() : (part == 2 ? e->sd_bnd_pos.get() : nullptr);
-        HIP_OK(crp::gat_attention(A, heads, d, slope, bias, el, ldel, er, lder, (const T *) g.recv.get(), g.ld, Vv.p, Vv.ld, (const T *) x.recv,
-                                  x.ld, Ov.p, Ov.ld, lsed, pd, pos, s));
-    };
-
-    if (timing) { HIP_OK(crp_stream_sync(s)); }
-    t0 = get_wtime_sec();
-    if (e->A_int != nullptr && !timing)
-    {
-        // the interior part first on s; both packs and exchanges beside it on the engine's second stream, from the point of s
-        // where the operands are ready; the boundary part after both have landed (pack_exchange_run2, rp_attention.cpp)
-        HIP_OK(crp_event_record(e->ev_packed, s));
-        product(e->A_int, 1);
-        HIP_OK(crp_stream_wait_event(e->xstream, e->ev_packed));
-        pack_rows(e, x, Vv.p, Vv.ld, e->xstream);
-        exchange_rows(e, x, x.recv, e->xstream);
-        pack_er(e->xstream);
-        exchange_er(e->xstream);
-        HIP_OK(crp_event_record(e->ev_landed, e->xstream));
-        HIP_OK(crp_stream_wait_event(s, e->ev_landed));
-        product(e->A_bnd, 2);
-    }
-    else
-    {
-        pack_rows(e, x, Vv.p, Vv.ld, s);
-        pack_er(s);
-        lap(e, s, t0, &e->t_pack);
-        if (e->nproc > 1)
-        {
-            exchange_rows(e, x, x.recv, s);
-            exchange_er(s);
-        }
-        lap(e, s, t0, &e->t_a2a);
-        run_parts(e, product);
-    }
-    if (lse_host) HIP_OK(crp_dev_memcpy(lse, lsed, (size_t) m * nh * sizeof(T), 1, s));
-    if (p_host) HIP_OK(crp_dev_memcpy(p_out, pd, nnz * nh * sizeof(T), 1, s));
-    const bool synced = crp::finish(Ov, s, [&] { lap(e, s, t0, &e->t_spmm); });
-    complete(e, s, synced, lse_host || p_host || !V_on_dev || timing);
-    e->t_exec += get_wtime_sec() - t_begin;
-    e->n_exec++;
+        HIP_OK(crp::gat_attention(A, heads, d, slope, bias, el, ldel, er, lder, (const T *) gx.recv, gx.ld, Vv.p, Vv.ld, (const T *) x.recv, x.ld,
+                                  Ov.p, Ov.ld, lsev.dev, pv.dev, part_positions(e, part), s));
+    });
+    lsev.download(s);
+    pv.download(s);
+    finish_call(e, Ov, s, t0, lsev.staged || pv.staged || !V_on_dev || timing, t_begin);
 }
 
 // ---- GATv2 (crp_rp_spmm_gatv2{,_f32}_ex): XS is the score operand and the value operand, so it is the one operand that travels, as
@@ -138,10 +87,8 @@ static void gatv2_impl(crp_rp_spmm *e, int layout, int heads, double slope, int 
                        long long ldXS, T *O, long long ldO, T *lse, T *p_out, void *stream_)
 {
     if (e == NULL) return;
-    ASSERT_PRINTF(!e->plan_only, "rp_spmm_gatv2 on a plan-only engine (no device state)\n");
-    ASSERT_PRINTF(layout == 0 || layout == 1, "layout must be 0 or 1\n");
-    ASSERT_PRINTF(bias == 0 || bias == 1, "bias must be 0 or 1\n");
-    ASSERT_PRINTF(slope - slope == 0.0, "slope must be finite\n");
+    check_call(e, "rp_spmm_gatv2", "layout", layout);
+    check_scores(bias, slope, "slope");
     ASSERT_PRINTF(heads >= 1 && e->glb_n % heads == 0, "rp_spmm_gatv2: heads (%d) must be positive and divide the %d columns\n", heads, e->glb_n);
     const int n = e->glb_n, kb = e->loc_B_nrow, m = e->A_nrow;
     const int d = n / heads;                            // one head's width
@@ -167,50 +114,24 @@ static void gatv2_impl(crp_rp_spmm *e, int layout, int heads, double slope, int 
         return;
     }
     const bool X_on_dev = on_device(XS), O_on_dev = on_device(O);
-    const bool lse_host = lse != NULL && m > 0 && !on_device(lse), p_host = p_out != NULL && nnz > 0 && !on_device(p_out);
 
     // ---- XS and O as device-resident row-major views: XS takes B's buffers and the forward exchange, O takes C's
     const crp::InView<T> Xv = crp::operand_in(layout, XS, ldXS, kb, n, X_on_dev, e->B_stage, e->B_rm, s);
     const crp::OutView<T> Ov = crp::operand_out(layout, O, ldO, m, n, O_on_dev, e->C_stage, e->C_rm);
-    T *lsed = lse_host ? e->at_lse.grow<T>((size_t) m * nh) : lse;
-    T *pd = p_host ? e->sd_out.grow<T>(nnz * nh) : p_out;
+    const HostVec<T> lsev = host_vec(lse, lse != NULL ? (size_t) m * nh : 0, e->at_lse);
+    const HostVec<T> pv = host_vec(p_out, p_out != NULL ? nnz * nh : 0, e->sd_out);
 
-    // the parts of a split engine write O and lse through their row maps and p_out through their positions in A_val
-    auto product = [&](crp_csr_dev_p A, int part) {
+    // ---- pack and exchange XS; the kernels: the parts of a split engine write O and lse through their row maps and p_out through
+    // their positions in A_val
+    const Traveller<T> travellers[] = {{x, Xv.p, Xv.ld, x.recv}};
+    pack_exchange_run(e, s, t0, PACK_ON_EXCHANGE, travellers, [&](crp_csr_dev_p A, int part) {
         if (crp_csr_dev_nrow(A) == 0) return;
-        const int *pos = part == 1 ? e->sd_int_pos.get() : (part == 2 ? e->sd_bnd_pos.get() : nullptr);
-        HIP_OK(crp::gatv2_attention(A, heads, d, slope, bias, XT, ldXT, Xv.p, Xv.ld, (const T *) x.recv, x.ld, av, Ov.p, Ov.ld, lsed, pd, pos, s));
-    };
-
-    if (timing) { HIP_OK(crp_stream_sync(s)); }
-    t0 = get_wtime_sec();
-    if (e->A_int != nullptr && !timing)
-    {
-        // the interior part first on s; the pack and the exchange beside it on the engine's second stream, from the point of s where
-        // the operand is ready; the boundary part after it has landed
-        HIP_OK(crp_event_record(e->ev_packed, s));
-        product(e->A_int, 1);
-        HIP_OK(crp_stream_wait_event(e->xstream, e->ev_packed));
-        pack_rows(e, x, Xv.p, Xv.ld, e->xstream);
-        exchange_rows(e, x, x.recv, e->xstream);
-        HIP_OK(crp_event_record(e->ev_landed, e->xstream));
-        HIP_OK(crp_stream_wait_event(s, e->ev_landed));
-        product(e->A_bnd, 2);
-    }
-    else
-    {
-        pack_rows(e, x, Xv.p, Xv.ld, s);
-        lap(e, s, t0, &e->t_pack);
-        if (e->nproc > 1) exchange_rows(e, x, x.recv, s);
-        lap(e, s, t0, &e->t_a2a);
-        run_parts(e, product);
-    }
-    if (lse_host) HIP_OK(crp_dev_memcpy(lse, lsed, (size_t) m * nh * sizeof(T), 1, s));
-    if (p_host) HIP_OK(crp_dev_memcpy(p_out, pd, nnz * nh * sizeof(T), 1, s));
-    const bool synced = crp::finish(Ov, s, [&] { lap(e, s, t0, &e->t_spmm); });
-    complete(e, s, synced, lse_host || p_host || !X_on_dev || timing);
-    e->t_exec += get_wtime_sec() - t_begin;
-    e->n_exec++;
+        HIP_OK(crp::gatv2_attention(A, heads, d, slope, bias, XT, ldXT, Xv.p, Xv.ld, (const T *) x.recv, x.ld, av, Ov.p, Ov.ld, lsev.dev, pv.dev,
+                                    part_positions(e, part), s));
+    });
+    lsev.download(s);
+    pv.download(s);
+    finish_call(e, Ov, s, t0, lsev.staged || pv.staged || !X_on_dev || timing, t_begin);
 }
 
 extern "C" {

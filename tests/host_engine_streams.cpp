@@ -12,6 +12,10 @@
 // matrix handle (its values), so the check is conservative.  Negative control: the same checker on the same log with one
 // stream_wait_event removed must report a race.  This is the only place the overlap path's order can be checked without several
 // devices; it says nothing about what a real transport does inside alltoallv_dev_f64.
+//
+// The call list runs twice, each time on a fresh engine: with timing off (the overlap path; every check above) and with the phases
+// timed (everything in sequence on the caller's stream; the race checker again).  `--dump` prints both logs as text, one op per line
+// with streams, events and buffers numbered in order of first appearance: the dumps of two builds of csrc/ compare with diff.
 #include "host_device_standins.h"
 
 // ---- rank 0 of 2 -------------------------------------------------------------------------------------------------------------
@@ -111,7 +115,16 @@ template <class T> struct Dev      // a caller's device array
     ~Dev() { crp_dev_free(p); }
 };
 
-int main()
+// ---- one pass over the call list ---------------------------------------------------------------------------------------------------
+struct Pass
+{
+    void *caller = NULL, *caller2 = NULL;                  // the caller's streams (tokens: destroyed by the end of the pass)
+    std::vector<std::pair<size_t, size_t>> gat_calls;      // the log's [first, end) of every GAT / GATv2 call
+    size_t probe = 0;                                      // ... and which of them the GAT negative control takes apart
+};
+
+// a fresh split engine, every call of the list with this timing mode, the engine freed; g_log holds the log of it all, from empty
+static Pass run_calls(int timing)
 {
     // 4 of 8 rows on rank 0, B rows 0 .. 3 here and 4 .. 7 on the peer; rows 0 and 1 name local columns only (interior), rows 2 and 3
     // name columns of the peer (boundary)
@@ -126,16 +139,18 @@ int main()
     comm.alltoall_i32 = f_alltoall; comm.alltoallv_i32 = f_alltoallv; comm.allgatherv_bytes = f_allgatherv; comm.barrier = f_barrier;
     comm.reduce_f64 = f_reduce_f64; comm.reduce_u64 = f_reduce_u64; comm.alltoallv_dev_f64 = f_exchange; comm.free = f_free;
 
+    g_log.clear();
     g_logging = true;
     crp_rp_spmm_p e = NULL;
     crp_rp_spmm_init(0, m, rp.data(), ci.data(), va.data(), displs, N, &comm, &e);
     int n_int = 0, n_bnd = 0;
     crp_rp_spmm_overlap_rows(e, &n_int, &n_bnd);
     CHECK(n_int == 2 && n_bnd == 2, "the engine is not split: %d interior, %d boundary rows", n_int, n_bnd);
-    crp_rp_spmm_set_timing(e, 0);
-    void *caller = NULL, *caller2 = NULL;
-    std::vector<std::pair<size_t, size_t>> gat_calls;      // the log's [first, end) of every GAT / GATv2 call
-    size_t probe = 0;                                      // ... and which of them the GAT negative control takes apart
+    crp_rp_spmm_set_timing(e, timing);
+    Pass pass;
+    void *&caller = pass.caller, *&caller2 = pass.caller2;
+    std::vector<std::pair<size_t, size_t>> &gat_calls = pass.gat_calls;
+    size_t &probe = pass.probe;
     crp_stream_create(&caller);
     crp_stream_create(&caller2);
     {
@@ -213,6 +228,71 @@ int main()
     crp_stream_destroy(caller2);
     g_logging = false;
     check_balanced("split row engine");
+    return pass;
+}
+
+// the log as text, one op per line: kind, call, stream, event, buffers read, buffers written.  Streams, events and buffers are named
+// by their index in order of first appearance (a freed buffer's address gets a new index when it appears again), so the dumps of
+// two builds compare as text
+static void dump(const char *title, const std::vector<Op> &log)
+{
+    static const char *const kinds[] = {"work", "record", "wait", "sync", "forget"};
+    std::map<const void *, size_t> streams, events, buffers;
+    size_t n_buffers = 0;
+    auto name = [](std::map<const void *, size_t> &ids, const void *p) { return ids.emplace(p, ids.size()).first->second; };
+    printf("# %s: %zu ops\n", title, log.size());
+    for (const Op &op : log)
+    {
+        printf("%s %s", kinds[op.kind], op.call);
+        if (op.kind == OP_FORGET)
+        {
+            for (const void *b : op.writes)
+            {
+                if (buffers.count(b)) printf(" b%zu", buffers[b]);
+                buffers.erase(b);
+            }
+            printf("\n");
+            continue;
+        }
+        if (op.stream == NULL) printf(" s-null");
+        else printf(" s%zu", name(streams, op.stream));
+        if (op.event != NULL) printf(" e%zu", name(events, op.event));
+        for (int w = 0; w < 2; w++)
+        {
+            printf(w == 0 ? " r:" : " w:");
+            for (const void *b : w == 0 ? op.reads : op.writes)
+            {
+                if (!buffers.count(b)) buffers[b] = n_buffers++;
+                printf(" b%zu", buffers[b]);
+            }
+        }
+        printf("\n");
+    }
+}
+
+static void report(const char *pass, const std::vector<Op> &log, const std::vector<Race> &found)
+{
+    for (size_t i = 0; i < found.size() && i < 10; i++)
+        fprintf(stderr, "%s: race: #%zu %s (stream %p) and #%zu %s (stream %p) on buffer %p\n", pass, found[i].first, log[found[i].first].call,
+                log[found[i].first].stream, found[i].second, log[found[i].second].call, log[found[i].second].stream, found[i].buffer);
+}
+
+// `--dump`: the two passes' logs on stdout, ahead of the checks
+int main(int argc, char **argv)
+{
+    // the timed pass first, its log set aside: g_log then holds the pass with timing off, which the checks below were written for
+    const Pass timed = run_calls(1);
+    std::vector<Op> timed_log;
+    timed_log.swap(g_log);
+    const Pass off = run_calls(0);
+    void *const caller = off.caller, *const caller2 = off.caller2;
+    const std::vector<std::pair<size_t, size_t>> &gat_calls = off.gat_calls;
+    const size_t probe = off.probe;
+    if (argc > 1 && strcmp(argv[1], "--dump") == 0)
+    {
+        dump("timing off", g_log);
+        dump("timing on", timed_log);
+    }
 
     // ---- the log reached the overlap path, and it is ordered
     std::set<void *> work_streams;
@@ -226,10 +306,22 @@ int main()
     CHECK(work_streams.count(caller) && work_streams.count(caller2) && work_streams.size() >= 4, "work on %zu streams only", work_streams.size());
     CHECK(exchanges > 0 && waits > 0, "no exchange on the engine's second stream (%ld) or no wait (%ld)", exchanges, waits);
     const std::vector<Race> found = races(g_log);
-    for (size_t i = 0; i < found.size() && i < 10; i++)
-        fprintf(stderr, "race: #%zu %s (stream %p) and #%zu %s (stream %p) on buffer %p\n", found[i].first, g_log[found[i].first].call,
-                g_log[found[i].first].stream, found[i].second, g_log[found[i].second].call, g_log[found[i].second].stream, found[i].buffer);
+    report("timing off", g_log, found);
     CHECK(found.empty(), "%zu unordered pairs of conflicting accesses", found.size());
+
+    // ---- the same calls with the phases timed: everything in sequence on the caller's stream, so no exchange leaves it, and what
+    // the engine's own streams do beside it (first-call uploads, value updates) is ordered all the same
+    long timed_exchanges = 0;
+    for (const Op &op : timed_log)
+    {
+        if (op.kind != OP_WORK || strcmp(op.call, "alltoallv_dev_f64") != 0) continue;
+        CHECK(op.stream == timed.caller || op.stream == timed.caller2, "a timed exchange off the caller's stream");
+        timed_exchanges++;
+    }
+    CHECK(timed_exchanges > 0, "the timed pass made no exchange");
+    const std::vector<Race> timed_found = races(timed_log);
+    report("timing on", timed_log, timed_found);
+    CHECK(timed_found.empty(), "timing on: %zu unordered pairs of conflicting accesses", timed_found.size());
 
     // ---- negative control: without its first wait for the exchange stream, the caller's stream races with the exchange
     std::map<void *, void *> recorded_on;
@@ -289,7 +381,8 @@ int main()
     CHECK(!gat_broken.empty(), "the checker does not see the race of a GAT call without wait #%zu", gat_victim);
     CHECK(on_narrow, "none of the %zu races without wait #%zu is the boundary kernel's read of the narrow receive buffer", gat_broken.size(), gat_victim);
     printf("HOST_ENGINE_STREAMS_OK ops=%zu streams=%zu exchanges=%ld cross_stream_waits=%ld needed=%ld control_races=%zu gat_calls=%zu "
-           "gat_exchanges=%ld gat_cross_stream_waits=%ld gat_zero_fills=%ld gat_control_races=%zu\n", g_log.size(), work_streams.size(), exchanges, cross,
-           needed, broken.size(), gat_calls.size(), gat_exchanges, gat_waits, gat_zero_fills, gat_broken.size());
+           "gat_exchanges=%ld gat_cross_stream_waits=%ld gat_zero_fills=%ld gat_control_races=%zu timed_ops=%zu timed_exchanges=%ld\n", g_log.size(),
+           work_streams.size(), exchanges, cross, needed, broken.size(), gat_calls.size(), gat_exchanges, gat_waits, gat_zero_fills, gat_broken.size(),
+           timed_log.size(), timed_exchanges);
     return 0;
 }

@@ -70,7 +70,8 @@ def test_engine_stream_order_under_asan_ubsan(tmp_path):
     stream, its own stream and the exchange stream -- exec, exec_t, sddmm, attention, attention_bwd, the GAT and GATv2 forward (csrc/rp_gat.cpp: two
     packs and two exchanges beside the interior kernel, and the narrow buffers set up again for another number of heads),
     update_values and update_values_dev, on two caller streams -- and the same checker reports a race once one stream_wait_event
-    is taken out of the log, for a GAT call on the narrow receive buffer among others (tests/host_engine_streams.cpp)."""
+    is taken out of the log, for a GAT call on the narrow receive buffer among others; the same call list with the phases timed is
+    ordered too, every exchange on a caller's stream (tests/host_engine_streams.cpp; its --dump prints both logs for diff)."""
     gxx = shutil.which("g++")
     if gxx is None:
         pytest.skip("no g++")
